@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of the denoise forward at batch 256, 128x128x3, fp32, per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,20 +16,33 @@ N=8 — sharded contiguously, weak scaling), inputs already resident in HBM.  Ra
 (seeded synthetic) weights and ONE RCCL broadcast of the packed blob distributes them; the
 forward itself has no collective.  Prints one JSON line on rank 0.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the outputs (--dump-outputs) and the
+line.  --full adds every other measurement and check listed below (parity, the second broadcast, the legs, cpu_baseline);
+--no-extras and --no-cpu-baseline trim a --full run.
+
+--dump-outputs DIR: after the timed steps, the last step's output ([B,3,S,S] fp32, what a caller of the forward receives)
+is written as DIR/output.npy (DIR/output_rank<r>.npy, one per rank, when N > 1).  Inputs and weights are seeded, so the same
+arguments give the same inputs on every run.  Above 64 MB in all, a fixed seeded sample of whole images (then of whole rows)
+is written instead.
+
 Extra objects on that line:
   roofline      dominant kernel of the forward: FLOPs the matrix pipe EXECUTES per launch (Winograd launches: 24/72 or 16/36 of
                 the direct-convolution count) / its mean launch duration from HIP events recorded on the launch stream
                 during the timed steps; peak = gfx950 dense fp32 matrix rate (157.3 TFLOP/s); `frac` <= 1 by
                 construction; `achieved_algorithmic` = direct-convolution FLOPs / the same time
   layers        every launch: ms, executed and algorithmic TFLOP/s, GB/s, fraction of its own (mfma|hbm) roofline
+  rccl          (N>1, or --force-dist) what RCCL reports for the weights communicator and the one broadcast
+  rehearsal     only with --rehearse-shared-gpu: the N>1 code path with all ranks on cuda:0 over gloo (one-GPU boxes); not a scaling number
+ only with --full (with --full --no-extras: parity and rccl.broadcast_ms alone):
+  parity        two images of the timed output against the CPU oracle; with N>1 (or --force-dist) also max_abs_err_all_ranks, the worst
+                error over ALL ranks of two images of each rank's own shard (ranks > 0 run on the broadcast weights)
+  rccl.broadcast_ms  a second broadcast on the kept communicator: the transfer alone
+  pcie_inclusive, latency_n1  host-buffer round trips and single-image latency
   configs       (N=1 only) short legs at BASELINE.json configs[3] (B=256, 256x256, fp32) and configs[4] (B=512, fp16
                 storage): images/sec, slowest launch, parity spot check
   hot_weights_leg, dist_world1_leg  (N=1 only) 5 steps on the He-gain weight set; RCCL communicator + weights broadcast at world size 1
   split16_leg   (N=1 only) the opt-in split-operand algorithm of the 3x3 layers (conv_algo="split16") on the same batch: images/sec and error on both weight sets
-  rccl, parity.max_abs_err_all_ranks  (N>1, or --force-dist) what RCCL reports for the weights communicator and the one broadcast; the worst
-                error over ALL ranks of two images of each rank's own shard against the CPU oracle (ranks > 0 run on the broadcast weights)
-  rehearsal     only with --rehearse-shared-gpu: the N>1 code path with all ranks on cuda:0 over gloo (one-GPU boxes); not a scaling number
-  cpu_baseline  (N=1 only) the CPU oracle = the reference's forward re-stated on the ATen CPU
+  cpu_baseline  (N=1 only, not with --no-cpu-baseline) the CPU oracle = the reference's forward re-stated on the ATen CPU
                 operators the reference itself calls, timed on this host's cores on a bounded sample
 """
 import argparse
@@ -243,6 +256,26 @@ def timed_forwards(model, x, steps, warmup):
     return elapsed, launch_ms, nfw, y
 
 
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: all files of one run together
+
+
+def dump_output(y, path, max_bytes, seed=0):
+    """Write the output tensor `y` [N,C,H,W] as float32 .npy at `path`.  If it is larger than `max_bytes` (less room for the
+    header), a fixed sample is written: whole images chosen by a seeded generator, then (if one image is still too large) whole
+    rows of them, both in ascending order.  The sample depends only on the shape, so two builds write the same elements."""
+    rng = np.random.default_rng(seed)
+    budget = max_bytes - 4096
+    for dim in (0, 2):
+        if y.numel() * 4 <= budget:
+            break
+        keep = max(1, budget // (y.numel() * 4 // y.shape[dim]))
+        idx = np.sort(rng.choice(y.shape[dim], keep, replace=False))
+        y = y.index_select(dim, torch.from_numpy(idx).to(y.device))
+    a = y.float().cpu().numpy()
+    np.save(path, a)
+    return list(a.shape)
+
+
 def extra_config(model, sd_default, tag, B, S, dtype, steps=20, warmup=5):
     """One of BASELINE.json's other single-GPU configs as a short leg of the default run (so the driver's record carries
     a number it timed itself): images/sec, slowest launch, parity spot check of the timed output against the CPU oracle."""
@@ -286,9 +319,15 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="f32 = the reference's arithmetic (the headline metric); f16 = BASELINE configs[4] (half storage, "
                          "fp16 MFMA with fp32 accumulators) — a different numerical contract, reported for that config only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline: parity against the CPU oracle, the second broadcast, "
+                         "the host-pipeline, latency, configs, hot-weights, split16 and world-size-1 RCCL legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/output.npy (float32; a fixed seeded sample above 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the host-pipeline and single-image-latency legs (profiling runs: only the timed batches launch kernels)")
+                    help="with --full: skip the host-pipeline, latency, configs and other legs and the CPU baseline "
+                         "(profiling runs: only the timed batches launch kernels)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) even with one rank: rehearses the N>1 code path on a 1-GPU box")
     ap.add_argument("--self-launch", action="store_true",
@@ -297,6 +336,8 @@ def main():
                     help="REHEARSAL of the N>1 code path on a box with fewer GPUs than ranks: every rank uses cuda:0 and the process group runs on gloo "
                          "(RCCL refuses two ranks on one device, so the blob travels by the fallback transport); the line is marked and is not a scaling number")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if (args.gpus > 1 or args.self_launch) and "WORLD_SIZE" not in os.environ:
         # started as a plain command: become the launcher of N ranks (no GPU call has been made, none is made here)
@@ -344,8 +385,9 @@ def main():
     bcast = None
     if use_dist:
         bcast = cdist.broadcast_weights_ex(model, src=0)         # the job's one collective (communicator set-up + ncclBroadcast)
-        again = cdist.broadcast_weights_ex(model, src=0)         # a second one on the kept communicator: the transfer alone
-        bcast["broadcast_ms_cached_comm"] = again["broadcast_ms"]
+        if args.full:
+            again = cdist.broadcast_weights_ex(model, src=0)     # a second one on the kept communicator: the transfer alone
+            bcast["broadcast_ms_cached_comm"] = again["broadcast_ms"]
 
     begin, end = cdist.shard_range(B * world, rank, world)
     x_host, clean_host, noisy_host = synth.make_batch(end - begin, S, S, first_index=begin)
@@ -375,8 +417,13 @@ def main():
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "output" if world == 1 else f"output_rank{rank}"
+        dumped = {name: dump_output(y, os.path.join(args.dump_outputs, name + ".npy"), DUMP_MAX_BYTES // world)}
     err_all_ranks = None
-    if use_dist:
+    if use_dist and args.full:
         # every rank checks the first two images of ITS shard against the CPU oracle (untimed): a rank other than 0 can only pass with the
         # weights the broadcast delivered (it started from its own random init); the worst error over the ranks goes into the line
         try:
@@ -417,27 +464,32 @@ def main():
         }
         if bcast is not None:
             # nranks = what RCCL ITSELF reports for the C-ABI communicator (cid_comm_count = ncclCommCount), not WORLD_SIZE
-            res["rccl"] = {"nranks": bcast["nranks"], "transport": bcast["transport"], "broadcast_ms": round(bcast["broadcast_ms_cached_comm"], 3),
+            res["rccl"] = {"nranks": bcast["nranks"], "transport": bcast["transport"],
                            "first_broadcast_ms": round(bcast["broadcast_ms"], 3), "comm_setup_ms": round(bcast["setup_ms"], 2),
                            "blob_bytes": int(model.pack_weights().numel()), "collectives_in_forward": 0}
+            if "broadcast_ms_cached_comm" in bcast:
+                res["rccl"]["broadcast_ms"] = round(bcast["broadcast_ms_cached_comm"], 3)
         if args.rehearse_shared_gpu:
             res["rehearsal"] = (f"{world} ranks SHARING cuda:0 over gloo: exercises launcher, sharding, barrier, max-over-ranks timing and the aggregate; "
                                 "not a scaling measurement, and no RCCL (two ranks on one device are refused)")
-        # parity spot-check on the timed output: 2 images vs the CPU oracle
-        try:
-            from oracle import torch_oracle
+        if dumped is not None:
+            res["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}   # rank 0's file; the other ranks write their own
+        if args.full:
+            # parity spot-check on the timed output: 2 images vs the CPU oracle
+            try:
+                from oracle import torch_oracle
 
-            ref = torch_oracle.forward(sd, x_host[:2]).numpy()
-            got = y[:2].cpu().numpy()
-            res["parity"] = {"max_abs_err_vs_cpu_oracle": float(np.abs(got - ref).max()),
-                             "psnr_delta_db": abs(cid.psnr(got, clean_host[:2]) - cid.psnr(ref, clean_host[:2])),
-                             "tolerance": "max|delta|<=1e-5, psnr_delta<=0.01 dB" if not f16 else
-                                          "fp16 storage: max|delta|<=5e-4 at default weight scale (tests/test_gpu_parity.py)"}
-            if err_all_ranks is not None:
-                res["parity"]["max_abs_err_all_ranks"] = err_all_ranks     # ranks > 0 run on the broadcast weights
-        except Exception as e:  # pragma: no cover
-            res["parity"] = {"error": str(e)[:200]}
-        if args.no_extras:
+                ref = torch_oracle.forward(sd, x_host[:2]).numpy()
+                got = y[:2].cpu().numpy()
+                res["parity"] = {"max_abs_err_vs_cpu_oracle": float(np.abs(got - ref).max()),
+                                 "psnr_delta_db": abs(cid.psnr(got, clean_host[:2]) - cid.psnr(ref, clean_host[:2])),
+                                 "tolerance": "max|delta|<=1e-5, psnr_delta<=0.01 dB" if not f16 else
+                                              "fp16 storage: max|delta|<=5e-4 at default weight scale (tests/test_gpu_parity.py)"}
+                if err_all_ranks is not None:
+                    res["parity"]["max_abs_err_all_ranks"] = err_all_ranks     # ranks > 0 run on the broadcast weights
+            except Exception as e:  # pragma: no cover
+                res["parity"] = {"error": str(e)[:200]}
+        if args.no_extras or not args.full:
             emit(res)
             if use_dist:
                 dist.barrier()

@@ -20,7 +20,7 @@ for spec in argv[1:]:
 res = {name: [] for name, _ in arms}
 for r in range(rounds):
     for name, env in arms:
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--no-cpu-baseline", "--steps", "30"] + extra,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "30"] + extra,
                              env=dict(os.environ, **env), capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

@@ -819,7 +819,7 @@ def test_bench_two_ranks_sharing_the_gpu():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--batch-per-gpu", "8", "--steps", "2", "--warmup", "1",
-                          "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300)
+                          "--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[-2000:]                            # ONE line on stdout, from rank 0
@@ -828,6 +828,33 @@ def test_bench_two_ranks_sharing_the_gpu():
     assert d["rccl"]["collectives_in_forward"] == 0 and d["rccl"]["transport"] in ("torch-distributed", "rccl-cabi")
     assert d["parity"]["max_abs_err_all_ranks"] <= 1e-5 and d["parity"]["max_abs_err_vs_cpu_oracle"] <= 1e-5
     assert d["value"] == pytest.approx(16 * 2 / (d["ms_per_step"] * 2 * 1e-3), rel=1e-3)     # whole-job images over the max-over-ranks time
+
+
+def test_bench_plain_run_dumps_the_timed_output(tmp_path, weight_sets):
+    """A plain bench.py run (no --full) prints one line with the headline keys and none of the --full objects; --dump-outputs writes
+    the last timed step's output, which is bit for bit the forward of the same seeded batch and weights in this process."""
+    import subprocess
+    import sys
+
+    import celebrity_image_denoiser_amd as cid
+
+    _need_gpu()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch-per-gpu", "4", "--size", "32", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["steps"] == 3
+    assert d["value"] == pytest.approx(4 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert not {"parity", "pcie_inclusive", "latency_n1", "configs", "hot_weights_leg", "split16_leg", "dist_world1_leg", "cpu_baseline"} & set(d)
+    y = np.load(os.path.join(tmp_path, "output.npy"))
+    assert y.dtype == np.float32 and y.shape == (4, 3, 32, 32) and d["outputs"]["arrays"] == {"output": [4, 3, 32, 32]}
+    m = cid.load(weight_sets["default"], device="cuda:0", strict=True)
+    m.conv_algo = "winograd42"
+    x, _, _ = synth.make_batch(4, 32, 32, first_index=0)
+    assert np.array_equal(_run(m, x), y)
 
 
 def test_rccl_broadcast_through_the_c_abi(weight_sets):

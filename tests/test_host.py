@@ -386,6 +386,35 @@ def test_bench_self_launch_propagates_a_failing_rank(tmp_path):
     assert all(os.path.exists(os.path.join(tmp_path, f"started{r}")) for r in range(3))
 
 
+def test_bench_dump_output_is_whole_or_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: an output within the limit is written whole as float32; a larger one as the same seeded sample of whole images
+    (then whole rows) on every call, within the limit."""
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "np", np, raising=False)
+    monkeypatch.setattr(bench, "torch", torch, raising=False)
+    g = torch.Generator().manual_seed(1)
+    small = torch.randn(4, 3, 16, 16, generator=g)
+    p = os.path.join(tmp_path, "small.npy")
+    assert bench.dump_output(small, p, 1 << 20) == [4, 3, 16, 16]
+    a = np.load(p)
+    assert a.dtype == np.float32 and np.array_equal(a, small.numpy())
+    big = torch.randn(40, 3, 32, 32, generator=g)   # 491,520 bytes
+    shapes, arrays = [], []
+    for k in range(2):
+        p = os.path.join(tmp_path, f"big{k}.npy")
+        shapes.append(bench.dump_output(big, p, 100_000))
+        arrays.append(np.load(p))
+        assert os.path.getsize(p) <= 100_000
+    assert shapes[0] == shapes[1] and 1 <= shapes[0][0] < 40 and shapes[0][1:] == [3, 32, 32]
+    assert np.array_equal(arrays[0], arrays[1])
+    rows = {tuple(r.ravel()) for r in big.numpy()}
+    assert all(tuple(r.ravel()) in rows for r in arrays[0])    # whole images of the output
+    huge = torch.randn(1, 3, 64, 64, generator=g)   # one image above the limit: whole rows of it
+    p = os.path.join(tmp_path, "huge.npy")
+    s = bench.dump_output(huge, p, 30_000)
+    assert s[:2] == [1, 3] and s[3] == 64 and 1 <= s[2] < 64 and os.path.getsize(p) <= 30_000
+
+
 def test_bench_plain_command_with_gpus_n_uses_the_launcher(monkeypatch):
     """main(): --gpus N > 1 without WORLD_SIZE goes to launch_ranks with the untouched command line and exits with its code;
     with WORLD_SIZE set (a rank started by torch.distributed.run or by the launcher) it does not."""
