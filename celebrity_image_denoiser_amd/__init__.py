@@ -9,6 +9,7 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     HostPipeline(model).run(host_batches)   upload / forward / download overlapped on three HIP streams
     GraphedForward(model, example)(x)       the forward at a fixed shape as one HIP-graph launch (N=1 serving latency)
     enhance_images(ckpt, in_dir, out_dir)   the reference's directory eval harnesses (denoisegan_eval.py / denoise_eavl_iter.py)
+    quality(a, b) / evaluate(denoised, clean)   PSNR / SSIM / MS-SSIM of device batches (the trainer's per-batch evaluation)
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -24,6 +25,8 @@ _LAZY = {
     "get_padding": ("api", "get_padding"),
     "load_state_safely": ("api", "load_state_safely"),
     "psnr": ("metrics", "psnr"),
+    "quality": ("metrics", "quality"),
+    "evaluate": ("metrics", "evaluate"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

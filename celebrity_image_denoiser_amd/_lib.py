@@ -15,6 +15,7 @@ CID_ALGO_DIRECT, CID_ALGO_WINOGRAD64, CID_ALGO_WINOGRAD42, CID_ALGO_SPLIT16 = 0,
 CID_FMT_F32_NCHW, CID_FMT_U8_NHWC = 0, 1
 CID_DTYPE_F32, CID_DTYPE_F16 = 0, 1
 CID_TAIL_FUSED, CID_TAIL_BANDS, CID_TAIL_TILES = 0, 1, 2
+CID_METRIC_PSNR, CID_METRIC_SSIM, CID_METRIC_MS_SSIM = 1, 2, 4
 
 # every symbol include/cid.h declares: (restype, argtypes)
 _c = ctypes
@@ -67,6 +68,9 @@ SYMBOLS = {
     "cid_comm_count": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int)]),
     "cid_broadcast_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p]),
     "cid_launch_work": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    "cid_quality_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_quality": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                               _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
 }
 
 _lib = None

@@ -24,3 +24,89 @@ def _np(x):
     if isinstance(x, np.ndarray):
         return x
     return x.detach().cpu().numpy()
+
+
+# ---- device metrics: PSNR / SSIM / MS-SSIM in HIP (cid_quality, include/cid.h) ----
+
+_METRIC_BITS = {"psnr": 1, "ssim": 2, "ms_ssim": 4}      # CID_METRIC_PSNR / _SSIM / _MS_SSIM
+_COLUMNS = {"psnr": 0, "ssim": 1, "ms_ssim": 2}          # columns of cid_quality's [N][3] output
+
+
+def _operand(x):
+    """(CID format, (N, H, W)) of an fp32 [N,3,H,W] or uint8 [N,H,W,3] tensor."""
+    import torch
+
+    from . import _lib
+
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise RuntimeError("quality() expects 4-d torch tensors: float32 [N,3,H,W] or uint8 [N,H,W,3]")
+    if x.dtype == torch.float32 and x.shape[1] == 3:
+        return _lib.CID_FMT_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
+    if x.dtype == torch.uint8 and x.shape[3] == 3:
+        return _lib.CID_FMT_U8_NHWC, (x.shape[0], x.shape[1], x.shape[2])
+    raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3], got {x.dtype} {list(x.shape)}")
+
+
+def _quality_table(a, b, metrics):
+    """cid_quality on the current stream: device float64 [N,3] (psnr_db, ssim, ms_ssim; columns not requested are NaN)."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+
+    names = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+    unknown = [m for m in names if m not in _METRIC_BITS]
+    if unknown or not names:
+        raise ValueError(f"metrics must be a non-empty subset of {tuple(_METRIC_BITS)}, got {names}")
+    bits = 0
+    for m in names:
+        bits |= _METRIC_BITS[m]
+    fa, shape_a = _operand(a)
+    fb, shape_b = _operand(b)
+    if shape_a != shape_b:
+        raise ValueError("Input images must have the same dimensions.")
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError("got a CPU tensor: the quality metrics are GPU-only; there is no CPU fallback")
+    if a.device != b.device:
+        raise RuntimeError(f"operands on different devices: {a.device} and {b.device}")
+    n, h, w = shape_a
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t()
+    rc = L.cid_quality_workspace_bytes(n, h, w, bits, ctypes.byref(nbytes))
+    if rc == 2:   # CID_ERR_SHAPE
+        raise ValueError(f"image size {h}x{w} (N={n}) not accepted for {names}: SSIM needs H, W >= 7; "
+                         "MS-SSIM needs min(H, W) > 160 (pytorch_msssim's assertion)")
+    _lib.check(None, rc)
+    a, b = a.contiguous(), b.contiguous()
+    dev = a.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(None, L.cid_quality(a.data_ptr(), fa, b.data_ptr(), fb, n, h, w, bits, out.data_ptr(),
+                                       ws.data_ptr(), nbytes.value, stream))
+    return out, names
+
+
+def quality(a, b, metrics=("psnr", "ssim", "ms_ssim")):
+    """Per-image PSNR (dB), SSIM and MS-SSIM of two device batches, computed by HIP kernels: {name: float64 tensor [N]} on the
+    inputs' GPU.  Definitions (include/cid.h): skimage peak_signal_noise_ratio / structural_similarity(channel_axis=2) with
+    data_range=2.0 on [-1,1] images, pytorch_msssim.MS_SSIM(data_range=1.0) on x*0.5+0.5 — the reference trainer's evaluation,
+    training.py:378-392.  Each operand is float32 [N,3,H,W] in [-1,1] or uint8 [N,H,W,3] (read as (u/255-0.5)/0.5); the two
+    may differ in format.  Runs on the current stream, workspace from torch's allocator.  CPU tensors raise RuntimeError."""
+    out, names = _quality_table(a, b, metrics)
+    return {m: out[:, _COLUMNS[m]].contiguous() for m in names}
+
+
+def evaluate(denoised_hr, clean_hr, ms_ssim: bool = True):
+    """Drop-in for the reference's DenoiseGANTrainer.evaluate (training.py:378-392): (psnr, ssim, lpips, msssim) as Python
+    floats, batch means of the per-image values, after one device-to-host copy of N x 3 doubles.
+
+    lpips is always 0.0: LPIPS needs pretrained AlexNet weights and is not computed; 0.0 is the value the trainer itself reports
+    when its LPIPS model is unavailable (training.py:284-287,385).  With ms_ssim=False msssim is 0.0 as well; with ms_ssim=True
+    images of min(H, W) <= 160 raise ValueError (pytorch_msssim's size assertion)."""
+    metrics = ("psnr", "ssim", "ms_ssim") if ms_ssim else ("psnr", "ssim")
+    out, _ = _quality_table(denoised_hr, clean_hr, metrics)
+    means = out.cpu().numpy().mean(axis=0)
+    return float(means[0]), float(means[1]), 0.0, float(means[2]) if ms_ssim else 0.0

@@ -261,6 +261,44 @@ int cid_comm_count(void* comm, int* nranks);   /* ncclCommCount: how many ranks 
 int cid_broadcast_weights(cid_handle_t h, void* comm, int root, int rank, void* stream);
 
 /*
+ * Image-quality metrics of denoised batches — the reference denoise trainer's evaluation, DenoiseGANTrainer.evaluate
+ * (backend/trainingcode/denoise_gan_code/training.py:378-392, once per batch at :432), on device tensors.  LPIPS (:282) is not
+ * provided: it needs pretrained AlexNet weights.  No handle: no weights are involved.
+ *
+ * For each image pair (a, b) of a batch (3 channels, H x W), three per-image values:
+ *   PSNR     skimage peak_signal_noise_ratio(a, b, data_range=2.0) on float32 inputs (training.py:380): d = a - b and d*d in fp32,
+ *            mse = mean of d*d over the 3*H*W values accumulated in fp64, psnr = 10*log10(2.0^2 / mse); mse == 0 gives +inf.
+ *   SSIM     skimage structural_similarity(a, b, channel_axis=2, data_range=2.0) with its defaults (training.py:381): per channel,
+ *            7x7 uniform (box) means ux, uy, uxx, uyy, uxy of a, b, a^2, b^2, ab; sample covariance cn = 49/48: vx = cn(uxx-ux^2),
+ *            vy = cn(uyy-uy^2), vxy = cn(uxy-ux*uy); C1 = (0.01*2)^2, C2 = (0.03*2)^2;
+ *            S = (2ux*uy+C1)(2vxy+C2) / ((ux^2+uy^2+C1)(vx+vy+C2)), averaged over the pixels at least 3 from every border (skimage's
+ *            crop(S, 3): no border mode is involved).  The image's value is the mean of its 3 channels.  Needs H >= 7 and W >= 7.
+ *   MS-SSIM  pytorch_msssim.MS_SSIM(data_range=1.0) v1.0 (training.py:283, :390) on x*0.5+0.5 (fp32): 11-tap Gaussian window,
+ *            sigma 1.5, float32 like torch (exp(-(k-5)^2/4.5), normalised), applied as a VALID separable convolution;
+ *            per level and channel, with Gaussian moments and compensation 1, C1 = 0.01^2, C2 = 0.03^2:
+ *              cs = mean((2sxy+C2)/(sx^2+sy^2+C2)),  ssim = mean((2mx*my+C1)/(mx^2+my^2+C1) * cs_map);
+ *            5 levels, between them avg_pool2d(2, stride 2, padding (H%2, W%2), count_include_pad) of both images (a side s becomes
+ *            (s+1)/2); per channel prod_{l<4} relu(cs_l)^w_l * relu(ssim_4)^w_4 with w = [0.0448, 0.2856, 0.3001, 0.2363, 0.1333];
+ *            the image's value is the mean of its 3 channels.  Needs min(H, W) > 160, as pytorch_msssim asserts.
+ * Operand formats (each operand its own): CID_FMT_F32_NCHW fp32 [N,3,H,W] in [-1,1]; CID_FMT_U8_NHWC uint8 [N,H,W,3], read as
+ * (u/255 - 0.5)/0.5 in fp32 with true divisions (the forward's u8 input arithmetic): a u8 image and its normalised fp32 copy give
+ * bit-identical metrics.
+ *
+ * cid_quality_workspace_bytes: device scratch one cid_quality call needs (per-tile partial sums; with MS-SSIM the pooled levels 1-4).
+ * cid_quality: asynchronous on `stream` (hipStream_t, NULL = default stream).  out: device double [N][3] = psnr_db, ssim, ms_ssim;
+ * columns not requested are NaN.  Every argument is checked on the host before any launch:
+ *   CID_ERR_INVALID    null pointer, unknown format, misaligned fp32 operand or out, metrics 0 or with unknown bits
+ *   CID_ERR_SHAPE      N < 1, H or W < 7 with SSIM, min(H, W) <= 160 with MS-SSIM, a plane of 2^31 pixels or more
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_quality_workspace_bytes() or not 256-byte aligned
+ * Reductions are deterministic (per-tile partial sums reduced in a fixed order in fp64, no atomics) and an image's tiling does not
+ * depend on N: an image's three values are bit-identical whatever batch it is in.
+ */
+enum { CID_METRIC_PSNR = 1, CID_METRIC_SSIM = 2, CID_METRIC_MS_SSIM = 4 };
+int cid_quality_workspace_bytes(int N, int H, int W, int metrics, size_t* bytes);
+int cid_quality(const void* a, int a_fmt, const void* b, int b_fmt, int N, int H, int W, int metrics, double* out,
+                void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
