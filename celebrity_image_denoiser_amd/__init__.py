@@ -10,6 +10,7 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     GraphedForward(model, example)(x)       the forward at a fixed shape as one HIP-graph launch (N=1 serving latency)
     enhance_images(ckpt, in_dir, out_dir)   the reference's directory eval harnesses (denoisegan_eval.py / denoise_eavl_iter.py)
     quality(a, b) / evaluate(denoised, clean)   PSNR / SSIM / MS-SSIM of device batches (the trainer's per-batch evaluation)
+    add_noise(clean_u8, kind)     the trainer's five noise kinds on device uint8 batches; evaluate_noise_types(model, clean_u8)
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -27,6 +28,9 @@ _LAZY = {
     "psnr": ("metrics", "psnr"),
     "quality": ("metrics", "quality"),
     "evaluate": ("metrics", "evaluate"),
+    "NOISE_TYPES": ("noise", "NOISE_TYPES"),
+    "add_noise": ("noise", "add_noise"),
+    "evaluate_noise_types": ("noise", "evaluate_noise_types"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

@@ -16,6 +16,7 @@ CID_FMT_F32_NCHW, CID_FMT_U8_NHWC = 0, 1
 CID_DTYPE_F32, CID_DTYPE_F16 = 0, 1
 CID_TAIL_FUSED, CID_TAIL_BANDS, CID_TAIL_TILES = 0, 1, 2
 CID_METRIC_PSNR, CID_METRIC_SSIM, CID_METRIC_MS_SSIM = 1, 2, 4
+CID_NOISE_GAUSSIAN, CID_NOISE_SALT_PEPPER, CID_NOISE_SPECKLE, CID_NOISE_POISSON, CID_NOISE_UNIFORM = 0, 1, 2, 3, 4
 
 # every symbol include/cid.h declares: (restype, argtypes)
 _c = ctypes
@@ -71,6 +72,8 @@ SYMBOLS = {
     "cid_quality_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
     "cid_quality": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_add_noise": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int,
+                                 _c.c_uint64, _c.c_uint64, _c.c_void_p]),
 }
 
 _lib = None

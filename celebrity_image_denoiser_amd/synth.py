@@ -157,3 +157,178 @@ def make_batch(n: int, h: int, w: int, first_index: int = 0, sigma: float = 25.0
     clean = clean_images_u8(n, h, w, first_index)
     noisy = add_gaussian_noise(clean, sigma, first_index)
     return normalize_u8(noisy), normalize_u8(clean), noisy
+
+
+# ---- the trainer's five noise kinds (noise_generation.py:6-39): bit-defined restatements of cid_add_noise ----
+#
+# Every draw comes from the hash streams above, never from np.random: image n of a call uses the seed
+# seed + first_index + n, and element e = (y*W + x)*3 + c of an image is element e of each stream.  All arithmetic is
+# float64 in the order written; results are np.clip(v, 0, 255).astype(np.uint8).  include/cid.h states the definitions and
+# noise.add_noise computes the same bits on the GPU.
+
+NOISE_TYPES = ("gaussian", "salt_pepper", "speckle", "poisson", "uniform")   # the trainer's list, training.py:247
+NOISE_DEFAULTS = {                       # the reference's keyword defaults, in cid_add_noise's params order
+    "gaussian": {"mean": 0.0, "sigma": 25.0},
+    "salt_pepper": {"salt_prob": 0.02, "pepper_prob": 0.02},
+    "speckle": {"mean": 0.0, "sigma": 0.1},
+    "poisson": {},
+    "uniform": {"low": 0.0, "high": 25.0},
+}
+NOISE_STREAMS = {
+    "gaussian": (1, 2),                   # add_gaussian_noise's streams
+    "speckle": (_fnv1a64("noise:speckle:u1"), _fnv1a64("noise:speckle:u2")),
+    "uniform": (_fnv1a64("noise:uniform"),),
+    "poisson": (_fnv1a64("noise:poisson"),),
+    "salt_pepper": tuple(_fnv1a64("noise:salt_pepper:" + s) for s in ("salt_row", "salt_col", "pepper_row", "pepper_col")),
+}
+POISSON_KMAX = 1023
+
+
+def _image_uniforms(seed: int, first_index: int, n: int, stream: int, per: int) -> np.ndarray:
+    """[n, per] float64: row i is hash_uniform(seed + first_index + i, stream, per)."""
+    return np.stack([hash_uniform(seed + first_index + i, stream, per) for i in range(n)]) if n else np.empty((0, per))
+
+
+def _box_muller(u1: np.ndarray, u2: np.ndarray) -> np.ndarray:
+    return np.sqrt(-2.0 * np.log(1.0 - u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def noise_values_np(clean_u8: np.ndarray, kind: str, seed: int = NOISE_SEED, first_index: int = 0, **params) -> np.ndarray:
+    """The float64 value v of every element before np.clip / uint8 truncation, for the kinds that have one (gaussian, speckle,
+    uniform); [N,H,W,3] like the input."""
+    if kind not in ("gaussian", "speckle", "uniform"):
+        raise ValueError(f"{kind!r} has no float64 pre-clip value (poisson and salt_pepper are integer draws)")
+    p = dict(NOISE_DEFAULTS[kind])
+    unknown = set(params) - set(p)
+    if unknown:
+        raise TypeError(f"unknown parameter(s) {sorted(unknown)} for {kind!r} noise; expected {sorted(p)}")
+    p.update(params)
+    n = clean_u8.shape[0]
+    per = int(np.prod(clean_u8.shape[1:]))
+    img = clean_u8.reshape(n, per).astype(np.float64)
+    streams = NOISE_STREAMS[kind]
+    if kind == "uniform":
+        u = _image_uniforms(seed, first_index, n, streams[0], per)
+        v = img + (p["low"] + (p["high"] - p["low"]) * u)
+    else:
+        z = _box_muller(_image_uniforms(seed, first_index, n, streams[0], per),
+                        _image_uniforms(seed, first_index, n, streams[1], per))
+        noise = p["mean"] + p["sigma"] * z
+        v = img + noise if kind == "gaussian" else img + img * noise
+    return v.reshape(clean_u8.shape)
+
+
+def _clip_u8(v: np.ndarray) -> np.ndarray:
+    return np.clip(v, 0, 255).astype(np.uint8)
+
+
+def add_speckle_noise(clean_u8: np.ndarray, mean: float = 0.0, sigma: float = 0.1, seed: int = NOISE_SEED,
+                      first_index: int = 0) -> np.ndarray:
+    """clip(img + img*(mean + sigma*z), 0, 255).astype(uint8) (noise_generation.py:24-28), z from Box-Muller on the speckle
+    streams."""
+    return _clip_u8(noise_values_np(clean_u8, "speckle", seed, first_index, mean=mean, sigma=sigma))
+
+
+def add_uniform_noise(clean_u8: np.ndarray, low: float = 0.0, high: float = 25.0, seed: int = NOISE_SEED,
+                      first_index: int = 0) -> np.ndarray:
+    """clip(img + (low + (high-low)*u), 0, 255).astype(uint8) (noise_generation.py:35-39; numpy's uniform is low + (high-low)*u)."""
+    return _clip_u8(noise_values_np(clean_u8, "uniform", seed, first_index, low=low, high=high))
+
+
+def poisson_cdf_table() -> np.ndarray:
+    """[256, POISSON_KMAX+1] float64: row lambda holds the running sums c_k of the inversion, p_0 = exp(-lambda) (math.exp: the
+    host libm, as cid_add_noise uses std::exp), p_k = (p_{k-1}*lambda)/k, c_k = c_{k-1} + p_k.  Each row is non-decreasing."""
+    lam = np.arange(256, dtype=np.float64)
+    p = np.array([math.exp(-float(v)) for v in range(256)], dtype=np.float64)
+    c = np.empty((256, POISSON_KMAX + 1), dtype=np.float64)
+    c[:, 0] = p
+    for k in range(1, POISSON_KMAX + 1):
+        p = (p * lam) / float(k)
+        c[:, k] = c[:, k - 1] + p
+    return c
+
+
+def add_poisson_noise(clean_u8: np.ndarray, seed: int = NOISE_SEED, first_index: int = 0) -> np.ndarray:
+    """np.random.poisson(img).astype(np.uint8) (noise_generation.py:30-33) by inversion: lambda = the pixel value, k = 0, c = p =
+    exp(-lambda); while u >= c and k < 1023: k += 1, p = (p*lambda)/k, c += p.  The result is k mod 256: the reference's cast
+    wraps, so about 48 % of the pixels at 255 come out dark.  That quirk is kept on purpose.
+
+    The loop stops at the first k with u < c_k, which for a non-decreasing row of the table is a binary search: the same bits,
+    without a Python loop per element."""
+    n = clean_u8.shape[0]
+    per = int(np.prod(clean_u8.shape[1:]))
+    lam = clean_u8.reshape(n, per)
+    u = _image_uniforms(seed, first_index, n, NOISE_STREAMS["poisson"][0], per)
+    table = poisson_cdf_table()
+    lam, u = lam.reshape(-1), u.reshape(-1)
+    order = np.argsort(lam, kind="stable")
+    bounds = np.searchsorted(lam[order], np.arange(257))
+    k = np.empty(lam.size, dtype=np.int64)
+    for v in range(256):
+        idx = order[bounds[v]:bounds[v + 1]]
+        k[idx] = np.searchsorted(table[v], u[idx], side="right")
+    k = np.minimum(k, POISSON_KMAX)
+    return (k & 255).astype(np.uint8).reshape(clean_u8.shape)
+
+
+def _mulhi64(z: np.ndarray, m: int) -> np.ndarray:
+    """floor(z*m / 2^64) for uint64 z and 0 <= m < 2^32, exact (32-bit halves)."""
+    assert 0 <= m < 2 ** 32
+    mm = np.uint64(m)
+    lo = (z & np.uint64(0xFFFFFFFF)) * mm
+    hi = (z >> np.uint64(32)) * mm
+    return (hi + (lo >> np.uint64(32))) >> np.uint64(32)
+
+
+def _hash_u64(seed: int, stream: int, n: int) -> np.ndarray:
+    """The full 64-bit draws z_j = splitmix64(splitmix64(seed ^ stream) + j), j < n (hash_uniform's integers)."""
+    base = splitmix64(np.array([(seed ^ stream) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))[0]
+    with np.errstate(over="ignore"):
+        return splitmix64(base + np.arange(n, dtype=np.uint64))
+
+
+def salt_pepper_coords(h: int, w: int, salt_prob: float = 0.02, pepper_prob: float = 0.02, seed: int = NOISE_SEED,
+                       index: int = 0):
+    """((salt_rows, salt_cols), (pepper_rows, pepper_cols)) of the image with global index `index`: n = int(float(h*w*3)*prob)
+    draws each, row = floor(z*(h-1) / 2^64), col = floor(z*(w-1) / 2^64) (numpy's randint(0, h-1): the last row and column are
+    never hit)."""
+    if h < 2 or w < 2:
+        raise ValueError(f"salt_pepper needs H, W >= 2 (numpy's randint(0, i-1) raises high <= low), got {h}x{w}")
+    per = h * w * 3
+    sr, sc, pr, pc = NOISE_STREAMS["salt_pepper"]
+    s = seed + index
+    out = []
+    for prob, (rs, cs) in ((salt_prob, (sr, sc)), (pepper_prob, (pr, pc))):
+        k = int(float(per) * prob)
+        out.append((_mulhi64(_hash_u64(s, rs, k), h - 1).astype(np.int64), _mulhi64(_hash_u64(s, cs, k), w - 1).astype(np.int64)))
+    return tuple(out)
+
+
+def add_salt_pepper_noise(clean_u8: np.ndarray, salt_prob: float = 0.02, pepper_prob: float = 0.02, seed: int = NOISE_SEED,
+                          first_index: int = 0) -> np.ndarray:
+    """noise_generation.py:12-22: int(float(H*W*3)*prob) salt draws set all 3 channels of their pixel to 255, then as many pepper
+    draws set theirs to 0 (pepper wins a collision).  The reference's third, channel coordinate is drawn but unused, so it is not
+    drawn here."""
+    n, h, w = clean_u8.shape[:3]
+    out = clean_u8.copy()
+    for i in range(n):
+        (sr, sc), (pr, pc) = salt_pepper_coords(h, w, salt_prob, pepper_prob, seed, first_index + i)
+        out[i, sr, sc, :] = 255
+        out[i, pr, pc, :] = 0
+    return out
+
+
+def add_noise_np(clean_u8: np.ndarray, kind: str, seed: int = NOISE_SEED, first_index: int = 0, **params) -> np.ndarray:
+    """uint8 [N,H,W,3] -> the same with `kind` noise (one of NOISE_TYPES, the reference's keyword names and defaults): the CPU
+    restatement of noise.add_noise / cid_add_noise.  With kind="gaussian" and mean 0 this is add_gaussian_noise bit for bit."""
+    if kind not in NOISE_DEFAULTS:
+        raise ValueError(f"unknown noise kind {kind!r}; expected one of {NOISE_TYPES}")
+    unknown = set(params) - set(NOISE_DEFAULTS[kind])
+    if unknown:
+        raise TypeError(f"unknown parameter(s) {sorted(unknown)} for {kind!r} noise; expected {sorted(NOISE_DEFAULTS[kind])}")
+    clean_u8 = np.ascontiguousarray(clean_u8, dtype=np.uint8)
+    if kind in ("gaussian", "speckle", "uniform"):
+        return _clip_u8(noise_values_np(clean_u8, kind, seed, first_index, **params))
+    if kind == "poisson":
+        return add_poisson_noise(clean_u8, seed, first_index)
+    return add_salt_pepper_noise(clean_u8, seed=seed, first_index=first_index, **params)

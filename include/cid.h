@@ -299,6 +299,38 @@ int cid_quality(const void* a, int a_fmt, const void* b, int b_fmt, int N, int H
                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Noise synthesis — the five noise kinds the reference's denoise trainer is trained on (DenoiseDataset over
+ * ['gaussian', 'salt_pepper', 'speckle', 'poisson', 'uniform'], backend/trainingcode/denoise_gan_code/training.py:247), each made
+ * from a clean uint8 image as noise_generation.py:6-39 does, with the reference's formulas and defaults.  No handle: no weights.
+ *
+ * clean_u8_nhwc and out_u8_nhwc are device uint8 [N,H,W,3]; out may equal clean (in place) but must not overlap it otherwise.
+ * Random draws come from counter-based splitmix64 streams, not np.random: image n uses seed' = seed + first_index + n and element
+ * e = (y*W + x)*3 + c; u = (z >> 11) * 2^-53 with z = splitmix64(splitmix64(seed' ^ stream) + e).  An image's noise depends only on
+ * (seed, its global index first_index + n, H, W).  Arithmetic is float64 in the order below; the result is clip(v, 0, 255)
+ * truncated to uint8.  The bit-defined restatement is synth.add_noise_np.
+ *   GAUSSIAN     params (mean, sigma), reference (0, 25), noise_generation.py:6-10: z = sqrt(-2 log(1-u1)) cos(2 pi u2) on streams
+ *                1 and 2, v = img + (mean + sigma*z).  With mean 0 this is exactly synth.add_gaussian_noise (bench.py's inputs).
+ *   SPECKLE      params (mean, sigma), reference (0, 0.1), :24-28: the same z on streams fnv1a64("noise:speckle:u1" / ":u2"),
+ *                v = img + img*(mean + sigma*z).
+ *   UNIFORM      params (low, high), reference (0, 25), :35-39: v = img + (low + (high-low)*u), stream fnv1a64("noise:uniform").
+ *   POISSON      no params, :30-33: lambda = the pixel value, k by inversion (p = exp(-lambda), c = p; while u >= c and k < 1023:
+ *                k += 1, p = (p*lambda)/k, c += p) on stream fnv1a64("noise:poisson"); exp(-lambda) is the host libm's.  The result is
+ *                k mod 256: the reference's np.random.poisson(u8).astype(np.uint8) wraps, so about 48 % of the pixels at 255 come out
+ *                dark (P(k >= 256 | lambda = 255)).  This quirk is reproduced on purpose.
+ *   SALT_PEPPER  params (salt_prob, pepper_prob), reference (0.02, 0.02), :12-22: n = int(float(H*W*3) * prob) draws of each;
+ *                draw j: row = floor(z_row(j) * (H-1) / 2^64), col = floor(z_col(j) * (W-1) / 2^64) (the last row and column are never
+ *                hit, as with randint(0, H-1)); all 3 channels of the pixel become 255 (salt), then 0 (pepper: pepper wins a
+ *                collision).  Streams fnv1a64("noise:salt_pepper:salt_row" / ":salt_col" / ":pepper_row" / ":pepper_col").
+ * Asynchronous on `stream` (hipStream_t, NULL = default stream).  Every argument is checked on the host before any launch:
+ *   CID_ERR_INVALID  null pointer, unknown kind, nparams not the kind's count (params may be NULL when it is 0), a non-finite
+ *                    parameter, sigma < 0, a probability outside [0, 1], low > high
+ *   CID_ERR_SHAPE    N < 1, H or W < 1 (< 2 for SALT_PEPPER: numpy's randint(0, 0) raises), H*W*3 >= 2^31
+ */
+enum { CID_NOISE_GAUSSIAN = 0, CID_NOISE_SALT_PEPPER = 1, CID_NOISE_SPECKLE = 2, CID_NOISE_POISSON = 3, CID_NOISE_UNIFORM = 4 };
+int cid_add_noise(const void* clean_u8_nhwc, void* out_u8_nhwc, int N, int H, int W, int kind, const double* params, int nparams,
+                  uint64_t seed, uint64_t first_index, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
