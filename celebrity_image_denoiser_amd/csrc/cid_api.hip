@@ -1169,7 +1169,13 @@ int cid_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes,
         {"upconv2", D2, 128, d.Hu2, d.Wu2, 128, 0},      //                                            app.py:94
         {"up1", CAT1, 64, d.Hu1, d.Wu1, 128, 0},         //                                            app.py:96
         {"upconv1.0", T4, 64, d.Hu1, d.Wu1, 64, 0},      // after its ReLU (app.py:75-76); with CID_TAIL_FUSED the region holds
-                                                         // the 27 z planes [N, 27, Hu1, Wu1] instead
+                                                         // the z planes instead (include/cid.h)
+        // the first convolution of each two-conv block, after its ReLU (app.py:43-44,51-52,59-60,67-68): every launch writes a
+        // region of its own (enum Buf), so these are still intact after the forward
+        {"down1.0", T0, 64, d.H, d.W, 64, 0},
+        {"down2.0", T1, 128, d.H1, d.W1, 128, 0},
+        {"bottleneck.0", T2, 256, d.H2, d.W2, 256, 0},
+        {"upconv2.0", T3, 128, d.Hu2, d.Wu2, 128, 0},
     };
     for (const Row& r : rows)
         if (std::strcmp(stage, r.name) == 0) {

@@ -351,7 +351,8 @@ class DenoiseGenerator(nn.Module):
 
     def stage_output(self, stage: str, n: int, h: int, w: int) -> torch.Tensor:
         """Testing aid: the output of the reference module's submodule `stage` ("down1", "pool1", "down2", "pool2",
-        "bottleneck", "up2", "upconv2", "up1" — what a forward hook on it would record, app.py:81-96) as left in the
+        "bottleneck", "up2", "upconv2", "up1" — what a forward hook on it would record, app.py:81-96 — or a block's first
+        convolution after its ReLU: "down1.0", "down2.0", "bottleneck.0", "upconv2.0", or "upconv1.0" with an unfused last layer) as left in the
         activation arena by the LAST forward of an [n,3,h,w] batch, returned as a fresh fp32 NCHW tensor.  Skip tensors
         ("down1", "down2") cover only the top-left region the concat keeps (cid_stage_view, include/cid.h)."""
         L = _lib.lib()

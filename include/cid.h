@@ -199,7 +199,11 @@ enum { CID_ALGO_DIRECT = 0, CID_ALGO_WINOGRAD64 = 2, CID_ALGO_WINOGRAD42 = 3, CI
  *   CID_DTYPE_F16  IEEE half storage, v_mfma_f32_32x32x16_f16 with fp32 accumulators, bias/ReLU/pool in fp32,
  *                  one rounding to half per stored element; direct implicit GEMM for all ten GEMM layers.
  * The caller-side tensors (cid_forward / cid_forward_ex) keep their formats; only the arena and the weight
- * segments read change.  A different numerical contract from the reference's fp32 (tolerances: tests/).
+ * segments read change.  A different numerical contract from the reference's fp32 (tolerances: tests/): against the fp32
+ * forward, max|delta| <= 5e-3 on image-like inputs and <= 7e-3 on white noise in [-1, 1] with He-gain weights (the format's
+ * own error: 4.7e-3 at most over 64 images of 128x128 in a CPU emulation of the rounding points, plus a margin).  Each
+ * launch's stored halfs are round-to-nearest-even (subnormals kept) of its fp32 result within the fp32 summation bound
+ * (oracle/f16_oracle.py, tests/test_f16_launches.py).
  */
 enum { CID_DTYPE_F32 = 0, CID_DTYPE_F16 = 1 };   /* (the half path's kernels use v_mfma_f32_16x16x32_f16 since round 2) */
 int cid_set_compute_dtype(cid_handle_t h, int dtype);
@@ -231,9 +235,14 @@ int cid_launch_work_ex(cid_handle_t h, int i, int N, int H, int W, double* flops
  * Where the output of one of the reference module's stages lives in the workspace of an [N,3,H,W] forward (NHWC,
  * fp32 — or half elements from the same base when the compute dtype is CID_DTYPE_F16).  `stage` is the attribute name of
  * the reference module whose forward-hook output it is (backend/app.py:42-78): "down1", "pool1", "down2", "pool2",
- * "bottleneck", "up2", "upconv2", "up1", plus "upconv1.0" (upconv1[0] after its ReLU: the last layer's input; with
- * CID_TAIL_FUSED that region holds the 27 planes z[N,27,Hs,Ws] instead and the view does not apply).  Element (n, y, x, c) of the stage is at
+ * "bottleneck", "up2", "upconv2", "up1", plus "upconv1.0" (upconv1[0] after its ReLU: the last layer's input) and the first
+ * convolution of each two-conv block after its ReLU: "down1.0" (64 x H x W), "down2.0" (128 x H/2 x W/2), "bottleneck.0"
+ * (256 x H/4 x W/4) and "upconv2.0" (128 channels, the size of "up2").  Element (n, y, x, c) of the stage is at
  *     offset_bytes/elem_size + ((n*Hs + y)*Ws + x)*pixel_stride + channel_offset + c        for y < Hs, x < Ws, c < C.
+ * With CID_TAIL_FUSED the "upconv1.0" region holds the fused tail's z planes instead and the formula does not apply; z row
+ * r = 3 tap + co (tap = 3 kh + kw) is upconv1[2]'s contraction sum_ci upconv1.0[ci] * W[co][ci][kh][kw] at each pixel:
+ *     CID_DTYPE_F32  fp32 z[N][27][Hs][Ws]
+ *     CID_DTYPE_F16  half z[N][7 groups][Hs][Ws][4]: row r is slot r % 4 of group r / 4; slot 3 of group 6 is a zero pad.
  * Skip tensors ("down1", "down2") are stored only over the region the concat keeps (top-left crop, app.py:90-92,97-99).
  * "upconv1" (pre-tanh) is never stored: it is fused into the last kernel.  Testing aid for per-stage parity.
  */

@@ -113,6 +113,17 @@ def test_stage_views_and_fused_launch_accounting():
     assert L.cid_stage_view(b"bottleneck", 2, 13, 18, *args) == 0 and (c.value, hs.value, ws.value, ps.value, co.value) == (256, 3, 4, 256, 0)
     assert L.cid_stage_view(b"up1", 2, 13, 18, *args) == 0 and (c.value, co.value) == (64, 0)
     assert L.cid_stage_view(b"upconv1", 2, 13, 18, *args) == 3                               # fused into the last kernel: never stored
+    # the first convolution of each block: t0 / t1 / t2 / t3, every one in a region of its own
+    assert L.cid_stage_view(b"down1.0", 2, 13, 18, *args) == 0 and (off.value, c.value, hs.value, ws.value, ps.value, co.value) == (0, 64, 13, 18, 64, 0)
+    assert L.cid_stage_view(b"down2.0", 2, 13, 18, *args) == 0 and (c.value, hs.value, ws.value, ps.value, co.value) == (128, 6, 9, 128, 0)
+    t1_off = off.value
+    assert L.cid_stage_view(b"pool1", 2, 13, 18, *args) == 0 and off.value < t1_off
+    assert L.cid_stage_view(b"bottleneck.0", 2, 13, 18, *args) == 0 and (c.value, hs.value, ws.value, ps.value, co.value) == (256, 3, 4, 256, 0)
+    t2_off = off.value
+    assert L.cid_stage_view(b"bottleneck", 2, 13, 18, *args) == 0 and off.value > t2_off
+    assert L.cid_stage_view(b"upconv2.0", 2, 13, 18, *args) == 0 and (c.value, hs.value, ws.value, ps.value, co.value) == (128, 6, 8, 128, 0)
+    t3_off = off.value
+    assert L.cid_stage_view(b"upconv2", 2, 13, 18, *args) == 0 and off.value > t3_off
     assert L.cid_stage_view(b"down1", 1, 3, 3, *args) == 2
     h = ctypes.c_void_p()
     assert L.cid_create(ctypes.byref(h)) == 0
