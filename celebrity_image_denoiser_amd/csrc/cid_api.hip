@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -29,40 +30,16 @@ using namespace cid;
 struct ncclUniqueIdBytes { char internal[128]; };   // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES = 128), passed by value
 
 enum Kind { HEAD, CONV, CONVT, TAIL };
-struct LayerDef { const char* name; Kind kind; int cin, cout; };
+struct LayerDef { const char* name; Kind kind; int cin, cout; bool pool = false; };   // pool: the 2x2 max-pool runs in this layer's epilogue
 constexpr int NL = 12;
-const LayerDef kLayers[NL] = {
-    {"down1.0", HEAD, 3, 64},        {"down1.2", CONV, 64, 64},        {"down2.0", CONV, 64, 128},
-    {"down2.2", CONV, 128, 128},     {"bottleneck.0", CONV, 128, 256}, {"bottleneck.2", CONV, 256, 256},
-    {"up2", CONVT, 256, 128},        {"upconv2.0", CONV, 256, 128},    {"upconv2.2", CONV, 128, 128},
-    {"up1", CONVT, 128, 64},         {"upconv1.0", CONV, 128, 64},     {"upconv1.2", TAIL, 64, 3},
+constexpr LayerDef kLayers[NL] = {
+    {"down1.0", HEAD, 3, 64},          {"down1.2", CONV, 64, 64, true},  {"down2.0", CONV, 64, 128},
+    {"down2.2", CONV, 128, 128, true}, {"bottleneck.0", CONV, 128, 256}, {"bottleneck.2", CONV, 256, 256},
+    {"up2", CONVT, 256, 128},          {"upconv2.0", CONV, 256, 128},    {"upconv2.2", CONV, 128, 128},
+    {"up1", CONVT, 128, 64},           {"upconv1.0", CONV, 128, 64},     {"upconv1.2", TAIL, 64, 3},
 };
-const char* kKernelNames[NL] = {
-    "k_conv_head", "k_gemm_conv<64, 64, 1,", "k_gemm_conv<64, 128, 0,", "k_gemm_conv<128, 128, 1,",
-    "k_gemm_conv<128, 256, 0,", "k_gemm_conv<256, 256, 0,", "k_gemm_conv<256, 128, 2,", "k_gemm_conv<256, 128, 0,",
-    "k_gemm_conv<128, 128, 0,", "k_convt_s32<128, 64>", "k_gemm_conv<128, 64, 0,", "k_conv_tail",
-};
-
-const char* kHalfKernelNames[NL] = {
-    "k_conv_head_h16", "k_conv3x3_h16<64, 64, 1,", "k_conv3x3_h16<64, 128, 0,", "k_conv3x3_h16<128, 128, 1,",
-    "k_conv3x3_h16<128, 256, 0,", "k_conv3x3_h16<256, 256, 0,", "k_convt_t16<256, 128>", "k_conv3x3_h16<256, 128, 0,",
-    "k_conv3x3_h16<128, 128, 0,", "k_convt_t16<128, 64>", "k_conv3x3_h16<128, 64, 0, false,", "k_conv_tail_h<",
-};
-const char* kWino64KernelNames[NL] = {
-    nullptr, "k_wino64_conv<64, 64, true,", "k_wino64_conv<64, 128, false,", "k_wino64_conv<128, 128, true,",
-    "k_wino64_conv<128, 256, false,", "k_wino64_conv<256, 256, false,", nullptr, "k_wino64_conv<256, 128, false,",
-    "k_wino64_conv<128, 128, false,", nullptr, "k_wino64_conv<128, 64, false,", nullptr,
-};
-const char* kSplitKernelNames[NL] = {   // conv_algo = "split16": the eight 3x3 layers on k_conv3x3_h16<..., F32IO = true>; everything else as the direct configuration
-    nullptr, "k_conv3x3_h16<64, 64, 1, false, false, true,", "k_conv3x3_h16<64, 128, 0, false, false, true,", "k_conv3x3_h16<128, 128, 1, false, false, true,",
-    "k_conv3x3_h16<128, 256, 0, false, false, true,", "k_conv3x3_h16<256, 256, 0, false, false, true,", "k_conv3x3_h16<256, 128, 2, false, false, true,", "k_conv3x3_h16<256, 128, 0, false, false, true,",
-    "k_conv3x3_h16<128, 128, 0, false, false, true,", "k_conv3x3_h16<128, 64, 2, false, false, true,", "k_conv3x3_h16<128, 64, 0, false, false, true,", nullptr,
-};
-const char* kWino42KernelNames[NL] = {
-    nullptr, "k_wino42_conv<64, 64, true,", "k_wino42_conv<64, 128, false,", "k_wino42_conv<128, 128, true,",
-    "k_wino42_conv<128, 256, false,", "k_wino42_conv<256, 256, false,", nullptr, "k_wino42_conv<256, 128, false,",
-    "k_wino42_conv<128, 128, false,", nullptr, "k_wino42_conv<128, 64, false,", nullptr,
-};
+// MODE template argument of the GEMM-shaped kernels: 0 conv 3x3, 1 conv 3x3 + 2x2 pool, 2 transposed conv 2x2 stride 2
+constexpr int mode_of(const LayerDef& L) { return L.kind == CONVT ? 2 : L.pool ? 1 : 0; }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline unsigned long long cdiv_ull(unsigned long long a, unsigned long long b) { return (a + b - 1) / b; }
@@ -319,11 +296,90 @@ struct cid_handle_s {
 
 namespace {
 
-// The fused form lives in the epilogue of upconv1[0]'s kernel: the Winograd kernels on the fp32 path (not the 9-tap direct one), k_conv3x3_h16 on the
-// fp16-storage path (one 3x3 algorithm there, so always).
-bool fused_tail_active(cid_handle_t h) {
-    return h->tail_algo == CID_TAIL_FUSED && (h->dtype == CID_DTYPE_F16 || h->algo != CID_ALGO_DIRECT);
+// A handle's three settings.  The null handle stands for the direct fp32 kernels with a separate last layer.
+struct Config { int dtype, algo, tail; };
+Config config_of(cid_handle_t h) {
+    return h ? Config{h->dtype, h->algo, h->tail_algo} : Config{CID_DTYPE_F32, CID_ALGO_DIRECT, CID_TAIL_BANDS};
 }
+
+// The kernel family (and instantiation class) of one launch.  run_forward launches what select_kernel picks and
+// cid_launch_kernel reports the name of the same pick.  Within a value, the shape still chooses the tile width (Winograd),
+// walking or not (k_conv3x3_h16) and bands or tiles (TAIL_BANDS above T2_MAXW).
+enum class Kern {
+    HEAD, HEAD_H16,               // k_conv_head / k_conv_head_h16
+    GEMM,                         // k_gemm_conv<CIN, COUT, MODE>: CID_ALGO_DIRECT, and up2 on the fp32 path
+    CONVT_S32,                    // k_convt_s32: up1 on the fp32 path
+    WINO64, WINO42,               // k_wino64_conv / k_wino42_conv
+    SPLIT, SPLIT_PAIR,            // CID_ALGO_SPLIT16, k_conv3x3_h16<..., F32IO>: one / two column blocks per workgroup
+    H16, CONVT_T16,               // fp16 storage: k_conv3x3_h16, k_convt_t16
+    Z_WINO64, Z_WINO42, Z_SPLIT, Z_H16,   // upconv1[0] with upconv1[2]'s contraction in its epilogue: z planes out
+    TAIL_BANDS, TAIL_TILES, TAIL_H,       // upconv1[2] as a launch of its own: k_conv_tail2, k_conv_tail, k_conv_tail_h
+    TAIL_Z, TAIL_ZH,                      // the nine-tap sum over the z planes: k_conv_tail_z (fp32), k_conv_tail_zh (half)
+};
+
+Kern select_kernel(const Config& c, int i) {
+    const LayerDef& L = kLayers[i];
+    const bool f16 = c.dtype == CID_DTYPE_F16;
+    // The fused form lives in the epilogue of upconv1[0]'s kernel: the Winograd and split-operand kernels on the fp32 path (not
+    // the 9-tap direct one), k_conv3x3_h16 on the fp16-storage path (one 3x3 algorithm there, so always).
+    const bool fused = c.tail == CID_TAIL_FUSED && (f16 || c.algo != CID_ALGO_DIRECT);
+    switch (L.kind) {
+        case HEAD: return f16 ? Kern::HEAD_H16 : Kern::HEAD;
+        case TAIL:
+            if (fused) return f16 ? Kern::TAIL_ZH : Kern::TAIL_Z;
+            return f16 ? Kern::TAIL_H : c.tail == CID_TAIL_BANDS ? Kern::TAIL_BANDS : Kern::TAIL_TILES;
+        case CONVT:
+            if (f16) return Kern::CONVT_T16;
+            if (c.algo == CID_ALGO_SPLIT16) return Kern::SPLIT_PAIR;
+            return L.cin == 128 ? Kern::CONVT_S32 : Kern::GEMM;
+        case CONV: break;
+    }
+    const bool z = fused && i == 10;
+    if (f16) return z ? Kern::Z_H16 : Kern::H16;
+    switch (c.algo) {
+        case CID_ALGO_WINOGRAD64: return z ? Kern::Z_WINO64 : Kern::WINO64;
+        case CID_ALGO_WINOGRAD42: return z ? Kern::Z_WINO42 : Kern::WINO42;
+        case CID_ALGO_SPLIT16: return z ? Kern::Z_SPLIT : L.cout >= 128 ? Kern::SPLIT_PAIR : Kern::SPLIT;
+        default: return Kern::GEMM;   // CID_ALGO_DIRECT
+    }
+}
+
+// The symbol prefix cid_launch_kernel reports: enough of the template argument list to tell the launch's instantiation from
+// the library's others (generator.launch_table and the tracked profiles match on it).
+std::string kernel_name(const Config& c, int i) {
+    const LayerDef& L = kLayers[i];
+    const std::string dims = std::to_string(L.cin) + ", " + std::to_string(L.cout);
+    const std::string mode = dims + ", " + std::to_string(mode_of(L)) + ",", pool = dims + (L.pool ? ", true," : ", false,");
+    switch (select_kernel(c, i)) {
+        case Kern::HEAD: return "k_conv_head";
+        case Kern::HEAD_H16: return "k_conv_head_h16";
+        case Kern::GEMM: return "k_gemm_conv<" + mode;
+        case Kern::CONVT_S32: return "k_convt_s32<" + dims + ">";
+        case Kern::WINO64: case Kern::Z_WINO64: return "k_wino64_conv<" + pool;
+        case Kern::WINO42: case Kern::Z_WINO42: return "k_wino42_conv<" + pool;
+        case Kern::SPLIT: case Kern::SPLIT_PAIR: return "k_conv3x3_h16<" + mode + " false, false, true,";
+        case Kern::H16: return "k_conv3x3_h16<" + mode + (i == 10 ? " false," : "");   // upconv1[0] also has a ZOUT instance
+        case Kern::CONVT_T16: return "k_convt_t16<" + dims + ">";
+        case Kern::Z_SPLIT: return "k_conv3x3_h16<" + mode + " true, false, true,";
+        case Kern::Z_H16: return "k_conv3x3_h16<" + mode + " true,";
+        case Kern::TAIL_BANDS: case Kern::TAIL_TILES: return "k_conv_tail";
+        case Kern::TAIL_H: return "k_conv_tail_h<";
+        case Kern::TAIL_Z: return c.algo == CID_ALGO_SPLIT16 ? "k_conv_tail_z<" : "k_conv_tail";   // Winograd: the family prefix, as in the tracked profiles
+        case Kern::TAIL_ZH: return "k_conv_tail_zh<";
+    }
+    return "";
+}
+// ... formatted once for every configuration, so that cid_launch_kernel can hand out pointers that stay valid
+struct KernelNames {
+    std::string s[2][CID_ALGO_SPLIT16 + 1][3][NL];
+    KernelNames() {
+        for (int dt = 0; dt < 2; ++dt)
+            for (int algo = 0; algo <= CID_ALGO_SPLIT16; ++algo)
+                for (int tail = 0; tail < 3; ++tail)
+                    for (int i = 0; i < NL; ++i) s[dt][algo][tail][i] = kernel_name(Config{dt, algo, tail}, i);
+    }
+};
+const KernelNames kKernelNames;
 
 int fail(cid_handle_t h, int code, const std::string& msg) {
     if (h) h->err = msg;
@@ -352,114 +408,35 @@ void for_each_weight(const LayerDef& L, F f) {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-struct TileGrid { int tx, ty, total, per_xcd; };
-TileGrid tiles_for(int N, int Hc, int Wc) {
-    TileGrid g;
-    g.tx = cdiv(Wc, TILE_W); g.ty = cdiv(Hc, TILE_H);
-    g.total = N * g.tx * g.ty;
-    g.per_xcd = cdiv(g.total, 8);
-    return g;
-}
-
-template <int CIN, int COUT, int MODE>
-hipError_t launch_gemm(hipStream_t s, const float* blob, int layer, const float* in, int Hin, int Win, int in_ps,
-                       float* out, int out_ps, int out_coff, int Hc, int Wc, int Hs, int Ws, float* pool, int N) {
-    GemmConvArgs a;
-    a.in = in; a.w = blob + kBlob.w_off[layer]; a.bias = blob + kBlob.b_off[layer];
-    a.out = out; a.pool = pool;
-    a.N = N; a.Hin = Hin; a.Win = Win; a.in_ps = in_ps;
-    a.Hc = Hc; a.Wc = Wc; a.Hs = Hs; a.Ws = Ws; a.out_ps = out_ps; a.out_coff = out_coff;
-    const TileGrid g = tiles_for(N, Hc, Wc);
-    a.tiles_x = g.tx; a.tiles_y = g.ty; a.tiles_total = g.total; a.tiles_per_xcd = g.per_xcd;
-        a.rcp_x = tile_rcp(g.tx); a.rcp_xy = tile_rcp(g.tx * g.ty);
-    constexpr int NB = (MODE == 2 ? 4 * COUT : COUT) / NTILE;
-    hipLaunchKernelGGL((k_gemm_conv<CIN, COUT, MODE>), dim3(8 * g.per_xcd * NB), dim3(THREADS), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int CIN, int COUT, bool POOL, int TC>
-hipError_t launch_wino64_tc(hipStream_t s, const WinoArgs& base) {
-    WinoArgs a = base;
-    constexpr int TRW = 32 / TC;
-    a.tiles_x = cdiv(a.Wc, 2 * TC); a.tiles_y = cdiv(a.Hc, 2 * TRW);
-    a.tiles_total = a.N * a.tiles_x * a.tiles_y; a.tiles_per_xcd = cdiv(a.tiles_total, 8);
+// The tile grid of a launch over N images of Hc x Wc computed pixels in tw x th tiles: the fields the kernels' tile decode
+// reads.  The head and tail kernels then walk groups of tiles (tile_groups); the others deal tiles to the eight XCD groups.
+template <typename A>
+void set_tiles(A& a, int N, int Hc, int Wc, int tw, int th) {
+    a.tiles_x = cdiv(Wc, tw); a.tiles_y = cdiv(Hc, th); a.tiles_total = N * a.tiles_x * a.tiles_y;
     a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(a.tiles_x * a.tiles_y);
-    hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, TC>), dim3(8 * a.tiles_per_xcd * (COUT / WN2)), dim3(THREADS), 0, s, a);
-    return hipGetLastError();
+    if constexpr (std::is_same_v<A, HeadArgs> || std::is_same_v<A, TailArgs>) tile_groups(a);
+    else a.tiles_per_xcd = cdiv(a.tiles_total, 8);
 }
 
-// upconv1[0] with the channel contraction of upconv1[2] folded into its epilogue: z planes instead of the 64-channel tensor.
-template <int TC>
-hipError_t launch_wino64_z_tc(hipStream_t s, const WinoArgs& base) {
-    WinoArgs a = base;
-    constexpr int TRW = 32 / TC;
-    a.tiles_x = cdiv(a.Wc, 2 * TC); a.tiles_y = cdiv(a.Hc, 2 * TRW);
-    a.tiles_total = a.N * a.tiles_x * a.tiles_y; a.tiles_per_xcd = cdiv(a.tiles_total, 8);
-    a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(a.tiles_x * a.tiles_y);
-    hipLaunchKernelGGL((k_wino64_conv<128, 64, false, TC, 0, true>), dim3(8 * a.tiles_per_xcd), dim3(THREADS), 0, s, a);
-    return hipGetLastError();
-}
-int wino42_grid(WinoArgs& a, int nb);
-extern int g_half_wg_per_cu;
-int device_cus();
-template <int TC>
-hipError_t launch_wino42_z_tc(hipStream_t s, const WinoArgs& base, const float* blob, int tab) {
-    WinoArgs a = base;
-    constexpr int TRW = 16 / TC;
-    a.slot_tab = reinterpret_cast<const unsigned*>(blob + kBlob.tab42_off[tab]);
-    a.tiles_x = cdiv(a.Wc, 4 * TC); a.tiles_y = cdiv(a.Hc, 2 * TRW);
-    a.tiles_total = a.N * a.tiles_x * a.tiles_y; a.tiles_per_xcd = cdiv(a.tiles_total, 8);
-    a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(a.tiles_x * a.tiles_y);
-    const int grid = wino42_grid(a, 1);
-    hipLaunchKernelGGL((k_wino42_conv<128, 64, false, TC, 0, true>), dim3(grid), dim3(THREADS), 0, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_upconv1_0_z(int algo, hipStream_t s, const float* blob, const float* in, int Hc, int Wc, float* zout, int N) {
-    WinoArgs a;
-    a.in = in; a.u = blob + kBlob.u_off[10]; a.bias = blob + kBlob.b_off[10];
-    a.out = nullptr; a.pool = nullptr; a.zw = blob + kBlob.w_off[11]; a.zout = zout;
-    a.N = N; a.Hin = Hc; a.Win = Wc; a.in_ps = 128; a.Hc = Hc; a.Wc = Wc; a.Hs = Hc; a.Ws = Wc;
-    a.out_ps = 64; a.out_coff = 0;
-    a.tiles_x = a.tiles_y = a.tiles_total = a.tiles_per_xcd = 0;
-    a.rcp_x = a.rcp_xy = 0; a.walk = 0;
-    if (algo == CID_ALGO_SPLIT16) {   // k_conv3x3_h16<128, 64, 0, ZOUT, ., F32IO>: `out` = the 27 fp32 z planes, `pool` = upconv1[2]'s hi | lo fragments
-        GemmConvArgsH g;
-        g.in = reinterpret_cast<const _Float16*>(in); g.w = reinterpret_cast<const _Float16*>(blob + kBlob.s_off[10]); g.bias = blob + kBlob.b_off[10];
-        g.out = reinterpret_cast<_Float16*>(zout); g.pool = const_cast<_Float16*>(reinterpret_cast<const _Float16*>(blob + kBlob.hzs_off));
-        g.N = N; g.Hin = Hc; g.Win = Wc; g.in_ps = 128; g.Hc = Hc; g.Wc = Wc; g.Hs = Hc; g.Ws = Wc; g.out_ps = 64; g.out_coff = 0;
-        const TileGrid tg = tiles_for(N, Hc, Wc);
-        g.tiles_x = tg.tx; g.tiles_y = tg.ty; g.tiles_total = tg.total; g.tiles_per_xcd = tg.per_xcd;
-        g.rcp_x = tile_rcp(tg.tx); g.rcp_xy = tile_rcp(tg.tx * tg.ty); g.walk = 0;
-        hipLaunchKernelGGL((k_conv3x3_h16<128, 64, 0, true, false, true>), dim3(8 * tg.per_xcd), dim3(THREADS), 0, s, g);
-        return hipGetLastError();
-    }
-    if (algo == CID_ALGO_WINOGRAD42) {
-        a.u = blob + kBlob.u42_off[10];
-        if (Wc > 16) return launch_wino42_z_tc<8>(s, a, blob, 0);
-        return launch_wino42_z_tc<4>(s, a, blob, 1);
-    }
-    a.slot_tab = reinterpret_cast<const unsigned*>(blob + kBlob.tab_off[Wc > 32 ? 0 : 1]);
-    return Wc > 32 ? launch_wino64_z_tc<32>(s, a) : launch_wino64_z_tc<16>(s, a);
-}
-hipError_t launch_tail_z(hipStream_t s, const float* z, const float* bias, void* out, const Window& crop, int N, int H, int W, bool u8) {
-    TailZArgs a;
-    a.z = z; a.bias = bias; a.out = out; a.crop = crop; a.N = N; a.H = H; a.W = W;
-    a.blocks_per_image = cdiv(H * W, THREADS);
-    a.rcp_w = tile_rcp((unsigned)W); a.rcp_blocks = tile_rcp((unsigned)a.blocks_per_image);
-    if (u8) hipLaunchKernelGGL((k_conv_tail_z<true>), dim3(N * a.blocks_per_image), dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_tail_z<false>), dim3(N * a.blocks_per_image), dim3(THREADS), 0, s, a);
-    return hipGetLastError();
+// One GEMM-shaped layer's tensors, NHWC.  The arena regions are sized for fp32; the fp16-storage path keeps its half tensors
+// in the front half of the same regions, and the split-operand kernels read fp32 through GemmConvArgsH's half pointers.
+struct LayerIO {
+    const float* in; int Hin, Win, in_ps;   // input image, pixel stride in_ps
+    float* out; int out_ps, out_coff;       // output, pixel stride out_ps, from channel out_coff (a slice of a concat tensor)
+    int Hc, Wc;                             // pixels computed (a transposed convolution: input pixels)
+    int Hs, Ws;                             // pixels stored, the top-left crop of Hc x Wc (a skip tensor)
+    float* pool;                            // the 2x2-pooled output of a pooling layer, else null
+};
+template <typename A>
+void set_layer_io(A& a, int N, const LayerIO& io) {
+    a.in = reinterpret_cast<decltype(a.in)>(io.in); a.out = reinterpret_cast<decltype(a.out)>(io.out);
+    a.pool = reinterpret_cast<decltype(a.pool)>(io.pool);
+    a.N = N; a.Hin = io.Hin; a.Win = io.Win; a.in_ps = io.in_ps;
+    a.Hc = io.Hc; a.Wc = io.Wc; a.Hs = io.Hs; a.Ws = io.Ws; a.out_ps = io.out_ps; a.out_coff = io.out_coff;
 }
 
-hipError_t launch_tail_zh(hipStream_t s, const void* z, const float* bias, void* out, const Window& crop, int N, int H, int W, bool u8) {
-    TailZArgs a;
-    a.z = static_cast<const float*>(z); a.bias = bias; a.out = out; a.crop = crop; a.N = N; a.H = H; a.W = W;
-    a.blocks_per_image = cdiv(H * W, THREADS);
-    a.rcp_w = tile_rcp((unsigned)W); a.rcp_blocks = tile_rcp((unsigned)a.blocks_per_image);
-    if (u8) hipLaunchKernelGGL((k_conv_tail_zh<true>), dim3(N * a.blocks_per_image), dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_tail_zh<false>), dim3(N * a.blocks_per_image), dim3(THREADS), 0, s, a);
-    return hipGetLastError();
-}
+// What every launch of one forward shares.
+struct Ctx { hipStream_t s; const float* blob; int N; Config c; };
 
 // Grid of a k_wino42_conv launch over `tiles_per_xcd` tiles per XCD group and NB column blocks.  Small launches: one workgroup
 // per (tile, column block), a.walk = 0.  Once there are more items than the chip holds at a time — two workgroups per CU (LDS
@@ -511,175 +488,212 @@ int wino42_grid(WinoArgs& a, int nb) {
     return 8 * walkers;
 }
 
-template <int CIN, int COUT, bool POOL, int TC>
-hipError_t launch_wino42_tc(hipStream_t s, const WinoArgs& base, const float* blob, int tab) {
-    WinoArgs a = base;
-    constexpr int TRW = 16 / TC;
-    a.slot_tab = reinterpret_cast<const unsigned*>(blob + kBlob.tab42_off[tab]);
-    a.tiles_x = cdiv(a.Wc, 4 * TC); a.tiles_y = cdiv(a.Hc, 2 * TRW);
-    a.tiles_total = a.N * a.tiles_x * a.tiles_y; a.tiles_per_xcd = cdiv(a.tiles_total, 8);
-    a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(a.tiles_x * a.tiles_y);
-    const int grid = wino42_grid(a, COUT / WN2);
-    hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, TC>), dim3(grid), dim3(THREADS), 0, s, a);
+template <int CIN, int COUT, int MODE>
+hipError_t launch_gemm(const Ctx& x, int layer, const LayerIO& io) {
+    GemmConvArgs a;
+    set_layer_io(a, x.N, io);
+    a.w = x.blob + kBlob.w_off[layer]; a.bias = x.blob + kBlob.b_off[layer];
+    set_tiles(a, x.N, io.Hc, io.Wc, TILE_W, TILE_H);
+    constexpr int NB = (MODE == 2 ? 4 * COUT : COUT) / NTILE;
+    hipLaunchKernelGGL((k_gemm_conv<CIN, COUT, MODE>), dim3(8 * a.tiles_per_xcd * NB), dim3(THREADS), 0, x.s, a);
     return hipGetLastError();
 }
 
-// One 3x3 GEMM layer, by the handle's algorithm: MODE 0/1 of k_gemm_conv or Winograd.
-template <int CIN, int COUT, int MODE>
-hipError_t launch_conv3x3(int algo, hipStream_t s, const float* blob, int layer, const float* in, int Hin, int Win, int in_ps,
-                          float* out, int out_ps, int out_coff, int Hc, int Wc, int Hs, int Ws, float* pool, int N) {
-    if (algo == 0) return launch_gemm<CIN, COUT, MODE>(s, blob, layer, in, Hin, Win, in_ps, out, out_ps, out_coff, Hc, Wc, Hs, Ws, pool, N);
-    if (algo == CID_ALGO_SPLIT16) {
-        // split-operand convolution on the fp16 MFMA, fp32 tensors in and out (conv_kernels_f16.h, F32IO): one (8x32-pixel tile, 64-channel column block) per workgroup, two per CU
-        if (in_ps != CIN) return hipErrorInvalidValue;   // the kernel takes the pixel stride of its input as CIN (true of every layer of this network)
-        GemmConvArgsH a;
-        a.in = reinterpret_cast<const _Float16*>(in); a.w = reinterpret_cast<const _Float16*>(blob + kBlob.s_off[layer]); a.bias = blob + kBlob.b_off[layer];
-        a.out = reinterpret_cast<_Float16*>(out); a.pool = reinterpret_cast<_Float16*>(pool);
-        a.N = N; a.Hin = Hin; a.Win = Win; a.in_ps = in_ps; a.Hc = Hc; a.Wc = Wc; a.Hs = Hs; a.Ws = Ws; a.out_ps = out_ps; a.out_coff = out_coff;
-        const TileGrid g = tiles_for(N, Hc, Wc);
-        a.tiles_x = g.tx; a.tiles_y = g.ty; a.tiles_total = g.total; a.tiles_per_xcd = g.per_xcd;
-        a.rcp_x = tile_rcp(g.tx); a.rcp_xy = tile_rcp(g.tx * g.ty); a.walk = 0;
-        if constexpr (COUT >= 128) {   // two column blocks per workgroup from one staging of the input tile (conv_kernels_f16.h, PAIR)
-            static const int pair = env_wg_per_cu("CID_SPLIT_PAIR", 1, 1);   // measurement aid: 0 = one column block per workgroup (same box: the six launches +8 % slower, profiles/r04_ab_split16_pair.txt)
-            if (pair) {
-                hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, MODE, false, false, true, true>), dim3(8 * g.per_xcd * (COUT / NTILE / 2)), dim3(THREADS), 0, s, a);
-                return hipGetLastError();
-            }
-        }
-        hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, MODE, false, false, true>), dim3(8 * g.per_xcd * (COUT / NTILE)), dim3(THREADS), 0, s, a);
-        return hipGetLastError();
-    }
+// up1 on the fp32 path: streaming form, persistent workgroups (two per CU) over runs of TP input pixels
+template <int CIN, int COUT>
+hipError_t launch_convt_s32(const Ctx& x, int layer, const LayerIO& io) {
+    using CG = ConvTGeom32<CIN, COUT>;
+    GemmConvArgs a;
+    set_layer_io(a, x.N, io);
+    a.w = x.blob + kBlob.w_off[layer]; a.bias = x.blob + kBlob.b_off[layer];
+    a.tiles_x = (io.Hin * io.Win + CG::TP - 1) / CG::TP; a.tiles_y = 1; a.tiles_total = x.N * a.tiles_x; a.tiles_per_xcd = 0;
+    a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(io.Win);
+    const int wgs = device_cus() * 2;
+    hipLaunchKernelGGL((k_convt_s32<CIN, COUT>), dim3(a.tiles_total < wgs ? a.tiles_total : wgs), dim3(THREADS), 0, x.s, a);
+    return hipGetLastError();
+}
+
+// The Winograd kernels' arguments.  ZOUT (upconv1[0] only): the channel contraction of upconv1[2] folded into the epilogue,
+// z planes into io.out instead of the 64-channel tensor.
+template <bool ZOUT>
+WinoArgs wino_args(const Ctx& x, int layer, const LayerIO& io, size_t u_off) {
     WinoArgs a;
-    a.in = in; a.u = blob + kBlob.u_off[layer]; a.bias = blob + kBlob.b_off[layer]; a.slot_tab = nullptr;
-    a.out = out; a.pool = pool; a.zw = nullptr; a.zout = nullptr;
-    a.N = N; a.Hin = Hin; a.Win = Win; a.in_ps = in_ps; a.Hc = Hc; a.Wc = Wc; a.Hs = Hs; a.Ws = Ws;
-    a.out_ps = out_ps; a.out_coff = out_coff;
-    a.tiles_x = a.tiles_y = a.tiles_total = a.tiles_per_xcd = 0;
-    a.rcp_x = a.rcp_xy = 0; a.walk = 0;
-    if (algo == CID_ALGO_WINOGRAD42) {   // 16 tiles of 4x2 pixels per workgroup: 8 x 2 (32x4 pixels), or 4 x 4 (16x8) for rows of 16 pixels or fewer.
-        // 16 x 1 (64x2 pixels) fetches 4 input rows for 2 of output: same-box 24.4k images/s against 24.8k (8 x 2) and 24.7k (4 x 4 everywhere)
-        a.u = blob + kBlob.u42_off[layer];
-        if (Wc > 16) return launch_wino42_tc<CIN, COUT, MODE == 1, 8>(s, a, blob, 0);
-        return launch_wino42_tc<CIN, COUT, MODE == 1, 4>(s, a, blob, 1);
-    }
-    // 32 tile-columns (64 pixels) per workgroup when the rows are wide enough, else 16 x 2 tile-rows
-    a.slot_tab = reinterpret_cast<const unsigned*>(blob + kBlob.tab_off[Wc > 32 ? 0 : 1]);
-    return Wc > 32 ? launch_wino64_tc<CIN, COUT, MODE == 1, 32>(s, a) : launch_wino64_tc<CIN, COUT, MODE == 1, 16>(s, a);
+    set_layer_io(a, x.N, io);
+    a.u = x.blob + u_off; a.bias = x.blob + kBlob.b_off[layer];
+    a.zw = ZOUT ? x.blob + kBlob.w_off[11] : nullptr; a.zout = ZOUT ? io.out : nullptr;
+    if (ZOUT) a.out = nullptr;
+    a.walk = 0;
+    return a;
 }
 
-template <int CIN, int COUT, int MODE, bool ZOUT = false>
-hipError_t launch_gemm_h(hipStream_t s, const float* blob, int layer, const void* in, int Hin, int Win, int in_ps,
-                         void* out, int out_ps, int out_coff, int Hc, int Wc, int Hs, int Ws, void* pool, int N);
-
-// One GEMM-shaped layer under the handle's storage type and algorithm.  The arena regions are sized for fp32; the
-// fp16-storage path keeps its half tensors in the front half of the same regions.
-template <int CIN, int COUT, int MODE>
-hipError_t launch_layer(cid_handle_t h, hipStream_t s, const float* blob, int layer, float* in, int Hin, int Win, int in_ps,
-                        float* out, int out_ps, int out_coff, int Hc, int Wc, int Hs, int Ws, float* pool, int N) {
-    if (h->dtype == CID_DTYPE_F16)
-        return launch_gemm_h<CIN, COUT, MODE>(s, blob, layer, in, Hin, Win, in_ps, out, out_ps, out_coff, Hc, Wc, Hs, Ws, pool, N);
-    if constexpr (MODE == 2) {
-        static const int split_t = env_wg_per_cu("CID_SPLIT_CONVT", 1, 1);   // measurement aid: 0 = the transposed convolutions stay on the fp32-MFMA kernels under conv_algo "split16"
-        if (h->algo == CID_ALGO_SPLIT16 && split_t) {
-            // ConvTranspose2d(k=2, s=2) in the split-operand form: (tap, 64 channels) column blocks, two per workgroup, over 8x32-pixel tiles of the INPUT
-            if (in_ps != CIN) return hipErrorInvalidValue;
-            GemmConvArgsH a;
-            a.in = reinterpret_cast<const _Float16*>(in); a.w = reinterpret_cast<const _Float16*>(blob + kBlob.s_off[layer]); a.bias = blob + kBlob.b_off[layer];
-            a.out = reinterpret_cast<_Float16*>(out); a.pool = nullptr;
-            a.N = N; a.Hin = Hin; a.Win = Win; a.in_ps = in_ps; a.Hc = Hc; a.Wc = Wc; a.Hs = Hs; a.Ws = Ws; a.out_ps = out_ps; a.out_coff = out_coff;
-            const TileGrid g = tiles_for(N, Hc, Wc);
-            a.tiles_x = g.tx; a.tiles_y = g.ty; a.tiles_total = g.total; a.tiles_per_xcd = g.per_xcd;
-            a.rcp_x = tile_rcp(g.tx); a.rcp_xy = tile_rcp(g.tx * g.ty); a.walk = 0;
-            hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, 2, false, false, true, true>), dim3(8 * g.per_xcd * (4 * COUT / NTILE / 2)), dim3(THREADS), 0, s, a);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (MODE == 2 && CIN == 128) {   // up1: streaming form, persistent workgroups (two per CU) over runs of TP input pixels
-        using CG = ConvTGeom32<CIN, COUT>;
-        GemmConvArgs a;
-        a.in = in; a.w = blob + kBlob.w_off[layer]; a.bias = blob + kBlob.b_off[layer];
-        a.out = out; a.pool = nullptr;
-        a.N = N; a.Hin = Hin; a.Win = Win; a.in_ps = in_ps;
-        a.Hc = Hc; a.Wc = Wc; a.Hs = Hs; a.Ws = Ws; a.out_ps = out_ps; a.out_coff = out_coff;
-        a.tiles_x = (Hin * Win + CG::TP - 1) / CG::TP; a.tiles_y = 1; a.tiles_total = N * a.tiles_x; a.tiles_per_xcd = 0;
-        a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(Win);
-        const int wgs = device_cus() * 2;
-        hipLaunchKernelGGL((k_convt_s32<CIN, COUT>), dim3(a.tiles_total < wgs ? a.tiles_total : wgs), dim3(THREADS), 0, s, a);
-        return hipGetLastError();
-    } else if constexpr (MODE == 2)
-        return launch_gemm<CIN, COUT, MODE>(s, blob, layer, in, Hin, Win, in_ps, out, out_ps, out_coff, Hc, Wc, Hs, Ws, pool, N);
-    else
-        return launch_conv3x3<CIN, COUT, MODE>(h->algo, s, blob, layer, in, Hin, Win, in_ps, out, out_ps, out_coff, Hc, Wc, Hs, Ws, pool, N);
-}
-
-hipError_t launch_head(hipStream_t s, const HeadArgs& a, int grid, bool u8, bool f16) {
-    if (u8 && f16) hipLaunchKernelGGL((k_conv_head_h16<true>), dim3(grid), dim3(THREADS), 0, s, a);
-    else if (u8) hipLaunchKernelGGL((k_conv_head<true>), dim3(grid), dim3(THREADS), 0, s, a);
-    else if (f16) hipLaunchKernelGGL((k_conv_head_h16<false>), dim3(grid), dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_head<false>), dim3(grid), dim3(THREADS), 0, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_tail(hipStream_t s, const TailArgs& a, int grid, bool u8, bool f16) {
-    if (u8 && f16) hipLaunchKernelGGL((k_conv_tail_h<true>), dim3(grid), dim3(THREADS), 0, s, a);
-    else if (u8) hipLaunchKernelGGL((k_conv_tail<true, false>), dim3(grid), dim3(THREADS), 0, s, a);
-    else if (f16) hipLaunchKernelGGL((k_conv_tail_h<false>), dim3(grid), dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_tail<false, false>), dim3(grid), dim3(THREADS), 0, s, a);
+// 32 tile-columns (64 pixels) per workgroup when the rows are wide enough, else 16 x 2 tile-rows
+template <int CIN, int COUT, bool POOL, bool ZOUT>
+hipError_t launch_wino64(const Ctx& x, int layer, const LayerIO& io) {
+    WinoArgs a = wino_args<ZOUT>(x, layer, io, kBlob.u_off[layer]);
+    const bool wide = io.Wc > 32;
+    a.slot_tab = reinterpret_cast<const unsigned*>(x.blob + kBlob.tab_off[wide ? 0 : 1]);
+    set_tiles(a, x.N, io.Hc, io.Wc, wide ? 64 : 32, wide ? 2 : 4);   // TC tile-columns of 2x2 pixels, 32 / TC tile-rows
+    const dim3 grid(8 * a.tiles_per_xcd * (COUT / WN2));
+    if (wide) hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, 32, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
+    else hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, 16, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_tail2(hipStream_t s, const Tail2Args& a, bool u8) {
-    if (u8) hipLaunchKernelGGL((k_conv_tail2<true>), dim3(a.groups_total), dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_tail2<false>), dim3(a.groups_total), dim3(THREADS), 0, s, a);
+// 16 tiles of 4x2 pixels per workgroup: 8 x 2 (32x4 pixels), or 4 x 4 (16x8) for rows of 16 pixels or fewer.
+// 16 x 1 (64x2 pixels) fetches 4 input rows for 2 of output: same-box 24.4k images/s against 24.8k (8 x 2) and 24.7k (4 x 4 everywhere)
+template <int CIN, int COUT, bool POOL, bool ZOUT>
+hipError_t launch_wino42(const Ctx& x, int layer, const LayerIO& io) {
+    WinoArgs a = wino_args<ZOUT>(x, layer, io, kBlob.u42_off[layer]);
+    const bool wide = io.Wc > 16;
+    a.slot_tab = reinterpret_cast<const unsigned*>(x.blob + kBlob.tab42_off[wide ? 0 : 1]);
+    set_tiles(a, x.N, io.Hc, io.Wc, wide ? 32 : 16, wide ? 4 : 8);   // TC tile-columns of 4x2 pixels, 16 / TC tile-rows
+    const dim3 grid(wino42_grid(a, COUT / WN2));
+    if (wide) hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, 8, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
+    else hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, 4, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
     return hipGetLastError();
 }
 
-template <int CIN, int COUT, int MODE, bool ZOUT>
-hipError_t launch_gemm_h(hipStream_t s, const float* blob, int layer, const void* in, int Hin, int Win, int in_ps,
-                         void* out, int out_ps, int out_coff, int Hc, int Wc, int Hs, int Ws, void* pool, int N) {
+// conv_algo "split16": split-operand convolution on the fp16 MFMA, fp32 tensors in and out (conv_kernels_f16.h, F32IO): one
+// (8x32-pixel tile, 64-channel column block) per workgroup, or two column blocks from one staging of the input tile (PAIR).
+// A transposed convolution's column blocks are (tap, 64 channels) over tiles of its INPUT.  ZOUT: `out` = the 27 fp32 z
+// planes, `pool` = upconv1[2]'s hi | lo fragments.
+template <int CIN, int COUT, int MODE, bool ZOUT, bool PAIR>
+hipError_t launch_split16(const Ctx& x, int layer, const LayerIO& io) {
+    if (io.in_ps != CIN) return hipErrorInvalidValue;   // the kernel takes the pixel stride of its input as CIN (true of every layer of this network)
     GemmConvArgsH a;
-    a.in = static_cast<const _Float16*>(in); a.w = reinterpret_cast<const _Float16*>(blob + kBlob.h_off[layer]);
-    a.bias = blob + kBlob.b_off[layer];
-    a.out = static_cast<_Float16*>(out); a.pool = static_cast<_Float16*>(pool);
-    if (ZOUT) a.pool = const_cast<_Float16*>(reinterpret_cast<const _Float16*>(blob + kBlob.hz_off));   // ZOUT: `out` = the z planes, `pool` = the last layer's weights (read only)
-    a.N = N; a.Hin = Hin; a.Win = Win; a.in_ps = in_ps;
-    a.Hc = Hc; a.Wc = Wc; a.Hs = Hs; a.Ws = Ws; a.out_ps = out_ps; a.out_coff = out_coff;
-    const TileGrid g = tiles_for(N, Hc, Wc);
-    a.tiles_x = g.tx; a.tiles_y = g.ty; a.tiles_total = g.total; a.tiles_per_xcd = g.per_xcd;
-        a.rcp_x = tile_rcp(g.tx); a.rcp_xy = tile_rcp(g.tx * g.ty);
+    set_layer_io(a, x.N, io);
+    a.w = reinterpret_cast<const _Float16*>(x.blob + kBlob.s_off[layer]); a.bias = x.blob + kBlob.b_off[layer];
+    if (ZOUT) a.pool = const_cast<_Float16*>(reinterpret_cast<const _Float16*>(x.blob + kBlob.hzs_off));
+    set_tiles(a, x.N, io.Hc, io.Wc, TILE_W, TILE_H);
+    a.walk = 0;
+    constexpr int NB = (MODE == 2 ? 4 * COUT : COUT) / NTILE / (PAIR ? 2 : 1);
+    hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, MODE, ZOUT, false, true, PAIR>), dim3(8 * a.tiles_per_xcd * NB), dim3(THREADS), 0, x.s, a);
+    return hipGetLastError();
+}
+
+// The fp16-storage path: k_conv3x3_h16 (MODE 0/1; ZOUT: `out` = the z planes, `pool` = the last layer's weights, read only)
+// or k_convt_t16 (MODE 2).
+template <int CIN, int COUT, int MODE, bool ZOUT>
+hipError_t launch_gemm_h(const Ctx& x, int layer, const LayerIO& io) {
+    GemmConvArgsH a;
+    set_layer_io(a, x.N, io);
+    a.w = reinterpret_cast<const _Float16*>(x.blob + kBlob.h_off[layer]); a.bias = x.blob + kBlob.b_off[layer];
+    if (ZOUT) a.pool = const_cast<_Float16*>(reinterpret_cast<const _Float16*>(x.blob + kBlob.hz_off));
+    set_tiles(a, x.N, io.Hc, io.Wc, TILE_W, TILE_H);
     constexpr int NB = (MODE == 2 ? 4 * COUT : COUT) / NTILE;
     a.walk = 0;
     if constexpr (MODE == 2 && !ZOUT) {
         // streaming form: persistent workgroups (two waves per SIMD: 2 per CU of four waves, 1 of eight) over runs of TP input pixels
         using CG = ConvTGeom<CIN, COUT>;
-        a.tiles_x = (Hin * Win + CG::TP - 1) / CG::TP; a.tiles_total = N * a.tiles_x;
-        a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(Win);
+        a.tiles_x = (io.Hin * io.Win + CG::TP - 1) / CG::TP; a.tiles_total = x.N * a.tiles_x;
+        a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(io.Win);
         const int wgs = device_cus() * 2 / CG::CB;
-        hipLaunchKernelGGL((k_convt_t16<CIN, COUT>), dim3(a.tiles_total < wgs ? a.tiles_total : wgs), dim3(64 * CG::NW), 0, s, a);
+        hipLaunchKernelGGL((k_convt_t16<CIN, COUT>), dim3(a.tiles_total < wgs ? a.tiles_total : wgs), dim3(64 * CG::NW), 0, x.s, a);
     } else if constexpr (MODE != 2) {
-        if (in_ps != CIN) return hipErrorInvalidValue;   // k_conv3x3_h16 takes the pixel stride of its input as CIN (true of every layer of this network)
+        if (io.in_ps != CIN) return hipErrorInvalidValue;   // k_conv3x3_h16 takes the pixel stride of its input as CIN (true of every layer of this network)
         // walking workgroups (conv_kernels_f16.h): three per CU (47 KiB of LDS, <= 168 VGPRs) once there are more items than that —
         // on the layers with CIN <= 128, where an item is short beside its prologue (same-box: down1.2 -15 %, down2.0 -11 %, the
         // CIN = 128 layers -0.3...-1.5 %).  With CIN = 256 walking LOSES 3-5 %: a tile's NB column blocks then run one after the
         // other in one workgroup and the 174 KB halo tile of the second pass has left the XCD's L2 (96 walkers x 174 KB), while
         // sibling workgroups dispatched back to back share one fetch (profiles/r03_ab_f16_walk.txt).
-        int grid = 8 * g.per_xcd * NB;
+        int grid = 8 * a.tiles_per_xcd * NB;
         const int walkers = g_half_wg_per_cu * device_cus() / 8;
-        if (CIN <= 128 && g_half_wg_per_cu > 0 && walkers >= 1 && grid > 8 * walkers && g.per_xcd >= walkers) { a.walk = walkers; grid = 8 * walkers; }   // >= one tile per walker, as in wino42_grid
+        if (CIN <= 128 && g_half_wg_per_cu > 0 && walkers >= 1 && grid > 8 * walkers && a.tiles_per_xcd >= walkers) { a.walk = walkers; grid = 8 * walkers; }   // >= one tile per walker, as in wino42_grid
         // the pooling launches (MODE 1) never walk: their walking variants were the last kernels of the library with spilled registers (4 VGPRs, 20 B of
         // scratch per lane) and walking is slower than one item per workgroup on them by the widest margin (-7...-10 % on down1.2)
         if constexpr (MODE == 0) {
-            if (a.walk) { hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, MODE, ZOUT, true>), dim3(grid), dim3(THREADS), 0, s, a); return hipGetLastError(); }
+            if (a.walk) { hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, MODE, ZOUT, true>), dim3(grid), dim3(THREADS), 0, x.s, a); return hipGetLastError(); }
         }
-        a.walk = 0; grid = 8 * g.per_xcd * NB;
-        hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, MODE, ZOUT, false>), dim3(grid), dim3(THREADS), 0, s, a);
+        a.walk = 0; grid = 8 * a.tiles_per_xcd * NB;
+        hipLaunchKernelGGL((k_conv3x3_h16<CIN, COUT, MODE, ZOUT, false>), dim3(grid), dim3(THREADS), 0, x.s, a);
     }
+    return hipGetLastError();
+}
+
+// One GEMM-shaped layer (launches 1..10) with the kernel select_kernel picks for it.  Only the instantiations a layer can
+// reach are compiled: upconv1[0] is the one layer with a fused (ZOUT) form, up1 the one on k_convt_s32.
+template <int LAYER>
+hipError_t launch_layer(const Ctx& x, const LayerIO& io) {
+    constexpr int CIN = kLayers[LAYER].cin, COUT = kLayers[LAYER].cout, MODE = mode_of(kLayers[LAYER]);
+    constexpr bool CONV = MODE != 2, Z = LAYER == 10, S32 = MODE == 2 && CIN == 128;
+    switch (select_kernel(x.c, LAYER)) {
+        case Kern::GEMM: if constexpr (!S32) return launch_gemm<CIN, COUT, MODE>(x, LAYER, io); break;
+        case Kern::CONVT_S32: if constexpr (S32) return launch_convt_s32<CIN, COUT>(x, LAYER, io); break;
+        case Kern::WINO64: if constexpr (CONV) return launch_wino64<CIN, COUT, MODE == 1, false>(x, LAYER, io); break;
+        case Kern::WINO42: if constexpr (CONV) return launch_wino42<CIN, COUT, MODE == 1, false>(x, LAYER, io); break;
+        case Kern::SPLIT: if constexpr (CONV && COUT < 128) return launch_split16<CIN, COUT, MODE, false, false>(x, LAYER, io); break;
+        case Kern::SPLIT_PAIR: if constexpr (!CONV || COUT >= 128) return launch_split16<CIN, COUT, MODE, false, true>(x, LAYER, io); break;
+        case Kern::H16: if constexpr (CONV) return launch_gemm_h<CIN, COUT, MODE, false>(x, LAYER, io); break;
+        case Kern::CONVT_T16: if constexpr (!CONV) return launch_gemm_h<CIN, COUT, MODE, false>(x, LAYER, io); break;
+        case Kern::Z_WINO64: if constexpr (Z) return launch_wino64<CIN, COUT, false, true>(x, LAYER, io); break;
+        case Kern::Z_WINO42: if constexpr (Z) return launch_wino42<CIN, COUT, false, true>(x, LAYER, io); break;
+        case Kern::Z_SPLIT: if constexpr (Z) return launch_split16<CIN, COUT, MODE, true, false>(x, LAYER, io); break;
+        case Kern::Z_H16: if constexpr (Z) return launch_gemm_h<CIN, COUT, MODE, true>(x, LAYER, io); break;
+        default: break;
+    }
+    return hipErrorInvalidValue;   // not a kernel of this layer
+}
+
+// down1[0]: Conv 3->64 + ReLU, the caller's image placed at `src` inside the H x W network input -> NHWC t0
+hipError_t launch_head(const Ctx& x, const void* in, bool u8, const Window& src, float* out, int H, int W) {
+    const bool f16 = select_kernel(x.c, 0) == Kern::HEAD_H16;
+    HeadArgs a;
+    a.in = in; a.w = x.blob + (f16 ? kBlob.h_off[0] : kBlob.w_off[0]); a.bias = x.blob + kBlob.b_off[0]; a.out = out;
+    a.N = x.N; a.H = H; a.W = W; a.src = src;
+    set_tiles(a, x.N, H, W, TILE_W, TILE_H);
+    const dim3 grid(8 * a.groups_per_xcd);
+    if (u8 && f16) hipLaunchKernelGGL((k_conv_head_h16<true>), grid, dim3(THREADS), 0, x.s, a);
+    else if (u8) hipLaunchKernelGGL((k_conv_head<true>), grid, dim3(THREADS), 0, x.s, a);
+    else if (f16) hipLaunchKernelGGL((k_conv_head_h16<false>), grid, dim3(THREADS), 0, x.s, a);
+    else hipLaunchKernelGGL((k_conv_head<false>), grid, dim3(THREADS), 0, x.s, a);
+    return hipGetLastError();
+}
+
+// upconv1[2] + tanh from the t4 region (H x W) -> the `crop` window of the caller's tensor: the last layer itself on upconv1[0]'s
+// 64 channels, or the nine-tap shifted sum + bias + tanh over the z planes a fused upconv1[0] left there.
+hipError_t launch_tail(const Ctx& x, const float* t4, void* out, bool u8, const Window& crop, int H, int W) {
+    const Kern k = select_kernel(x.c, 11);
+    const float* bias = x.blob + kBlob.b_off[11];
+    if (k == Kern::TAIL_Z || k == Kern::TAIL_ZH) {   // one thread per pixel
+        TailZArgs a;
+        a.z = t4; a.bias = bias; a.out = out; a.crop = crop; a.N = x.N; a.H = H; a.W = W;
+        a.blocks_per_image = cdiv(H * W, THREADS);
+        a.rcp_w = tile_rcp((unsigned)W); a.rcp_blocks = tile_rcp((unsigned)a.blocks_per_image);
+        const dim3 grid(x.N * a.blocks_per_image);
+        if (k == Kern::TAIL_ZH && u8) hipLaunchKernelGGL((k_conv_tail_zh<true>), grid, dim3(THREADS), 0, x.s, a);
+        else if (k == Kern::TAIL_ZH) hipLaunchKernelGGL((k_conv_tail_zh<false>), grid, dim3(THREADS), 0, x.s, a);
+        else if (u8) hipLaunchKernelGGL((k_conv_tail_z<true>), grid, dim3(THREADS), 0, x.s, a);
+        else hipLaunchKernelGGL((k_conv_tail_z<false>), grid, dim3(THREADS), 0, x.s, a);
+        return hipGetLastError();
+    }
+    if (k == Kern::TAIL_BANDS && W <= T2_MAXW) {   // row-band kernel: z once per pixel
+        Tail2Args a;
+        a.in = t4; a.w = x.blob + kBlob.w_off[11]; a.bias = bias; a.out = out; a.crop = crop;
+        a.N = x.N; a.H = H; a.W = W;
+        tail2_plan(a);
+        if (u8) hipLaunchKernelGGL((k_conv_tail2<true>), dim3(a.groups_total), dim3(THREADS), 0, x.s, a);
+        else hipLaunchKernelGGL((k_conv_tail2<false>), dim3(a.groups_total), dim3(THREADS), 0, x.s, a);
+        return hipGetLastError();
+    }
+    // 8x32 tiles with halo: TAIL_TILES, TAIL_BANDS on images wider than T2_MAXW, and the fp16-storage path (TAIL_H)
+    const bool f16 = k == Kern::TAIL_H;
+    TailArgs a;
+    a.in = t4; a.w = x.blob + (f16 ? kBlob.h_off[11] : kBlob.w_off[11]); a.bias = bias; a.out = out; a.crop = crop;
+    a.N = x.N; a.H = H; a.W = W;
+    set_tiles(a, x.N, H, W, TILE_W, TILE_H);
+    const dim3 grid(8 * a.groups_per_xcd);
+    if (u8 && f16) hipLaunchKernelGGL((k_conv_tail_h<true>), grid, dim3(THREADS), 0, x.s, a);
+    else if (u8) hipLaunchKernelGGL((k_conv_tail<true, false>), grid, dim3(THREADS), 0, x.s, a);
+    else if (f16) hipLaunchKernelGGL((k_conv_tail_h<false>), grid, dim3(THREADS), 0, x.s, a);
+    else hipLaunchKernelGGL((k_conv_tail<false, false>), grid, dim3(THREADS), 0, x.s, a);
     return hipGetLastError();
 }
 
 // (H, W) = the network input.  `src` places the caller's image inside it (the band around it is uint8 0 = -1.0 normalised), `crop`
 // is the window of the network output the caller's tensor receives; null = identity (no padding, whole output).
+// `ev`: NL + 1 events to record around the launches; null = the next armed set of cid_timing_begin, if there is one.
 int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, void* ws, size_t ws_bytes,
-                hipStream_t s, hipEvent_t* ev /* NL+1 events or null */, const Window* src_win = nullptr, const Window* crop_win = nullptr) {
+                hipStream_t s, hipEvent_t* ev = nullptr, const Window* src_win = nullptr, const Window* crop_win = nullptr) {
     if (!h) return CID_ERR_INVALID;
     if (!in || !out || !ws) return fail(h, CID_ERR_INVALID, "cid_forward: null pointer");
     if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_forward: no device weights attached (call cid_upload_weights or cid_attach_weights)");
@@ -695,10 +709,12 @@ int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_f
         return fail(h, CID_ERR_INVALID, "cid_forward: unknown tensor format");
     if (((uintptr_t)ws & 255) || ((uintptr_t)h->dev_blob & 255) || (in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)))
         return fail(h, CID_ERR_WORKSPACE, "cid_forward: workspace/weights must be 256-byte aligned, fp32 input 4-byte aligned");
+    const bool armed = !ev && h->tev_used < h->tev_forwards;
+    if (armed) ev = h->tev.data() + (size_t)h->tev_used * (NL + 1);
     float* base = static_cast<float*>(ws);
     float* B[NBUF];
     for (int b = 0; b < NBUF; ++b) B[b] = base + p.off[b];
-    const float* blob = h->dev_blob;
+    const Ctx x{s, h->dev_blob, N, config_of(h)};
     hipError_t e = hipSuccess;
     int li = 0;
 #define STEP(call)                                                                         \
@@ -711,67 +727,41 @@ int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_f
         ++li;                                                                              \
     } while (0)
 
-    {   // down1[0]: Conv 3->64 + ReLU, NCHW in -> NHWC t0            app.py:43-44
-        HeadArgs a;
-        a.in = in; a.w = blob + (h->dtype == CID_DTYPE_F16 ? kBlob.h_off[0] : kBlob.w_off[0]); a.bias = blob + kBlob.b_off[0]; a.out = B[T0];
-        a.N = N; a.H = H; a.W = W;
-        a.src = src_win ? *src_win : Window{0, 0, H, W};
-        const TileGrid g = tiles_for(N, H, W);
-        a.tiles_x = g.tx; a.tiles_y = g.ty; a.tiles_total = g.total;
-        tile_groups(a);
-        a.rcp_x = tile_rcp(g.tx); a.rcp_xy = tile_rcp(g.tx * g.ty);
-        STEP(launch_head(s, a, 8 * a.groups_per_xcd, in_fmt == CID_FMT_U8_NHWC, h->dtype == CID_DTYPE_F16));
-    }
+    // down1[0]: Conv 3->64 + ReLU, NCHW in -> NHWC t0                                    app.py:43-44
+    STEP(launch_head(x, in, in_fmt == CID_FMT_U8_NHWC, src_win ? *src_win : Window{0, 0, H, W}, B[T0], H, W));
     // down1[2] + ReLU -> e1 into cat1[:, 64:128] (cropped to Hu1 x Wu1), pool1 -> p1     app.py:45-48,97-100
-    STEP((launch_layer<64, 64, 1>(h, s, blob, 1, B[T0], H, W, 64, B[CAT1], 128, 64, 2 * d.H1, 2 * d.W1, d.Hu1, d.Wu1, B[P1], N)));
+    STEP(launch_layer<1>(x, {.in = B[T0], .Hin = H, .Win = W, .in_ps = 64, .out = B[CAT1], .out_ps = 128, .out_coff = 64,
+                             .Hc = 2 * d.H1, .Wc = 2 * d.W1, .Hs = d.Hu1, .Ws = d.Wu1, .pool = B[P1]}));
     // down2[0] + ReLU                                                                    app.py:51-52
-    STEP((launch_layer<64, 128, 0>(h, s, blob, 2, B[P1], d.H1, d.W1, 64, B[T1], 128, 0, d.H1, d.W1, d.H1, d.W1, nullptr, N)));
+    STEP(launch_layer<2>(x, {.in = B[P1], .Hin = d.H1, .Win = d.W1, .in_ps = 64, .out = B[T1], .out_ps = 128, .out_coff = 0,
+                             .Hc = d.H1, .Wc = d.W1, .Hs = d.H1, .Ws = d.W1, .pool = nullptr}));
     // down2[2] + ReLU -> e2 into cat2[:, 128:256] (cropped), pool2 -> p2                 app.py:53-56,90-93
-    STEP((launch_layer<128, 128, 1>(h, s, blob, 3, B[T1], d.H1, d.W1, 128, B[CAT2], 256, 128, d.Hu2, d.Wu2, d.Hu2, d.Wu2, B[P2], N)));
+    STEP(launch_layer<3>(x, {.in = B[T1], .Hin = d.H1, .Win = d.W1, .in_ps = 128, .out = B[CAT2], .out_ps = 256, .out_coff = 128,
+                             .Hc = d.Hu2, .Wc = d.Wu2, .Hs = d.Hu2, .Ws = d.Wu2, .pool = B[P2]}));
     // bottleneck                                                                         app.py:59-62
-    STEP((launch_layer<128, 256, 0>(h, s, blob, 4, B[P2], d.H2, d.W2, 128, B[T2], 256, 0, d.H2, d.W2, d.H2, d.W2, nullptr, N)));
-    STEP((launch_layer<256, 256, 0>(h, s, blob, 5, B[T2], d.H2, d.W2, 256, B[BT], 256, 0, d.H2, d.W2, d.H2, d.W2, nullptr, N)));
+    STEP(launch_layer<4>(x, {.in = B[P2], .Hin = d.H2, .Win = d.W2, .in_ps = 128, .out = B[T2], .out_ps = 256, .out_coff = 0,
+                             .Hc = d.H2, .Wc = d.W2, .Hs = d.H2, .Ws = d.W2, .pool = nullptr}));
+    STEP(launch_layer<5>(x, {.in = B[T2], .Hin = d.H2, .Win = d.W2, .in_ps = 256, .out = B[BT], .out_ps = 256, .out_coff = 0,
+                             .Hc = d.H2, .Wc = d.W2, .Hs = d.H2, .Ws = d.W2, .pool = nullptr}));
     // up2: ConvT 256->128 -> cat2[:, 0:128]                                              app.py:65,89
-    STEP((launch_layer<256, 128, 2>(h, s, blob, 6, B[BT], d.H2, d.W2, 256, B[CAT2], 256, 0, d.H2, d.W2, d.H2, d.W2, nullptr, N)));
+    STEP(launch_layer<6>(x, {.in = B[BT], .Hin = d.H2, .Win = d.W2, .in_ps = 256, .out = B[CAT2], .out_ps = 256, .out_coff = 0,
+                             .Hc = d.H2, .Wc = d.W2, .Hs = d.H2, .Ws = d.W2, .pool = nullptr}));
     // upconv2                                                                            app.py:67-70
-    STEP((launch_layer<256, 128, 0>(h, s, blob, 7, B[CAT2], d.Hu2, d.Wu2, 256, B[T3], 128, 0, d.Hu2, d.Wu2, d.Hu2, d.Wu2, nullptr, N)));
-    STEP((launch_layer<128, 128, 0>(h, s, blob, 8, B[T3], d.Hu2, d.Wu2, 128, B[D2], 128, 0, d.Hu2, d.Wu2, d.Hu2, d.Wu2, nullptr, N)));
+    STEP(launch_layer<7>(x, {.in = B[CAT2], .Hin = d.Hu2, .Win = d.Wu2, .in_ps = 256, .out = B[T3], .out_ps = 128, .out_coff = 0,
+                             .Hc = d.Hu2, .Wc = d.Wu2, .Hs = d.Hu2, .Ws = d.Wu2, .pool = nullptr}));
+    STEP(launch_layer<8>(x, {.in = B[T3], .Hin = d.Hu2, .Win = d.Wu2, .in_ps = 128, .out = B[D2], .out_ps = 128, .out_coff = 0,
+                             .Hc = d.Hu2, .Wc = d.Wu2, .Hs = d.Hu2, .Ws = d.Wu2, .pool = nullptr}));
     // up1: ConvT 128->64 -> cat1[:, 0:64]                                                app.py:73,96
-    STEP((launch_layer<128, 64, 2>(h, s, blob, 9, B[D2], d.Hu2, d.Wu2, 128, B[CAT1], 128, 0, d.Hu2, d.Wu2, d.Hu2, d.Wu2, nullptr, N)));
-    const bool fused_tail = fused_tail_active(h);
-    const Window crop = crop_win ? *crop_win : Window{0, 0, d.Hu1, d.Wu1};
-    if (fused_tail && h->dtype == CID_DTYPE_F16) {
-        // the same on the fp16-storage path: z[N][9][Hu1][Wu1][4] halfs into the t4 region                         app.py:75-77
-        STEP((launch_gemm_h<128, 64, 0, true>(s, blob, 10, B[CAT1], d.Hu1, d.Wu1, 128, B[T4], 64, 0, d.Hu1, d.Wu1, d.Hu1, d.Wu1, nullptr, N)));
-        STEP(launch_tail_zh(s, B[T4], blob + kBlob.b_off[11], out, crop, N, d.Hu1, d.Wu1, out_fmt == CID_FMT_U8_NHWC));
-    } else if (fused_tail) {
-        // upconv1[0] + ReLU, with upconv1[2]'s channel contraction in its epilogue: z planes into the t4 region     app.py:75-77
-        STEP(launch_upconv1_0_z(h->algo, s, blob, B[CAT1], d.Hu1, d.Wu1, B[T4], N));
-        // the nine-tap shifted sum + bias + tanh, -> NCHW out                              app.py:77,103
-        STEP(launch_tail_z(s, B[T4], blob + kBlob.b_off[11], out, crop, N, d.Hu1, d.Wu1, out_fmt == CID_FMT_U8_NHWC));
-    } else {
-    // upconv1[0] + ReLU                                                                  app.py:75-76
-    STEP((launch_layer<128, 64, 0>(h, s, blob, 10, B[CAT1], d.Hu1, d.Wu1, 128, B[T4], 64, 0, d.Hu1, d.Wu1, d.Hu1, d.Wu1, nullptr, N)));
-    // upconv1[2] + tanh, NHWC t4 -> NCHW out                                            app.py:77,103
-    if (h->dtype == CID_DTYPE_F32 && d.Wu1 <= T2_MAXW && h->tail_algo == CID_TAIL_BANDS) {   // row-band kernel: z once per pixel
-        Tail2Args a;
-        a.in = B[T4]; a.w = blob + kBlob.w_off[11]; a.bias = blob + kBlob.b_off[11]; a.out = out; a.crop = crop;
-        a.N = N; a.H = d.Hu1; a.W = d.Wu1;
-        tail2_plan(a);
-        STEP(launch_tail2(s, a, out_fmt == CID_FMT_U8_NHWC));
-    } else {   // 8x32 tiles with halo: images wider than 128 pixels, and the fp16-storage path
-        TailArgs a;
-        a.in = B[T4]; a.w = blob + (h->dtype == CID_DTYPE_F16 ? kBlob.h_off[11] : kBlob.w_off[11]); a.bias = blob + kBlob.b_off[11]; a.out = out; a.crop = crop;
-        a.N = N; a.H = d.Hu1; a.W = d.Wu1;
-        const TileGrid g = tiles_for(N, d.Hu1, d.Wu1);
-        a.tiles_x = g.tx; a.tiles_y = g.ty; a.tiles_total = g.total;
-        tile_groups(a);
-        a.rcp_x = tile_rcp(g.tx); a.rcp_xy = tile_rcp(g.tx * g.ty);
-        STEP(launch_tail(s, a, 8 * a.groups_per_xcd, out_fmt == CID_FMT_U8_NHWC, h->dtype == CID_DTYPE_F16));
-    }
-    }
+    STEP(launch_layer<9>(x, {.in = B[D2], .Hin = d.Hu2, .Win = d.Wu2, .in_ps = 128, .out = B[CAT1], .out_ps = 128, .out_coff = 0,
+                             .Hc = d.Hu2, .Wc = d.Wu2, .Hs = d.Hu2, .Ws = d.Wu2, .pool = nullptr}));
+    // upconv1[0] + ReLU -> t4; fused tail: upconv1[2]'s channel contraction in its epilogue, z planes into t4    app.py:75-77
+    STEP(launch_layer<10>(x, {.in = B[CAT1], .Hin = d.Hu1, .Win = d.Wu1, .in_ps = 128, .out = B[T4], .out_ps = 64, .out_coff = 0,
+                              .Hc = d.Hu1, .Wc = d.Wu1, .Hs = d.Hu1, .Ws = d.Wu1, .pool = nullptr}));
+    // upconv1[2] + tanh, NHWC t4 -> NCHW out                                             app.py:77,103
+    STEP(launch_tail(x, B[T4], out, out_fmt == CID_FMT_U8_NHWC, crop_win ? *crop_win : Window{0, 0, d.Hu1, d.Wu1}, d.Hu1, d.Wu1));
 #undef STEP
     if (ev && hipEventRecord(ev[NL], s) != hipSuccess) return fail(h, CID_ERR_HIP, "hipEventRecord failed");
+    if (armed) ++h->tev_used;
     return CID_OK;
 }
 
@@ -975,11 +965,7 @@ int cid_forward(cid_handle_t h, const float* in, float* out, int N, int H, int W
 
 int cid_forward_ex(cid_handle_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W,
                    void* ws, size_t ws_bytes, void* stream) {
-    hipEvent_t* ev = nullptr;
-    if (h && h->tev_used < h->tev_forwards) ev = h->tev.data() + (size_t)h->tev_used * (NL + 1);
-    const int rc = run_forward(h, in, in_fmt, out, out_fmt, N, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream), ev);
-    if (ev && rc == CID_OK) ++h->tev_used;
-    return rc;
+    return run_forward(h, in, in_fmt, out, out_fmt, N, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 int cid_forward_padded(cid_handle_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W,
@@ -999,11 +985,7 @@ int cid_forward_padded(cid_handle_t h, const void* in, int in_fmt, void* out, in
         return fail(h, CID_ERR_SHAPE, m);
     }
     const Window src{pad_top, pad_left, H, W}, crop{pad_top, pad_left, H, W};
-    hipEvent_t* ev = nullptr;
-    if (h->tev_used < h->tev_forwards) ev = h->tev.data() + (size_t)h->tev_used * (NL + 1);
-    const int rc = run_forward(h, in, in_fmt, out, out_fmt, N, (int)Hp, (int)Wp, ws, ws_bytes, static_cast<hipStream_t>(stream), ev, &src, &crop);
-    if (ev && rc == CID_OK) ++h->tev_used;
-    return rc;
+    return run_forward(h, in, in_fmt, out, out_fmt, N, (int)Hp, (int)Wp, ws, ws_bytes, static_cast<hipStream_t>(stream), nullptr, &src, &crop);
 }
 
 int cid_view_u8(const float* in_nchw, void* out_u8_nhwc, int N, int H, int W, void* stream) {
@@ -1090,17 +1072,8 @@ int cid_forward_timed(cid_handle_t h, const float* in, float* out, int N, int H,
 const char* cid_launch_name(int i) { return (i >= 0 && i < NL) ? kLayers[i].name : nullptr; }
 const char* cid_launch_kernel(cid_handle_t h, int i) {
     if (i < 0 || i >= NL) return nullptr;
-    if (h && h->dtype == CID_DTYPE_F16) {
-        if (i >= 10 && fused_tail_active(h)) return i == 10 ? "k_conv3x3_h16<128, 64, 0, true," : "k_conv_tail_zh<";
-        return kHalfKernelNames[i];
-    }
-    if (h && h->algo == CID_ALGO_SPLIT16) {
-        if (i >= 10 && fused_tail_active(h)) return i == 10 ? "k_conv3x3_h16<128, 64, 0, true, false, true," : "k_conv_tail_z<";
-        return kSplitKernelNames[i] ? kSplitKernelNames[i] : kKernelNames[i];
-    }
-    if (h && h->algo == CID_ALGO_WINOGRAD42 && kWino42KernelNames[i]) return kWino42KernelNames[i];
-    if (h && h->algo != CID_ALGO_DIRECT && kWino64KernelNames[i]) return kWino64KernelNames[i];
-    return kKernelNames[i];
+    const Config c = config_of(h);
+    return kKernelNames.s[c.dtype][c.algo][c.tail][i].c_str();
 }
 
 int cid_set_conv_algo(cid_handle_t h, int algo) {
@@ -1301,13 +1274,14 @@ int cid_launch_work_ex(cid_handle_t h, int i, int N, int H, int W, double* flops
     // the pools' reads are what the fusion removes, their writes remain): in every configuration of the handle
     if (i == 1) *bytes += 4.0 * N * (double)d.H1 * d.W1 * kLayers[1].cout;
     if (i == 3) *bytes += 4.0 * N * (double)d.H2 * d.W2 * kLayers[3].cout;
-    if (!h || !fused_tail_active(h) || i < 10) return rc;
+    const Kern tail = select_kernel(config_of(h), 11);
+    if ((tail != Kern::TAIL_Z && tail != Kern::TAIL_ZH) || i < 10) return rc;
     const double px = (double)N * d.Hu1 * d.Wu1;
     double f11, b11;
     cid_launch_work(11, N, H, W, &f11, &b11);
     // z elements per pixel: 27 fp32 planes; on the fp16-storage path 7 groups x 4 halfs (27 rows and a pad), counted here in
     // fp32-sized elements like every other activation of that path (bench.py halves the bytes between the first and the last tensor)
-    const double zc = h->dtype == CID_DTYPE_F16 ? 28 : 27;
+    const double zc = tail == Kern::TAIL_ZH ? 28 : 27;
     if (i == 10) {
         *flops += f11;
         *bytes += 4.0 * px * (zc - 64) + 4.0 * ref_weight_count(kLayers[11]);

@@ -388,9 +388,10 @@ class DenoiseGenerator(nn.Module):
 
     @property
     def tail_algo(self) -> str:
-        """"fused" (default: the last layer's channel contraction runs inside upconv1[0]'s kernel — Winograd or split16; with conv_algo
-        "direct" or compute_dtype "f16" it behaves as "bands"), "bands" (separate row-band kernel, images up to 128 pixels
-        wide) or "tiles" (round 1's tiled kernel).  Same function; all go through the parity tests."""
+        """"fused" (default: the last layer's channel contraction runs inside upconv1[0]'s kernel — Winograd, split16 or, with
+        compute_dtype "f16", the fp16 kernel under every conv_algo; with conv_algo "direct" in f32 it behaves as "tiles"), "bands"
+        (separate row-band kernel, images up to 128 pixels wide; f16 runs it as "tiles") or "tiles" (round 1's tiled kernel).
+        Same function; all go through the parity tests."""
         a = ctypes.c_int()
         _lib.check(self._cid, _lib.lib().cid_get_tail_algo(self._cid, ctypes.byref(a)))
         return {_lib.CID_TAIL_TILES: "tiles", _lib.CID_TAIL_BANDS: "bands"}.get(a.value, "fused")

@@ -211,13 +211,13 @@ int cid_get_compute_dtype(cid_handle_t h, int* dtype);
 int cid_set_conv_algo(cid_handle_t h, int algo);
 int cid_get_conv_algo(cid_handle_t h, int* algo);
 /*
- * How the last layer (upconv1[2] = Conv2d(64,3,3,p=1) + tanh, backend/app.py:77,103) runs on the fp32 path; same function:
+ * How the last layer (upconv1[2] = Conv2d(64,3,3,p=1) + tanh, backend/app.py:77,103) runs; same function:
  *   CID_TAIL_FUSED  (default) its 64 -> 27 (tap x channel) contraction runs in the epilogue of upconv1[0]'s kernel, on the
  *                   tile still in LDS; the last launch is the nine-tap shifted sum + bias + tanh over 27 fp32 planes (CID_DTYPE_F32; needs
- *                   a Winograd algorithm, with CID_ALGO_DIRECT the handle behaves as CID_TAIL_BANDS) or over 7 planes of 4 halfs (the same 27
- *                   rows 3 tap + co and a pad; CID_DTYPE_F16, round 4).
+ *                   a Winograd algorithm or CID_ALGO_SPLIT16, with CID_ALGO_DIRECT the handle behaves as CID_TAIL_TILES) or over 7 planes
+ *                   of 4 halfs (the same 27 rows 3 tap + co and a pad; CID_DTYPE_F16, with every conv algorithm, round 4).
  *   CID_TAIL_BANDS  separate kernel: a workgroup slides down a band of rows, the contraction is computed once per pixel
- *                   (images up to 128 pixels wide, wider ones take CID_TAIL_TILES)
+ *                   (images up to 128 pixels wide, wider ones take CID_TAIL_TILES; CID_DTYPE_F16 takes its own tiled kernel)
  *   CID_TAIL_TILES  separate kernel: 8x32-pixel tiles, the contraction is computed over each tile's halo (round 1's kernel)
  */
 enum { CID_TAIL_FUSED = 0, CID_TAIL_BANDS = 1, CID_TAIL_TILES = 2 };
