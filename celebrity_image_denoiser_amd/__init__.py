@@ -11,6 +11,8 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     enhance_images(ckpt, in_dir, out_dir)   the reference's directory eval harnesses (denoisegan_eval.py / denoise_eavl_iter.py)
     quality(a, b) / evaluate(denoised, clean)   PSNR / SSIM / MS-SSIM of device batches (the trainer's per-batch evaluation)
     add_noise(clean_u8, kind)     the trainer's five noise kinds on device uint8 batches; evaluate_noise_types(model, clean_u8)
+    DenoiseDiscriminator() / load_discriminator(ckpt)   the trainer's discriminator (eval or train-mode BatchNorm)
+    trainer_losses(D, denoised, clean)                  the trainer's d_loss / g_loss / content_loss / adv_loss of one batch
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -31,6 +33,9 @@ _LAZY = {
     "NOISE_TYPES": ("noise", "NOISE_TYPES"),
     "add_noise": ("noise", "add_noise"),
     "evaluate_noise_types": ("noise", "evaluate_noise_types"),
+    "DenoiseDiscriminator": ("discriminator", "DenoiseDiscriminator"),
+    "load_discriminator": ("discriminator", "load_discriminator"),
+    "trainer_losses": ("discriminator", "trainer_losses"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

@@ -16,6 +16,7 @@ CID_FMT_F32_NCHW, CID_FMT_U8_NHWC = 0, 1
 CID_DTYPE_F32, CID_DTYPE_F16 = 0, 1
 CID_TAIL_FUSED, CID_TAIL_BANDS, CID_TAIL_TILES = 0, 1, 2
 CID_METRIC_PSNR, CID_METRIC_SSIM, CID_METRIC_MS_SSIM = 1, 2, 4
+CID_DISC_MOMENTUM_NONE = -1.0
 CID_NOISE_GAUSSIAN, CID_NOISE_SALT_PEPPER, CID_NOISE_SPECKLE, CID_NOISE_POISSON, CID_NOISE_UNIFORM = 0, 1, 2, 3, 4
 
 # every symbol include/cid.h declares: (restype, argtypes)
@@ -74,6 +75,17 @@ SYMBOLS = {
                                _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "cid_add_noise": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_int,
                                  _c.c_uint64, _c.c_uint64, _c.c_void_p]),
+    "cid_disc_create": (_c.c_int, [_c.POINTER(_c.c_void_p)]),
+    "cid_disc_destroy": (None, [_c.c_void_p]),
+    "cid_disc_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_disc_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_disc_packed_weights_bytes": (_c.c_size_t, []),
+    "cid_disc_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_disc_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_disc_forward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                    _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_disc_losses": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                   _c.c_void_p, _c.c_void_p]),
 }
 
 _lib = None
@@ -116,4 +128,11 @@ def lib() -> ctypes.CDLL:
 def check(handle, code: int):
     if code != CID_OK:
         msg = lib().cid_last_error(handle)
+        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
+
+
+def check_disc(handle, code: int):
+    """check() for a cid_disc_t handle."""
+    if code != CID_OK:
+        msg = lib().cid_disc_last_error(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")

@@ -49,11 +49,11 @@ def _numpy_scalar_globals():
     return [scalar, np.dtype] + sorted({type(np.dtype(k)) for k in kinds}, key=lambda t: t.__name__)
 
 
-def _read_checkpoint_file(path: str) -> Mapping:
+def _read_checkpoint_file(path: str, key_candidates: Sequence[str] = ("generator", "state_dict", "G")) -> Mapping:
     """Checkpoint file -> flat state_dict of CPU tensors.
 
     The torch-free reader (ckpt.py: closed unpickling allow-list, nothing in the file can execute) handles the zip
-    format every torch >= 1.6 writes.  Only when the file is NOT such an archive (the pre-1.6 legacy stream, for which
+    format every torch >= 1.6 writes.  `key_candidates`: where the state_dict sits in a checkpoint dict (extract_state_dict).  Only when the file is NOT such an archive (the pre-1.6 legacy stream, for which
     the reader raises its explicit ValueError / zipfile.BadZipFile) does torch.load take over — with
     weights_only=True, so no pickle in the file gets to run code either way.  Every other failure (a checkpoint that
     references a disallowed global, a truncated storage, out-of-range strides) propagates: it is a bad file, not a
@@ -63,11 +63,11 @@ def _read_checkpoint_file(path: str) -> Mapping:
     from .ckpt import read_state_dict
 
     try:
-        return {k: torch.from_numpy(v) for k, v in read_state_dict(path).items()}
+        return {k: torch.from_numpy(v) for k, v in read_state_dict(path, key_candidates).items()}
     except (ValueError, zipfile.BadZipFile) as e:
         logger.info("%s is not a zip checkpoint (%s): reading the legacy format with torch.load(weights_only=True)", path, e)
         with torch.serialization.safe_globals(_numpy_scalar_globals()):
-            return extract_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+            return extract_state_dict(torch.load(path, map_location="cpu", weights_only=True), key_candidates)
 
 
 def load_state_safely(model: torch.nn.Module, checkpoint_path: str,

@@ -1,0 +1,236 @@
+"""The trainer's discriminator (`DenoiseDiscriminator`, reference backend/trainingcode/denoise_gan_code/training.py:77-98) on the GPU.
+
+    DenoiseDiscriminator()                   nn.Module with the reference's parameter names (model.0 ... model.12, BatchNorm buffers
+                                             included); forward(x) -> fp32 [N] probabilities, eval or train mode
+    load_discriminator(path_or_state_dict)   -> DenoiseDiscriminator from the "discriminator" entry of a trainer checkpoint
+    trainer_losses(D, denoised, clean)       -> the trainer's d_loss / g_loss / content_loss / adv_loss of one batch
+
+Everything numeric runs in HIP kernels behind cid_disc_* (include/cid.h).  Forward only: the output carries no autograd history,
+so the trainer's d_loss.backward() on it raises torch's own "does not require grad" error.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Mapping, Optional, Union
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+_CONVS = ("model.0", "model.2", "model.5", "model.8", "model.12")
+_BNS = (3, 6, 9)
+
+
+class _BnArg(ctypes.Structure):
+    """cid_disc_bn (include/cid.h)."""
+    _fields_ = [("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("running_mean", ctypes.c_void_p),
+                ("running_var", ctypes.c_void_p), ("num_batches_tracked", ctypes.c_void_p), ("eps", ctypes.c_double),
+                ("momentum", ctypes.c_double)]
+
+
+def _out_side(s: int) -> int:
+    return (s - 1) // 2 + 1
+
+
+class DenoiseDiscriminator(nn.Module):
+    """The reference's discriminator.  `self.model` is a Sequential of stock layers used as parameter containers, so state_dict keys,
+    .to(), load_state_dict(), .train() and .eval() behave as in the reference.  forward dispatches on self.training:
+      eval   BatchNorm with the running buffers;
+      train  BatchNorm with batch statistics, and the running buffers and num_batches_tracked of model.3 / model.6 / model.9 are
+             updated in place on the device, as nn.BatchNorm2d does (momentum and eps are read from the containers at every call).
+    The forward is asynchronous on the current stream and carries no autograd history."""
+
+    def __init__(self):
+        super().__init__()
+        self.model = nn.Sequential(
+            nn.Conv2d(3, 64, kernel_size=3, padding=1),
+            nn.LeakyReLU(0.2),
+            nn.Conv2d(64, 64, kernel_size=3, stride=2, padding=1),
+            nn.BatchNorm2d(64),
+            nn.LeakyReLU(0.2),
+            nn.Conv2d(64, 128, kernel_size=3, padding=1),
+            nn.BatchNorm2d(128),
+            nn.LeakyReLU(0.2),
+            nn.Conv2d(128, 128, kernel_size=3, stride=2, padding=1),
+            nn.BatchNorm2d(128),
+            nn.LeakyReLU(0.2),
+            nn.AdaptiveAvgPool2d(1),
+            nn.Conv2d(128, 1, kernel_size=1),
+            nn.Sigmoid(),
+        )
+        self._cid = ctypes.c_void_p()
+        _lib.check_disc(None, _lib.lib().cid_disc_create(ctypes.byref(self._cid)))
+        self._blob = None          # packed convolution weights on the device (uint8 tensor, owns the memory)
+        self._packed_sig = None
+        self._ws = None            # workspace (uint8 tensor, grow-only)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_cid", None):
+                _lib.lib().cid_disc_destroy(self._cid)
+                self._cid = None
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ weights
+    def _conv_params(self):
+        return [(f"{name}.{kind}", getattr(self.model[int(name.split('.')[1])], kind)) for name in _CONVS for kind in ("weight", "bias")]
+
+    def _signature(self):
+        # p._version counts in-place updates made through the tensor API; after writes through `p.data` call pack_weights(force=True)
+        return tuple((k, p.data_ptr(), p._version, str(p.device)) for k, p in self._conv_params())
+
+    def _device(self) -> torch.device:
+        return next(self.parameters()).device
+
+    def pack_weights(self, force: bool = False) -> torch.Tensor:
+        """Repack the ten convolution tensors into the kernels' layout on the module's GPU (if they changed since the last call)."""
+        sig = self._signature()
+        if not force and self._blob is not None and sig == self._packed_sig:
+            return self._blob
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("DenoiseDiscriminator runs only on an AMD GPU (HIP kernels behind libcid.so); move it with "
+                               ".to('cuda') first. There is no CPU fallback.")
+        L = _lib.lib()
+        for key, p in self._conv_params():
+            a = np.ascontiguousarray(p.detach().to("cpu", torch.float32).numpy())
+            shape = (ctypes.c_int64 * a.ndim)(*a.shape)
+            _lib.check_disc(self._cid, L.cid_disc_set_weight(self._cid, key.encode(), a.ctypes.data, shape, a.ndim))
+        blob = torch.empty(L.cid_disc_packed_weights_bytes(), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check_disc(self._cid, L.cid_disc_upload_weights(self._cid, blob.data_ptr(), stream))
+        self._blob, self._packed_sig = blob, sig
+        return blob
+
+    # ------------------------------------------------------------------ forward
+    def _bn_args(self, dev: torch.device):
+        arr = (_BnArg * 3)()
+        for i, idx in enumerate(_BNS):
+            bn = self.model[idx]
+            if not (bn.affine and bn.track_running_stats):
+                raise NotImplementedError(f"model.{idx}: only BatchNorm2d(affine=True, track_running_stats=True) is supported")
+            ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+            if any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in ts):
+                raise RuntimeError(f"model.{idx}: BatchNorm tensors must be contiguous float32 on {dev}")
+            nbt = bn.num_batches_tracked
+            if nbt.device != dev or nbt.dtype != torch.int64:
+                raise RuntimeError(f"model.{idx}.num_batches_tracked must be int64 on {dev}")
+            mom = bn.momentum
+            arr[i] = _BnArg(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                            nbt.data_ptr(), float(bn.eps), _lib.CID_DISC_MOMENTUM_NONE if mom is None else float(mom))
+            if mom is not None and (not np.isfinite(mom) or mom < 0):
+                raise ValueError(f"model.{idx}.momentum must be finite and >= 0 or None, got {mom}")
+            if not np.isfinite(bn.eps) or bn.eps < 0:
+                raise ValueError(f"model.{idx}.eps must be finite and >= 0, got {bn.eps}")
+        return arr
+
+    def _ensure_workspace(self, n: int, h: int, w: int, training: bool, device: torch.device) -> None:
+        need = ctypes.c_size_t()
+        _lib.check_disc(self._cid, _lib.lib().cid_disc_workspace_bytes(n, h, w, int(training), ctypes.byref(need)))
+        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
+            if self._ws is not None:
+                torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
+            self._ws = None
+            self._ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """fp32 [N,3,H,W] in [-1,1] or uint8 [N,H,W,3] on the GPU -> fp32 [N] probabilities on the same GPU (reference forward,
+        training.py:97-98).  In train mode the BatchNorm running buffers are updated in place."""
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("DenoiseDiscriminator expects a torch.Tensor")
+        if x.dtype == torch.uint8:
+            if x.dim() != 4 or x.shape[3] != 3:
+                raise RuntimeError(f"expected a uint8 input of shape [N,H,W,3], got {list(x.shape)}")
+            fmt, (n, h, w) = _lib.CID_FMT_U8_NHWC, (x.shape[0], x.shape[1], x.shape[2])
+        elif x.dtype == torch.float32:
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise RuntimeError(f"expected a float32 input of shape [N,3,H,W], got {list(x.shape)}")
+            fmt, (n, h, w) = _lib.CID_FMT_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
+        else:
+            raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3] input, got {x.dtype}")
+        if x.device.type != "cuda":
+            raise RuntimeError("DenoiseDiscriminator.forward got a CPU tensor: this implementation is GPU-only (hand-written HIP "
+                               "kernels); there is no CPU fallback. Move the input with .to('cuda').")
+        dev = self._device()
+        if x.device != dev:
+            raise RuntimeError(f"input on {x.device} but module parameters on {dev}")
+        if n < 1 or h < 1 or w < 1:
+            raise RuntimeError(f"empty input {list(x.shape)}")
+        training = self.training
+        if training and n * _out_side(_out_side(h)) * _out_side(_out_side(w)) == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                             f"{torch.Size([n, 128, 1, 1])}")
+        bn = self._bn_args(dev)
+        self.pack_weights()
+        self._ensure_workspace(n, h, w, training, dev)
+        x = x.contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check_disc(self._cid, _lib.lib().cid_disc_forward(self._cid, x.data_ptr(), fmt, out.data_ptr(), n, h, w, bn,
+                                                                   int(training), self._ws.data_ptr(), self._ws.numel(), stream))
+        return out
+
+
+def load_discriminator(source: Union[str, Mapping, None] = None, device: Optional[Union[str, torch.device]] = None,
+                       strict: bool = False) -> DenoiseDiscriminator:
+    """Build a DenoiseDiscriminator on `device` (default: current GPU) from a trainer checkpoint path (its "discriminator" entry,
+    training.py:362, read with the torch-free reader), a checkpoint dict or a state_dict; "module." prefixes are stripped as for
+    the generator.  `source=None` keeps the default initialisation.  Returns the module in eval mode."""
+    from .api import _read_checkpoint_file, extract_state_dict
+
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError("celebrity_image_denoiser_amd.load_discriminator: an AMD GPU is required (no CPU fallback)")
+    model = DenoiseDiscriminator()
+    if isinstance(source, str):
+        model.load_state_dict(_read_checkpoint_file(source, key_candidates=("discriminator",)), strict=strict)
+    elif source is not None:
+        sd = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(v))
+              for k, v in extract_state_dict(source, ("discriminator",)).items()}
+        model.load_state_dict(sd, strict=strict)
+    model.to(device).eval()
+    model.pack_weights()
+    return model
+
+
+def _image_operand(x: torch.Tensor, what: str):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise RuntimeError(f"{what}: expected fp32 [N,3,H,W] or uint8 [N,H,W,3]")
+    if x.dtype == torch.float32 and x.shape[1] == 3:
+        return x.contiguous(), _lib.CID_FMT_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
+    if x.dtype == torch.uint8 and x.shape[3] == 3:
+        return x.contiguous(), _lib.CID_FMT_U8_NHWC, (x.shape[0], x.shape[1], x.shape[2])
+    raise RuntimeError(f"{what}: expected fp32 [N,3,H,W] or uint8 [N,H,W,3], got {x.dtype} {list(x.shape)}")
+
+
+def trainer_losses(discriminator: DenoiseDiscriminator, denoised: torch.Tensor, clean: torch.Tensor) -> dict:
+    """The trainer's losses of one batch (training.py:412-424) -> {"d_loss", "g_loss", "content_loss", "adv_loss"} as floats:
+        p_real = D(clean), p_fake = D(denoised)
+        d_loss = BCE(p_real, 1) + BCE(p_fake, 0)      content_loss = MSE(denoised, clean)
+        adv_loss = BCE(p_fake, 1)                     g_loss = content_loss + 0.001 * adv_loss
+    BCE clamps its logs at -100 as nn.BCELoss does; the reductions run in one HIP kernel in fp64 (one device-to-host copy).
+    Each operand is fp32 [N,3,H,W] in [-1,1] or uint8 [N,H,W,3] (read as the forward reads it).  Two differences from the trainer:
+    D is evaluated twice at its current weights (the trainer evaluates :421 after D's optimizer step), and in train mode each of
+    the two calls updates the BatchNorm running statistics."""
+    den, fd, sd = _image_operand(denoised, "denoised")
+    cln, fc, sc = _image_operand(clean, "clean")
+    if sd != sc:
+        raise RuntimeError(f"denoised and clean differ in size: {sd} vs {sc}")
+    if den.device != cln.device or den.device.type != "cuda":
+        raise RuntimeError("trainer_losses: both batches must be on the discriminator's GPU")
+    p_real = discriminator(cln)
+    p_fake = discriminator(den)
+    out = torch.empty(4, dtype=torch.float64, device=den.device)
+    n, h, w = sd
+    with torch.cuda.device(den.device):
+        stream = torch.cuda.current_stream(den.device).cuda_stream
+        _lib.check(None, _lib.lib().cid_disc_losses(p_real.data_ptr(), p_fake.data_ptr(), den.data_ptr(), fd, cln.data_ptr(), fc,
+                                                     n, h, w, out.data_ptr(), stream))
+    d_loss, g_loss, content, adv = out.cpu().tolist()
+    return {"d_loss": d_loss, "g_loss": g_loss, "content_loss": content, "adv_loss": adv}

@@ -63,14 +63,18 @@ def add_noise(clean_u8, kind: str, *, seed: int = synth.NOISE_SEED, first_index:
 
 
 def evaluate_noise_types(model, clean_u8, kinds=NOISE_TYPES, seed: int = synth.NOISE_SEED, first_index: int = 0,
-                         max_batch: int = None) -> dict:
+                         max_batch: int = None, discriminator=None) -> dict:
     """How well `model` denoises each noise kind, all on the GPU: per kind, add_noise -> model.forward_u8(noisy, out_u8=False) ->
     metrics.quality(denoised, clean_u8), plus metrics.quality(noisy, clean_u8) for the input's own PSNR.
 
     clean_u8 is a device uint8 [N,H,W,3] batch with H and W multiples of 4 (so that the forward's output matches it).  Returns
     {kind: {"psnr_noisy", "psnr", "ssim", "ms_ssim"}}: float64 means over the batch of the per-image values (numpy's mean of
     the values copied to the host).  "ms_ssim" is left out when min(H, W) <= 160, where MS-SSIM is not defined.  max_batch
-    bounds the images per forward; the results do not depend on it beyond the forward's own batch independence."""
+    bounds the images per forward; the results do not depend on it beyond the forward's own batch independence.
+
+    With a `discriminator` (discriminator.DenoiseDiscriminator), each kind's dict also holds "d_loss" and "g_loss": the trainer's
+    two per-epoch numbers (training.py:455) from discriminator.trainer_losses(discriminator, denoised, clean), here per noise kind
+    on held-out images; with max_batch they are averaged over the chunks weighted by chunk size."""
     import numpy as np
     import torch
 
@@ -90,9 +94,12 @@ def evaluate_noise_types(model, clean_u8, kinds=NOISE_TYPES, seed: int = synth.N
     if step < 1:
         raise ValueError(f"max_batch must be >= 1, got {max_batch}")
     clean_u8 = clean_u8.contiguous()
+    if discriminator is not None:
+        from .discriminator import trainer_losses
     result = {}
     for kind in kinds:
         vals = {m: [] for m in ("psnr_noisy",) + names}
+        losses = {"d_loss": 0.0, "g_loss": 0.0}
         for i0 in range(0, n, step):
             clean = clean_u8[i0:i0 + step]
             noisy = add_noise(clean, kind, seed=seed, first_index=first_index + i0)
@@ -101,5 +108,11 @@ def evaluate_noise_types(model, clean_u8, kinds=NOISE_TYPES, seed: int = synth.N
             vals["psnr_noisy"].append(metrics.quality(noisy, clean, ("psnr",))["psnr"].cpu().numpy())
             for m in names:
                 vals[m].append(q[m].cpu().numpy())
+            if discriminator is not None:
+                lo = trainer_losses(discriminator, denoised, clean)
+                for m in losses:
+                    losses[m] += lo[m] * clean.shape[0]
         result[kind] = {m: float(np.concatenate(v).mean()) for m, v in vals.items()}
+        if discriminator is not None:
+            result[kind].update({m: v / n for m, v in losses.items()})
     return result

@@ -340,6 +340,73 @@ int cid_add_noise(const void* clean_u8_nhwc, void* out_u8_nhwc, int N, int H, in
                   uint64_t seed, uint64_t first_index, void* stream);
 
 /*
+ * The trainer's discriminator — DenoiseDiscriminator (backend/trainingcode/denoise_gan_code/training.py:77-98), which the trainer calls
+ * three times per step (:412, :413, :421) in train mode (:397) and whose outputs give the per-epoch "G Loss" / "D Loss" (:414-424, :455).
+ * Its own handle: the generator's handle and packed blob are specific to the generator.  Forward only (no autograd).
+ *
+ *   0 Conv2d(3,64,3,p=1)  1 LeakyReLU(0.2)                        2 Conv2d(64,64,3,s=2,p=1)   3 BatchNorm2d(64)   4 LeakyReLU(0.2)
+ *   5 Conv2d(64,128,3,p=1)   6 BatchNorm2d(128)   7 LeakyReLU(0.2)   8 Conv2d(128,128,3,s=2,p=1) 9 BatchNorm2d(128) 10 LeakyReLU(0.2)
+ *  11 AdaptiveAvgPool2d(1)  12 Conv2d(128,1,1)  13 Sigmoid;   forward(x) = model(x).view(-1): one probability per image.
+ * For an H x W input, layer 2 gives H2 = (H-1)/2 + 1 (integer division) and layer 8 H4 = (H2-1)/2 + 1; any H, W >= 1 is valid.
+ *
+ * cid_disc_set_weight takes the ten convolution tensors by their state_dict keys "model.{0,2,5,8,12}.{weight,bias}" (fp32, reference
+ * layout [Cout,Cin,kh,kw] / [Cout]); they are packed into the kernels' layout on the host.  The BatchNorm tensors ("model.{3,6,9}.*")
+ * are not staged (CID_ERR_KEY): they are passed as device pointers at every forward, so that train-mode updates land in the caller's
+ * own buffers.  cid_disc_upload_weights copies the packed blob (cid_disc_packed_weights_bytes(), 256-byte aligned, caller-owned) to
+ * the device and attaches it; it needs all ten tensors (CID_ERR_STATE otherwise).
+ *
+ * cid_disc_forward: in is fp32 [N,3,H,W] in [-1,1] (CID_FMT_F32_NCHW, what the trainer feeds) or uint8 [N,H,W,3] (CID_FMT_U8_NHWC,
+ * decoded as (u/255 - 0.5)/0.5 with the forward's arithmetic: a u8 image and its normalised fp32 copy give identical bits); out_prob
+ * is device fp32 [N].  bn[0..2] describe model.3, model.6, model.9:
+ *   eval (training = 0): BatchNorm uses the running buffers, (z - running_mean) * rsqrt(running_var + eps) * gamma + beta;
+ *            num_batches_tracked and momentum are not read.
+ *   train (training = 1): BatchNorm normalises with the batch mean and the biased batch variance over N*Hl*Wl values per channel,
+ *            then updates the buffers in place: running = (1 - m) * running + m * batch_stat, with the UNBIASED variance for
+ *            running_var, and num_batches_tracked += 1.  m = momentum, or with CID_DISC_MOMENTUM_NONE (nn.BatchNorm2d(momentum=None))
+ *            m = 1 / num_batches_tracked after the increment.  The statistics, the updates and the counter run on the device:
+ *            there is no host synchronisation inside a forward.  A BatchNorm input with one value per channel (N*H4*W4 == 1) is
+ *            CID_ERR_SHAPE, where torch raises "Expected more than 1 value per channel when training".
+ * Arithmetic: fp32 convolutions (exact-fp32 MFMA for layers 2, 5, 8), batch statistics, the average pool, the 1x1 layer and the sigmoid
+ * in fp64.  Deterministic: per-tile partial sums reduced in a fixed order, no atomics; an image's tiling does not depend on N, so in
+ * eval mode an image's probability is bit-identical in any batch.  Asynchronous on `stream` (hipStream_t, NULL = default stream).
+ * Every argument is checked on the host before any launch:
+ *   CID_ERR_INVALID    null pointer (num_batches_tracked only in train mode), unknown format, misaligned fp32 operand, eps not
+ *                      finite or negative, in train mode a momentum that is not finite or negative other than CID_DISC_MOMENTUM_NONE
+ *   CID_ERR_SHAPE      N < 1, H < 1, W < 1, H*W >= 2^31, train mode with N*H4*W4 == 1
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_disc_workspace_bytes(N, H, W, training) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_disc_losses: the trainer's loss arithmetic of one batch (training.py:412-424) from the two probability vectors of
+ * p_real = D(clean) and p_fake = D(denoised) (device fp32 [N]) and the two image batches (fp32 [N,3,H,W] or uint8 [N,H,W,3], each its
+ * own format) -> device double out[4] = d_loss = BCE(p_real, 1) + BCE(p_fake, 0), g_loss = content + 0.001 * adv,
+ * content_loss = MSE(denoised, clean), adv_loss = BCE(p_fake, 1).  BCE clamps its logs at -100 as nn.BCELoss does.  One workgroup,
+ * fp64, fixed order.  CID_ERR_INVALID for a null pointer, an unknown format or a misaligned operand; CID_ERR_SHAPE for N, H or W < 1.
+ */
+typedef struct cid_disc_s* cid_disc_t;
+typedef struct {
+    const float* gamma;              /* device fp32 [C] (weight)  */
+    const float* beta;               /* device fp32 [C] (bias)    */
+    float* running_mean;             /* device fp32 [C], updated in train mode */
+    float* running_var;              /* device fp32 [C], updated in train mode */
+    int64_t* num_batches_tracked;    /* device int64 [1], updated in train mode */
+    double eps;                      /* the container's eps       */
+    double momentum;                 /* the container's momentum, or CID_DISC_MOMENTUM_NONE */
+} cid_disc_bn;
+#define CID_DISC_MOMENTUM_NONE (-1.0)
+#define CID_DISC_NUM_WEIGHTS 10
+int cid_disc_create(cid_disc_t* out);
+void cid_disc_destroy(cid_disc_t d);
+const char* cid_disc_last_error(cid_disc_t d);
+int cid_disc_set_weight(cid_disc_t d, const char* key, const float* host_data, const int64_t* shape, int ndim);
+size_t cid_disc_packed_weights_bytes(void);
+int cid_disc_upload_weights(cid_disc_t d, void* device_blob, void* stream);
+int cid_disc_workspace_bytes(int N, int H, int W, int training, size_t* bytes);
+int cid_disc_forward(cid_disc_t d, const void* in, int in_fmt, float* out_prob, int N, int H, int W, const cid_disc_bn* bn,
+                     int training, void* workspace, size_t workspace_bytes, void* stream);
+int cid_disc_losses(const float* p_real, const float* p_fake, const void* denoised, int d_fmt, const void* clean, int c_fmt,
+                    int N, int H, int W, double* out, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
