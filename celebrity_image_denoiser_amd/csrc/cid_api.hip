@@ -354,7 +354,7 @@ std::string kernel_name(const Config& c, int i) {
     switch (select_kernel(c, i)) {
         case Kern::HEAD: return "k_conv_head";
         case Kern::HEAD_H16: return "k_conv_head_h16";
-        case Kern::GEMM: return "k_gemm_conv<" + mode;
+        case Kern::GEMM: return "k_gemm_conv<" + dims + ", " + std::to_string(mode_of(L));   // MODE is the last template argument: no comma
         case Kern::CONVT_S32: return "k_convt_s32<" + dims + ">";
         case Kern::WINO64: case Kern::Z_WINO64: return "k_wino64_conv<" + pool;
         case Kern::WINO42: case Kern::Z_WINO42: return "k_wino42_conv<" + pool;
@@ -535,8 +535,8 @@ hipError_t launch_wino64(const Ctx& x, int layer, const LayerIO& io) {
     a.slot_tab = reinterpret_cast<const unsigned*>(x.blob + kBlob.tab_off[wide ? 0 : 1]);
     set_tiles(a, x.N, io.Hc, io.Wc, wide ? 64 : 32, wide ? 2 : 4);   // TC tile-columns of 2x2 pixels, 32 / TC tile-rows
     const dim3 grid(8 * a.tiles_per_xcd * (COUT / WN2));
-    if (wide) hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, 32, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
-    else hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, 16, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
+    if (wide) hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, 32, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
+    else hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, 16, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
     return hipGetLastError();
 }
 
@@ -549,8 +549,8 @@ hipError_t launch_wino42(const Ctx& x, int layer, const LayerIO& io) {
     a.slot_tab = reinterpret_cast<const unsigned*>(x.blob + kBlob.tab42_off[wide ? 0 : 1]);
     set_tiles(a, x.N, io.Hc, io.Wc, wide ? 32 : 16, wide ? 4 : 8);   // TC tile-columns of 4x2 pixels, 16 / TC tile-rows
     const dim3 grid(wino42_grid(a, COUT / WN2));
-    if (wide) hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, 8, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
-    else hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, 4, 0, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
+    if (wide) hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, 8, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
+    else hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, 4, ZOUT>), grid, dim3(THREADS), 0, x.s, a);
     return hipGetLastError();
 }
 

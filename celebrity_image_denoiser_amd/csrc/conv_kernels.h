@@ -167,16 +167,8 @@ __device__ __forceinline__ void wide_store_full(float* stg, int lane, ValFn val,
 //   epilogue : bias/ReLU/pool/scatter straight from the accumulators (bias was loaded in the
 //              prologue: a load left pending here makes hipcc wait vmcnt(0) before every guarded
 //              store, and since CDNA4's vmcnt counts stores too that serialises the whole tail).
-//
-// ABLATE (timing experiments only, csrc/tools/layer_bench.hip; results are wrong when non-zero):
-//   bit 0: no halo prefetch/restage after chunk 0   bit 1: B fragments loaded once
-//   bit 2: A fragments read once per chunk          bit 3: no epilogue stores
-//   bit 4 (results stay correct, MODE 2): wave 0 writes s_memtime stamps and HW_ID to a.pool (layer_bench <N> trace, tools/trace_stats.py)
-template <int CIN, int COUT, int MODE, int ABLATE = 0, int WPS = 2>
-__global__ void __launch_bounds__(THREADS, WPS) k_gemm_conv(const GemmConvArgs a) {
-#ifndef CID_EXPERIMENTS
-    static_assert(ABLATE == 0, "ablation/trace variants are built only by csrc/tools (-DCID_EXPERIMENTS)");
-#endif
+template <int CIN, int COUT, int MODE>
+__global__ void __launch_bounds__(THREADS, 2) k_gemm_conv(const GemmConvArgs a) {
     constexpr int TAPS = (MODE == 2) ? 1 : 9;
     constexpr int HALO = (MODE == 2) ? 0 : 1;
     constexpr int LW = TILE_W + 2 * HALO;            // LDS tile width in pixels
@@ -203,17 +195,6 @@ __global__ void __launch_bounds__(THREADS, WPS) k_gemm_conv(const GemmConvArgs a
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
-    // ABLATE bit 4 (trace experiment, MODE 2 only): wave 0 records s_memtime at four points and its HW_ID into a.pool
-    unsigned long long* trace = (ABLATE & 16) ? reinterpret_cast<unsigned long long*>(a.pool) + (size_t)blockIdx.x * 8 : nullptr;
-    if ((ABLATE & 16) && tid == 0) {
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        trace[0] = __builtin_readcyclecounter();
-        trace[4] = hwid;
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        trace[5] = xcc;
-    }
 
     // output-channel block of this workgroup (MODE 2: nb also selects the (kh,kw) tap)
     constexpr int CB = COUT / NTILE;
@@ -273,24 +254,23 @@ __global__ void __launch_bounds__(THREADS, WPS) k_gemm_conv(const GemmConvArgs a
 
     auto chunk = [&](auto first_tag, auto pref_tag, int ck) {
         constexpr bool FIRST = decltype(first_tag)::value;                  // chunk 0: accumulate onto a zero C operand
-        constexpr bool PREF = decltype(pref_tag)::value && !(ABLATE & 1);   // another chunk follows
+        constexpr bool PREF = decltype(pref_tag)::value;                    // another chunk follows
         f32x4 acur[2], anxt[2];
 #pragma unroll
         for (int m = 0; m < 2; ++m) acur[m] = lds[lds_slot(pbase0 + m * LW, h)];
 #pragma unroll
         for (int st = 0; st < SPC; ++st) {
-            if (st + 1 < SPC && !(ABLATE & 4)) {
+            if (st + 1 < SPC) {
                 const int t2 = (st + 1) >> 2, g2 = (st + 1) & 3;
                 const int off = (TAPS == 9) ? ((t2 / 3) * LW + (t2 % 3)) : 0;
 #pragma unroll
                 for (int m = 0; m < 2; ++m) anxt[m] = lds[lds_slot(pbase0 + m * LW + off, 2 * g2 + h)];
             }
-            if ((decltype(pref_tag)::value || st + DIST < SPC) && !(ABLATE & 2)) {
+            if (decltype(pref_tag)::value || st + DIST < SPC) {
                 bq[(st + DIST) % NBUF][0] = b_load(ck * SPC + st + DIST, 0);
                 bq[(st + DIST) % NBUF][1] = b_load(ck * SPC + st + DIST, 1);
             }
             if (PREF && st < NLOAD) pre[st] = halo_load(st, ck + 1);
-            constexpr int BSEL = (ABLATE & 2) ? 0 : -1;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -299,12 +279,12 @@ __global__ void __launch_bounds__(THREADS, WPS) k_gemm_conv(const GemmConvArgs a
                     for (int ns = 0; ns < 2; ++ns) {
                         if (FIRST && st == 0 && e == 0) {
                             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                            acc[m][ns] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[m][e], bq[BSEL < 0 ? st % NBUF : 0][ns][e], zero, 0, 0, 0);
+                            acc[m][ns] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[m][e], bq[st % NBUF][ns][e], zero, 0, 0, 0);
                         } else {
-                            acc[m][ns] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[m][e], bq[BSEL < 0 ? st % NBUF : 0][ns][e], acc[m][ns], 0, 0, 0);
+                            acc[m][ns] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[m][e], bq[st % NBUF][ns][e], acc[m][ns], 0, 0, 0);
                         }
                     }
-            if (st + 1 < SPC && !(ABLATE & 4)) {
+            if (st + 1 < SPC) {
 #pragma unroll
                 for (int m = 0; m < 2; ++m) acur[m] = anxt[m];
             }
@@ -322,23 +302,9 @@ __global__ void __launch_bounds__(THREADS, WPS) k_gemm_conv(const GemmConvArgs a
         }
     };
     static_assert(NCHUNK >= 2, "first and last chunk are separate instantiations");
-    if ((ABLATE & 16) && tid == 0) trace[1] = __builtin_readcyclecounter();
     chunk(std::true_type{}, std::true_type{}, 0);
     for (int ck = 1; ck + 1 < NCHUNK; ++ck) chunk(std::false_type{}, std::true_type{}, ck);
     chunk(std::false_type{}, std::false_type{}, NCHUNK - 1);
-    if ((ABLATE & 16) && tid == 0) trace[2] = __builtin_readcyclecounter();
-
-    if (ABLATE & 8) {   // keep the accumulators alive without the store tail
-        float sum = 0.f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int ns = 0; ns < 2; ++ns)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sum += acc[m][ns][r];
-        if (sum == 123.456f) a.out[tid] = sum;
-        return;
-    }
 
     // ---- epilogue: D[row = pixel column, col = output channel]; lane holds channel j = lane&31 ----
     // and pixel columns xo(r) = (r&3) + 8*(r>>2) + 4*h for its 16 accumulator registers r.  Each wave
@@ -362,11 +328,6 @@ __global__ void __launch_bounds__(THREADS, WPS) k_gemm_conv(const GemmConvArgs a
             else
                 wide_store<32>(stg, lane, val, xo,
                                [&](int px) -> float* { return (rowok && x0 + px < a.Wc) ? orow + (size_t)(x0 + px) * step : nullptr; });
-        }
-        if ((ABLATE & 16) && tid == 0) {
-            trace[3] = __builtin_readcyclecounter();                 // all stores issued
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            trace[6] = __builtin_readcyclecounter();                 // ... and written back
         }
     } else {
 #pragma unroll
@@ -459,16 +420,12 @@ inline void tile_groups(Args& a) {
 
 // IN_U8: the caller's image is uint8 HWC (what PIL hands the reference); ToTensor (/255) and Normalize(0.5,0.5)
 // (app.py:401-405) are applied on the fly, in fp32, with true divisions like torchvision: (u8/255 - 0.5)/0.5.
-// ABLATE (timing experiments only, tools/headtail_bench.hip; wrong results when non-zero): 1 no input loads, 2 no MFMAs, 4 no stores.
 //
 // A workgroup walks `a.tiles_per_wg` consecutive tiles.  The input elements of the NEXT tile are requested (into
 // registers) before the current tile's MFMAs and stores, so after the first tile no input latency is exposed
 // (tools/headtail_bench: removing the input loads altogether was worth 0.05 of this kernel's 0.23 ms).
-template <bool IN_U8, int ABLATE = 0>
+template <bool IN_U8>
 __global__ void __launch_bounds__(THREADS, 4) k_conv_head(const HeadArgs a) {
-#ifndef CID_EXPERIMENTS
-    static_assert(ABLATE == 0, "ablation/trace variants are built only by csrc/tools (-DCID_EXPERIMENTS)");
-#endif
     constexpr int LW = 36, LH = TILE_H + 2, PLANE = LW * LH;   // 34 used columns, padded to 36
     constexpr int STG16 = 16 * WS_STRIDE;                      // store staging per wave: 16 pixels x 64 channels
     __shared__ __attribute__((aligned(16))) float lds[3 * PLANE + 4 * STG16];   // input planes | store staging (21.7 KB)
@@ -507,7 +464,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_conv_head(const HeadArgs a) {
             const int sy = gy - a.src.top, sx = gx - a.src.left;                 // the caller's image
             const bool ok = net && (unsigned)sy < (unsigned)a.src.H && (unsigned)sx < (unsigned)a.src.W;
             const unsigned goff = !ok ? 0x7ffffff0u : IN_U8 ? (unsigned)((sy * a.src.W + sx) * 3 + pc[it]) : (unsigned)(((pc[it] * a.src.H + sy) * a.src.W + sx) * 4);
-            if (ABLATE & 1) { staged[it] = (float)tid; continue; }
             // three kinds of element: the image; the black band the server pads with (-1.0 once normalised); the convolution's
             // zero padding outside the network input, which applies to the NORMALISED tensor: 0, not (0/255 - 0.5)/0.5
             const float fill = net ? -1.f : 0.f;
@@ -557,7 +513,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_conv_head(const HeadArgs a) {
                 const float av = lds[(hs.dist == 0 ? base_col : hs.dist == 1 ? base_row : base_plane) + o0];
 #pragma unroll
                 for (int ns = 0; ns < 2; ++ns) {
-                    if ((ABLATE & 2) && s > 0) { acc[ns][s] += av * bw[ns][s]; continue; }
                     if (s == 0) {
                         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                         acc[ns] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bw[ns][s], zero, 0, 0, 0);
@@ -565,13 +520,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_conv_head(const HeadArgs a) {
                         acc[ns] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bw[ns][s], acc[ns], 0, 0, 0);
                     }
                 }
-            }
-            if (ABLATE & 4) {
-                float sum = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sum += acc[0][r] + acc[1][r];
-                if (sum == 123.456f) static_cast<float*>(a.out)[tid] = sum;
-                continue;
             }
             const int y = y0 + 2 * wave + m;
             const bool rowok = y < a.H;
@@ -614,17 +562,13 @@ struct TailArgs {
 };
 // OUT_U8: the reference's view transform and PIL conversion folded in: y*0.5+0.5, clamp to [0,1] (app.py:435),
 // then ToPILImage's mul(255).byte() — truncation, not rounding (app.py:471-472; denoisegan_eval.py:97-98).
-// ABLATE (timing experiments only): 1 no input loads, 2 no MFMAs, 8 no gather/tanh/store epilogue.
 //
 // A workgroup walks `a.tiles_per_wg` consecutive tiles.  The loads of a tile's second 32-channel chunk fly under the
 // first chunk's MFMAs, and the NEXT tile's first chunk under the second chunk's MFMAs and the epilogue, in the same
 // registers: after the first tile no memory latency is exposed (tools/headtail_bench: the load phase alone is
 // 0.17 ms of the 0.30 ms this kernel took when it ran load -> product -> load -> product -> epilogue).
-template <bool OUT_U8, bool IN_F16 = false, int ABLATE = 0>
+template <bool OUT_U8, bool IN_F16 = false>
 __global__ void __launch_bounds__(THREADS, 2) k_conv_tail(const TailArgs a) {
-#ifndef CID_EXPERIMENTS
-    static_assert(ABLATE == 0, "ablation/trace variants are built only by csrc/tools (-DCID_EXPERIMENTS)");
-#endif
     constexpr int LW = TILE_W + 2, LH = TILE_H + 2, LPIX = LW * LH;   // 340 halo pixels
     constexpr int MT = (LPIX + 31) / 32, LP = MT * 32;                // 11 M tiles, 352 rows
     constexpr int NSLOT = LPIX * 8, NLOAD = (NSLOT + THREADS - 1) / THREADS;
@@ -671,7 +615,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_conv_tail(const TailArgs a) {
     auto load_chunk = [&](int ck) {
 #pragma unroll
         for (int it = 0; it < NLOAD; ++it) {
-            if (ABLATE & 1) { stage[it] = f32x4{(float)tid, 1.f, 2.f, 3.f}; continue; }
             if (IN_F16) {
                 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
                 const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(rsrc_in, goff[it], ck * (KCHUNK * 2), 0);
@@ -703,7 +646,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_conv_tail(const TailArgs a) {
                     const f32x4 av = lds[lds_slot(mtile * 32 + i, 2 * g + h)];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        if (ABLATE & 2) { acc[t][4 * g + e] = av[e] * wb[ck][g][e]; continue; }
                         if (FIRST && g == 0 && e == 0) {
                             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                             acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], wb[ck][g][e], zero, 0, 0, 0);
@@ -738,51 +680,44 @@ __global__ void __launch_bounds__(THREADS, 2) k_conv_tail(const TailArgs a) {
         __syncthreads();
         product(std::false_type{}, 1);
         __syncthreads();   // every wave is done reading x: the LDS becomes z[352][33]
-        if (!(ABLATE & 8)) {
-            float* zl = reinterpret_cast<float*>(lds);
+        float* zl = reinterpret_cast<float*>(lds);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int mtile = wave + 4 * q;
-                if (mtile < MT) {
+        for (int q = 0; q < 3; ++q) {
+            const int mtile = wave + 4 * q;
+            if (mtile < MT) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) zl[(mtile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * ZS + i] = acc[q][r];
-                }
+                for (int r = 0; r < 16; ++r) zl[(mtile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * ZS + i] = acc[q][r];
             }
-            __syncthreads();
-            const int row = tid >> 5, col = tid & 31;
-            const int pb = row * LW + col;
-            float o[3] = {bias_v[0], bias_v[1], bias_v[2]};
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const float* zp = zl + (pb + (tap / 3) * LW + (tap % 3)) * ZS + tap * 3;
-#pragma unroll
-                for (int co = 0; co < 3; ++co) o[co] += zp[co];
-            }
-            const int y = y0 + row, x = x0 + col;
-            const int cy = y - a.crop.top, cx = x - a.crop.left;       // the caller's tensor
-            if (y < a.H && x < a.W && (unsigned)cy < (unsigned)a.crop.H && (unsigned)cx < (unsigned)a.crop.W) {
-                if (OUT_U8) {
-                    unsigned char* op = static_cast<unsigned char*>(a.out) + ((size_t)(n * a.crop.H + cy) * a.crop.W + cx) * 3;
-#pragma unroll
-                    for (int co = 0; co < 3; ++co) {
-                        const float v = fminf(fmaxf(tanhf(o[co]) * 0.5f + 0.5f, 0.f), 1.f);
-                        op[co] = (unsigned char)(v * 255.0f);
-                    }
-                } else {
-                    const size_t plane = (size_t)a.crop.H * a.crop.W;
-                    float* op = static_cast<float*>(a.out) + (size_t)n * 3 * plane + (size_t)cy * a.crop.W + cx;
-                    op[0] = tanhf(o[0]);
-                    op[plane] = tanhf(o[1]);
-                    op[2 * plane] = tanhf(o[2]);
-                }
-            }
-            __syncthreads();   // everyone is done gathering z before the next tile's pieces overwrite it
-        } else {
-            float sum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sum += acc[0][r] + acc[1][r] + acc[2][r];
-            if (sum == 123.456f) static_cast<float*>(a.out)[tid] = sum;
         }
+        __syncthreads();
+        const int row = tid >> 5, col = tid & 31;
+        const int pb = row * LW + col;
+        float o[3] = {bias_v[0], bias_v[1], bias_v[2]};
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const float* zp = zl + (pb + (tap / 3) * LW + (tap % 3)) * ZS + tap * 3;
+#pragma unroll
+            for (int co = 0; co < 3; ++co) o[co] += zp[co];
+        }
+        const int y = y0 + row, x = x0 + col;
+        const int cy = y - a.crop.top, cx = x - a.crop.left;       // the caller's tensor
+        if (y < a.H && x < a.W && (unsigned)cy < (unsigned)a.crop.H && (unsigned)cx < (unsigned)a.crop.W) {
+            if (OUT_U8) {
+                unsigned char* op = static_cast<unsigned char*>(a.out) + ((size_t)(n * a.crop.H + cy) * a.crop.W + cx) * 3;
+#pragma unroll
+                for (int co = 0; co < 3; ++co) {
+                    const float v = fminf(fmaxf(tanhf(o[co]) * 0.5f + 0.5f, 0.f), 1.f);
+                    op[co] = (unsigned char)(v * 255.0f);
+                }
+            } else {
+                const size_t plane = (size_t)a.crop.H * a.crop.W;
+                float* op = static_cast<float*>(a.out) + (size_t)n * 3 * plane + (size_t)cy * a.crop.W + cx;
+                op[0] = tanhf(o[0]);
+                op[plane] = tanhf(o[1]);
+                op[2 * plane] = tanhf(o[2]);
+            }
+        }
+        __syncthreads();   // everyone is done gathering z before the next tile's pieces overwrite it
         n = nn; y0 = ny0; x0 = nx0;
     }
 }
@@ -837,12 +772,8 @@ inline void tail2_plan(Tail2Args& a, int rows = 0) {
     a.rcp_bands = tile_rcp((unsigned)a.bands_per_image);
 }
 
-// ABLATE (timing experiments only): 1 no input loads, 2 no MFMAs, 4 no gather/tanh/stores.
-template <bool OUT_U8, int ABLATE = 0>
+template <bool OUT_U8>
 __global__ void __launch_bounds__(THREADS, 3) k_conv_tail2(const Tail2Args a) {
-#ifndef CID_EXPERIMENTS
-    static_assert(ABLATE == 0, "ablation/trace variants are built only by csrc/tools (-DCID_EXPERIMENTS)");
-#endif
     constexpr int WAVE_SLOTS = 32 * 8;                     // wave-private x buffer: 32 pixels x 8 quads of 16 B = 4 KiB
     constexpr int NPW = 4;                                 // pieces (16 B per lane, 8 pixels) per wave and chunk
     constexpr int ZE = T2_MAXW + 2, ZC = 27;               // z row: 130 entries x 27 columns
@@ -888,7 +819,6 @@ __global__ void __launch_bounds__(THREADS, 3) k_conv_tail2(const Tail2Args a) {
     f32x4 stage[4][NPW];                                   // chunk (row zr_first + k, half) lives in stage[2*(k&1) + half]
     auto request = [&](auto slot_tag, int zr, int half) {
         constexpr int SLOT = decltype(slot_tag)::value;
-        if (ABLATE & 1) return;
         const bool ok = zr >= 0 && zr < a.H && zr <= zr_last;
         const int zc = ok ? zr : 0;
         const __amdgpu_buffer_rsrc_t rsrc_row = __builtin_amdgcn_make_buffer_rsrc((void*)(inb + (size_t)zc * a.W * 64), (short)0, ok ? a.W * 256 : 0, 0x00020000);
@@ -898,7 +828,6 @@ __global__ void __launch_bounds__(THREADS, 3) k_conv_tail2(const Tail2Args a) {
     };
     auto to_lds = [&](auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
-        if (ABLATE & 1) return;
 #pragma unroll
         for (int m = 0; m < NPW; ++m) xw[wslot[m]] = stage[SLOT][m];
     };
@@ -957,7 +886,6 @@ __global__ void __launch_bounds__(THREADS, 3) k_conv_tail2(const Tail2Args a) {
             const f32x4 av = xw[sl];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if (ABLATE & 2) { acc[4 * g + e] = av[e] * wb[HALF][g][e]; continue; }
                 if (FIRST && g == 0 && e == 0) {
                     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], wb[HALF][g][e], zero, 0, 0, 0);
@@ -970,7 +898,6 @@ __global__ void __launch_bounds__(THREADS, 3) k_conv_tail2(const Tail2Args a) {
     // gather z row `zr` (slot Z) into the partial sums; emit output row zr-1 (dropped by the range check outside the band)
     auto gather_emit = [&](auto z_tag, int zr) {
         constexpr int Z = decltype(z_tag)::value;
-        if (ABLATE & 4) return;
         const float* zs = zl + Z * ZROW;
         float tot[3];
 #pragma unroll

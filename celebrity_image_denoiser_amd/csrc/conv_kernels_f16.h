@@ -15,13 +15,6 @@
 #pragma once
 #include "conv_kernels.h"
 
-#if (defined(H16_SPLIT_IN) || defined(H16_SPLIT_OUT)) && !defined(CID_EXPERIMENTS)
-#error "the split-operand prototype is built only by csrc/tools (-DCID_EXPERIMENTS)"
-#endif
-#ifndef H16_ABLATE   // timing / energy experiments of csrc/tools/h16_trace only (wrong results when non-zero): 1 no B DMA after a workgroup's first item,
-#define H16_ABLATE 0  // 2 no halo loads after the first item, 4 no stores, 8 fragments read from LDS once per item (MFMAs on stale registers)
-#endif
-
 namespace cid {
 
 constexpr int HPS = 5;   // LDS slots (16 B) per pixel: 4 data (32 halfs) + 1 pad
@@ -238,7 +231,7 @@ __device__ __forceinline__ void h16_store_row(int lane, V value, const __amdgpu_
         for (int r = 0; r < per; ++r) {
             const int dp = (NPIX / 2) * pg + (NPIX == 32 ? (r & 1) + 4 * (r >> 1) : 2 * r);   // compile-time
             const f16x4 v = {(_Float16)value(pg, 0, r), (_Float16)value(pg, 1, r), (_Float16)value(pg, 2, r), (_Float16)value(pg, 3, r)};
-            const unsigned vo = (!(H16_ABLATE & 4) && (full || (rowok && p0 + dp < xlim))) ? lane_off : 0x7ffffff0u;
+            const unsigned vo = (full || (rowok && p0 + dp < xlim)) ? lane_off : 0x7ffffff0u;
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rsrc, vo, row_off + (unsigned)(dp * stride * 2), /*nt*/ 2);   // re-measured r4: plain stores -1.8 %
         }
 }
@@ -260,10 +253,6 @@ __device__ __forceinline__ void h16_epilogue(const Args& a, f32x4 (&acc)[2][2][4
             const int y = __builtin_amdgcn_readfirstlane(y0 + 2 * wave + m);
             const unsigned row_off = (unsigned)(((y * a.Ws + x0) * a.out_ps + a.out_coff + cobase) * 2);
             h16_store_row<32>(lane, [&](int pg, int cg, int r) { return fmaxf(acc[m][pg][cg][r] + bias_v[cg], 0.f); }, ro, row_off, a.out_ps, a.Ws - x0, y < a.Hs, full);
-#ifdef H16_SPLIT_OUT   // experiment (csrc/tools/split_proto, -DCID_EXPERIMENTS): the fp32 result kept as TWO halfs — hi = half(v) at channel c (above), lo = half(v - hi) at channel out_ps / 2 + c
-            h16_store_row<32>(lane, [&](int pg, int cg, int r) { const float v = fmaxf(acc[m][pg][cg][r] + bias_v[cg], 0.f); return v - (float)(_Float16)v; }, ro,
-                              row_off + (unsigned)a.out_ps, a.out_ps, a.Ws - x0, y < a.Hs, full);
-#endif
         }
     }
     if (MODE == 1) {   // 2x2 max-pool, floor mode: registers (r, r+1), r even, of the wave's two rows are one window
@@ -544,9 +533,6 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
     // PAIR (F32IO only): one workgroup computes TWO 64-channel column blocks of its tile from one staging of the input — the hi / lo planes of a chunk serve nine sub-steps into
     // `acc` (block 2 nbp) and nine into `acc2` (block 2 nbp + 1): half the loads, conversions, LDS writes and chunk seams per MFMA, half the workgroups.
     static_assert(!PAIR || (F32IO && !ZOUT && !WALK && (MODE == 2 || COUT % 128 == 0)), "PAIR: split16 layers with at least two column blocks");
-#ifndef CID_EXPERIMENTS
-    static_assert(H16_ABLATE == 0, "ablation variants are built only by csrc/tools (-DCID_EXPERIMENTS)");
-#endif
     static_assert(MODE == 0 || MODE == 1 || (MODE == 2 && F32IO && PAIR), "3x3 layers; MODE 2 (2x2 stride-2 transposed convolution) only in the split-operand form");
     static_assert(!ZOUT || (COUT == 64 && MODE == 0), "the fused last layer contracts the 64 channels of ONE column block");
     constexpr int LW = TILE_W + 2, LH = TILE_H + 2, LPIX = LW * LH;       // 340
@@ -598,7 +584,6 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
         return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), (short)0, a.Hin * a.Win * CIN * (F32IO ? 4 : 2), 0x00020000);
     };
     // halo pieces: piece s = it*256 + tid = (pixel s >> 2, k-group s & 3) -> LDS slot HB + (tid & 3) * PLANE + (tid >> 2) + 64 it
-    bool abl_on = false;   // H16_ABLATE: a workgroup's first item runs in full (so LDS holds real data), the ablation applies from its second
     unsigned goff[NLOAD];
     auto halo_offsets = [&](int ty0, int tx0, int lane_id) {
 #pragma unroll
@@ -617,12 +602,10 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
     const bool halo_last = F32IO ? (NLOAD - 1) * 32 + (tid >> 3) < LPIX : (NLOAD - 1) * 64 + (tid >> 2) < LPIX;          // does this thread's last piece exist (pixels 320..339 of 340)
     f32x4 pre[NLOAD];
     auto request_halo = [&](const __amdgpu_buffer_rsrc_t& rsrc, int ck, int zs) {
-        if ((H16_ABLATE & 2) && abl_on) return;
 #pragma unroll
         for (int it = 0; it < NLOAD; ++it) pre[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, goff[it], zs + ck * (F32IO ? 128 : 64), 0));
     };
     auto halo_to_lds = [&]() {
-        if ((H16_ABLATE & 2) && abl_on) return;
 #pragma unroll
         for (int it = 0; it < NLOAD; ++it) {
             if (F32IO) {   // four fp32 channels -> their hi halfs (8 bytes into the hi planes) and the halfs of what hi leaves (the lo planes)
@@ -641,7 +624,6 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
     const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, CIN * COUT * (MODE == 2 ? 4 : 9) * 2 * (F32IO ? 3 : 1), 0x00020000);
     const unsigned vlane = lane * 16;
     auto dma_b = [&](int wb, int g) {   // wb = byte offset of the item's column block in the packed weights
-        if ((H16_ABLATE & 1) && abl_on) return;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int soff = wb + g * (BSUB * 16) + (wave_s + 4 * j) * 1024;
@@ -668,11 +650,6 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
         n2 = uni(n2); y02 = uni(y02); x02 = uni(x02); local2 = uni(local2); nb2 = uni(nb2); has_next = uni(has_next) != 0;
     };
 
-#ifdef H16_TRACE   // experiment (csrc/tools/h16_trace): thread 0 sums s_memtime over the phases of ALL its items into a.pool (MODE 0 only), results unchanged
-    unsigned long long* trace = reinterpret_cast<unsigned long long*>(a.pool) + (size_t)blockIdx.x * 8;
-    unsigned long long tr_t0 = __builtin_readcyclecounter(), tr_last = tr_t0, tr_main = 0, tr_epi = 0, tr_bnd = 0, tr_items = 0;
-    auto tr_lap = [&](unsigned long long& acc_) { const unsigned long long t = __builtin_readcyclecounter(); acc_ += t - tr_last; tr_last = t; };
-#endif
     // ---- prologue of the workgroup's first item ----
     __amdgpu_buffer_rsrc_t rsrc_in = image_rsrc(n);
     halo_offsets(y0, x0, tid);
@@ -712,25 +689,6 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
             request_halo(image_rsrc(n2), 0, zs);
         }
         f16x8 ar[4][2], bf[3][4];
-        if ((H16_ABLATE & 8) && !FIRST && abl_on) {   // no LDS reads: the MFMAs run on whatever the (opaque) registers hold
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int pg = 0; pg < 2; ++pg) asm volatile("" : "=v"(ar[r][pg]));
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int cg = 0; cg < 4; ++cg) asm volatile("" : "=v"(bf[dy][cg]));
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int pg = 0; pg < 2; ++pg)
-#pragma unroll
-                        for (int cg = 0; cg < 4; ++cg) A[m][pg][cg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ar[m + dy][pg], bf[dy][cg], A[m][pg][cg], 0, 0, 0);
-            return;
-        }
 #pragma unroll
         for (int cg = 0; cg < 4; ++cg) bf[0][cg] = bq[cg * 64];
 #pragma unroll
@@ -805,8 +763,7 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
     };
     auto seam_keep_halo = [&]() {   // the same with the NLOAD halo loads issued behind the B DMA still in flight
         static_assert(NLOAD == (F32IO ? 11 : 6), "vmcnt immediate below");
-        if (H16_ABLATE & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (F32IO) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
+        if (F32IO) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         __syncthreads();
     };
@@ -824,9 +781,6 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
         wbase = nb * NSUB * (BSUB * 16) + zs;
         const int cobase = nb * NTILE;
         const f32x4 bias_v = *reinterpret_cast<const f32x4*>(a.bias + (MODE == 2 ? 0 : cobase) + 4 * c16 + zs);   // column c16 of group cg = channel 4 c16 + cg (MODE 2: its epilogue loads its own)
-#ifdef H16_TRACE
-        tr_lap(tr_bnd);     // prologue of the first item / boundary of the later ones
-#endif
         if constexpr (MODE == 2) {
             // two column blocks per workgroup (PAIR): per chunk one sub-step into `acc` (block nb) and one into `acc2` (block nb + 1); sub-step s reads B buffer s & 1 and
             // the DMA's base offset picks the block whose sub-chunk comes next
@@ -899,30 +853,6 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
             }
             substep(F{}, T{}, NSUB - 1, 2 + HALO_SLOTS);
         } else {
-#ifdef H16_SPLIT_IN
-        {   // experiment (csrc/tools/split_proto, -DCID_EXPERIMENTS): split-operand fp32 convolution.  A pixel holds [hi | lo] halfs of C = CIN / 2 fp32 channels, the packed
-            // weights [hi_w | lo_w] as 2 C input channels.  Halo chunk ck < NCH (hi_x) runs SIX sub-steps — its three tap columns against hi_w, then against lo_w, from the same
-            // fragments — and chunk NCH + c (lo_x) three against hi_w: 9 NCH sub-steps.  Sub-step s reads B buffer s & 1 and requests the sub-chunk of step s + 1 into the other one;
-            // which packed sub-chunk that is goes through `wbase` (dma_b fetches wbase + (s + 1) sub-chunks).
-            static_assert(!WALK && !ZOUT && NCHUNK % 2 == 0, "prototype: one item per workgroup, plain epilogue");
-            constexpr int NCH = NCHUNK / 2, NSEQ = 9 * NCH;
-            const int wbase0 = wbase;
-            auto packed_of = [&](int q) { if (q < 6 * NCH) { const int c = q / 6, j = q - 6 * c; return j < 3 ? 3 * c + j : 3 * (NCH + c) + j - 3; } return q - 6 * NCH; };
-            auto aim = [&](int q) { wbase = wbase0 + (packed_of(q + 1) - (q + 1)) * (BSUB * 16); };
-            aim(0); substep(T{}, F{}, 0, 0); seam();
-            for (int q = 1; q < NSEQ - 1; ++q) {
-                int ck, j, nsub;
-                if (q < 6 * NCH) { ck = q / 6; j = q - 6 * ck; nsub = 6; } else { const int t = q - 6 * NCH; ck = NCH + t / 3; j = t - 3 * (t / 3); nsub = 3; }
-                const int dx = j >= 3 ? j - 3 : j;
-                const int req = (j == nsub - 2 && ck + 1 < NCHUNK) ? ck + 1 : -1;
-                aim(q);
-                substep(F{}, F{}, q, dx, req);
-                if (j == nsub - 1) chunk_seam(); else if (req >= 0) seam_keep_halo(); else seam();
-            }
-            wbase = wbase0;
-            substep(F{}, T{}, NSEQ - 1, 2);
-        }
-#else
         substep(T{}, F{}, 0, 0); seam();
         substep(F{}, F{}, 1, 1, 1); seam_keep_halo();
         substep(F{}, F{}, 2, 2); chunk_seam();
@@ -934,13 +864,8 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
         substep(F{}, F{}, NSUB - 3, 0); seam();
         substep(F{}, F{}, NSUB - 2, 1); seam();
         substep(F{}, T{}, NSUB - 1, 2);
-#endif
         }
 
-#ifdef H16_TRACE
-        asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[1][1][3]));
-        tr_lap(tr_main);
-#endif
         {   // no barrier: the epilogue touches no LDS (round 4), so a wave stores while its siblings finish their MFMAs
             int lane_e;    // opaque copy of the lane id: keeps the epilogue's address arithmetic out of the item loop's registers
             asm volatile("v_mov_b32 %0, %1" : "=v"(lane_e) : "v"(tid & 63));
@@ -960,27 +885,15 @@ __global__ void __launch_bounds__(THREADS, F32IO ? 2 : 3) k_conv3x3_h16(const Ge
                 h16_epilogue<COUT, MODE>(a, acc, bias_v, n, y0, x0, wave, lane_e, cobase);
             }
         }
-#ifdef H16_TRACE
-        tr_lap(tr_epi);
-        ++tr_items;
-#endif
         if (!has_next) break;                                  // workgroup-uniform
         // ---- item boundary: the prefetched item becomes the current one ----
         n = n2; y0 = y02; x0 = x02; local = local2; nb = nb2;
-        if (H16_ABLATE) abl_on = true;
         rsrc_in = image_rsrc(n);
         __syncthreads();   // every wave has read its last fragments of this item: the halo planes may be written again
         halo_to_lds();     // its loads are younger than the B DMA issued with them: their arrival vouches for B buffer 0 as well
         decode_next();
         __syncthreads();
     }
-#ifdef H16_TRACE
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        trace[0] = tr_t0; trace[1] = tr_main; trace[2] = tr_epi; trace[3] = tr_bnd; trace[5] = tr_items;
-        trace[4] = __builtin_readcyclecounter();
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // layer_bench.hip — timing experiments on single layers of the forward (not part of the product).
 // Build: make -C celebrity_image_denoiser_amd/csrc tools     Run on the GPU box: ./layer_bench
 // Each variant is run ROUNDS times, interleaved with the others in one process; prints median ms
-// and algorithmic TFLOP/s.  ABLATE variants compute wrong results by design (see conv_kernels.h).
+// and algorithmic TFLOP/s.
 #include "../conv_kernels.h"
 #include "../wino64_kernels.h"
 #include "../wino42_kernels.h"
@@ -26,7 +26,7 @@ static float* dalloc(size_t n, float scale) {
     return d;
 }
 
-template <int CIN, int COUT, int MODE, int ABLATE, int WPS>
+template <int CIN, int COUT, int MODE>
 static Variant make(const char* name, int N, int H, int W, float* in, float* w, float* bias, float* out, float* pool) {
     GemmConvArgs a{};
     a.in = in; a.w = w; a.bias = bias; a.out = out; a.pool = pool;
@@ -37,10 +37,10 @@ static Variant make(const char* name, int N, int H, int W, float* in, float* w, 
     constexpr int NB = (MODE == 2 ? 4 * COUT : COUT) / NTILE;
     const int grid = 8 * a.tiles_per_xcd * NB;
     const double flops = 2.0 * CIN * COUT * (MODE == 2 ? 4 : 9) * (double)N * H * W;
-    return {name, [=](hipStream_t s) { hipLaunchKernelGGL((k_gemm_conv<CIN, COUT, MODE, ABLATE, WPS>), dim3(grid), dim3(THREADS), 0, s, a); }, flops};
+    return {name, [=](hipStream_t s) { hipLaunchKernelGGL((k_gemm_conv<CIN, COUT, MODE>), dim3(grid), dim3(THREADS), 0, s, a); }, flops};
 }
 
-template <int CIN, int COUT, bool POOL, int TC, int ABLATE>
+template <int CIN, int COUT, bool POOL, int TC>
 static Variant makew64(const char* name, int N, int H, int W, float* in, float* u, float* bias, float* out, float* pool) {
     WinoArgs a{};
     a.in = in; a.u = u; a.bias = bias; a.out = out; a.pool = pool;
@@ -60,10 +60,10 @@ static Variant makew64(const char* name, int N, int H, int W, float* in, float* 
     a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(a.tiles_x * a.tiles_y);
     const int grid = 8 * a.tiles_per_xcd * (COUT / WN2);
     const double flops = 2.0 * CIN * COUT * 9 * (double)N * H * W;   // algorithmic (direct) FLOPs
-    return {name, [=](hipStream_t s) { hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, TC, ABLATE>), dim3(grid), dim3(THREADS), 0, s, a); }, flops};
+    return {name, [=](hipStream_t s) { hipLaunchKernelGGL((k_wino64_conv<CIN, COUT, POOL, TC>), dim3(grid), dim3(THREADS), 0, s, a); }, flops};
 }
 
-template <int CIN, int COUT, bool POOL, int TC, int ABLATE>
+template <int CIN, int COUT, bool POOL, int TC>
 static Variant makew42(const char* name, int N, int H, int W, float* in, float* u, float* bias, float* out, float* pool) {
     WinoArgs a{};
     a.in = in; a.u = u; a.bias = bias; a.out = out; a.pool = pool;
@@ -79,7 +79,7 @@ static Variant makew42(const char* name, int N, int H, int W, float* in, float* 
     a.rcp_x = tile_rcp(a.tiles_x); a.rcp_xy = tile_rcp(a.tiles_x * a.tiles_y);
     const int grid = 8 * a.tiles_per_xcd * (COUT / WN2);
     const double flops = 2.0 * CIN * COUT * 9 * (double)N * H * W;   // algorithmic (direct) FLOPs
-    return {name, [=](hipStream_t s) { hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, TC, ABLATE>), dim3(grid), dim3(THREADS), 0, s, a); }, flops};
+    return {name, [=](hipStream_t s) { hipLaunchKernelGGL((k_wino42_conv<CIN, COUT, POOL, TC>), dim3(grid), dim3(THREADS), 0, s, a); }, flops};
 }
 
 int main(int argc, char** argv) {
@@ -101,101 +101,14 @@ int main(int argc, char** argv) {
     float* uB = dalloc((size_t)256 * 256 * 16, 0.05f);
     float* u42A = dalloc((size_t)128 * 64 * 24, 0.05f);
     float* u42B = dalloc((size_t)256 * 256 * 24, 0.05f);
-    v.push_back(make<128, 64, 0, 0, 2>("A direct 128->64@128", N, 128, 128, inA, wA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 0>("A wino64 base", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 1>("A wino64 no-dma", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 2>("A wino64 no-B-loads", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 4>("A wino64 no-A-build", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 16>("A wino64 no-global-stores", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 8>("A wino64 no-epilogue", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 15>("A wino64 mfma-only", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 47>("A wino64 mfma-only no-barrier", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 33>("A wino64 no-dma no-barrier", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 47 + 64>("A wino64 mfma-only no-prologue-dma", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew64<128, 64, false, 32, 128>("A wino64 no-dephase", N, 128, 128, inA, uA, bA, outA, poolA));
-    v.push_back(makew42<128, 64, false, 8, 0>("A wino42 base", N, 128, 128, inA, u42A, bA, outA, poolA));
-    v.push_back(makew42<128, 64, false, 8, 1>("A wino42 no-dma", N, 128, 128, inA, u42A, bA, outA, poolA));
-    v.push_back(makew42<128, 64, false, 8, 2>("A wino42 no-B-loads", N, 128, 128, inA, u42A, bA, outA, poolA));
-    v.push_back(makew42<128, 64, false, 8, 4>("A wino42 no-V-build", N, 128, 128, inA, u42A, bA, outA, poolA));
-    v.push_back(makew42<128, 64, false, 8, 8>("A wino42 no-epilogue", N, 128, 128, inA, u42A, bA, outA, poolA));
-    v.push_back(makew42<128, 64, false, 8, 15>("A wino42 mfma-only", N, 128, 128, inA, u42A, bA, outA, poolA));
-    v.push_back(makew42<256, 256, false, 8, 0>("B wino42 base", N, 32, 32, inB, u42B, bB, outB, nullptr));
-    v.push_back(makew42<256, 256, false, 8, 4>("B wino42 no-V-build", N, 32, 32, inB, u42B, bB, outB, nullptr));
-    v.push_back(makew42<256, 256, false, 8, 15>("B wino42 mfma-only", N, 32, 32, inB, u42B, bB, outB, nullptr));
-    v.push_back(make<256, 256, 0, 0, 2>("B direct 256->256@32", N, 32, 32, inB, wB, bB, outB, nullptr));
-    v.push_back(makew64<256, 256, false, 16, 0>("B wino64 base", N, 32, 32, inB, uB, bB, outB, nullptr));
-    v.push_back(makew64<256, 256, false, 16, 15>("B wino64 mfma-only", N, 32, 32, inB, uB, bB, outB, nullptr));
-    {   // up1 shape: ConvT 128 -> 64 on 64x64 inputs (output 128x128x64); reuse inA (>= N*64*64*128) and outA
-        v.push_back(make<128, 64, 2, 0, 2>("T convT 128->64@64 base", N, 64, 64, inA, wA, bA, outA, nullptr));
-        v.push_back(make<128, 64, 2, 1, 2>("T no-halo-prefetch", N, 64, 64, inA, wA, bA, outA, nullptr));
-        v.push_back(make<128, 64, 2, 2, 2>("T no-B-loads", N, 64, 64, inA, wA, bA, outA, nullptr));
-        v.push_back(make<128, 64, 2, 8, 2>("T no-stores", N, 64, 64, inA, wA, bA, outA, nullptr));
-        v.push_back(make<128, 64, 2, 15, 2>("T mfma-only", N, 64, 64, inA, wA, bA, outA, nullptr));
-    }
-    if (argc > 2 && std::string(argv[2]) == "trace") {
-        // One launch of the transposed conv (up1 shape) with s_memtime stamps per workgroup: where does a workgroup's time go,
-        // and what happens on a CU between one workgroup's stores and the next one's first MFMA?
-        const int H = 64, W = 64;
-        const int tiles = N * ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H - 1) / TILE_H);
-        const int nwg = 8 * ((tiles + 7) / 8) * 4;
-        unsigned long long* tr; CK(hipMalloc(&tr, (size_t)nwg * 8 * 8)); CK(hipMemset(tr, 0, (size_t)nwg * 8 * 8));
-        Variant t = make<128, 64, 2, 16, 2>("trace", N, H, W, inA, wA, bA, outA, reinterpret_cast<float*>(tr));
-        t.run(s); CK(hipStreamSynchronize(s));    // warm
-        CK(hipMemset(tr, 0, (size_t)nwg * 8 * 8));
-        t.run(s); CK(hipStreamSynchronize(s));
-        std::vector<unsigned long long> h((size_t)nwg * 8);
-        CK(hipMemcpy(h.data(), tr, h.size() * 8, hipMemcpyDeviceToHost));
-        std::FILE* f = std::fopen("gpurun_out/convt_trace.csv", "w");
-        std::fprintf(f, "wg,t_start,t_main,t_main_end,t_stores_issued,t_stores_done,hw_id,xcc_id\n");
-        for (int i = 0; i < nwg; ++i)
-            if (h[(size_t)i * 8])
-                std::fprintf(f, "%d,%llu,%llu,%llu,%llu,%llu,%llu,%llu\n", i, h[(size_t)i * 8], h[(size_t)i * 8 + 1], h[(size_t)i * 8 + 2],
-                             h[(size_t)i * 8 + 3], h[(size_t)i * 8 + 6], h[(size_t)i * 8 + 4], h[(size_t)i * 8 + 5]);
-        std::fclose(f);
-        std::printf("trace written: %d workgroups\n", nwg);
-        // (the F(4x2) kernel's phase trace lives in tools/w42_bench)
-        {   // the same for the dominant Winograd launch (upconv1.0 shape)
-            const int nwg2 = 8 * ((N * 2 * 64 + 7) / 8);
-            unsigned long long* tr2; CK(hipMalloc(&tr2, (size_t)nwg2 * 16 * 8)); CK(hipMemset(tr2, 0, (size_t)nwg2 * 16 * 8));
-            Variant w = makew64<128, 64, false, 32, 256>("trace64", N, 128, 128, inA, uA, bA, outA, reinterpret_cast<float*>(tr2));
-            w.run(s); CK(hipStreamSynchronize(s));
-            CK(hipMemset(tr2, 0, (size_t)nwg2 * 16 * 8));
-            w.run(s); CK(hipStreamSynchronize(s));
-            std::vector<unsigned long long> h2((size_t)nwg2 * 16);
-            CK(hipMemcpy(h2.data(), tr2, h2.size() * 8, hipMemcpyDeviceToHost));
-            std::FILE* f2 = std::fopen("gpurun_out/wino64_trace.csv", "w");
-            std::fprintf(f2, "wg,t_start,t_main,t_main_end,t_stores_issued,t_stores_done,hw_id,xcc_id,t_table,t_dma_issued,t_dma_landed,t_dma_all,t_ep_b1,t_ep_b2,t_ep_b3,t_dma0,t_dma1\n");
-            for (int i = 0; i < nwg2; ++i) {
-                const unsigned long long* r = h2.data() + (size_t)i * 16;
-                if (r[0])
-                    std::fprintf(f2, "%d,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu\n", i, r[0], r[1], r[2], r[3], r[6], r[4], r[5],
-                                 r[8], r[9], r[10], r[11], r[12], r[13], r[14], r[15], r[7]);
-            }
-            std::fclose(f2);
-            std::printf("wino64 trace written: %d workgroups\n", nwg2);
-            // main-loop duration (stamps 1 -> 2) with one component removed at a time
-            auto main_median = [&](Variant v2, const char* nm) {
-                (void)hipMemset(tr2, 0, (size_t)nwg2 * 16 * 8);
-                v2.run(s); (void)hipStreamSynchronize(s);
-                (void)hipMemset(tr2, 0, (size_t)nwg2 * 16 * 8);
-                v2.run(s); (void)hipStreamSynchronize(s);
-                (void)hipMemcpy(h2.data(), tr2, h2.size() * 8, hipMemcpyDeviceToHost);
-                std::vector<unsigned long long> d, tot;
-                for (int i = 0; i < nwg2; ++i) { const unsigned long long* r = h2.data() + (size_t)i * 16; if (r[0] && r[2] > r[1]) { d.push_back(r[2] - r[1]); tot.push_back((r[3] ? r[3] : r[2]) - r[0]); } }
-                std::sort(d.begin(), d.end()); std::sort(tot.begin(), tot.end());
-                std::printf("%-34s main loop median %6llu cycles, workgroup (start -> stores issued) %6llu\n", nm, d[d.size() / 2], tot[tot.size() / 2]);
-            };
-            float* trf = reinterpret_cast<float*>(tr2);
-            main_median(makew64<128, 64, false, 32, 256>("", N, 128, 128, inA, uA, bA, outA, trf), "wino64 base");
-            main_median(makew64<128, 64, false, 32, 256 + 1>("", N, 128, 128, inA, uA, bA, outA, trf), "wino64 no DMA after prologue");
-            main_median(makew64<128, 64, false, 32, 256 + 2>("", N, 128, 128, inA, uA, bA, outA, trf), "wino64 B loaded once");
-            main_median(makew64<128, 64, false, 32, 256 + 4>("", N, 128, 128, inA, uA, bA, outA, trf), "wino64 A built once");
-            main_median(makew64<128, 64, false, 32, 256 + 32>("", N, 128, 128, inA, uA, bA, outA, trf), "wino64 no per-chunk barrier");
-            main_median(makew64<128, 64, false, 32, 256 + 7>("", N, 128, 128, inA, uA, bA, outA, trf), "wino64 MFMA + barriers only");
-            main_median(makew64<128, 64, false, 32, 256 + 39>("", N, 128, 128, inA, uA, bA, outA, trf), "wino64 MFMA only");
-        }
-        return 0;
-    }
+    v.push_back(make<128, 64, 0>("A direct 128->64@128", N, 128, 128, inA, wA, bA, outA, poolA));
+    v.push_back(makew64<128, 64, false, 32>("A wino64 base", N, 128, 128, inA, uA, bA, outA, poolA));
+    v.push_back(makew42<128, 64, false, 8>("A wino42 base", N, 128, 128, inA, u42A, bA, outA, poolA));
+    v.push_back(makew42<256, 256, false, 8>("B wino42 base", N, 32, 32, inB, u42B, bB, outB, nullptr));
+    v.push_back(make<256, 256, 0>("B direct 256->256@32", N, 32, 32, inB, wB, bB, outB, nullptr));
+    v.push_back(makew64<256, 256, false, 16>("B wino64 base", N, 32, 32, inB, uB, bB, outB, nullptr));
+    // up1 shape: ConvT 128 -> 64 on 64x64 inputs (output 128x128x64); reuse inA (>= N*64*64*128) and outA
+    v.push_back(make<128, 64, 2>("T convT 128->64@64 base", N, 64, 64, inA, wA, bA, outA, nullptr));
     std::vector<std::vector<float>> ms(v.size());
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (auto& x : v) x.run(s);   // warm-up

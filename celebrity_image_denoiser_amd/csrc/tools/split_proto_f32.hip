@@ -1,4 +1,4 @@
-// Experiment (round 4), third form of the split-operand prototype (see split_proto.hip): k_conv3x3_h16<..., F32IO = true> reads and writes the FP32
+// Experiment (round 4), third form of the split-operand prototype (the first two are recorded in profiles/r04_split_operand_prototype.txt): k_conv3x3_h16<..., F32IO = true> reads and writes the FP32
 // tensors of the fp32 path — a drop-in shape for the Winograd launches.  While staging a 32-channel chunk of the halo tile it splits every fp32 value into
 // hi = half(x) and lo = half(x - hi) (two sets of LDS planes), runs nine sub-steps per chunk (hi_x.hi_w, hi_x.lo_w, lo_x.hi_w per tap column; the host packs the
 // weight sub-chunks in that order) on v_mfma_f32_16x16x32_f16 with fp32 accumulators, and stores fp32 (16 bytes per lane and pixel) — 66.6 KiB of LDS, two workgroups per CU.

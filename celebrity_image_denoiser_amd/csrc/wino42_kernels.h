@@ -86,14 +86,9 @@ __device__ __forceinline__ void w42_out4(const float (&m)[6], float (&y)[4]) {
     y[3] = __builtin_fmaf(3.375f, d34, __builtin_fmaf(0.421875f, d12, m[5]));
 }
 
-// ABLATE (timing experiments only, tools/layer_bench; wrong results when non-zero): 1 no DMA after the prologue, 2 B quads loaded once,
-// 4 V built once, 8 no epilogue, 256 s_memtime phase sums of thread 0 into a.zout (results stay correct, non-ZOUT layers).
-template <int CIN, int COUT, bool POOL, int TC, int ABLATE = 0, bool ZOUT = false>
+template <int CIN, int COUT, bool POOL, int TC, bool ZOUT = false>
 __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
     static_assert(!ZOUT || (COUT == 64 && !POOL), "ZOUT contracts exactly the 64 channels of the workgroup's column block");
-#ifndef CID_EXPERIMENTS
-    static_assert(ABLATE == 0, "ablation/trace variants are built only by csrc/tools (-DCID_EXPERIMENTS)");
-#endif
     using Gm = W42Geom<TC>;
     constexpr int TRW = Gm::TRW, RS = Gm::RS, QS = Gm::QS, BUF = Gm::BUF, NROUND = Gm::NROUND, RW = Gm::RW;
     constexpr int NCHUNK = CIN / WK, NU = 2 * NCHUNK;
@@ -139,14 +134,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // = row a
     const int m16 = lane & 15, g = lane >> 4;
     const int tr = m16 / TC, tc = m16 - tr * TC;
-    // ABLATE & 256 (tools/w42_bench): thread 0 sums, over the workgroup's tiles, the shader cycles spent in the main loop, the
-    // epilogue and the tile boundary, into a.zout[blockIdx.x * 8 ...] (non-ZOUT variants): start, sums, end, tile count
-    unsigned long long* trace = (ABLATE & 256) ? reinterpret_cast<unsigned long long*>(a.zout) + (size_t)blockIdx.x * 8 : nullptr;
-    unsigned long long tr_start = 0, tr_main = 0, tr_epi = 0, tr_bnd = 0, tr_t = 0, tr_tiles = 0;
-    if (ABLATE & 256) tr_start = tr_t = __builtin_readcyclecounter();
-    auto tr_lap = [&](unsigned long long& acc) {
-        if (ABLATE & 256) { const unsigned long long now = __builtin_readcyclecounter(); acc += now - tr_t; tr_t = now; }
-    };
 
     // ---- LDS-DMA sources (same table format as k_wino64_conv) ----
     const size_t img_elems = (size_t)a.Hin * a.Win * a.in_ps;
@@ -345,11 +332,11 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
         constexpr int RB = FIRST ? 2 : PAR, OB = FIRST ? 1 : 1 - PAR, TB = FIRST ? 0 : PAR;   // read / other / DMA-target buffer
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const bool build = ((k == 0) || MORE) && !(ABLATE & 4);
+            const bool build = (k == 0) || MORE;
             const int nhalf = (k == 0) ? 2 * boff(RB) : 2 * boff(OB);   // the next unit: this buffer's other half, or the other buffer
             const int gu = ck * 2 + k;
             if (build) flip_half();
-            if (FIRST && k == 0 && !(ABLATE & 1)) dma_chunk(1, 1);   // chunk 1 lands under unit 0
+            if (FIRST && k == 0) dma_chunk(1, 1);   // chunk 1 lands under unit 0
 #pragma unroll
             for (int grp = 0; grp < 12; ++grp) {
                 const int e2 = grp / 6, b = grp - 6 * e2;
@@ -359,10 +346,10 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
                     if (grp == 8) make_v(vnxt, 0);
                     if (grp == 10) make_v(vnxt, 1);
                 }
-                if (DMA && k == 1 && grp >= 6 && grp - 6 < RW && !(ABLATE & 1)) dma_round(rsrc_in, tpar, TB, ck + 2, grp - 6);
+                if (DMA && k == 1 && grp >= 6 && grp - 6 < RW) dma_round(rsrc_in, tpar, TB, ck + 2, grp - 6);
                 // next tile, chunk 0 -> X.  Only if there is one (workgroup-uniform: a scalar branch): one item per workgroup and a walker's
                 // last item used to issue the RW rounds against an all-sentinel offset table
-                if (!MORE && k == 1 && grp >= 6 && grp - 6 < RW && !(ABLATE & 1) && has_next) dma_round(rsrc_next, tpar ^ 1, 2, 0, grp - 6);
+                if (!MORE && k == 1 && grp >= 6 && grp - 6 < RW && has_next) dma_round(rsrc_next, tpar ^ 1, 2, 0, grp - 6);
 #pragma unroll
                 for (int cg = 0; cg < 4; ++cg) {
 #ifdef CID_W42_ASM_MFMA
@@ -383,8 +370,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
                 }
                 // ring slot b: refilled with the quad six uses ahead (the other k-step of this unit, the next unit's first, or — at
                 // the end of a tile — the first quads of the next tile: same column block, so the stream simply starts over)
-                if (ABLATE & 2) {}
-                else if (grp + RING < 12) bq[grp % RING] = b_load(gu, grp + RING);
+                if (grp + RING < 12) bq[grp % RING] = b_load(gu, grp + RING);
                 else if (MORE || k == 0) bq[grp % RING] = b_load(gu + 1, grp + RING - 12);
                 else bq[grp % RING] = b_load(0, grp + RING - 12, true);
                 __builtin_amdgcn_sched_barrier(0);
@@ -411,7 +397,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
     using F = std::false_type;
     for (;;) {   // ---- one tile per iteration ----
     tile_scalars();
-    tr_lap(tr_bnd);
     // The main loop runs at wave priority 1, epilogue and tile boundary at 0: when the sibling workgroup's wave on this SIMD is in its
     // epilogue, this wave's MFMA stream goes first and the epilogue's vector instructions take the gaps (same-box +0.85 % on the forward,
     // -2 % on the CIN = 64 layers and upconv1.0; the opposite assignment +-0: profiles/r03_ab_wino42_walk.txt).  Round 2 had measured
@@ -426,26 +411,10 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
     chunk(F{}, T{}, F{}, F{}, NCHUNK - 2);
     chunk(F{}, F{}, F{}, T{}, NCHUNK - 1);
 
-    tr_lap(tr_main);
-    ++tr_tiles;
     __builtin_amdgcn_s_setprio(0);
 #ifdef CID_W42_ASM_MFMA
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7");   // MFMA write -> VALU read of the accumulators (up to 18 wait states for an 8-pass MFMA)
 #endif
-    if (ABLATE & 8) {   // keep the accumulators alive without the epilogue
-        float sum = 0.f;
-#pragma unroll
-        for (int b = 0; b < 6; ++b)
-#pragma unroll
-            for (int cg = 0; cg < 4; ++cg) sum += acc[b][cg][0] + acc[b][cg][1] + acc[b][cg][2] + acc[b][cg][3];
-        if (sum == 123.456f) a.out[tid] = sum;
-        if (!has_next) break;
-        load_slot_entries();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        next_tile();
-        continue;
-    }
     // ---- output transform ----
     // Everything lane-dependent below is derived from an opaque copy of the lane id made here, per tile: otherwise hipcc hoists the
     // epilogue's address arithmetic (staging and exchange addresses, store offsets) out of the tile loop and keeps it in VGPRs
@@ -620,16 +589,10 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
     // (three in the ZOUT variant, whose `return` leaves the lambda after the third).  s_barrier is not PC-matched, so waves meeting at
     // different program counters is what the hardware does anyway; what must hold — and does, by construction of the one lambda
     // body — is the equal COUNT.
-    tr_lap(tr_epi);
     if (!has_next) break;                                     // workgroup-uniform
     __syncthreads();   // every wave has left the exchange / staging area: buffers 0 / 1 may be written again
     next_tile();
     }   // ---- next tile ----
-    if ((ABLATE & 256) && tid == 0) {
-        trace[0] = tr_start; trace[1] = tr_main; trace[2] = tr_epi; trace[3] = tr_bnd; trace[5] = tr_tiles;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        trace[4] = __builtin_readcyclecounter();
-    }
 }
 
 }  // namespace cid

@@ -68,22 +68,15 @@ struct WinoArgs {
 
 constexpr int WN2 = 64;       // output channels per workgroup
 
-// ABLATE (timing experiments only, tools/layer_bench; wrong results when non-zero): 1 no DMA after the prologue,
-// 2 B quads loaded once, 4 A operand built once, 8 no epilogue, 16 epilogue without the global stores, 32 no per-chunk
-// barrier, 64 no prologue DMA, 128 no de-phasing of the two workgroups of a CU, 256 s_memtime trace into a.pool (results stay correct).
-//
 // ZOUT (upconv1[0], the producer of the last layer's input): instead of storing its 64 output channels the workgroup
 // applies the channel contraction of the NEXT layer, upconv1[2] = Conv2d(64, 3, 3, padding=1) (app.py:77), to them while they
 // are still in LDS:  z[p][3*tap + co] = sum_ci relu(y[p][ci]) * W2[co][ci][tap]  — a [pixels x 64] x [64 x 27] product that has no
 // halo, 32 more MFMAs per wave after the 512 of the main loop — and stores z as 27 planes [N, 27, H, W].  The last layer is
 // then only the nine-tap shifted sum, bias and tanh (k_conv_tail_z): the 64-channel tensor (268 B per pixel written here and
 // read there) never exists, 108 B per pixel of z take its place.
-template <int CIN, int COUT, bool POOL, int TC, int ABLATE = 0, bool ZOUT = false>
+template <int CIN, int COUT, bool POOL, int TC, bool ZOUT = false>
 __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
     static_assert(!ZOUT || (COUT == 64 && !POOL), "ZOUT contracts exactly the 64 channels of one column-block pair");
-#ifndef CID_EXPERIMENTS
-    static_assert(ABLATE == 0, "ablation/trace variants are built only by csrc/tools (-DCID_EXPERIMENTS)");
-#endif
     constexpr int TRW = 32 / TC;                 // tile rows per workgroup
     constexpr int LW = 2 * TC + 2, LH = 2 * TRW + 2;
     // LDS row stride in pixels.  TC=16 puts two tile rows in one 32-lane read; their slot offset (2 rows x LWS x 5 slots) must be
@@ -121,21 +114,13 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
     const int i = lane & 31, h = lane >> 5;
     const int tr = i / TC, tc = i - tr * TC;
 
-    // ABLATE bit 8 (trace experiment, results stay correct, non-POOL layers): thread 0 writes s_memtime stamps + HW_ID to a.pool
-    unsigned long long* trace = (ABLATE & 256) ? reinterpret_cast<unsigned long long*>(a.pool) + (size_t)blockIdx.x * 16 : nullptr;
-    if ((ABLATE & 256) && tid == 0) {
-        unsigned hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        trace[0] = __builtin_readcyclecounter(); trace[4] = hwid; trace[5] = xcc;
-    }
     const float bias_v = a.bias[nb * WN2 + (wave >> 1) * 32 + i];   // epilogue role of wave w: column block w>>1, tiles 16*(w&1)..+16
 
     if (blockIdx.x < 2 * 256) {   // de-phase the two workgroups of a CU once
         unsigned hwid;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         // Measured on this kernel (tools/layer_bench): without the de-phasing 2.40 ms, with it 2.27 ms (upconv1.0 shape).
-        if ((hwid & 1u) && !(ABLATE & 128)) {   // bit 7 (experiment): no de-phasing
+        if (hwid & 1u) {
             for (int sl = 0; sl < NCHUNK / 2; ++sl) __builtin_amdgcn_s_sleep(127);
         }
     }
@@ -170,7 +155,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
             voff[m] = (off & keep) | (0x7ffffff0u & ~keep);
         }
     }
-    if ((ABLATE & 256) && tid == 0) trace[8] = __builtin_readcyclecounter() + (voff[0] & 0u);   // slot table arrived, offsets formed
     const unsigned lds_base = (unsigned)(uintptr_t)(&lds[0]);
     auto dma_round = [&](int buf, int ck, int m) {   // round m of this wave: 64 slots of chunk ck -> LDS buffer `buf`
         if (wave + 4 * m < NROUND) {                   // wave-uniform
@@ -203,19 +187,14 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
     // ---- prologue: chunks 0 and 1 -> both LDS buffers; B of unit 0 ----
     // Only what the first unit needs is requested before the first MFMA: the B quads of unit 0 (L2 hits) and chunk 0.
     // Under load the vector-memory instructions of a cold prologue take ~1k cycles EACH to issue (s_memtime trace,
-    // tools/trace_stats.py): requesting chunk 1 here as well kept the workgroup out of its main loop 4k cycles longer;
+    // profiles/r01_wino64_trace_stats.txt): requesting chunk 1 here as well kept the workgroup out of its main loop 4k cycles longer;
     // it is requested at the start of chunk 0's unit 0 instead and has that unit to land.
     f32x4 bq[2][4];
 #pragma unroll
     for (int q = 0; q < 8; ++q) bq[q >> 2][q & 3] = b_load(0, q);
-    if ((ABLATE & 256) && tid == 0) trace[7] = __builtin_readcyclecounter();    // B requested
-    if (!(ABLATE & 64)) dma_chunk(0, 0);   // bit 6 (experiment): no prologue DMA
-    if ((ABLATE & 256) && tid == 0) trace[15] = __builtin_readcyclecounter();   // chunk 0 requested
-    if ((ABLATE & 256) && tid == 0) trace[9] = __builtin_readcyclecounter();    // DMA and B loads issued
+    dma_chunk(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the DMA is invisible to hipcc's own wait counting
-    if ((ABLATE & 256) && tid == 0) trace[10] = __builtin_readcyclecounter();   // ... and landed (this wave)
     __syncthreads();
-    if ((ABLATE & 256) && tid == 0) trace[11] = __builtin_readcyclecounter();   // ... in every wave
 
     auto read_cols = [&](f32x4 (&xq)[2], f32x4 (&yq)[2], int bufbase, int g2, int c0) {
 #pragma unroll
@@ -261,8 +240,8 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
             const int nbuf = (k == 0) ? cur : nxt, ng2 = 1 - k;
             f32x4 xq[2], yq[2], t[4];
             // this buffer's last reads (building unit 1) happened during unit 0, before the barrier below
-            if (FIRST && k == 0 && !(ABLATE & 65)) dma_chunk(1, 1);          // chunk 1: see the prologue
-            const bool build = have_next_unit && !(ABLATE & 4);
+            if (FIRST && k == 0) dma_chunk(1, 1);   // chunk 1: see the prologue
+            const bool build = have_next_unit;
             // the eight LDS reads of the next unit's A operand go out two per MFMA group (groups 0-3), not four at a time
             auto read_col = [&](int slot, int c) {   // x and y of patch column c into pair slot `slot`
                 xq[slot] = lds[nbuf + xb + 2 * ng2 + col_off(c)];
@@ -290,7 +269,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
                     }
                 };
                 mfma(0);
-                if (DMA && k == 1 && !(ABLATE & 1)) {
+                if (DMA && k == 1) {
 #pragma unroll
                     for (int j = 0; j < DMA_PER_GROUP; ++j)
                         if (DMA_PER_GROUP * g + j < RW) dma_round(PAR, ck + 2, DMA_PER_GROUP * g + j);
@@ -318,10 +297,10 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 mfma(3);
-                if (have_next_unit && !(ABLATE & 2)) bq[nt][e] = b_load(ck * 2 + k + 1, nt * 4 + e);
+                if (have_next_unit) bq[nt][e] = b_load(ck * 2 + k + 1, nt * 4 + e);
                 __builtin_amdgcn_sched_barrier(0);
                 } else {
-                if (DMA && k == 1 && !(ABLATE & 1)) {
+                if (DMA && k == 1) {
 #pragma unroll
                     for (int j = 0; j < DMA_PER_GROUP; ++j)
                         if (DMA_PER_GROUP * g + j < RW) dma_round(PAR, ck + 2, DMA_PER_GROUP * g + j);
@@ -349,7 +328,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
                         acc[nt][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(vcur[b][e], bq[nt][e][b], acc[nt][b], 0, 0, 0);
                     }
                 }
-                if (have_next_unit && !(ABLATE & 2)) bq[nt][e] = b_load(ck * 2 + k + 1, nt * 4 + e);
+                if (have_next_unit) bq[nt][e] = b_load(ck * 2 + k + 1, nt * 4 + e);
                 __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -357,7 +336,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
 #pragma unroll
                 for (int b = 0; b < 4; ++b) vcur[b] = vnxt[b];
             }
-            if (MORE && k == 0 && !(ABLATE & 32)) {   // bit 5 (experiment): no per-chunk barrier
+            if (MORE && k == 0) {
                 // The DMA of chunk ck+1 was issued one chunk ago; the only vector-memory operations younger than it
                 // are the B refills of the previous unit (consumed above) and of this one: at most 8 outstanding
                 // means every DMA of this wave has landed; past the barrier every wave's has.
@@ -369,7 +348,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
     };
     using T = std::true_type;
     using F = std::false_type;
-    if ((ABLATE & 256) && tid == 0) trace[1] = __builtin_readcyclecounter();
     chunk(T{}, T{}, T{}, F{}, 0);
     chunk(F{}, T{}, std::integral_constant<bool, (NCHUNK > 3)>{}, T{}, 1);
     for (int ck = 2; ck + 2 < NCHUNK; ck += 2) {
@@ -379,28 +357,15 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
     }
     chunk(F{}, T{}, F{}, F{}, NCHUNK - 2);
     chunk(F{}, F{}, F{}, T{}, NCHUNK - 1);
-    if ((ABLATE & 256) && tid == 0) trace[2] = __builtin_readcyclecounter();
 
     // ---- output transform ----
     // Four code versions selected by a wave-uniform switch, so that "is this my own row / my own block" is a
     // compile-time fact (no selects).  Column transform of this wave's row: m'[nt][b'] (b' = 0,1);
     // A^T = [[1,1,1,0],[0,1,-1,-1]].
-    if (ABLATE & 8) {   // keep the accumulators alive without the epilogue
-        float sum = 0.f;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sum += acc[nt][b][r];
-        if (sum == 123.456f) a.out[tid] = sum;
-        return;
-    }
     auto epilogue = [&](auto wave_tag) {
         constexpr int W = decltype(wave_tag)::value;
         constexpr int NT_W = W >> 1, RH = W & 1;                // epilogue role: column block, tile half
         __syncthreads();                                        // raw tiles are dead: LDS becomes the exchange area
-        if ((ABLATE & 256) && tid == 0) trace[12] = __builtin_readcyclecounter();
         typedef float f32x2 __attribute__((ext_vector_type(2)));
         // exchange block (src row a, dst wave w): 8 registers x 64 lanes of f32x2 = 4 KiB at ((a*4 + w) * 512) f32x2
         f32x2* ex = reinterpret_cast<f32x2*>(lds);
@@ -417,7 +382,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
                 else ex[(W * 4 + w) * 512 + (r & 7) * 64 + lane] = m;
             }
         __syncthreads();
-        if ((ABLATE & 256) && tid == 0) trace[13] = __builtin_readcyclecounter();
         float y[2][2][8];   // [output row a'][column b'][register]
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) {
@@ -431,7 +395,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
             }
         }
         __syncthreads();                                        // exchange area is dead: reuse as store staging
-        if ((ABLATE & 256) && tid == 0) trace[14] = __builtin_readcyclecounter();
         float* stg = reinterpret_cast<float*>(lds) + W * (64 * WS32);
         // register rr of this wave is tile  T = 16*RH + (rr&3) + 8*(rr>>2) + 4*h  of the workgroup's 32
         auto tl_of = [&](int rr) { return (rr & 3) + 8 * (rr >> 2) + 4 * h; };
@@ -479,7 +442,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
             // lane (column j = i, half h) holds z[pixel (r&3) + 8*(r>>2) + 4*h][j]: registers 4q..4q+3 are four consecutive
             // pixels of one row of plane j — one 16-byte store each (H, W are multiples of 4: a group is inside or outside)
             const int yy = wy + NT_W;
-            if (i < 27 && yy < a.Hs && !(ABLATE & 16)) {
+            if (i < 27 && yy < a.Hs) {
                 float* zrow = a.zout + (((size_t)n * 27 + i) * a.Hs + yy) * a.Ws;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -492,9 +455,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
         wave_lds_fence();
         const int cbase = a.out_coff + nb * WN2 + NT_W * 32;
         const bool full = (y0 + 2 * TRW <= a.Hs) && (x0 + 2 * TC <= a.Ws);
-        if (ABLATE & 16) {
-            // experiment: everything but the global stores
-        } else if (full) {
+        if (full) {
             const int lane_off = (lane >> 3) * a.out_ps + (lane & 7) * 4;
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
@@ -533,11 +494,6 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino64_conv(const WinoArgs a) {
         case 1: epilogue(std::integral_constant<int, 1>{}); break;
         case 2: epilogue(std::integral_constant<int, 2>{}); break;
         default: epilogue(std::integral_constant<int, 3>{}); break;
-    }
-    if ((ABLATE & 256) && tid == 0) {
-        trace[3] = __builtin_readcyclecounter();                 // this wave's stores are issued
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        trace[6] = __builtin_readcyclecounter();                 // ... and written back
     }
 }
 
