@@ -11,7 +11,9 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     enhance_images(ckpt, in_dir, out_dir)   the reference's directory eval harnesses (denoisegan_eval.py / denoise_eavl_iter.py)
     quality(a, b) / evaluate(denoised, clean)   PSNR / SSIM / MS-SSIM of device batches (the trainer's per-batch evaluation)
     add_noise(clean_u8, kind)     the trainer's five noise kinds on device uint8 batches; evaluate_noise_types(model, clean_u8)
-    DenoiseDiscriminator() / load_discriminator(ckpt)   the trainer's discriminator (eval or train-mode BatchNorm)
+    DenoiseDiscriminator() / load_discriminator(ckpt)   the trainer's discriminator (eval or train-mode BatchNorm); with
+                                  autograd=True its forward is differentiable (HIP backward pass): d_loss.backward() and the
+                                  adversarial gradient on the denoised batch, for a stock torch.optim optimizer
     trainer_losses(D, denoised, clean)                  the trainer's d_loss / g_loss / content_loss / adv_loss of one batch
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h

@@ -10,6 +10,7 @@
 #include "quality_kernels.h"
 #include "noise_kernels.h"
 #include "disc_kernels.h"
+#include "disc_bwd_kernels.h"
 
 #include <dlfcn.h>
 
@@ -1642,6 +1643,124 @@ int dfail(cid_disc_t d, int code, const std::string& msg) {
     if (d) d->err = msg;
     return code;
 }
+
+// Where one forward keeps its tensors: two overlapping workspace regions (cid_disc_forward) or a per-call buffer (cid_disc_forward_saved).
+struct DiscBufs {
+    float *a0, *z2, *z5, *z8;
+    float* st[3];      // (scale, shift) pairs of the three BatchNorms
+    double* mi[3];     // (mean, invstd) pairs, or null
+    double* slab[3];   // train mode: per-tile partial sums
+};
+
+// The argument checks every forward entry point shares, in the order cid.h documents; `buf` is its workspace or saved buffer.
+int disc_check_forward(cid_disc_t d, const char* fn, const void* in, int in_fmt, const float* out, int N, int H, int W,
+                       const cid_disc_bn* bn, int training, const void* buf, DiscPlan& p) {
+    const std::string f = std::string(fn) + ": ";
+    if (!in || !out || !bn || !buf) return dfail(d, CID_ERR_INVALID, f + "null pointer");
+    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return dfail(d, CID_ERR_INVALID, f + "unknown input format");
+    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)out & 3))
+        return dfail(d, CID_ERR_INVALID, f + "misaligned fp32 operand");
+    if (training != 0 && training != 1) return dfail(d, CID_ERR_INVALID, f + "training must be 0 or 1");
+    for (int l = 0; l < 3; ++l) {
+        const cid_disc_bn& b = bn[l];
+        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || (training && !b.num_batches_tracked))
+            return dfail(d, CID_ERR_INVALID, f + "null BatchNorm pointer");
+        if (!disc_finite_nonneg(b.eps)) return dfail(d, CID_ERR_INVALID, f + "eps must be finite and >= 0");
+        if (training && !(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
+            return dfail(d, CID_ERR_INVALID, f + "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
+    }
+    if (disc_plan(N, H, W, training, p) != CID_OK)
+        return dfail(d, CID_ERR_SHAPE, training && N >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL
+                                           ? "Expected more than 1 value per channel when training"
+                                           : f + "input shape not accepted (N, H, W >= 1, H*W < 2^31)");
+    return CID_OK;
+}
+
+// The forward's launch sequence on checked arguments.
+int disc_forward_run(cid_disc_t d, const char* fn, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn,
+                     int training, const DiscPlan& p, const DiscBufs& b, hipStream_t s) {
+    const float* blob = d->dev_blob;
+    const auto herr = [&](const char* what) { return dfail(d, CID_ERR_HIP, std::string(fn) + ": " + what + ": " + hipGetErrorString(hipGetLastError())); };
+
+    if (!training) {
+        DiscBnEvalArgs e{};
+        for (int l = 0; l < 3; ++l) {
+            e.gamma[l] = bn[l].gamma;
+            e.beta[l] = bn[l].beta;
+            e.running_mean[l] = bn[l].running_mean;
+            e.running_var[l] = bn[l].running_var;
+            e.eps[l] = bn[l].eps;
+            e.st[l] = b.st[l];
+            e.C[l] = kDiscBnC[l];
+            e.mi[l] = b.mi[l];
+        }
+        hipLaunchKernelGGL(k_disc_bn_eval, dim3(3), dim3(128), 0, s, e);
+        if (hipPeekAtLastError() != hipSuccess) return herr("bn_eval");
+    }
+    // layer 0
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        DiscConv0Args a{in, b.a0, blob + kDiscBlob.off[0], H, W, n0};
+        const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
+        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_conv0<true>, grid, dim3(D_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_disc_conv0<false>, grid, dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("conv0");
+    }
+    const auto stats = [&](int l, long long pix) {
+        DiscStatsArgs a{};
+        a.slab = b.slab[l];
+        a.rows = (long long)N * p.tiles[l];
+        a.count = (double)N * (double)pix;
+        a.gamma = bn[l].gamma;
+        a.beta = bn[l].beta;
+        a.running_mean = bn[l].running_mean;
+        a.running_var = bn[l].running_var;
+        a.num_batches_tracked = reinterpret_cast<const long long*>(bn[l].num_batches_tracked);
+        a.eps = bn[l].eps;
+        a.momentum = bn[l].momentum == CID_DISC_MOMENTUM_NONE ? -1.0 : bn[l].momentum;
+        a.st = b.st[l];
+        a.mi = b.mi[l];
+        hipLaunchKernelGGL(k_disc_bn_stats, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
+        return hipPeekAtLastError();
+    };
+    const auto conv_args = [&](const float* src, float* dst, int ci, const float* st_in, int l, int Hin, int Win, int Ho, int Wo) {
+        DiscConvArgs a{};
+        a.in = src;
+        a.out = dst;
+        a.w = blob + kDiscBlob.off[ci];
+        a.st_in = st_in;
+        a.slab = training ? b.slab[l] : nullptr;
+        a.rows = (long long)N * p.tiles[l];
+        a.Hin = Hin;
+        a.Win = Win;
+        a.Ho = Ho;
+        a.Wo = Wo;
+        return a;
+    };
+    // layer 2 (reads a0, writes z2), BN3
+    if (disc_conv_launch<64, 64, 2, false>(conv_args(b.a0, b.z2, 1, nullptr, 0, H, W, p.H2, p.W2), 0, p, N, training, s) != hipSuccess)
+        return herr("conv2");
+    if (training && stats(0, (long long)p.H2 * p.W2) != hipSuccess) return herr("bn3 stats");
+    // layer 5 (reads z2 through BN3 + LeakyReLU, writes z5), BN6
+    if (disc_conv_launch<64, 128, 1, true>(conv_args(b.z2, b.z5, 2, b.st[0], 1, p.H2, p.W2, p.H2, p.W2), 1, p, N, training, s) != hipSuccess)
+        return herr("conv5");
+    if (training && stats(1, (long long)p.H2 * p.W2) != hipSuccess) return herr("bn6 stats");
+    // layer 8 (reads z5 through BN6 + LeakyReLU, writes z8), BN9
+    if (disc_conv_launch<128, 128, 2, true>(conv_args(b.z5, b.z8, 3, b.st[1], 2, p.H2, p.W2, p.H4, p.W4), 2, p, N, training, s) != hipSuccess)
+        return herr("conv8");
+    if (training && stats(2, (long long)p.H4 * p.W4) != hipSuccess) return herr("bn9 stats");
+    // head: BN9 + LeakyReLU, average pool, 1x1 conv, sigmoid
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        DiscHeadArgs a{b.z8, b.st[2], blob + kDiscBlob.off[4], out, (long long)p.H4 * p.W4, n0};
+        hipLaunchKernelGGL(k_disc_head, dim3((unsigned)std::min(kDiscChunk, N - n0)), dim3(D_HEAD_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("head");
+    }
+    if (training) {
+        hipLaunchKernelGGL(k_disc_bn_count, dim3(1), dim3(64), 0, s, reinterpret_cast<long long*>(bn[0].num_batches_tracked),
+                           reinterpret_cast<long long*>(bn[1].num_batches_tracked), reinterpret_cast<long long*>(bn[2].num_batches_tracked));
+        if (hipPeekAtLastError() != hipSuccess) return herr("bn count");
+    }
+    return CID_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1718,111 +1837,400 @@ int cid_disc_workspace_bytes(int N, int H, int W, int training, size_t* bytes) {
 int cid_disc_forward(cid_disc_t d, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn,
                      int training, void* workspace, size_t workspace_bytes, void* stream) {
     if (!d) return CID_ERR_INVALID;
-    if (!in || !out || !bn || !workspace) return dfail(d, CID_ERR_INVALID, "cid_disc_forward: null pointer");
-    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return dfail(d, CID_ERR_INVALID, "cid_disc_forward: unknown input format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)out & 3))
-        return dfail(d, CID_ERR_INVALID, "cid_disc_forward: misaligned fp32 operand");
-    if (training != 0 && training != 1) return dfail(d, CID_ERR_INVALID, "cid_disc_forward: training must be 0 or 1");
-    for (int l = 0; l < 3; ++l) {
-        const cid_disc_bn& b = bn[l];
-        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || (training && !b.num_batches_tracked))
-            return dfail(d, CID_ERR_INVALID, "cid_disc_forward: null BatchNorm pointer");
-        if (!disc_finite_nonneg(b.eps)) return dfail(d, CID_ERR_INVALID, "cid_disc_forward: eps must be finite and >= 0");
-        if (training && !(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
-            return dfail(d, CID_ERR_INVALID, "cid_disc_forward: momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
-    }
     DiscPlan p;
-    if (disc_plan(N, H, W, training, p) != CID_OK)
-        return dfail(d, CID_ERR_SHAPE, training && N >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL
-                                           ? "Expected more than 1 value per channel when training"
-                                           : "cid_disc_forward: input shape not accepted (N, H, W >= 1, H*W < 2^31)");
+    const int rc = disc_check_forward(d, "cid_disc_forward", in, in_fmt, out, N, H, W, bn, training, workspace, p);
+    if (rc != CID_OK) return rc;
     if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
         return dfail(d, CID_ERR_WORKSPACE, "cid_disc_forward: workspace smaller than cid_disc_workspace_bytes() or not 256-byte aligned");
     if (!d->dev_blob) return dfail(d, CID_ERR_STATE, "cid_disc_forward: weights not uploaded");
+    char* ws = static_cast<char*>(workspace);
+    DiscBufs b{};
+    b.a0 = b.z5 = reinterpret_cast<float*>(ws + p.regA);
+    b.z2 = b.z8 = reinterpret_cast<float*>(ws + p.regB);
+    for (int l = 0; l < 3; ++l) {
+        b.st[l] = reinterpret_cast<float*>(ws + p.st) + l * 256;
+        b.slab[l] = reinterpret_cast<double*>(ws + p.slab[l]);
+    }
+    return disc_forward_run(d, "cid_disc_forward", in, in_fmt, out, N, H, W, bn, training, p, b, static_cast<hipStream_t>(stream));
+}
+
+// ---- backward pass: the per-call saved buffer, the workspace plan and the launch sequence; kernels in disc_bwd_kernels.h ----
+}  // extern "C"
+
+namespace {
+
+// What cid_disc_forward_saved keeps for one call.
+struct DiscSavedPlan {
+    size_t a0, z2, z5, z8, st, mi, slab[3], total;
+};
+
+void disc_saved_plan(int N, int H, int W, int training, const DiscPlan& p, DiscSavedPlan& q) {
+    const size_t n = (size_t)N, f = sizeof(float);
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at += align256(bytes);
+        return o;
+    };
+    q.a0 = take(n * 64 * H * W * f);
+    q.z2 = take(n * 64 * p.H2 * p.W2 * f);
+    q.z5 = take(n * 128 * p.H2 * p.W2 * f);
+    q.z8 = take(n * 128 * p.H4 * p.W4 * f);
+    q.st = take(3 * 256 * f);
+    q.mi = take(3 * 256 * sizeof(double));
+    const int couts[3] = {64, 128, 128};
+    for (int l = 0; l < 3; ++l) q.slab[l] = training ? take((size_t)couts[l] * 2 * n * p.tiles[l] * sizeof(double)) : at;
+    q.total = at;
+}
+
+DiscBufs disc_saved_bufs(void* saved, const DiscSavedPlan& q) {
+    char* sv = static_cast<char*>(saved);
+    DiscBufs b{};
+    b.a0 = reinterpret_cast<float*>(sv + q.a0);
+    b.z2 = reinterpret_cast<float*>(sv + q.z2);
+    b.z5 = reinterpret_cast<float*>(sv + q.z5);
+    b.z8 = reinterpret_cast<float*>(sv + q.z8);
+    for (int l = 0; l < 3; ++l) {
+        b.st[l] = reinterpret_cast<float*>(sv + q.st) + l * 256;
+        b.mi[l] = reinterpret_cast<double*>(sv + q.mi) + l * 256;
+        b.slab[l] = reinterpret_cast<double*>(sv + q.slab[l]);
+    }
+    return b;
+}
+
+// Workspace of one backward call.  X holds the gradient of a6 and later of a0, Y the gradient of a3 (the forward's two regions).
+struct DiscBwdPlan {
+    int strips[3];                  // BatchNorm strips per image
+    int wg_tiles_x[3], wg_tiles[3]; // wgrad items per image of layers 2, 5, 8
+    int wg_splits[3];
+    int dg_tiles_x[3], dg_tiles[3]; // dgrad tiles of the largest class
+    int w0_strips, w0_splits;
+    size_t dl, mean, coef, bnslab, X, Y, part, part_b, part0, total;
+};
+
+constexpr int kDiscWgCD[3] = {64, 128, 128}, kDiscWgCX[3] = {64, 64, 128}, kDiscWgS[3] = {2, 1, 2};
+constexpr int kDiscDgTileRows[3] = {DiscDgradGeom<64, 64, 2>::TH, DiscDgradGeom<128, 64, 1>::TH, DiscDgradGeom<128, 128, 2>::TH};
+
+void disc_bwd_plan(int N, int H, int W, const DiscPlan& p, DiscBwdPlan& q) {
+    const size_t n = (size_t)N, f = sizeof(float);
+    const int ho[3] = {p.H2, p.H2, p.H4}, wo[3] = {p.W2, p.W2, p.W4};
+    const int hin[3] = {H, p.H2, p.H2}, win[3] = {W, p.W2, p.W2};
+    size_t bnslab = 0, part = 0, part_b = 0;
+    for (int l = 0; l < 3; ++l) {
+        q.strips[l] = (int)(((long long)ho[l] * wo[l] + D_BN_STRIP - 1) / D_BN_STRIP);
+        bnslab = std::max(bnslab, (size_t)kDiscBnC[l] * 2 * n * q.strips[l] * sizeof(double));
+        q.wg_tiles_x[l] = (wo[l] + D_TW - 1) / D_TW;
+        q.wg_tiles[l] = ((ho[l] + D_WG_TH - 1) / D_WG_TH) * q.wg_tiles_x[l];
+        const long long items = (long long)N * q.wg_tiles[l];
+        q.wg_splits[l] = (int)std::min<long long>(items, 512 / (kDiscWgCX[l] / 16));
+        part = std::max(part, (size_t)q.wg_splits[l] * kDiscWgCX[l] * kDiscWgCD[l] * 9 * f);
+        part_b = std::max(part_b, (size_t)q.wg_splits[l] * kDiscWgCD[l] * sizeof(double));
+        const int hc = (hin[l] + kDiscWgS[l] - 1) / kDiscWgS[l], wc = (win[l] + kDiscWgS[l] - 1) / kDiscWgS[l];
+        q.dg_tiles_x[l] = (wc + D_TW - 1) / D_TW;
+        q.dg_tiles[l] = ((hc + kDiscDgTileRows[l] - 1) / kDiscDgTileRows[l]) * q.dg_tiles_x[l];
+    }
+    q.w0_strips = (int)(((long long)H * W + 63) / 64);
+    q.w0_splits = (int)std::min<long long>((long long)N * q.w0_strips, 1024);
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at += align256(bytes);
+        return o;
+    };
+    q.dl = take(n * f);
+    q.mean = take(n * 128 * sizeof(double));
+    q.coef = take(3 * 128 * D_COEF * f);
+    q.bnslab = take(bnslab);
+    q.X = take(std::max(n * 128 * p.H2 * p.W2, n * 64 * H * W) * f);
+    q.Y = take(n * 64 * p.H2 * p.W2 * f);
+    q.part = take(part);
+    q.part_b = take(part_b);
+    q.part0 = take((size_t)q.w0_splits * 64 * 28 * sizeof(double));
+    q.total = at;
+}
+
+template <int CD, int CX, int S, bool BN_IN, bool HEAD>
+hipError_t disc_wgrad_launch(const DiscWgradArgs& a, float* dw, float* db, hipStream_t s) {
+    hipLaunchKernelGGL((k_disc_wgrad<CD, CX, S, BN_IN, HEAD>), dim3((unsigned)a.splits, CX / 16), dim3(D_THREADS), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const DiscWgradReduceArgs r{a.part, a.part_b, dw, db, a.splits, CD, CX};
+    hipLaunchKernelGGL(k_disc_wgrad_reduce, dim3((CD * CX * 9 + CD + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
+    return hipGetLastError();
+}
+
+template <int CD, int CX, int S, bool HEAD>
+hipError_t disc_dgrad_launch(const DiscDgradArgs& base, int tiles, int N, hipStream_t s) {
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        DiscDgradArgs a = base;
+        a.n0 = n0;
+        const dim3 grid((unsigned)tiles, (unsigned)std::min(kDiscChunk, N - n0), DiscDgradGeom<CD, CX, S>::CLASSES);
+        hipLaunchKernelGGL((k_disc_dgrad<CD, CX, S, HEAD>), grid, dim3(D_THREADS), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template <int C, bool HEAD>
+hipError_t disc_bn_part_launch(const DiscBnPartArgs& base, int N, hipStream_t s) {
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        DiscBnPartArgs a = base;
+        a.n0 = n0;
+        hipLaunchKernelGGL((k_disc_bn_bwd_part<C, HEAD>), dim3((unsigned)a.strips, (unsigned)std::min(kDiscChunk, N - n0)), dim3(D_THREADS), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// Shape checks shared by the backward entry points.
+int disc_bwd_shape(cid_disc_t d, const char* fn, int N, int H, int W, int training, DiscPlan& p) {
+    if (training != 0 && training != 1) return dfail(d, CID_ERR_INVALID, std::string(fn) + ": training must be 0 or 1");
+    if (disc_plan(N, H, W, training, p) != CID_OK)
+        return dfail(d, CID_ERR_SHAPE, std::string(fn) + ": shape not accepted (N, H, W >= 1, H*W < 2^31, more than one value per channel in train mode)");
+    return CID_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cid_disc_saved_bytes(int N, int H, int W, int training, size_t* bytes) {
+    if (!bytes || (training != 0 && training != 1)) return CID_ERR_INVALID;
+    DiscPlan p;
+    const int rc = disc_plan(N, H, W, training, p);
+    if (rc != CID_OK) return rc;
+    DiscSavedPlan q;
+    disc_saved_plan(N, H, W, training, p, q);
+    *bytes = q.total;
+    return CID_OK;
+}
+
+int cid_disc_forward_saved(cid_disc_t d, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn,
+                           int training, void* saved, size_t saved_bytes, void* stream) {
+    if (!d) return CID_ERR_INVALID;
+    DiscPlan p;
+    const int rc = disc_check_forward(d, "cid_disc_forward_saved", in, in_fmt, out, N, H, W, bn, training, saved, p);
+    if (rc != CID_OK) return rc;
+    DiscSavedPlan q;
+    disc_saved_plan(N, H, W, training, p, q);
+    if (saved_bytes < q.total || ((uintptr_t)saved & 255))
+        return dfail(d, CID_ERR_WORKSPACE, "cid_disc_forward_saved: saved buffer smaller than cid_disc_saved_bytes() or not 256-byte aligned");
+    if (!d->dev_blob) return dfail(d, CID_ERR_STATE, "cid_disc_forward_saved: weights not uploaded");
+    return disc_forward_run(d, "cid_disc_forward_saved", in, in_fmt, out, N, H, W, bn, training, p, disc_saved_bufs(saved, q),
+                            static_cast<hipStream_t>(stream));
+}
+
+int cid_disc_backward_workspace_bytes(int N, int H, int W, int training, size_t* bytes) {
+    if (!bytes || (training != 0 && training != 1)) return CID_ERR_INVALID;
+    DiscPlan p;
+    const int rc = disc_plan(N, H, W, training, p);
+    if (rc != CID_OK) return rc;
+    DiscBwdPlan q;
+    disc_bwd_plan(N, H, W, p, q);
+    *bytes = q.total;
+    return CID_OK;
+}
+
+int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* grad_prob, int N, int H, int W, const cid_disc_bn* bn,
+                      int training, const void* saved, size_t saved_bytes, const cid_disc_grads* g, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (!d) return CID_ERR_INVALID;
+    const char* fn = "cid_disc_backward";
+    if (!in || !grad_prob || !bn || !saved || !g || !workspace) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: null pointer");
+    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: unknown input format");
+    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)grad_prob & 3))
+        return dfail(d, CID_ERR_INVALID, "cid_disc_backward: misaligned fp32 operand");
+    for (int l = 0; l < 3; ++l)
+        if (!bn[l].gamma) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: null BatchNorm weight pointer");
+    bool misaligned = ((uintptr_t)g->input & 3) != 0;
+    for (int i = 0; i < 5; ++i) misaligned = misaligned || ((uintptr_t)g->w[i] & 3) || ((uintptr_t)g->b[i] & 3);
+    for (int l = 0; l < 3; ++l) misaligned = misaligned || ((uintptr_t)g->gamma[l] & 3) || ((uintptr_t)g->beta[l] & 3);
+    if (misaligned) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: misaligned gradient pointer");
+    if (g->input && in_fmt != CID_FMT_F32_NCHW)
+        return dfail(d, CID_ERR_INVALID, "cid_disc_backward: a uint8 input has no gradient (grads.input must be null)");
+    DiscPlan p;
+    const int rc = disc_bwd_shape(d, fn, N, H, W, training, p);
+    if (rc != CID_OK) return rc;
+    DiscSavedPlan sp;
+    disc_saved_plan(N, H, W, training, p, sp);
+    if (saved_bytes < sp.total || ((uintptr_t)saved & 255))
+        return dfail(d, CID_ERR_WORKSPACE, "cid_disc_backward: saved buffer smaller than cid_disc_saved_bytes() or not 256-byte aligned");
+    DiscBwdPlan q;
+    disc_bwd_plan(N, H, W, p, q);
+    if (workspace_bytes < q.total || ((uintptr_t)workspace & 255))
+        return dfail(d, CID_ERR_WORKSPACE, "cid_disc_backward: workspace smaller than cid_disc_backward_workspace_bytes() or not 256-byte aligned");
+    if (!d->dev_blob) return dfail(d, CID_ERR_STATE, "cid_disc_backward: weights not uploaded");
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
+    const DiscBufs sv = disc_saved_bufs(const_cast<void*>(saved), sp);
     char* ws = static_cast<char*>(workspace);
-    float* regA = reinterpret_cast<float*>(ws + p.regA);
-    float* regB = reinterpret_cast<float*>(ws + p.regB);
-    float* st[3];
-    for (int l = 0; l < 3; ++l) st[l] = reinterpret_cast<float*>(ws + p.st) + l * 256;
+    float* dl = reinterpret_cast<float*>(ws + q.dl);
+    double* mean = reinterpret_cast<double*>(ws + q.mean);
+    float* coef[3];
+    for (int l = 0; l < 3; ++l) coef[l] = reinterpret_cast<float*>(ws + q.coef) + l * 128 * D_COEF;
+    double* bnslab = reinterpret_cast<double*>(ws + q.bnslab);
+    float* X = reinterpret_cast<float*>(ws + q.X);
+    float* Y = reinterpret_cast<float*>(ws + q.Y);
+    float* part = reinterpret_cast<float*>(ws + q.part);
+    double* part_b = reinterpret_cast<double*>(ws + q.part_b);
+    double* part0 = reinterpret_cast<double*>(ws + q.part0);
     const float* blob = d->dev_blob;
-    const auto herr = [&](const char* what) { return dfail(d, CID_ERR_HIP, std::string("cid_disc_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    const auto herr = [&](const char* what) { return dfail(d, CID_ERR_HIP, std::string(fn) + ": " + what + ": " + hipGetErrorString(hipGetLastError())); };
 
-    if (!training) {
-        DiscBnEvalArgs e{};
-        for (int l = 0; l < 3; ++l) {
-            e.gamma[l] = bn[l].gamma;
-            e.beta[l] = bn[l].beta;
-            e.running_mean[l] = bn[l].running_mean;
-            e.running_var[l] = bn[l].running_var;
-            e.eps[l] = bn[l].eps;
-            e.st[l] = st[l];
-            e.C[l] = kDiscBnC[l];
-        }
-        hipLaunchKernelGGL(k_disc_bn_eval, dim3(3), dim3(128), 0, s, e);
-        if (hipPeekAtLastError() != hipSuccess) return herr("bn_eval");
-    }
-    // layer 0
+    // what is asked for at or below each stage: head(8) > bn9(7) > conv8(6) > bn6(5) > conv5(4) > bn3(3) > conv2(2) > conv0(1) > input(0)
+    const bool want[9] = {g->input != nullptr, g->w[0] || g->b[0], g->w[1] || g->b[1], g->gamma[0] || g->beta[0], g->w[2] || g->b[2],
+                          g->gamma[1] || g->beta[1], g->w[3] || g->b[3], g->gamma[2] || g->beta[2], g->w[4] || g->b[4]};
+    bool below[10];   // below[k]: something at a stage < k is asked for
+    below[0] = false;
+    for (int k = 0; k < 9; ++k) below[k + 1] = below[k] || want[k];
+    if (!below[9]) return CID_OK;
+    const long long P4 = (long long)p.H4 * p.W4, P2 = (long long)p.H2 * p.W2;
+
+    // head
     for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscConv0Args a{in, regA, blob + kDiscBlob.off[0], H, W, n0};
-        const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_conv0<true>, grid, dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_disc_conv0<false>, grid, dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("conv0");
+        DiscHeadBwdArgs a{sv.z8, sv.st[2], blob + kDiscBlob.off[4], grad_prob, mean, dl, P4, n0};
+        hipLaunchKernelGGL(k_disc_head_bwd, dim3((unsigned)std::min(kDiscChunk, N - n0)), dim3(D_HEAD_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("head");
     }
-    const auto stats = [&](int l, long long pix) {
-        DiscStatsArgs a{};
-        a.slab = reinterpret_cast<const double*>(ws + p.slab[l]);
-        a.rows = (long long)N * p.tiles[l];
-        a.count = (double)N * (double)pix;
-        a.gamma = bn[l].gamma;
-        a.beta = bn[l].beta;
-        a.running_mean = bn[l].running_mean;
-        a.running_var = bn[l].running_var;
-        a.num_batches_tracked = reinterpret_cast<const long long*>(bn[l].num_batches_tracked);
-        a.eps = bn[l].eps;
-        a.momentum = bn[l].momentum == CID_DISC_MOMENTUM_NONE ? -1.0 : bn[l].momentum;
-        a.st = st[l];
-        hipLaunchKernelGGL(k_disc_bn_stats, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
+    {
+        DiscHeadReduceArgs a{mean, dl, blob + kDiscBlob.off[4], g->w[4], g->b[4], coef[2], (double)P4, N};
+        hipLaunchKernelGGL(k_disc_head_reduce, dim3(1), dim3(128), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("head reduce");
+    }
+    if (!below[8]) return CID_OK;
+
+    const auto bn_reduce = [&](int l, long long pix) {
+        DiscBnRedArgs a{bnslab, (long long)N * q.strips[l], (double)N * (double)pix, bn[l].gamma, sv.st[l], sv.mi[l], training,
+                        coef[l], g->gamma[l], g->beta[l]};
+        hipLaunchKernelGGL(k_disc_bn_bwd_reduce, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
         return hipPeekAtLastError();
     };
-    const auto conv_args = [&](const float* src, float* dst, int ci, const float* st_in, int l, int Hin, int Win, int Ho, int Wo) {
-        DiscConvArgs a{};
-        a.in = src;
-        a.out = dst;
-        a.w = blob + kDiscBlob.off[ci];
+    const auto bn_part = [&](int l, const float* z, const float* up, long long pix) {
+        DiscBnPartArgs a{z, up, dl, coef[l], sv.st[l], sv.mi[l], bnslab, (long long)N * q.strips[l], pix, q.strips[l], 0};
+        return a;
+    };
+    const auto wg_args = [&](int l, const DiscDzSrc& dz, const float* ain, const float* st_in, int Hin, int Win, int Ho, int Wo) {
+        DiscWgradArgs a{};
+        a.dz = dz;
+        a.ain = ain;
         a.st_in = st_in;
-        a.slab = training ? reinterpret_cast<double*>(ws + p.slab[l]) : nullptr;
-        a.rows = (long long)N * p.tiles[l];
+        a.part = part;
+        a.part_b = part_b;
+        a.items = (long long)N * q.wg_tiles[l];
+        a.splits = q.wg_splits[l];
         a.Hin = Hin;
         a.Win = Win;
         a.Ho = Ho;
         a.Wo = Wo;
+        a.tiles_x = q.wg_tiles_x[l];
+        a.tiles = q.wg_tiles[l];
         return a;
     };
-    // layer 2 (reads a0, writes z2), BN3
-    if (disc_conv_launch<64, 64, 2, false>(conv_args(regA, regB, 1, nullptr, 0, H, W, p.H2, p.W2), 0, p, N, training, s) != hipSuccess)
-        return herr("conv2");
-    if (training && stats(0, (long long)p.H2 * p.W2) != hipSuccess) return herr("bn3 stats");
-    // layer 5 (reads z2 through BN3 + LeakyReLU, writes z5), BN6
-    if (disc_conv_launch<64, 128, 1, true>(conv_args(regB, regA, 2, st[0], 1, p.H2, p.W2, p.H2, p.W2), 1, p, N, training, s) != hipSuccess)
-        return herr("conv5");
-    if (training && stats(1, (long long)p.H2 * p.W2) != hipSuccess) return herr("bn6 stats");
-    // layer 8 (reads z5 through BN6 + LeakyReLU, writes z8), BN9
-    if (disc_conv_launch<128, 128, 2, true>(conv_args(regA, regB, 3, st[1], 2, p.H2, p.W2, p.H4, p.W4), 2, p, N, training, s) != hipSuccess)
-        return herr("conv8");
-    if (training && stats(2, (long long)p.H4 * p.W4) != hipSuccess) return herr("bn9 stats");
-    // head: BN9 + LeakyReLU, average pool, 1x1 conv, sigmoid
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscHeadArgs a{regB, st[2], blob + kDiscBlob.off[4], out, (long long)p.H4 * p.W4, n0};
-        hipLaunchKernelGGL(k_disc_head, dim3((unsigned)std::min(kDiscChunk, N - n0)), dim3(D_HEAD_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("head");
+    const auto dg_args = [&](int l, int ci, const DiscDzSrc& dz, float* out, int Hin, int Win, int Ho, int Wo) {
+        DiscDgradArgs a{};
+        a.dz = dz;
+        a.w = blob + kDiscBlob.off[ci];
+        a.out = out;
+        a.Hin = Hin;
+        a.Win = Win;
+        a.Ho = Ho;
+        a.Wo = Wo;
+        a.tiles_x = q.dg_tiles_x[l];
+        return a;
+    };
+
+    // BN9 (upstream: the head's dl[n] * w12[c] / P4), layer 8
+    if (disc_bn_part_launch<128, true>(bn_part(2, sv.z8, nullptr, P4), N, s) != hipSuccess) return herr("bn9 sums");
+    if (bn_reduce(2, P4) != hipSuccess) return herr("bn9 reduce");
+    const DiscDzSrc dz8{sv.z8, nullptr, dl, coef[2]};
+    if (want[6] && disc_wgrad_launch<128, 128, 2, true, true>(wg_args(2, dz8, sv.z5, sv.st[1], p.H2, p.W2, p.H4, p.W4), g->w[3], g->b[3], s) != hipSuccess)
+        return herr("wgrad8");
+    if (!below[6]) return CID_OK;
+    if (disc_dgrad_launch<128, 128, 2, true>(dg_args(2, 3, dz8, X, p.H2, p.W2, p.H4, p.W4), q.dg_tiles[2], N, s) != hipSuccess) return herr("dgrad8");
+    // BN6, layer 5
+    if (disc_bn_part_launch<128, false>(bn_part(1, sv.z5, X, P2), N, s) != hipSuccess) return herr("bn6 sums");
+    if (bn_reduce(1, P2) != hipSuccess) return herr("bn6 reduce");
+    const DiscDzSrc dz5{sv.z5, X, nullptr, coef[1]};
+    if (want[4] && disc_wgrad_launch<128, 64, 1, true, false>(wg_args(1, dz5, sv.z2, sv.st[0], p.H2, p.W2, p.H2, p.W2), g->w[2], g->b[2], s) != hipSuccess)
+        return herr("wgrad5");
+    if (!below[4]) return CID_OK;
+    if (disc_dgrad_launch<128, 64, 1, false>(dg_args(1, 2, dz5, Y, p.H2, p.W2, p.H2, p.W2), q.dg_tiles[1], N, s) != hipSuccess) return herr("dgrad5");
+    // BN3, layer 2
+    if (disc_bn_part_launch<64, false>(bn_part(0, sv.z2, Y, P2), N, s) != hipSuccess) return herr("bn3 sums");
+    if (bn_reduce(0, P2) != hipSuccess) return herr("bn3 reduce");
+    const DiscDzSrc dz2{sv.z2, Y, nullptr, coef[0]};
+    if (want[2] && disc_wgrad_launch<64, 64, 2, false, false>(wg_args(0, dz2, sv.a0, nullptr, H, W, p.H2, p.W2), g->w[1], g->b[1], s) != hipSuccess)
+        return herr("wgrad2");
+    if (!below[2]) return CID_OK;
+    if (disc_dgrad_launch<64, 64, 2, false>(dg_args(0, 1, dz2, X, H, W, p.H2, p.W2), q.dg_tiles[0], N, s) != hipSuccess) return herr("dgrad2");
+    // layer 0
+    if (want[1]) {
+        DiscWgrad0Args a{in, sv.a0, X, part0, (long long)N * q.w0_strips, q.w0_splits, q.w0_strips, H, W};
+        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_wgrad0<true>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_disc_wgrad0<false>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("wgrad0");
+        DiscWgrad0ReduceArgs r{part0, g->w[0], g->b[0], q.w0_splits};
+        hipLaunchKernelGGL(k_disc_wgrad0_reduce, dim3((64 * 28 + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
+        if (hipPeekAtLastError() != hipSuccess) return herr("wgrad0 reduce");
     }
-    if (training) {
-        hipLaunchKernelGGL(k_disc_bn_count, dim3(1), dim3(64), 0, s, reinterpret_cast<long long*>(bn[0].num_batches_tracked),
-                           reinterpret_cast<long long*>(bn[1].num_batches_tracked), reinterpret_cast<long long*>(bn[2].num_batches_tracked));
-        if (hipPeekAtLastError() != hipSuccess) return herr("bn count");
+    if (want[0]) {
+        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+            DiscDgrad0Args a{sv.a0, X, blob + kDiscBlob.off[0], g->input, H, W, n0};
+            const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
+            hipLaunchKernelGGL(k_disc_dgrad0, grid, dim3(D_THREADS), 0, s, a);
+            if (hipPeekAtLastError() != hipSuccess) return herr("dgrad0");
+        }
+    }
+    return CID_OK;
+}
+
+int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, void* device_blob, void* stream) {
+    if (!d) return CID_ERR_INVALID;
+    if (!dev_params || !device_blob) return dfail(d, CID_ERR_INVALID, "cid_disc_pack_weights_device: null pointer");
+    for (int i = 0; i < CID_DISC_NUM_WEIGHTS; ++i)
+        if (!dev_params[i] || ((uintptr_t)dev_params[i] & 3))
+            return dfail(d, CID_ERR_INVALID, "cid_disc_pack_weights_device: null or misaligned parameter pointer");
+    if ((uintptr_t)device_blob & 255) return dfail(d, CID_ERR_WORKSPACE, "cid_disc_pack_weights_device: blob must be 256-byte aligned");
+    DiscPackArgs a{};
+    for (int i = 0; i < kDiscConvs; ++i) {
+        a.w[i] = dev_params[2 * i];
+        a.b[i] = dev_params[2 * i + 1];
+        a.off[i] = (int)kDiscBlob.off[i];
+        a.cin[i] = kDiscConv[i].cin;
+        a.cout[i] = kDiscConv[i].cout;
+        a.kk[i] = kDiscConv[i].k * kDiscConv[i].k;
+    }
+    a.blob = static_cast<float*>(device_blob);
+    a.total = (int)kDiscBlob.total;
+    hipLaunchKernelGGL(k_disc_pack, dim3((a.total + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    if (hipGetLastError() != hipSuccess) return dfail(d, CID_ERR_HIP, "cid_disc_pack_weights_device: launch failed");
+    d->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_disc_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int W, int training, unsigned char* const* masks, void* stream) {
+    if (!saved || !masks || (training != 0 && training != 1)) return CID_ERR_INVALID;
+    for (int i = 0; i < 4; ++i)
+        if (!masks[i]) return CID_ERR_INVALID;
+    DiscPlan p;
+    const int rc = disc_plan(N, H, W, training, p);
+    if (rc != CID_OK) return rc;
+    DiscSavedPlan sp;
+    disc_saved_plan(N, H, W, training, p, sp);
+    if (saved_bytes < sp.total || ((uintptr_t)saved & 255)) return CID_ERR_WORKSPACE;
+    const DiscBufs sv = disc_saved_bufs(const_cast<void*>(saved), sp);
+    const float* z[4] = {sv.a0, sv.z2, sv.z5, sv.z8};
+    const float* st[4] = {nullptr, sv.st[0], sv.st[1], sv.st[2]};
+    const int C[4] = {64, 64, 128, 128};
+    const long long P[4] = {(long long)H * W, (long long)p.H2 * p.W2, (long long)p.H2 * p.W2, (long long)p.H4 * p.W4};
+    for (int i = 0; i < 4; ++i) {
+        DiscMaskArgs a{z[i], st[i], masks[i], (long long)N * C[i] * P[i], P[i], C[i]};
+        const long long blocks = (a.total + D_THREADS - 1) / D_THREADS;
+        if (blocks > 0x7fffffffLL) return CID_ERR_SHAPE;
+        hipLaunchKernelGGL(k_disc_masks, dim3((unsigned)blocks), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
+        if (hipGetLastError() != hipSuccess) return CID_ERR_HIP;
     }
     return CID_OK;
 }

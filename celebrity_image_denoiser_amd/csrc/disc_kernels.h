@@ -19,6 +19,8 @@
 //   * k_disc_bn_stats (train): one workgroup per channel reduces the slab in a fixed order in fp64, writes the channel's (scale,
 //     shift) for the next layer's staging and updates running_mean / running_var in the module's own buffers.
 //   * k_disc_bn_eval (eval): (scale, shift) of all three BatchNorms from the running buffers.
+//     Both also write the (mean, invstd) pairs in fp64 when the call keeps its tensors for a backward pass (cid_disc_forward_saved;
+//     the backward kernels are in disc_bwd_kernels.h).
 //   * k_disc_head: one 1024-thread workgroup per image: BN9 + LeakyReLU of z8, the global average (fp64, fixed order), the 1x1 convolution and
 //     the sigmoid.
 //   * k_disc_bn_count (train): num_batches_tracked += 1 of the three BatchNorms, after every statistics launch has read them.
@@ -35,6 +37,10 @@ constexpr int D_TW = 16;   // output pixels per tile row (one MFMA column tile)
 typedef float d_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float d_lrelu(float v) { return v > 0.0f ? v : v * 0.2f; }
+
+// BatchNorm as the kernels apply it: y = s*z + t in one fused multiply-add.  Every forward kernel and every backward kernel
+// (disc_bwd_kernels.h) evaluates y through this function, so the backward's LeakyReLU mask (y > 0) is the forward's decision.
+__device__ __forceinline__ float d_bn(float s, float z, float t) { return fmaf(s, z, t); }
 
 // u8 image -> fp32 as ToTensor + Normalize(0.5, 0.5) with true divisions: the forward's u8 input arithmetic (k_conv_head).
 __device__ __forceinline__ float d_u8(unsigned char u) { return ((float)u / 255.0f - 0.5f) / 0.5f; }
@@ -172,7 +178,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_conv(const DiscConvArgs a
                     if (BN_IN) {
                         const int c = chunk * 8 + h * 4;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = d_lrelu(fmaf(lds_st[2 * (c + j)], v[j], lds_st[2 * (c + j) + 1]));
+                        for (int j = 0; j < 4; ++j) v[j] = d_lrelu(d_bn(lds_st[2 * (c + j)], v[j], lds_st[2 * (c + j) + 1]));
                     }
                 }
 #pragma unroll
@@ -275,6 +281,7 @@ struct DiscStatsArgs {
     const long long* num_batches_tracked;
     double eps, momentum;         // momentum < 0: None (1 / num_batches_tracked after this call's increment)
     float* st;                    // out: (scale, shift) pairs [C]
+    double* mi;                   // out, may be null: (mean, invstd) pairs [C] that the backward pass normalises with
 };
 
 __global__ void __launch_bounds__(D_THREADS) k_disc_bn_stats(const DiscStatsArgs a) {
@@ -306,6 +313,10 @@ __global__ void __launch_bounds__(D_THREADS) k_disc_bn_stats(const DiscStatsArgs
         const double sc = (double)a.gamma[c] / sqrt(var + a.eps);
         a.st[2 * c] = (float)sc;
         a.st[2 * c + 1] = (float)((double)a.beta[c] - mean * sc);
+        if (a.mi) {
+            a.mi[2 * c] = mean;
+            a.mi[2 * c + 1] = 1.0 / sqrt(var + a.eps);
+        }
         const double m = a.momentum < 0.0 ? 1.0 / (double)(a.num_batches_tracked[0] + 1) : a.momentum;
         a.running_mean[c] = (float)((1.0 - m) * (double)a.running_mean[c] + m * mean);
         a.running_var[c] = (float)((1.0 - m) * (double)a.running_var[c] + m * var_u);
@@ -321,6 +332,7 @@ struct DiscBnEvalArgs {
     double eps[3];
     float* st[3];
     int C[3];
+    double* mi[3];                // may be null: (running_mean, invstd) pairs [C] for the backward pass
 };
 
 __global__ void __launch_bounds__(128) k_disc_bn_eval(const DiscBnEvalArgs a) {
@@ -329,6 +341,10 @@ __global__ void __launch_bounds__(128) k_disc_bn_eval(const DiscBnEvalArgs a) {
     const double sc = (double)a.gamma[l][c] / sqrt((double)a.running_var[l][c] + a.eps[l]);
     a.st[l][2 * c] = (float)sc;
     a.st[l][2 * c + 1] = (float)((double)a.beta[l][c] - (double)a.running_mean[l][c] * sc);
+    if (a.mi[l]) {
+        a.mi[l][2 * c] = (double)a.running_mean[l][c];
+        a.mi[l][2 * c + 1] = 1.0 / sqrt((double)a.running_var[l][c] + a.eps[l]);
+    }
 }
 
 __global__ void __launch_bounds__(64) k_disc_bn_count(long long* a, long long* b, long long* c) {
@@ -360,7 +376,7 @@ __global__ void __launch_bounds__(D_HEAD_THREADS) k_disc_head(const DiscHeadArgs
     const float s = a.st[2 * c], sh = a.st[2 * c + 1];
     const float* zc = a.z + ((n * 16 + c / 8) * (size_t)a.P) * 8 + (c & 7);
     double sum = 0.0;
-    for (long long p = grp; p < a.P; p += D_HEAD_GROUPS) sum += (double)d_lrelu(fmaf(s, zc[p * 8], sh));
+    for (long long p = grp; p < a.P; p += D_HEAD_GROUPS) sum += (double)d_lrelu(d_bn(s, zc[p * 8], sh));
     red[tid] = sum;
     __syncthreads();
     double tot = 0.0;

@@ -6,8 +6,13 @@ Cases: B=16 256^2 (the trainer's batch, training.py:504-505) and B=256 128^2 (be
 share of the 157.3 TFLOP/s fp32 MFMA peak.  The ATen baseline is the module's own stock nn.Sequential (the same weights and BatchNorm
 containers) under torch.no_grad().
 
+With --backward (train mode only) it also times one differentiable forward plus its backward, all 16 parameter gradients and the
+input gradient: DenoiseDiscriminator(autograd=True) (cid_disc_forward_saved + cid_disc_backward) next to the stock nn.Sequential
+through torch autograd (ATen/MIOpen).  The shares printed for these rows count 3x the forward's FLOPs (forward, data gradient,
+weight gradient).
+
     python celebrity_image_denoiser_amd/csrc/tools/disc_bench.py [--reps 5] [--iters 20] [--case N,H,W ...] [--no-aten] [--no-gen]
-                                                                 [--json out.json]
+                                                                 [--backward] [--json out.json]
 """
 import argparse
 import json
@@ -68,6 +73,7 @@ def main():
     ap.add_argument("--case", action="append", default=None, help="N,H,W (repeatable); default: the two cases above")
     ap.add_argument("--no-aten", action="store_true", help="skip the ATen/MIOpen baseline")
     ap.add_argument("--no-gen", action="store_true", help="skip the generator's forward")
+    ap.add_argument("--backward", action="store_true", help="also time forward_saved + backward (train mode) next to ATen's")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -76,6 +82,7 @@ def main():
     cases = [tuple(int(v) for v in c.split(",")) for c in args.case] if args.case else CASES
     torch.manual_seed(0)
     disc = cid.load_discriminator(None, device=dev)
+    disc_ag = cid.load_discriminator(disc.state_dict(), device=dev, autograd=True) if args.backward else None
     gen = None if args.no_gen else cid.load(synth.make_state_dict("default"), device=dev, strict=True)
     rows = []
     for n, h, w in cases:
@@ -90,6 +97,28 @@ def main():
                 with torch.no_grad():
                     row[mode + "_aten"] = summary(timed(lambda: disc.model(x).view(-1), args.reps, args.iters), n, flops)
         disc.eval()
+        if args.backward:
+            gp = torch.full((n,), -1.0 / n, device=dev)
+            xg = x.clone().requires_grad_(True)
+
+            def step(fwd, params):
+                for q in params:
+                    q.grad = None
+                xg.grad = None
+                fwd(xg).backward(gp)
+
+            disc_ag.train()
+            row["train_fwd_bwd"] = summary(timed(lambda: step(disc_ag, list(disc_ag.parameters())), args.reps, args.iters), n, 3 * flops)
+            if not args.no_aten:
+                disc.train()
+                row["train_fwd_bwd_aten"] = summary(timed(lambda: step(lambda t: disc.model(t).view(-1), list(disc.parameters())),
+                                                          args.reps, args.iters), n, 3 * flops)
+                disc.eval()
+            line = f"B={n:3d} {h}x{w} {3 * flops / 1e9:.0f} GFLOP train forward_saved + backward | " + fmt("hip", row["train_fwd_bwd"])
+            if "train_fwd_bwd_aten" in row:
+                line += " | " + fmt("aten", row["train_fwd_bwd_aten"]) + \
+                    f" | hip/aten {row['train_fwd_bwd']['ms_median'] / row['train_fwd_bwd_aten']['ms_median']:.2f}"
+            print(line, flush=True)
         if gen is not None:
             y = torch.empty_like(x)
             row["generator_ms_median"] = statistics.median(timed(lambda: gen(x, out=y), args.reps, max(1, args.iters // 4)))

@@ -1,12 +1,15 @@
 """The trainer's discriminator (`DenoiseDiscriminator`, reference backend/trainingcode/denoise_gan_code/training.py:77-98) on the GPU.
 
-    DenoiseDiscriminator()                   nn.Module with the reference's parameter names (model.0 ... model.12, BatchNorm buffers
+    DenoiseDiscriminator(autograd=False)     nn.Module with the reference's parameter names (model.0 ... model.12, BatchNorm buffers
                                              included); forward(x) -> fp32 [N] probabilities, eval or train mode
     load_discriminator(path_or_state_dict)   -> DenoiseDiscriminator from the "discriminator" entry of a trainer checkpoint
     trainer_losses(D, denoised, clean)       -> the trainer's d_loss / g_loss / content_loss / adv_loss of one batch
 
-Everything numeric runs in HIP kernels behind cid_disc_* (include/cid.h).  Forward only: the output carries no autograd history,
-so the trainer's d_loss.backward() on it raises torch's own "does not require grad" error.  There is no CPU fallback.
+Everything numeric runs in HIP kernels behind cid_disc_* (include/cid.h).  By default the module is forward only: the output carries
+no autograd history, so the trainer's d_loss.backward() on it raises torch's own "does not require grad" error.  With autograd=True
+the forward records a torch.autograd.Function whose backward is cid_disc_backward: the trainer's discriminator step
+(training.py:410-417) and the adversarial half of its generator step (:421-425) then run on these kernels, with a stock
+torch.optim optimizer doing the update.  No double backward.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -30,6 +33,12 @@ class _BnArg(ctypes.Structure):
                 ("momentum", ctypes.c_double)]
 
 
+class _GradsArg(ctypes.Structure):
+    """cid_disc_grads (include/cid.h)."""
+    _fields_ = [("w", ctypes.c_void_p * 5), ("b", ctypes.c_void_p * 5), ("gamma", ctypes.c_void_p * 3),
+                ("beta", ctypes.c_void_p * 3), ("input", ctypes.c_void_p)]
+
+
 def _out_side(s: int) -> int:
     return (s - 1) // 2 + 1
 
@@ -40,10 +49,13 @@ class DenoiseDiscriminator(nn.Module):
       eval   BatchNorm with the running buffers;
       train  BatchNorm with batch statistics, and the running buffers and num_batches_tracked of model.3 / model.6 / model.9 are
              updated in place on the device, as nn.BatchNorm2d does (momentum and eps are read from the containers at every call).
-    The forward is asynchronous on the current stream and carries no autograd history."""
+    The forward is asynchronous on the current stream.  With autograd=False (the default) it carries no autograd history.  With
+    autograd=True, grad mode on and a parameter or the input requiring grad, it is differentiable once: each call keeps its own
+    activations (cid_disc_saved_bytes per call) until its backward has run, and weight changes are repacked on the device."""
 
-    def __init__(self):
+    def __init__(self, autograd: bool = False):
         super().__init__()
+        self._autograd = bool(autograd)
         self.model = nn.Sequential(
             nn.Conv2d(3, 64, kernel_size=3, padding=1),
             nn.LeakyReLU(0.2),
@@ -65,6 +77,7 @@ class DenoiseDiscriminator(nn.Module):
         self._blob = None          # packed convolution weights on the device (uint8 tensor, owns the memory)
         self._packed_sig = None
         self._ws = None            # workspace (uint8 tensor, grow-only)
+        self._bws = None           # backward workspace (uint8 tensor, grow-only)
 
     def __del__(self):
         try:
@@ -95,6 +108,20 @@ class DenoiseDiscriminator(nn.Module):
             raise RuntimeError("DenoiseDiscriminator runs only on an AMD GPU (HIP kernels behind libcid.so); move it with "
                                ".to('cuda') first. There is no CPU fallback.")
         L = _lib.lib()
+        if self._autograd:
+            # a training loop changes the weights at every step: pack on the device, into one blob that stays in place
+            ts = [p.detach() for _, p in self._conv_params()]
+            if any(t.dtype != torch.float32 or t.device != dev for t in ts):
+                raise RuntimeError(f"DenoiseDiscriminator: convolution parameters must be float32 on {dev}")
+            ts = [t.contiguous() for t in ts]
+            if self._blob is None or self._blob.device != dev:
+                self._blob = torch.empty(L.cid_disc_packed_weights_bytes(), dtype=torch.uint8, device=dev)
+            ptrs = (ctypes.c_void_p * 10)(*[t.data_ptr() for t in ts])
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check_disc(self._cid, L.cid_disc_pack_weights_device(self._cid, ptrs, self._blob.data_ptr(), stream))
+            self._packed_sig = sig
+            return self._blob
         for key, p in self._conv_params():
             a = np.ascontiguousarray(p.detach().to("cpu", torch.float32).numpy())
             shape = (ctypes.c_int64 * a.ndim)(*a.shape)
@@ -166,6 +193,8 @@ class DenoiseDiscriminator(nn.Module):
                              f"{torch.Size([n, 128, 1, 1])}")
         bn = self._bn_args(dev)
         self.pack_weights()
+        if self._autograd and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return _DiscFunction.apply(self, fmt, (n, h, w), training, x, *self.parameters())
         self._ensure_workspace(n, h, w, training, dev)
         x = x.contiguous()
         out = torch.empty(n, dtype=torch.float32, device=dev)
@@ -176,18 +205,87 @@ class DenoiseDiscriminator(nn.Module):
         return out
 
 
+class _DiscFunction(torch.autograd.Function):
+    """forward = cid_disc_forward_saved into a buffer owned by this call's context, backward = cid_disc_backward."""
+
+    @staticmethod
+    def forward(ctx, module, fmt, shape, training, x, *params):
+        n, h, w = shape
+        dev = x.device
+        L = _lib.lib()
+        need = ctypes.c_size_t()
+        _lib.check_disc(module._cid, L.cid_disc_saved_bytes(n, h, w, int(training), ctypes.byref(need)))
+        saved = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        xc = x.detach().contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        bn = module._bn_args(dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check_disc(module._cid, L.cid_disc_forward_saved(module._cid, xc.data_ptr(), fmt, out.data_ptr(), n, h, w, bn,
+                                                                  int(training), saved.data_ptr(), saved.numel(), stream))
+        ctx.module, ctx.fmt, ctx.shape, ctx.training = module, fmt, shape, training
+        ctx.saved, ctx.x = saved, xc
+        ctx.names = [k for k, _ in module.named_parameters()]
+        ctx.versions = [p._version for p in params]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_prob):
+        module = ctx.module
+        params = list(module.parameters())
+        for name, p, v in zip(ctx.names, params, ctx.versions):
+            if p._version != v:
+                raise RuntimeError(f"DenoiseDiscriminator: parameter {name} was modified in place between a forward and its backward "
+                                   f"(version {p._version}, expected {v}); the gradient would be taken at the wrong weights")
+        n, h, w = ctx.shape
+        dev = ctx.x.device
+        L = _lib.lib()
+        needs = ctx.needs_input_grad
+        g = _GradsArg()
+        grads = [None] * len(params)
+        for i, (name, p) in enumerate(zip(ctx.names, params)):
+            if not needs[5 + i]:
+                continue
+            grads[i] = torch.empty(p.shape, dtype=torch.float32, device=dev)
+            layer, kind = name.rsplit(".", 1)
+            if layer in _CONVS:
+                (g.w if kind == "weight" else g.b)[_CONVS.index(layer)] = grads[i].data_ptr()
+            else:
+                (g.gamma if kind == "weight" else g.beta)[_BNS.index(int(layer.split(".")[1]))] = grads[i].data_ptr()
+        grad_x = None
+        if needs[4] and ctx.fmt == _lib.CID_FMT_F32_NCHW:
+            grad_x = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+            g.input = grad_x.data_ptr()
+        need = ctypes.c_size_t()
+        _lib.check_disc(module._cid, L.cid_disc_backward_workspace_bytes(n, h, w, int(ctx.training), ctypes.byref(need)))
+        if module._bws is None or module._bws.numel() < need.value or module._bws.device != dev:
+            module._bws = None
+            module._bws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        gp = grad_prob.to(torch.float32).contiguous()
+        bn = module._bn_args(dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check_disc(module._cid, L.cid_disc_backward(module._cid, ctx.x.data_ptr(), ctx.fmt, gp.data_ptr(), n, h, w, bn,
+                                                             int(ctx.training), ctx.saved.data_ptr(), ctx.saved.numel(),
+                                                             ctypes.byref(g), module._bws.data_ptr(), module._bws.numel(), stream))
+        ctx.saved = None
+        return (None, None, None, None, grad_x, *grads)
+
+
 def load_discriminator(source: Union[str, Mapping, None] = None, device: Optional[Union[str, torch.device]] = None,
-                       strict: bool = False) -> DenoiseDiscriminator:
+                       strict: bool = False, autograd: bool = False) -> DenoiseDiscriminator:
     """Build a DenoiseDiscriminator on `device` (default: current GPU) from a trainer checkpoint path (its "discriminator" entry,
     training.py:362, read with the torch-free reader), a checkpoint dict or a state_dict; "module." prefixes are stripped as for
-    the generator.  `source=None` keeps the default initialisation.  Returns the module in eval mode."""
+    the generator.  `source=None` keeps the default initialisation.  `autograd=True` makes the forward differentiable
+    (DenoiseDiscriminator).  Returns the module in eval mode."""
     from .api import _read_checkpoint_file, extract_state_dict
 
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     if device is None or torch.device(device).type != "cuda":
         raise RuntimeError("celebrity_image_denoiser_amd.load_discriminator: an AMD GPU is required (no CPU fallback)")
-    model = DenoiseDiscriminator()
+    model = DenoiseDiscriminator(autograd=autograd)
     if isinstance(source, str):
         model.load_state_dict(_read_checkpoint_file(source, key_candidates=("discriminator",)), strict=strict)
     elif source is not None:

@@ -342,7 +342,8 @@ int cid_add_noise(const void* clean_u8_nhwc, void* out_u8_nhwc, int N, int H, in
 /*
  * The trainer's discriminator — DenoiseDiscriminator (backend/trainingcode/denoise_gan_code/training.py:77-98), which the trainer calls
  * three times per step (:412, :413, :421) in train mode (:397) and whose outputs give the per-epoch "G Loss" / "D Loss" (:414-424, :455).
- * Its own handle: the generator's handle and packed blob are specific to the generator.  Forward only (no autograd).
+ * Its own handle: the generator's handle and packed blob are specific to the generator.  cid_disc_forward keeps nothing for a backward
+ * pass; cid_disc_forward_saved / cid_disc_backward (below) are the pair that does.
  *
  *   0 Conv2d(3,64,3,p=1)  1 LeakyReLU(0.2)                        2 Conv2d(64,64,3,s=2,p=1)   3 BatchNorm2d(64)   4 LeakyReLU(0.2)
  *   5 Conv2d(64,128,3,p=1)   6 BatchNorm2d(128)   7 LeakyReLU(0.2)   8 Conv2d(128,128,3,s=2,p=1) 9 BatchNorm2d(128) 10 LeakyReLU(0.2)
@@ -407,10 +408,65 @@ int cid_disc_losses(const float* p_real, const float* p_fake, const void* denois
                     int N, int H, int W, double* out, void* stream);
 
 /*
+ * The discriminator's backward pass (the trainer's d_loss.backward(), training.py:410-417, and the adversarial half of its generator
+ * step, :421-425).  Gradients of model.0 ... model.13 in fp32; every reduction accumulates in fp64 in a fixed order, no atomics;
+ * the GEMMs of layers 2, 5, 8 (data and weight gradient) run on the exact-fp32 MFMA.  The same call twice gives the same bits, and
+ * in eval mode the input gradient of an image does not depend on the batch it sits in.
+ *
+ * cid_disc_forward_saved is cid_disc_forward with a caller-owned PER-CALL buffer of cid_disc_saved_bytes(N, H, W, training) bytes
+ * (256-byte aligned) in place of the workspace: the activated a0, the raw z2, z5, z8, each BatchNorm's (scale, shift) and
+ * (mean, invstd) and, in train mode, the statistics slabs stay there for the backward pass.  One buffer per forward call: the
+ * trainer runs D(clean) and D(denoised.detach()) before one backward through both.  Probabilities and BatchNorm buffer updates are
+ * bit-identical to cid_disc_forward; the argument checks and error codes are the same, with CID_ERR_WORKSPACE for the saved buffer.
+ *
+ * cid_disc_backward: `in`, N, H, W, `training` and `saved` are those of the cid_disc_forward_saved call to differentiate (the
+ * packed weights must still be the ones that call used; bn[l].gamma is read, the other cid_disc_bn fields are not); grad_prob is
+ * device fp32 [N], the gradient of the loss with respect to the probabilities.  `g` holds device fp32 pointers for the results in the
+ * reference layouts: w[i], b[i] for model.{0,2,5,8,12} ([Cout,Cin,kh,kw] / [Cout]), gamma[l], beta[l] for model.{3,6,9}, input
+ * [N,3,H,W].  A null pointer skips that output and the work only it needs (no layer-0 data gradient without `input`; nothing
+ * below the deepest layer asked for).  Results OVERWRITE; accumulation is the caller's (autograd's) job.  A uint8 input has no
+ * gradient.  Train mode differentiates through the batch statistics of that forward call; eval mode treats the running buffers as
+ * constants.  Asynchronous on `stream`, no host synchronisation; workspace of cid_disc_backward_workspace_bytes(), 256-byte aligned.
+ *   CID_ERR_INVALID    null in / grad_prob / bn / bn[l].gamma / saved / g / workspace, unknown format, misaligned fp32 pointer,
+ *                      training not 0 or 1, g->input with a uint8 input
+ *   CID_ERR_SHAPE      as cid_disc_forward
+ *   CID_ERR_WORKSPACE  saved buffer or workspace too small or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_disc_pack_weights_device builds the forward's packed blob from the ten parameter tensors in DEVICE memory (fp32, reference
+ * layouts, in the order model.0.weight, model.0.bias, model.2.weight, ... model.12.bias) with one kernel on `stream` and attaches
+ * it: what cid_disc_set_weight x 10 + cid_disc_upload_weights produce, byte for byte, without the device-to-host copies.  A
+ * training loop calls it after every optimizer step.
+ */
+typedef struct {
+    float* w[5];         /* model.0, 2, 5, 8, 12 .weight */
+    float* b[5];         /* model.0, 2, 5, 8, 12 .bias   */
+    float* gamma[3];     /* model.3, 6, 9 .weight        */
+    float* beta[3];      /* model.3, 6, 9 .bias          */
+    float* input;        /* fp32 [N,3,H,W]               */
+} cid_disc_grads;
+int cid_disc_saved_bytes(int N, int H, int W, int training, size_t* bytes);
+int cid_disc_forward_saved(cid_disc_t d, const void* in, int in_fmt, float* out_prob, int N, int H, int W, const cid_disc_bn* bn,
+                           int training, void* saved, size_t saved_bytes, void* stream);
+int cid_disc_backward_workspace_bytes(int N, int H, int W, int training, size_t* bytes);
+int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* grad_prob, int N, int H, int W, const cid_disc_bn* bn,
+                      int training, const void* saved, size_t saved_bytes, const cid_disc_grads* g, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, void* device_blob, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
 int cid_debug_poison_lds(void* stream);
+/*
+ * Testing aid (no reference counterpart): the four LeakyReLU masks of a cid_disc_forward_saved call exactly as the backward kernels
+ * decide them, uint8 (1 where the slope is 1, 0 where it is 0.2): masks[0] [N,64,H,W] (model.1), masks[1] [N,64,H2,W2] (model.4),
+ * masks[2] [N,128,H2,W2] (model.7), masks[3] [N,128,H4,W4] (model.10).  LeakyReLU's derivative is discontinuous, so a gradient check
+ * against a float64 reference is only meaningful with the reference on the same side of zero at every unit.
+ */
+int cid_disc_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int W, int training, unsigned char* const* masks,
+                         void* stream);
 /*
  * Testing / measurement aid (no reference counterpart; process-wide): workgroups per CU of the Winograd F(4x2) launches.
  * k >= 1: a launch with more (tile, column block) items than k workgroups per CU is run by that many WALKING workgroups
