@@ -84,15 +84,16 @@ def load_state_safely(model: torch.nn.Module, checkpoint_path: str,
 
 
 def load(source: Union[str, Mapping, None] = None, device: Optional[Union[str, torch.device]] = None,
-         strict: bool = False) -> DenoiseGenerator:
+         strict: bool = False, autograd: bool = False) -> DenoiseGenerator:
     """Build a DenoiseGenerator on `device` (default: current GPU) and load weights from a checkpoint
     path, a checkpoint dict or a state_dict.  `source=None` keeps the random initialisation — the
-    state the reference server runs in when its checkpoint is missing (app.py:333-336)."""
+    state the reference server runs in when its checkpoint is missing (app.py:333-336).  `autograd=True` makes the forward
+    differentiable (DenoiseGenerator)."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     if device is None or torch.device(device).type != "cuda":
         raise RuntimeError("celebrity_image_denoiser_amd.load: an AMD GPU is required (no CPU fallback)")
-    model = DenoiseGenerator()
+    model = DenoiseGenerator(autograd=autograd)
     if isinstance(source, str):
         model.load_state_dict(_read_checkpoint_file(source), strict=strict)
     elif source is not None:

@@ -11,6 +11,7 @@
 #include "noise_kernels.h"
 #include "disc_kernels.h"
 #include "disc_bwd_kernels.h"
+#include "gen_bwd_kernels.h"
 
 #include <dlfcn.h>
 
@@ -695,7 +696,8 @@ hipError_t launch_tail(const Ctx& x, const float* t4, void* out, bool u8, const 
 // is the window of the network output the caller's tensor receives; null = identity (no padding, whole output).
 // `ev`: NL + 1 events to record around the launches; null = the next armed set of cid_timing_begin, if there is one.
 int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, void* ws, size_t ws_bytes,
-                hipStream_t s, hipEvent_t* ev = nullptr, const Window* src_win = nullptr, const Window* crop_win = nullptr) {
+                hipStream_t s, hipEvent_t* ev = nullptr, const Window* src_win = nullptr, const Window* crop_win = nullptr,
+                const Config* cfg = nullptr) {
     if (!h) return CID_ERR_INVALID;
     if (!in || !out || !ws) return fail(h, CID_ERR_INVALID, "cid_forward: null pointer");
     if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_forward: no device weights attached (call cid_upload_weights or cid_attach_weights)");
@@ -711,12 +713,12 @@ int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_f
         return fail(h, CID_ERR_INVALID, "cid_forward: unknown tensor format");
     if (((uintptr_t)ws & 255) || ((uintptr_t)h->dev_blob & 255) || (in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)))
         return fail(h, CID_ERR_WORKSPACE, "cid_forward: workspace/weights must be 256-byte aligned, fp32 input 4-byte aligned");
-    const bool armed = !ev && h->tev_used < h->tev_forwards;
+    const bool armed = !ev && !cfg && h->tev_used < h->tev_forwards;
     if (armed) ev = h->tev.data() + (size_t)h->tev_used * (NL + 1);
     float* base = static_cast<float*>(ws);
     float* B[NBUF];
     for (int b = 0; b < NBUF; ++b) B[b] = base + p.off[b];
-    const Ctx x{s, h->dev_blob, N, config_of(h)};
+    const Ctx x{s, h->dev_blob, N, cfg ? *cfg : config_of(h)};   // cfg: this call's configuration in place of the handle's (cid_forward_saved)
     hipError_t e = hipSuccess;
     int li = 0;
 #define STEP(call)                                                                         \
@@ -2247,6 +2249,310 @@ int cid_disc_losses(const float* p_real, const float* p_fake, const void* den, i
     DiscLossArgs a{p_real, p_fake, den, clean, d_fmt, c_fmt, N, (long long)H * W, out};
     hipLaunchKernelGGL(k_disc_losses, dim3(1), dim3(D_LOSS_THREADS), 0, static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
+}
+
+}  // extern "C"
+
+// ---- the generator's backward pass (gen_bwd_kernels.h) ----
+namespace {
+
+// Workspace of one cid_backward call: the gradients of the activations (NHWC fp32, finished dz where a ReLU follows) and the
+// partial tiles of the weight gradients.  G4 (dz of upconv1.0) is dead before GT0 (dz of down1.0) is written and GD2 before GT1.
+struct GenBwdPlan {
+    size_t dz16, G4, dcat1, gd2, gt3, dcat2, gbt, gt2, dp2, dp1, part, part_b, part27, part27_b, total;
+    int splits[NL];       // range split of each GEMM-shaped layer's weight gradient
+    int w27_strips, w27_splits;
+};
+
+// The weight-gradient GEMM of layer l: row operand channels R, column operand channels C, taps, and the row operand's size.
+struct GenWg { int R, C, taps, Hr, Wr; };
+GenWg gen_wg(int l, const Dims& d) {
+    const LayerDef& L = kLayers[l];
+    const int res = (l == 1 || l == 10) ? 0 : (l == 4 || l == 5 || l == 6) ? 2 : 1;   // resolution of the row operand
+    const int Hr = res == 0 ? d.H : res == 1 ? d.H1 : d.H2, Wr = res == 0 ? d.W : res == 1 ? d.W1 : d.W2;
+    if (L.kind == CONVT) return {L.cin, L.cout, 4, Hr, Wr};
+    return {L.cout, L.cin, 9, Hr, Wr};
+}
+int gen_wg_tiles_x(const GenWg& g) { return cdiv(g.Wr, G_TW); }
+int gen_wg_tiles(const GenWg& g) { return cdiv(g.Hr, G_WG_TH) * gen_wg_tiles_x(g); }
+
+void gen_bwd_plan(const Dims& d, GenBwdPlan& q) {
+    const size_t n = (size_t)d.N, f = sizeof(float);
+    const size_t s0 = n * d.H * d.W, s1 = n * d.H1 * d.W1, s2 = n * d.H2 * d.W2;
+    size_t part = 0, part_b = 0;
+    for (int l = 1; l <= 10; ++l) {
+        const GenWg g = gen_wg(l, d);
+        const long long items = (long long)d.N * gen_wg_tiles(g);
+        const int groups = (g.C / 16) * std::max(1, g.R / 128);
+        q.splits[l] = (int)std::min<long long>(items, std::max(1, 1024 / groups));
+        part = std::max(part, (size_t)q.splits[l] * g.R * g.C * g.taps * f);
+        part_b = std::max(part_b, (size_t)q.splits[l] * std::max(g.R, g.C) * sizeof(double));
+    }
+    q.splits[0] = q.splits[11] = 0;
+    q.w27_strips = (int)(((long long)d.H * d.W + 63) / 64);
+    q.w27_splits = (int)std::min<long long>((long long)d.N * q.w27_strips, 1024);
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at += align256(bytes);
+        return o;
+    };
+    q.dz16 = take(s0 * 3 * f);
+    q.G4 = take(s0 * 64 * f);
+    q.dcat1 = take(s0 * 128 * f);
+    q.gd2 = take(s1 * 128 * f);
+    q.gt3 = take(s1 * 128 * f);
+    q.dcat2 = take(s1 * 256 * f);
+    q.gbt = take(s2 * 256 * f);
+    q.gt2 = take(s2 * 256 * f);
+    q.dp2 = take(s2 * 128 * f);
+    q.dp1 = take(s1 * 64 * f);
+    q.part = take(part);
+    q.part_b = take(part_b);
+    q.part27 = take((size_t)q.w27_splits * 64 * 28 * sizeof(double));
+    q.part27_b = take((size_t)q.w27_splits * 3 * sizeof(double));
+    q.total = at;
+}
+
+// Why an [N,3,H,W] batch cannot be differentiated, or nullptr.
+const char* gen_bwd_shape_error(int N, int H, int W, Dims& d) {
+    if (const char* why = shape_error(N, H, W, d)) return why;
+    if (H % 4 || W % 4)
+        return "H and W must be multiples of 4 for the differentiable forward (for other sizes the skip tensors are stored only over the crop, "
+               "so the max-pool routing outside it cannot be recovered)";
+    return nullptr;
+}
+
+struct GenView { const float* p; int ps, coff; };
+
+template <int CD, int CXB, int TAPS>
+hipError_t gen_dgrad_launch(GenDgradArgs a, int N, hipStream_t s) {
+    using G = GenDgradGeom<CXB, TAPS>;
+    a.tiles_x = cdiv(a.W, G_TW);
+    a.tiles = cdiv(a.H, G::TH) * a.tiles_x;
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        a.n0 = n0;
+        const dim3 grid((unsigned)(a.tiles * (a.CX / CXB)), (unsigned)std::min(kDiscChunk, N - n0));
+        hipLaunchKernelGGL((k_gen_dgrad<CD, CXB, TAPS>), grid, dim3(G_THREADS), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// The data gradient of GEMM-shaped layer l (1 ... 10).
+hipError_t gen_dgrad(int l, const GenDgradArgs& a, int N, hipStream_t s) {
+    switch (l) {
+        case 10: return gen_dgrad_launch<64, 128, 9>(a, N, s);
+        case 9: return gen_dgrad_launch<64, 128, 4>(a, N, s);
+        case 8: case 7: case 3: return gen_dgrad_launch<128, 128, 9>(a, N, s);
+        case 6: return gen_dgrad_launch<128, 128, 4>(a, N, s);
+        case 5: case 4: return gen_dgrad_launch<256, 128, 9>(a, N, s);
+        case 2: return gen_dgrad_launch<128, 64, 9>(a, N, s);
+        case 1: return gen_dgrad_launch<64, 64, 9>(a, N, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t gen_wgrad(const GenWg& g, GenWgradArgs a, float* dw, float* db, hipStream_t s) {
+    a.Hr = g.Hr; a.Wr = g.Wr; a.R = g.R; a.C = g.C;
+    a.tiles_x = gen_wg_tiles_x(g); a.tiles = gen_wg_tiles(g);
+    const bool convt = g.taps == 4;
+    const int crb = g.R >= 128 ? 128 : 64;
+    const dim3 grid((unsigned)a.splits, (unsigned)(g.C / 16), (unsigned)(g.R / crb));
+    if (convt) hipLaunchKernelGGL((k_gen_wgrad<128, true>), grid, dim3(G_THREADS), 0, s, a);
+    else if (crb == 128) hipLaunchKernelGGL((k_gen_wgrad<128, false>), grid, dim3(G_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((k_gen_wgrad<64, false>), grid, dim3(G_THREADS), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int nb = convt ? g.C : g.R;
+    const GenWgradReduceArgs r{a.part, a.part_b, dw, db, a.splits, g.R, g.C, g.taps, nb};
+    hipLaunchKernelGGL(k_gen_wgrad_reduce, dim3((unsigned)cdiv(g.R * g.C * g.taps + nb, G_THREADS)), dim3(G_THREADS), 0, s, r);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int cid_saved_bytes(int N, int H, int W, size_t* bytes) { return cid_workspace_bytes(N, H, W, bytes); }
+
+int cid_forward_saved(cid_handle_t h, const float* in, float* out, int N, int H, int W, void* saved, size_t saved_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!in || !out || !saved) return fail(h, CID_ERR_INVALID, "cid_forward_saved: null pointer");
+    if (h->dtype != CID_DTYPE_F32) return fail(h, CID_ERR_STATE, "cid_forward_saved: the differentiable forward needs compute dtype CID_DTYPE_F32");
+    Dims d;
+    if (const char* why = gen_bwd_shape_error(N, H, W, d)) {
+        char m[384];
+        std::snprintf(m, sizeof m, "cid_forward_saved: input [%d,3,%d,%d] not accepted: %s", N, H, W, why);
+        return fail(h, CID_ERR_SHAPE, m);
+    }
+    if (saved_bytes < make_plan(d).total_bytes || ((uintptr_t)saved & 255))
+        return fail(h, CID_ERR_WORKSPACE, "cid_forward_saved: saved buffer smaller than cid_saved_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_forward_saved: no device weights attached (call cid_upload_weights or cid_attach_weights)");
+    // the last layer as a launch of its own: the fused form never stores upconv1.0, which the backward pass reads
+    const Config cfg{CID_DTYPE_F32, h->algo, CID_TAIL_TILES};
+    return run_forward(h, in, CID_FMT_F32_NCHW, out, CID_FMT_F32_NCHW, N, H, W, saved, saved_bytes, static_cast<hipStream_t>(stream), nullptr,
+                       nullptr, nullptr, &cfg);
+}
+
+int cid_backward_workspace_bytes(int N, int H, int W, size_t* bytes) {
+    if (!bytes) return CID_ERR_INVALID;
+    Dims d;
+    if (gen_bwd_shape_error(N, H, W, d)) return CID_ERR_SHAPE;
+    GenBwdPlan q;
+    gen_bwd_plan(d, q);
+    *bytes = q.total;
+    return CID_OK;
+}
+
+int cid_backward(cid_handle_t h, const float* in, const float* out, const float* grad_out, int N, int H, int W, const void* saved,
+                 size_t saved_bytes, const cid_grads* g, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    const char* fn = "cid_backward";
+    if (!in || !out || !grad_out || !saved || !g || !workspace) return fail(h, CID_ERR_INVALID, "cid_backward: null pointer");
+    if (h->dtype != CID_DTYPE_F32) return fail(h, CID_ERR_STATE, "cid_backward: the backward pass needs compute dtype CID_DTYPE_F32");
+    bool misaligned = ((uintptr_t)in & 3) || ((uintptr_t)out & 3) || ((uintptr_t)grad_out & 3) || ((uintptr_t)g->input & 3);
+    for (int l = 0; l < NL; ++l) misaligned = misaligned || ((uintptr_t)g->w[l] & 3) || ((uintptr_t)g->b[l] & 3);
+    if (misaligned) return fail(h, CID_ERR_INVALID, "cid_backward: misaligned fp32 pointer");
+    Dims d;
+    if (const char* why = gen_bwd_shape_error(N, H, W, d)) {
+        char m[384];
+        std::snprintf(m, sizeof m, "cid_backward: input [%d,3,%d,%d] not accepted: %s", N, H, W, why);
+        return fail(h, CID_ERR_SHAPE, m);
+    }
+    const Plan p = make_plan(d);
+    if (saved_bytes < p.total_bytes || ((uintptr_t)saved & 255))
+        return fail(h, CID_ERR_WORKSPACE, "cid_backward: saved buffer smaller than cid_saved_bytes() or not 256-byte aligned");
+    GenBwdPlan q;
+    gen_bwd_plan(d, q);
+    if (workspace_bytes < q.total || ((uintptr_t)workspace & 255))
+        return fail(h, CID_ERR_WORKSPACE, "cid_backward: workspace smaller than cid_backward_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_backward: no device weights attached (call cid_upload_weights or cid_attach_weights)");
+
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const float* sv = static_cast<const float*>(saved);
+    const float* B[NBUF];
+    for (int b = 0; b < NBUF; ++b) B[b] = sv + p.off[b];
+    char* ws = static_cast<char*>(workspace);
+    const auto wsf = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    float* dz16 = wsf(q.dz16);
+    float *G4 = wsf(q.G4), *dcat1 = wsf(q.dcat1), *gd2 = wsf(q.gd2), *gt3 = wsf(q.gt3), *dcat2 = wsf(q.dcat2), *gbt = wsf(q.gbt);
+    float *gt2 = wsf(q.gt2), *dp2 = wsf(q.dp2), *dp1 = wsf(q.dp1), *gt0 = G4, *gt1 = gd2;
+    float* part = wsf(q.part);
+    double* part_b = reinterpret_cast<double*>(ws + q.part_b);
+    double* part27 = reinterpret_cast<double*>(ws + q.part27);
+    double* part27_b = reinterpret_cast<double*>(ws + q.part27_b);
+    const float* blob = h->dev_blob;
+    const auto herr = [&](const char* what) { return fail(h, CID_ERR_HIP, std::string(fn) + ": " + what + ": " + hipGetErrorString(hipGetLastError())); };
+
+    // below[l]: the input gradient or a parameter gradient of a layer before l is asked for, so layer l's data gradient is needed
+    bool need[NL], below[NL + 1];
+    below[0] = g->input != nullptr;
+    for (int l = 0; l < NL; ++l) {
+        need[l] = g->w[l] || g->b[l];
+        below[l + 1] = below[l] || need[l];
+    }
+    if (!below[NL]) return CID_OK;
+
+    // Per GEMM-shaped layer l: the layer's input (column operand of a convolution's weight gradient, the stored activation), its dz
+    // (the gradient of its pre-activation output) and where its data gradient goes, with the activation whose mask finishes it.
+    struct Row { GenView in; GenView dz; float* dout; int out_ps; const float* act; int act_ps; int Ho, Wo; };
+    const Row rows[NL] = {
+        {},
+        /* 1 down1.2     */ {{B[T0], 64, 0}, {dcat1, 128, 64}, gt0, 64, B[T0], 64, d.H, d.W},
+        /* 2 down2.0     */ {{B[P1], 64, 0}, {gt1, 128, 0}, dp1, 64, nullptr, 0, d.H1, d.W1},
+        /* 3 down2.2     */ {{B[T1], 128, 0}, {dcat2, 256, 128}, gt1, 128, B[T1], 128, d.H1, d.W1},
+        /* 4 bottleneck.0*/ {{B[P2], 128, 0}, {gt2, 256, 0}, dp2, 128, nullptr, 0, d.H2, d.W2},
+        /* 5 bottleneck.2*/ {{B[T2], 256, 0}, {gbt, 256, 0}, gt2, 256, B[T2], 256, d.H2, d.W2},
+        /* 6 up2         */ {{B[BT], 256, 0}, {dcat2, 256, 0}, gbt, 256, B[BT], 256, d.H2, d.W2},
+        /* 7 upconv2.0   */ {{B[CAT2], 256, 0}, {gt3, 128, 0}, dcat2, 256, nullptr, 0, d.H1, d.W1},
+        /* 8 upconv2.2   */ {{B[T3], 128, 0}, {gd2, 128, 0}, gt3, 128, B[T3], 128, d.H1, d.W1},
+        /* 9 up1         */ {{B[D2], 128, 0}, {dcat1, 128, 0}, gd2, 128, B[D2], 128, d.H1, d.W1},
+        /*10 upconv1.0   */ {{B[CAT1], 128, 0}, {G4, 64, 0}, dcat1, 128, nullptr, 0, d.H, d.W},
+        {},
+    };
+
+    // upconv1.2 (+ tanh)
+    {
+        const long long total = (long long)N * 3 * H * W;
+        hipLaunchKernelGGL(k_gen_dz16, dim3((unsigned)((total + G_THREADS - 1) / G_THREADS)), dim3(G_THREADS), 0, s, grad_out, out, dz16, total);
+        if (hipPeekAtLastError() != hipSuccess) return herr("dz16");
+    }
+    if (need[11]) {
+        const GenWgrad27Args a{dz16, B[T4], 64, 0, part27, part27_b, (long long)N * q.w27_strips, q.w27_splits, q.w27_strips, H, W};
+        hipLaunchKernelGGL(k_gen_wgrad27<true>, dim3((unsigned)q.w27_splits), dim3(G_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("upconv1.2 weight gradient");
+        const GenWgrad27ReduceArgs r{part27, part27_b, g->w[11], g->b[11], q.w27_splits};
+        hipLaunchKernelGGL(k_gen_wgrad27_reduce<true>, dim3((unsigned)cdiv(64 * 28 + 3, G_THREADS)), dim3(G_THREADS), 0, s, r);
+        if (hipPeekAtLastError() != hipSuccess) return herr("upconv1.2 weight gradient reduce");
+    }
+    if (!below[11]) return CID_OK;
+    {
+        const long long pixels = (long long)N * H * W;
+        const GenDgradTailArgs a{dz16, blob + kBlob.raw_w_off[11], B[T4], G4, pixels, H, W};
+        hipLaunchKernelGGL(k_gen_dgrad_tail, dim3((unsigned)((pixels + 63) / 64)), dim3(G_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("upconv1.2 data gradient");
+    }
+
+    for (int l = 10; l >= 1; --l) {
+        const Row& r = rows[l];
+        const bool convt = kLayers[l].kind == CONVT;
+        if (need[l]) {
+            const GenWg wg = gen_wg(l, d);
+            GenWgradArgs a{};
+            // row operand: dz of a convolution, the input of a transposed convolution; column operand: the other one
+            const GenView& ro = convt ? r.in : r.dz;
+            const GenView& co = convt ? r.dz : r.in;
+            a.r = ro.p; a.r_ps = ro.ps; a.r_coff = ro.coff;
+            a.c = co.p; a.c_ps = co.ps; a.c_coff = co.coff;
+            a.part = part; a.part_b = part_b;
+            a.items = (long long)N * gen_wg_tiles(wg);
+            a.splits = q.splits[l];
+            if (gen_wgrad(wg, a, g->w[l], g->b[l], s) != hipSuccess) return herr((std::string(kLayers[l].name) + " weight gradient").c_str());
+        }
+        if (!below[l]) return CID_OK;
+        GenDgradArgs a{};
+        a.dz = r.dz.p; a.dz_ps = r.dz.ps; a.dz_coff = r.dz.coff;
+        a.w = blob + kBlob.raw_w_off[l];
+        a.act = r.act; a.act_ps = r.act_ps; a.act_coff = 0;
+        a.out = r.dout; a.out_ps = r.out_ps; a.out_coff = 0;
+        a.H = r.Ho; a.W = r.Wo; a.CX = kLayers[l].cin;
+        if (gen_dgrad(l, a, N, s) != hipSuccess) return herr((std::string(kLayers[l].name) + " data gradient").c_str());
+        if (l == 4 || l == 2) {   // the pooled tensor's gradient is complete: finish dz of the skip tensor under it
+            GenPoolBwdArgs pa{};
+            const int C = l == 4 ? 128 : 64;
+            pa.e = l == 4 ? B[CAT2] : B[CAT1]; pa.e_ps = 2 * C; pa.e_coff = C;
+            pa.dp = l == 4 ? dp2 : dp1;
+            pa.io = l == 4 ? dcat2 : dcat1; pa.io_ps = 2 * C; pa.io_coff = C;
+            pa.Hp = r.Ho; pa.Wp = r.Wo;
+            pa.total = (long long)N * r.Ho * r.Wo * (C / 4);
+            const long long blocks = (pa.total + G_THREADS - 1) / G_THREADS;
+            if (blocks > 0x7fffffffLL) return fail(h, CID_ERR_SHAPE, "cid_backward: batch too large for one call");
+            if (l == 4) hipLaunchKernelGGL(k_gen_pool_bwd<128>, dim3((unsigned)blocks), dim3(G_THREADS), 0, s, pa);
+            else hipLaunchKernelGGL(k_gen_pool_bwd<64>, dim3((unsigned)blocks), dim3(G_THREADS), 0, s, pa);
+            if (hipPeekAtLastError() != hipSuccess) return herr("max-pool gradient");
+        }
+    }
+
+    // down1.0
+    if (need[0]) {
+        const GenWgrad27Args a{in, gt0, 64, 0, part27, part27_b, (long long)N * q.w27_strips, q.w27_splits, q.w27_strips, H, W};
+        hipLaunchKernelGGL(k_gen_wgrad27<false>, dim3((unsigned)q.w27_splits), dim3(G_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("down1.0 weight gradient");
+        const GenWgrad27ReduceArgs r{part27, part27_b, g->w[0], g->b[0], q.w27_splits};
+        hipLaunchKernelGGL(k_gen_wgrad27_reduce<false>, dim3((unsigned)cdiv(64 * 28, G_THREADS)), dim3(G_THREADS), 0, s, r);
+        if (hipPeekAtLastError() != hipSuccess) return herr("down1.0 weight gradient reduce");
+    }
+    if (g->input) {
+        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+            const GenDgradHeadArgs a{gt0, blob + kBlob.raw_w_off[0], g->input, H, W, n0};
+            const dim3 grid((unsigned)(((long long)H * W + G_THREADS - 1) / G_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
+            hipLaunchKernelGGL(k_gen_dgrad_head, grid, dim3(G_THREADS), 0, s, a);
+            if (hipPeekAtLastError() != hipSuccess) return herr("down1.0 data gradient");
+        }
+    }
+    return CID_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,131 @@
+"""Times the generator's training step pieces on the GPU with device events after a warm-up:
+
+    forward            cid_forward (DenoiseGenerator(), fused last layer)
+    forward + backward DenoiseGenerator(autograd=True): cid_forward_saved + cid_backward, all 24 parameter gradients and the input gradient
+    aten               the same network on the module's own stock nn layers through torch autograd (ATen/MIOpen fp32), same process
+    repack             pack_weights() after an in-place change of every parameter (what an optimizer step costs the next forward:
+                       24 device-to-host copies, the host repack, one upload)
+
+Cases: B=16 256^2 (the trainer's batch, training.py:504-505) and B=64 128^2.  For each: median ms per call over --reps windows of
+--iters calls [min-max], images/s, algorithmic TFLOP/s and its share of the 157.3 TFLOP/s fp32 MFMA peak; the forward + backward rows
+count 3x the forward's algorithmic FLOPs (forward, data gradient, weight gradient).
+
+    python celebrity_image_denoiser_amd/csrc/tools/gen_bench.py [--reps 5] [--iters 20] [--case N,H,W ...] [--no-aten] [--json out.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import celebrity_image_denoiser_amd as cid  # noqa: E402
+from celebrity_image_denoiser_amd import synth  # noqa: E402
+from celebrity_image_denoiser_amd.generator import launch_table  # noqa: E402
+
+MFMA_F32_PEAK = 157.3e12
+CASES = ((16, 256, 256), (64, 128, 128))
+
+
+def timed(fn, reps, iters):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / iters)
+    return out
+
+
+def summary(t, n, flops):
+    med = statistics.median(t)
+    return {"ms_median": med, "ms_min": min(t), "ms_max": max(t), "images_per_s": n / med * 1e3,
+            "tflops": flops / med / 1e9, "mfma_share": flops / med / 1e-3 / MFMA_F32_PEAK}
+
+
+def fmt(name, r):
+    return (f"{name} {r['ms_median']:.3f} ms [{r['ms_min']:.3f}-{r['ms_max']:.3f}] {r['images_per_s']:.0f} img/s "
+            f"{r['tflops']:.1f} TF/s {100 * r['mfma_share']:.0f}% of 157.3")
+
+
+def stock_forward(m, x):
+    """The reference forward (app.py:80-103) on the module's stock nn layers: ATen/MIOpen."""
+    e1 = m.down1(x)
+    e2 = m.down2(m.pool1(e1))
+    b = m.bottleneck(m.pool2(e2))
+    d2 = m.upconv2(torch.cat([m.up2(b), e2], 1))
+    return torch.tanh(m.upconv1(torch.cat([m.up1(d2), e1], 1)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--case", action="append", default=None, help="N,H,W (repeatable); default: the two cases above")
+    ap.add_argument("--no-aten", action="store_true", help="skip the ATen/MIOpen baseline")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("gen_bench needs a GPU")
+    dev = "cuda:0"
+    cases = [tuple(int(v) for v in c.split(",")) for c in args.case] if args.case else CASES
+    sd = synth.make_state_dict("default")
+    gen = cid.load(sd, device=dev, strict=True)
+    gen_ag = cid.load(sd, device=dev, strict=True, autograd=True)
+    rows = []
+    for n, h, w in cases:
+        u8 = synth.add_gaussian_noise(synth.clean_images_u8(16, h, w), 25.0)
+        x = torch.from_numpy(synth.normalize_u8(u8)).to(dev).repeat((n + 15) // 16, 1, 1, 1)[:n].contiguous()
+        flops = sum(r[2] for r in launch_table(n, h, w))
+        row = {"N": n, "H": h, "W": w, "gflop": flops / 1e9}
+        y = torch.empty_like(x)
+        row["forward"] = summary(timed(lambda: gen(x, out=y), args.reps, args.iters), n, flops)
+        go = torch.randn(x.shape, device=dev, generator=torch.Generator(dev).manual_seed(1)) / x.numel()
+        xg = x.clone().requires_grad_(True)
+
+        def step(fwd, params):
+            for q in params:
+                q.grad = None
+            xg.grad = None
+            fwd(xg).backward(go)
+
+        row["fwd_bwd"] = summary(timed(lambda: step(gen_ag, list(gen_ag.parameters())), args.reps, args.iters), n, 3 * flops)
+        if not args.no_aten:
+            with torch.no_grad():
+                row["forward_aten"] = summary(timed(lambda: stock_forward(gen, x), args.reps, args.iters), n, flops)
+            row["fwd_bwd_aten"] = summary(timed(lambda: step(lambda t: stock_forward(gen, t), list(gen.parameters())), args.reps, args.iters),
+                                          n, 3 * flops)
+        rows.append(row)
+        for key, label, f in (("forward", "forward", flops), ("fwd_bwd", "forward_saved + backward", 3 * flops)):
+            line = f"B={n:3d} {h}x{w} {f / 1e9:.0f} GFLOP {label} | " + fmt("hip", row[key])
+            if key + "_aten" in row:
+                line += " | " + fmt("aten", row[key + "_aten"]) + f" | hip/aten {row[key]['ms_median'] / row[key + '_aten']['ms_median']:.2f}"
+            print(line, flush=True)
+
+    # the host repack after an optimizer step: every parameter changed in place, then pack_weights()
+    def repack():
+        with torch.no_grad():
+            for q in gen_ag.parameters():
+                q.mul_(1.0)
+        gen_ag.pack_weights()
+
+    t = timed(repack, args.reps, max(1, args.iters // 4))
+    rows.append({"repack_ms_median": statistics.median(t), "repack_ms_min": min(t), "repack_ms_max": max(t)})
+    print(f"host repack after an optimizer step (pack_weights): {statistics.median(t):.1f} ms [{min(t):.1f}-{max(t):.1f}]", flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

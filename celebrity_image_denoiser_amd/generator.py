@@ -14,6 +14,11 @@ key names, `.to()`, `state_dict()` and `load_state_dict()` behave as in the refe
 `forward` never touches ATen compute: it hands raw device pointers to `cid_forward`
 (include/cid.h), which runs the hand-written gfx950 kernels.  There is no CPU path — a CPU
 tensor or a missing libcid.so raises.
+
+By default the module is forward only: its output carries no autograd history.  With
+`DenoiseGenerator(autograd=True)` the forward records a torch.autograd.Function whose backward is
+`cid_backward`: the trainer's generator step (training.py:420-426, g_loss.backward() through the
+generator) then runs on these kernels, with a stock torch.optim optimizer doing the update.
 """
 from __future__ import annotations
 
@@ -33,11 +38,27 @@ def _block(cin, cmid, cout, last_relu=True):
     return nn.Sequential(*layers)
 
 
-class DenoiseGenerator(nn.Module):
-    """Two-level U-Net denoiser; parameters as in reference backend/app.py:39-78."""
+class _GradsArg(ctypes.Structure):
+    """cid_grads (include/cid.h)."""
+    _fields_ = [("w", ctypes.c_void_p * 12), ("b", ctypes.c_void_p * 12), ("input", ctypes.c_void_p)]
 
-    def __init__(self):
+
+_LAYERS = ("down1.0", "down1.2", "down2.0", "down2.2", "bottleneck.0", "bottleneck.2", "up2", "upconv2.0", "upconv2.2", "up1",
+           "upconv1.0", "upconv1.2")   # cid_grads order (cid_param_key)
+
+
+class DenoiseGenerator(nn.Module):
+    """Two-level U-Net denoiser; parameters as in reference backend/app.py:39-78.
+
+    With autograd=False (the default) the forward carries no autograd history.  With autograd=True, grad mode on and the input or
+    a parameter requiring grad, `forward` is differentiable once: each call keeps its own activations (cid_saved_bytes per call)
+    until its backward has run.  That path takes fp32 [N,3,H,W] with H and W multiples of 4 (the trainer's 256 x 256), compute
+    dtype "f32", one call's size limit; anything else raises.  Under torch.no_grad(), or when nothing requires grad, it is the
+    default forward."""
+
+    def __init__(self, autograd: bool = False):
         super().__init__()
+        self._autograd = bool(autograd)
         # parameter containers only — indices 0 and 2 of each Sequential hold the convs, as in the reference
         self.down1 = _block(3, 64, 64)
         self.pool1 = nn.MaxPool2d(2, 2)
@@ -53,6 +74,7 @@ class DenoiseGenerator(nn.Module):
         self._blob = None          # packed weights on the device (torch uint8 tensor, owns the memory)
         self._packed_sig = None    # signature of the parameters the blob was packed from
         self._ws = None            # activation arena (torch uint8 tensor, grow-only)
+        self._bws = None           # backward workspace (torch uint8 tensor, grow-only)
 
     def __del__(self):
         try:
@@ -189,6 +211,9 @@ class DenoiseGenerator(nn.Module):
         """[N,3,H,W] fp32 in [-1,1] on the GPU -> [N,3,4*(H//4),4*(W//4)] fp32 in (-1,1).
         Same contract as the reference forward (app.py:80-103); asynchronous on the current stream.
         `out=` (not in the reference) writes into a caller-owned tensor instead of allocating."""
+        if (self._autograd and torch.is_grad_enabled() and isinstance(x, torch.Tensor)
+                and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return self._forward_autograd(x, out)
         if isinstance(x, torch.Tensor) and x.dim() == 4 and self._needs_stripes(x.shape[2], x.shape[3]):
             return self._forward_striped(x, out_u8=False, out=out)
         x, y, n, h, w = self._prepare(x, out)
@@ -197,6 +222,40 @@ class DenoiseGenerator(nn.Module):
             _lib.check(self._cid, _lib.lib().cid_forward(self._cid, x.data_ptr(), y.data_ptr(), n, h, w,
                                                          self._ws.data_ptr(), self._ws.numel(), stream))
         return y
+
+    def _forward_autograd(self, x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """The differentiable forward (cid_forward_saved): what it cannot differentiate raises here, before any launch."""
+        if out is not None:
+            raise RuntimeError("DenoiseGenerator(autograd=True): out= cannot be combined with a differentiable forward")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"expected input of shape [N,3,H,W], got {list(x.shape)}")
+        h, w = x.shape[2], x.shape[3]
+        if self.compute_dtype != "f32":
+            raise RuntimeError('DenoiseGenerator(autograd=True): the backward pass needs compute_dtype "f32" '
+                               '(there is no fp16-storage backward); use torch.no_grad() for an f16 forward')
+        if self._needs_stripes(h, w):
+            raise RuntimeError(f"DenoiseGenerator(autograd=True): a {h}x{w} image is beyond one call's size limit and would be cut into "
+                               "stripes, which the backward pass does not support; use torch.no_grad() or smaller crops")
+        if h < 4 or w < 4 or h % 4 or w % 4:
+            raise RuntimeError(f"DenoiseGenerator(autograd=True): H and W must be multiples of 4 to differentiate, got {h}x{w} "
+                               "(for other sizes the skip tensors are stored only over the crop, so the max-pool routing outside it "
+                               "cannot be recovered); crop or pad the batch, or use torch.no_grad()")
+        self._prepare_checks(x)
+        self.pack_weights()
+        return _GenFunction.apply(self, x, *self.parameters())
+
+    def _prepare_checks(self, x: torch.Tensor) -> None:
+        if x.device.type != "cuda":
+            raise RuntimeError(
+                "DenoiseGenerator.forward got a CPU tensor: this implementation is GPU-only (hand-written HIP "
+                "kernels); there is no CPU fallback. Move the input with .to('cuda')."
+            )
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"expected float32 input (the reference computes in fp32), got {x.dtype}")
+        if x.device != self._device():
+            raise RuntimeError(f"input on {x.device} but module parameters on {self._device()}")
+        if x.shape[0] < 1:
+            raise RuntimeError("empty batch")
 
     # ------------------------------------------------------------------ images beyond one call's size limit
     # The kernels address one image's activations with 32-bit byte offsets: cid_forward refuses H*W >= 4,194,303 pixels
@@ -431,6 +490,73 @@ class DenoiseGenerator(nn.Module):
         with torch.cuda.device(dev):
             _lib.check(self._cid, _lib.lib().cid_timing_end(self._cid, stream, ms, ctypes.byref(n)))
         return list(ms), n.value
+
+
+class _GenFunction(torch.autograd.Function):
+    """forward = cid_forward_saved into a buffer owned by this call's context, backward = cid_backward."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        n, _, h, w = x.shape
+        dev = x.device
+        L = _lib.lib()
+        need = ctypes.c_size_t()
+        _lib.check(module._cid, L.cid_saved_bytes(n, h, w, ctypes.byref(need)))
+        saved = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        xc = x.detach().contiguous()
+        y = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(module._cid, L.cid_forward_saved(module._cid, xc.data_ptr(), y.data_ptr(), n, h, w, saved.data_ptr(),
+                                                        saved.numel(), stream))
+        ctx.module, ctx.shape = module, (n, h, w)
+        ctx.saved, ctx.x, ctx.y = saved, xc, y.detach()
+        ctx.names = [k for k, _ in module.named_parameters()]
+        ctx.versions = [p._version for p in params]
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        module = ctx.module
+        params = list(module.parameters())
+        for name, p, v in zip(ctx.names, params, ctx.versions):
+            if p._version != v:
+                raise RuntimeError(f"DenoiseGenerator: parameter {name} was modified in place between a forward and its backward "
+                                   f"(version {p._version}, expected {v}); the gradient would be taken at the wrong weights")
+        if ctx.saved is None:
+            raise RuntimeError("DenoiseGenerator: this forward has already been differentiated (its activations were released)")
+        n, h, w = ctx.shape
+        dev = ctx.x.device
+        L = _lib.lib()
+        needs = ctx.needs_input_grad
+        g = _GradsArg()
+        grads = [None] * len(params)
+        for i, (name, p) in enumerate(zip(ctx.names, params)):
+            if not needs[2 + i]:
+                continue
+            grads[i] = torch.empty(p.shape, dtype=torch.float32, device=dev)
+            layer, kind = name.rsplit(".", 1)
+            (g.w if kind == "weight" else g.b)[_LAYERS.index(layer)] = grads[i].data_ptr()
+        grad_x = None
+        if needs[1]:
+            grad_x = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+            g.input = grad_x.data_ptr()
+        need = ctypes.c_size_t()
+        _lib.check(module._cid, L.cid_backward_workspace_bytes(n, h, w, ctypes.byref(need)))
+        if module._bws is None or module._bws.numel() < need.value or module._bws.device != dev:
+            if module._bws is not None:
+                torch.cuda.synchronize(module._bws.device)   # kernels of an earlier backward may still use the old workspace
+            module._bws = None
+            module._bws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        go = grad_out.to(torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(module._cid, L.cid_backward(module._cid, ctx.x.data_ptr(), ctx.y.data_ptr(), go.data_ptr(), n, h, w,
+                                                   ctx.saved.data_ptr(), ctx.saved.numel(), ctypes.byref(g),
+                                                   module._bws.data_ptr(), module._bws.numel(), stream))
+        ctx.saved = None
+        return (None, grad_x, *grads)
 
 
 def launch_table(n: int, h: int, w: int, model: "DenoiseGenerator" = None):

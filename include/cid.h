@@ -455,6 +455,50 @@ int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* gra
 int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, void* device_blob, void* stream);
 
 /*
+ * The generator's backward pass — g_loss.backward() through DenoiseGenerator in the trainer's generator step
+ * (backend/trainingcode/denoise_gan_code/training.py:420-426; the module itself :59-74).  fp32 NCHW in and out, CID_DTYPE_F32 only.
+ *
+ * cid_forward_saved is cid_forward with a caller-owned PER-CALL buffer of cid_saved_bytes(N, H, W) bytes (= cid_workspace_bytes, 256-byte
+ * aligned) in place of the arena; it has the arena's layout, so cid_stage_view applies to it, "upconv1.0" included: the last layer
+ * always runs as CID_TAIL_TILES here (the fused form never stores upconv1.0, which the backward pass reads), whatever the handle's
+ * tail algorithm, and the handle is not changed.  The 3x3 layers run under the handle's conv algorithm.  H and W must be multiples
+ * of 4 (CID_ERR_SHAPE otherwise): for other sizes the skip tensors are stored only over the crop the concat keeps, so the max-pool
+ * routing outside it cannot be recovered.  cid_forward keeps accepting every size.  CID_DTYPE_F16 -> CID_ERR_STATE.
+ *
+ * cid_backward: `in`, N, H, W and `saved` are those of the cid_forward_saved call to differentiate, `out` its output y and grad_out
+ * the gradient of the loss with respect to y (both fp32 [N,3,H,W]); the packed weights must still be the ones that call used.
+ * `grads` holds device fp32 pointers for the results in kLayers order (cid_param_key(2 l) / (2 l + 1): down1.0, down1.2, down2.0,
+ * down2.2, bottleneck.0, bottleneck.2, up2, upconv2.0, upconv2.2, up1, upconv1.0, upconv1.2) and reference layouts: Conv2d weights
+ * [Cout,Cin,3,3], the two ConvTranspose2d weights [Cin,Cout,2,2], biases [Cout], input [N,3,H,W].  A null pointer skips that output
+ * and the work only it needs (no weight-gradient launch for a layer with neither pointer, nothing below the deepest layer asked
+ * for); a gradient's bits do not depend on which others were asked for.  Results OVERWRITE; accumulation is the caller's
+ * (autograd's) job.  `saved` is only read; the gradients of the activations live in `workspace`
+ * (cid_backward_workspace_bytes(N, H, W), 256-byte aligned).  Asynchronous on `stream`, no host synchronisation.
+ *
+ * What is computed is the reference graph: dz of the last layer = grad_out * (1 - y^2); a 3x3 convolution's data gradient is the full
+ * correlation with flipped taps and zero padding, its weight gradient the contraction over N*H*W; ReLU's mask is a > 0 of the stored
+ * activation; the concat's gradient slices go to the transposed convolution and the skip; max-pool routes the gradient to the first
+ * element in window scan order (0,0), (0,1), (1,0), (1,1) equal to the pooled value (ATen's rule).  Matrix work runs on the exact-fp32
+ * MFMA; every sum over pixels or images (bias gradients, the partial weight-gradient tiles, the two K = 27 layers) accumulates in fp64
+ * in a fixed order, no atomics: the same call twice gives the same bits.  Every argument is checked before any launch, in this order:
+ *   CID_ERR_INVALID    null handle / in / out / grad_out / saved / grads / workspace, misaligned fp32 pointer
+ *   CID_ERR_STATE      compute dtype CID_DTYPE_F16
+ *   CID_ERR_SHAPE      as cid_forward, or H or W not a multiple of 4
+ *   CID_ERR_WORKSPACE  saved buffer or workspace too small or not 256-byte aligned
+ *   CID_ERR_STATE      no weights attached
+ */
+typedef struct {
+    float* w[12];        /* weight gradients, kLayers order, reference shapes */
+    float* b[12];        /* bias gradients                                    */
+    float* input;        /* fp32 [N,3,H,W]                                    */
+} cid_grads;
+int cid_saved_bytes(int N, int H, int W, size_t* bytes);
+int cid_forward_saved(cid_handle_t h, const float* in, float* out, int N, int H, int W, void* saved, size_t saved_bytes, void* stream);
+int cid_backward_workspace_bytes(int N, int H, int W, size_t* bytes);
+int cid_backward(cid_handle_t h, const float* in, const float* out, const float* grad_out, int N, int H, int W, const void* saved,
+                 size_t saved_bytes, const cid_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
