@@ -32,6 +32,8 @@ SYMBOLS = {
     "cid_param_key": (_c.c_char_p, [_c.c_int]),
     "cid_packed_weights_bytes": (_c.c_size_t, []),
     "cid_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_pack_weights_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_packed_segment": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_char_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
     "cid_export_packed": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t]),
     "cid_import_packed": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t]),
     "cid_attach_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p]),

@@ -12,6 +12,7 @@
 #include "disc_kernels.h"
 #include "disc_bwd_kernels.h"
 #include "gen_bwd_kernels.h"
+#include "gen_pack_kernels.h"
 
 #include <dlfcn.h>
 
@@ -224,6 +225,70 @@ size_t packed_index_s16(const LayerDef& L, int co, int ci, int kh, int j) {
     const int ck = ci >> 5, kg = (ci >> 3) & 3, e = ci & 7;
     const int nchunk = L.cin / 32;
     return ((((((size_t)(nb * nchunk + ck) * 9 + j) * 3 + kh) * 4 + cg) * 64) + kg * 16 + c) * 8 + e;
+}
+
+// The blob's segments in blob order, each with the alignment gap after it: what cid_packed_segment enumerates and what
+// k_gen_pack (gen_pack_kernels.h) fills.  `count` = the elements (fp32 words, or halfs in the half families) that carry data;
+// the rest of the segment is zero.
+struct SegDef { size_t off; std::string name; GenPackFamily fam; int layer, src; size_t count; };
+const std::vector<SegDef>& blob_segments() {
+    static const std::vector<SegDef> segs = [] {
+        std::vector<SegDef> v;
+        for (int l = 0; l < NL; ++l) {
+            const LayerDef& L = kLayers[l];
+            const std::string n = L.name;
+            const size_t nw = ref_weight_count(L);
+            const GenPackFamily wf = L.kind == HEAD ? GP_W_HEAD : L.kind == TAIL ? GP_W_TAIL : L.kind == CONV ? GP_W_GEMM : L.cin == 128 ? GP_W_CONVT_S32 : GP_W_GEMM_T;
+            v.push_back({kBlob.w_off[l], "w:" + n, wf, l, 2 * l, packed_weight_count(L)});
+            v.push_back({kBlob.b_off[l], "b:" + n, GP_COPY, l, 2 * l + 1, (size_t)L.cout});
+            v.push_back({kBlob.raw_w_off[l], "raw_w:" + n, GP_COPY, l, 2 * l, nw});
+            v.push_back({kBlob.raw_b_off[l], "raw_b:" + n, GP_COPY, l, 2 * l + 1, (size_t)L.cout});
+            if (L.kind == CONV) {
+                v.push_back({kBlob.u_off[l], "u:" + n, GP_U, l, 2 * l, nw / 9 * 16});
+                v.push_back({kBlob.u42_off[l], "u42:" + n, GP_U42, l, 2 * l, nw / 9 * 24});
+                v.push_back({kBlob.h_off[l], "h:" + n, GP_H_CONV, l, 2 * l, nw});
+                v.push_back({kBlob.s_off[l], "s16:" + n, GP_S_CONV, l, 2 * l, nw * 3});
+            } else if (L.kind == CONVT) {
+                v.push_back({kBlob.h_off[l], "h:" + n, GP_H_CONVT, l, 2 * l, nw});
+                v.push_back({kBlob.s_off[l], "s16:" + n, GP_S_CONVT, l, 2 * l, nw * 3});
+            } else {
+                v.push_back({kBlob.h_off[l], "h:" + n, L.kind == HEAD ? GP_H_HEAD : GP_H_TAIL, l, 2 * l, (size_t)4 * 64 * 8});
+            }
+        }
+        v.push_back({kBlob.tab_off[0], "tab:32", GP_TAB, 0, 0, (size_t)wino_slot_count(32, 1)});
+        v.push_back({kBlob.tab_off[1], "tab:16", GP_TAB, 0, 1, (size_t)wino_slot_count(16, 2)});
+        v.push_back({kBlob.tab42_off[0], "tab42:8", GP_TAB, 0, 2, (size_t)wino42_slot_table<8>(nullptr)});
+        v.push_back({kBlob.tab42_off[1], "tab42:4", GP_TAB, 0, 3, (size_t)wino42_slot_table<4>(nullptr)});
+        v.push_back({kBlob.hz_off, "hz", GP_HZ, NL - 1, 2 * (NL - 1), (size_t)2 * 2 * 64 * 8});
+        v.push_back({kBlob.hzs_off, "hzs", GP_HZS, NL - 1, 2 * (NL - 1), (size_t)2 * 2 * 2 * 64 * 8});
+        std::sort(v.begin(), v.end(), [](const SegDef& a, const SegDef& b) { return a.off < b.off; });
+        if (v.size() > (size_t)GP_MAX_SEGS) std::abort();   // GenPackArgs::seg holds them all
+        return v;
+    }();
+    return segs;
+}
+
+// k_gen_pack's arguments: the parameter pointers and the segment table.
+GenPackArgs gen_pack_args(const float* const* params, void* blob) {
+    const std::vector<SegDef>& segs = blob_segments();
+    static_assert(sizeof(GenPackArgs) <= 4096, "kernel arguments");
+    GenPackArgs a{};
+    for (int i = 0; i < CID_NUM_PARAMS; ++i) a.p[i] = params[i];
+    a.blob = static_cast<uint4*>(blob);
+    a.nseg = (int)std::min(segs.size(), (size_t)GP_MAX_SEGS);
+    unsigned items = 0;
+    for (int i = 0; i < a.nseg; ++i) {
+        const LayerDef& L = kLayers[segs[i].layer];
+        const size_t end = i + 1 < a.nseg ? segs[i + 1].off : kBlob.total;
+        const unsigned nq = (unsigned)((end - segs[i].off) / 4);
+        a.seg[i] = GenPackSeg{(unsigned)(segs[i].off / 4), nq, items, (unsigned)segs[i].count, (unsigned short)L.cin, (unsigned short)L.cout,
+                              (unsigned char)segs[i].fam, (unsigned char)segs[i].src};
+        const unsigned tiles = (nq + 63) / 64, group = (unsigned)gp_group(segs[i].fam);
+        if (group > 1 && (nq % 64 || tiles % group || segs[i].count != (size_t)nq * (segs[i].fam < GP_H_CONV ? 4 : 8))) std::abort();   // a grouped segment is whole groups, no padding
+        items += tiles / group;
+    }
+    a.nitems = items;
+    return a;
 }
 
 struct Dims {
@@ -919,6 +984,30 @@ int cid_upload_weights(cid_handle_t h, void* device_blob, void* stream) {
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
     if (e != hipSuccess) return fail(h, CID_ERR_HIP, std::string("cid_upload_weights: ") + hipGetErrorString(e));
     h->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_pack_weights_device(cid_handle_t h, const float* const* dev_params, void* device_blob, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!dev_params || !device_blob) return fail(h, CID_ERR_INVALID, "cid_pack_weights_device: null pointer");
+    for (int i = 0; i < CID_NUM_PARAMS; ++i)
+        if (!dev_params[i] || ((uintptr_t)dev_params[i] & 3))
+            return fail(h, CID_ERR_INVALID, "cid_pack_weights_device: null or misaligned parameter pointer");
+    if ((uintptr_t)device_blob & 255) return fail(h, CID_ERR_WORKSPACE, "cid_pack_weights_device: blob must be 256-byte aligned");
+    const GenPackArgs a = gen_pack_args(dev_params, device_blob);
+    hipLaunchKernelGGL(k_gen_pack, dim3((a.nitems + GP_THREADS / 64 - 1) / (GP_THREADS / 64)), dim3(GP_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    if (hipGetLastError() != hipSuccess) return fail(h, CID_ERR_HIP, "cid_pack_weights_device: launch failed");
+    h->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_packed_segment(int index, const char** name, size_t* offset_bytes, size_t* bytes) {
+    const std::vector<SegDef>& segs = blob_segments();
+    if (index < 0 || (size_t)index >= segs.size()) return CID_ERR_INVALID;
+    const size_t end = (size_t)index + 1 < segs.size() ? segs[index + 1].off : kBlob.total;
+    if (name) *name = segs[index].name.c_str();
+    if (offset_bytes) *offset_bytes = segs[index].off * sizeof(float);
+    if (bytes) *bytes = (end - segs[index].off) * sizeof(float);
     return CID_OK;
 }
 

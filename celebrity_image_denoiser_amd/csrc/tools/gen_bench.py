@@ -3,8 +3,14 @@
     forward            cid_forward (DenoiseGenerator(), fused last layer)
     forward + backward DenoiseGenerator(autograd=True): cid_forward_saved + cid_backward, all 24 parameter gradients and the input gradient
     aten               the same network on the module's own stock nn layers through torch autograd (ATen/MIOpen fp32), same process
-    repack             pack_weights() after an in-place change of every parameter (what an optimizer step costs the next forward:
-                       24 device-to-host copies, the host repack, one upload)
+    repack             pack_weights() of a forward-only module after an in-place change of every parameter: the host path (24
+                       device-to-host copies, the host repack, one upload)
+    repack_device      the same on DenoiseGenerator(autograd=True): cid_pack_weights_device, one kernel that writes the whole blob
+                       (what an optimizer step costs the trainer's next forward), with the blob's bytes against the 8 TB/s of HBM
+    touch              the in-place change alone (24 elementwise launches), which both repack rows contain
+    pack kernel        k_gen_pack by itself: forced packs queued behind a few forwards, so that the host has enqueued them all before
+                       the first one starts and the events around them see the kernels back to back; the blob's bytes over that time
+                       against the 8 TB/s of HBM
 
 Cases: B=16 256^2 (the trainer's batch, training.py:504-505) and B=64 128^2.  For each: median ms per call over --reps windows of
 --iters calls [min-max], images/s, algorithmic TFLOP/s and its share of the 157.3 TFLOP/s fp32 MFMA peak; the forward + backward rows
@@ -28,6 +34,7 @@ from celebrity_image_denoiser_amd import synth  # noqa: E402
 from celebrity_image_denoiser_amd.generator import launch_table  # noqa: E402
 
 MFMA_F32_PEAK = 157.3e12
+HBM_PEAK = 8.0e12
 CASES = ((16, 256, 256), (64, 128, 128))
 
 
@@ -112,16 +119,44 @@ def main():
                 line += " | " + fmt("aten", row[key + "_aten"]) + f" | hip/aten {row[key]['ms_median'] / row[key + '_aten']['ms_median']:.2f}"
             print(line, flush=True)
 
-    # the host repack after an optimizer step: every parameter changed in place, then pack_weights()
-    def repack():
+    # the repack after an optimizer step: every parameter changed in place, then pack_weights()
+    def repack(m, pack=True):
         with torch.no_grad():
-            for q in gen_ag.parameters():
+            for q in m.parameters():
                 q.mul_(1.0)
-        gen_ag.pack_weights()
+        if pack:
+            m.pack_weights()
 
-    t = timed(repack, args.reps, max(1, args.iters // 4))
-    rows.append({"repack_ms_median": statistics.median(t), "repack_ms_min": min(t), "repack_ms_max": max(t)})
-    print(f"host repack after an optimizer step (pack_weights): {statistics.median(t):.1f} ms [{min(t):.1f}-{max(t):.1f}]", flush=True)
+    blob_bytes = gen.pack_weights().numel()
+    it = max(1, args.iters // 4)
+    t = timed(lambda: repack(gen), args.reps, it)
+    td = timed(lambda: repack(gen_ag), args.reps, it)
+    t0 = timed(lambda: repack(gen_ag, pack=False), args.reps, it)
+    med, medd, med0 = statistics.median(t), statistics.median(td), statistics.median(t0)
+
+    def pack_kernel(n=20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(8):          # ~20 ms of queued work: the host is done enqueuing long before the packs start
+            gen(x, out=y)
+        e0.record()
+        for _ in range(n):
+            gen_ag.pack_weights(force=True)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    tk = [pack_kernel() for _ in range(args.reps)]
+    medk = statistics.median(tk)
+    rows.append({"repack_ms_median": med, "repack_ms_min": min(t), "repack_ms_max": max(t),
+                 "repack_device_ms_median": medd, "repack_device_ms_min": min(td), "repack_device_ms_max": max(td),
+                 "touch_ms_median": med0, "touch_ms_min": min(t0), "touch_ms_max": max(t0),
+                 "pack_kernel_ms_median": medk, "pack_kernel_ms_min": min(tk), "pack_kernel_ms_max": max(tk),
+                 "blob_bytes": blob_bytes, "device_over_host": medd / med, "pack_kernel_hbm_share": blob_bytes / (medk * 1e-3) / HBM_PEAK})
+    print(f"repack after an optimizer step (pack_weights, host path, autograd=False): {med:.3f} ms [{min(t):.3f}-{max(t):.3f}]", flush=True)
+    print(f"repack_device (pack_weights, device path, autograd=True): {medd:.4f} ms [{min(td):.4f}-{max(td):.4f}] = {medd / med:.5f} of the host path", flush=True)
+    print(f"touch (the in-place change of the 24 parameters alone): {med0:.4f} ms [{min(t0):.4f}-{max(t0):.4f}]", flush=True)
+    print(f"pack kernel (k_gen_pack back to back): {medk:.4f} ms [{min(tk):.4f}-{max(tk):.4f}] for the {blob_bytes / 1e6:.1f} MB blob: "
+          f"{blob_bytes / (medk * 1e-3) / 1e12:.2f} TB/s written, {blob_bytes / (medk * 1e-3) / HBM_PEAK:.3f} of 8 TB/s", flush=True)
     if args.json:
         with open(args.json, "w") as f:
             json.dump(rows, f, indent=1)

@@ -60,20 +60,23 @@ struct W42Geom {
 };
 
 // Host: LDS quad s of a chunk buffer -> packed (row << 20 | column << 8 | channel group), ~0u = deliver zeros.  Padded to 4*RW rounds.
+// wino42_slot_entry is entry s of that table (the device-side weight pack, gen_pack_kernels.h, fills the table from it too).
+template <int TC>
+__host__ __device__ inline unsigned wino42_slot_entry(int s) {
+    using Gm = W42Geom<TC>;
+    unsigned e = ~0u;
+    if (s < Gm::SLOTS) {
+        const int p = s / WPS, g = s % WPS, y = p / Gm::RS, r2 = p % Gm::RS, xp = r2 / Gm::QS, q = r2 % Gm::QS;
+        const int x = 4 * q + xp;
+        if (g < 4 && xp < 4 && x < Gm::LW) e = (unsigned)y << 20 | (unsigned)x << 8 | (unsigned)g;
+    }
+    return e;
+}
 template <int TC>
 inline int wino42_slot_table(unsigned* out /* may be null */) {
-    using Gm = W42Geom<TC>;
-    const int n = 4 * Gm::RW * 64;
+    const int n = 4 * W42Geom<TC>::RW * 64;
     if (out)
-        for (int s = 0; s < n; ++s) {
-            unsigned e = ~0u;
-            if (s < Gm::SLOTS) {
-                const int p = s / WPS, g = s % WPS, y = p / Gm::RS, r2 = p % Gm::RS, xp = r2 / Gm::QS, q = r2 % Gm::QS;
-                const int x = 4 * q + xp;
-                if (g < 4 && xp < 4 && x < Gm::LW) e = (unsigned)y << 20 | (unsigned)x << 8 | (unsigned)g;
-            }
-            out[s] = e;
-        }
+        for (int s = 0; s < n; ++s) out[s] = wino42_slot_entry<TC>(s);
     return n;
 }
 

@@ -35,18 +35,26 @@ constexpr int WS32 = 36;      // staging row stride (floats) for 32-channel slab
 // Host: the slot table of k_wino64_conv<.., TC>: LDS slot s (16 B) of the raw halo tile -> packed (row, column, group).
 // Must mirror the kernel's LDS order: pixel = s/5 (4 data slots + 1 pad), rows of LWS pixels, even columns then odd.
 // BTR = tile rows per workgroup = 32/TC.
-inline int wino_slot_table(int TC, int BTR, unsigned* out /* may be null */) {
-    const int LW = 2 * TC + 2, LH = 2 * BTR + 2, LWS = (TC == 16) ? 40 : LW, HWD = LWS / 2;
+// wino_slot_entry is entry s of that table (any s; the device-side weight pack, gen_pack_kernels.h, fills the table from it too).
+__host__ __device__ inline int wino_slot_count(int TC, int BTR) {
+    const int LW = 2 * TC + 2, LH = 2 * BTR + 2, LWS = (TC == 16) ? 40 : LW;
     // padded to 4 * RW rounds (RW = rounds per wave), so that every wave reads RW entries unconditionally: a guarded
     // load compiles to load -> wait -> next load, i.e. RW serialised memory latencies in every workgroup's prologue
     const int LPIX = LWS * LH, NROUND = (LPIX * WPS + 63) / 64, RW = (NROUND + 3) / 4;
-    if (out)
-        for (int s = 0; s < 4 * RW * 64; ++s) {
-            const int p = s / WPS, c = s - p * WPS;
-            const int hy = p / LWS, rem = p - hy * LWS, plane = rem / HWD, hx = 2 * (rem - plane * HWD) + plane;
-            out[s] = (s < NROUND * 64 && c < 4 && p < LPIX && hx < LW) ? ((unsigned)hy << 20 | (unsigned)hx << 8 | (unsigned)c) : ~0u;
-        }
     return 4 * RW * 64;
+}
+__host__ __device__ inline unsigned wino_slot_entry(int TC, int BTR, int s) {
+    const int LW = 2 * TC + 2, LH = 2 * BTR + 2, LWS = (TC == 16) ? 40 : LW, HWD = LWS / 2;
+    const int LPIX = LWS * LH, NROUND = (LPIX * WPS + 63) / 64;
+    const int p = s / WPS, c = s - p * WPS;
+    const int hy = p / LWS, rem = p - hy * LWS, plane = rem / HWD, hx = 2 * (rem - plane * HWD) + plane;
+    return (s < NROUND * 64 && c < 4 && p < LPIX && hx < LW) ? ((unsigned)hy << 20 | (unsigned)hx << 8 | (unsigned)c) : ~0u;
+}
+inline int wino_slot_table(int TC, int BTR, unsigned* out /* may be null */) {
+    const int n = wino_slot_count(TC, BTR);
+    if (out)
+        for (int s = 0; s < n; ++s) out[s] = wino_slot_entry(TC, BTR, s);
+    return n;
 }
 
 struct WinoArgs {

@@ -111,7 +111,13 @@ class DenoiseGenerator(nn.Module):
 
     def pack_weights(self, force: bool = False) -> torch.Tensor:
         """Repack the 24 parameter tensors into the kernels' layout on the module's GPU (if they
-        changed since the last call) and return the packed device blob."""
+        changed since the last call) and return the packed device blob.
+
+        A forward-only module packs on the host and uploads a fresh blob.  With autograd=True the blob is built on the device
+        by one kernel on the current stream (cid_pack_weights_device: the same bytes, no host synchronisation) and REWRITTEN IN
+        PLACE: the tensor returned keeps its identity across repacks (a blob taken over by adopt_packed_weights included), so
+        work on another stream that still reads it has to be ordered before the repack by the caller, as for the activation
+        arena."""
         sig = self._signature()
         if not force and self._blob is not None and sig == self._packed_sig:
             return self._blob
@@ -122,6 +128,21 @@ class DenoiseGenerator(nn.Module):
                 ".to('cuda') first. There is no CPU fallback."
             )
         L = _lib.lib()
+        if self._autograd:
+            # a training loop changes the weights at every step: pack on the device (cid_pack_weights_device), into one blob that
+            # stays in place.  The handle's host copy is not refreshed: pack_weights_host() stages the parameters itself.
+            ts = [p.detach() for _, p in self.named_parameters()]
+            if any(t.dtype != torch.float32 or t.device != dev for t in ts):
+                raise RuntimeError(f"DenoiseGenerator(autograd=True): parameters must be float32 on {dev}")
+            ts = [t.contiguous() for t in ts]
+            if self._blob is None or self._blob.device != dev:
+                self._blob = torch.empty(L.cid_packed_weights_bytes(), dtype=torch.uint8, device=dev)
+            ptrs = (ctypes.c_void_p * _lib.CID_NUM_PARAMS)(*[t.data_ptr() for t in ts])
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(self._cid, L.cid_pack_weights_device(self._cid, ptrs, self._blob.data_ptr(), stream))
+            self._packed_sig = sig
+            return self._blob
         self._stage_parameters()
         blob = torch.empty(L.cid_packed_weights_bytes(), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream

@@ -188,7 +188,8 @@ class GraphedForward:
         """Capture one forward.  The graph bakes in raw device addresses, so everything it touches is owned here: the
         input/output tensors, a PRIVATE activation arena (the model's own may be replaced when a later eager call needs a
         bigger one) and a reference to the packed weights blob it was captured with (a parameter update makes the model
-        pack a new blob; `__call__` notices and re-captures)."""
+        pack a new blob, or, with autograd=True, rewrite the same one under a new signature; `__call__` notices either and
+        re-captures)."""
         model, dev = self.model, self.static_in.device
         self._blob = model.pack_weights()
         self._sig = model._packed_sig

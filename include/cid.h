@@ -88,6 +88,34 @@ int cid_export_packed(cid_handle_t h, void* host_out, size_t bytes);
  * returns them in reference layout. */
 int cid_import_packed(cid_handle_t h, const void* host_in, size_t bytes);
 
+/*
+ * The packed blob built on the DEVICE from the 24 parameter tensors: `dev_params` holds 24 device pointers to fp32 tensors in the
+ * reference layouts, in cid_param_key order (down1.0.weight, down1.0.bias, ... upconv1.2.bias), each at least 4-byte aligned.  One
+ * kernel on `stream` writes every byte of `device_blob` (caller-owned, >= cid_packed_weights_bytes(), 256-byte aligned; its
+ * previous contents do not matter) and the blob is attached: what cid_set_weight x 24 + cid_upload_weights produce for the same
+ * values, byte for byte — the Winograd transforms in double rounded once, the half pieces, the LDS slot tables and the zeros of
+ * the alignment gaps included — without the device-to-host copies, the host transforms and the upload.  Asynchronous, no host
+ * synchronisation, no memcpy.  A training loop calls it after every optimizer step.
+ * The handle's HOST copy is NOT updated: cid_get_weight, cid_export_packed, cid_upload_weights and cid_missing_weights keep
+ * seeing what cid_set_weight / cid_import_packed last gave it (the convention of cid_disc_pack_weights_device).
+ * Outside the byte-for-byte contract: parameter values that are fp32 subnormals, larger than 65504 in magnitude (the half
+ * pieces overflow) or not finite.
+ *   CID_ERR_INVALID    null dev_params or device_blob; a null parameter pointer or one that is not 4-byte aligned
+ *   CID_ERR_WORKSPACE  device_blob not 256-byte aligned
+ * All of these are found before anything is launched.
+ */
+int cid_pack_weights_device(cid_handle_t h, const float* const* dev_params, void* device_blob, void* stream);
+
+/*
+ * The segments of the packed blob in blob order: index 0, 1, ... until CID_ERR_INVALID.  `name` is "<family>:<layer>" for the
+ * per-layer segments — w (direct kernels), b (bias), u / u42 (Winograd F(2x2,3x3) / F(4x2,3x3) filters), h (fp16 fragments), s16
+ * (split16 pieces), raw_w / raw_b (reference-layout copies) —, "tab:32", "tab:16", "tab42:8", "tab42:4" for the LDS slot tables and
+ * "hz", "hzs" for the fused last layer's fragments.  A segment's alignment padding counts to it, so the entries tile
+ * [0, cid_packed_weights_bytes()) exactly.  Any of the three outputs may be NULL.  Lets a comparison of two blobs name where
+ * they differ.
+ */
+int cid_packed_segment(int index, const char** name, size_t* offset_bytes, size_t* bytes);
+
 /* Adopt a device blob that already holds packed weights (e.g. filled by an RCCL broadcast from
  * the rank that ran cid_upload_weights).  No copy. */
 int cid_attach_weights(cid_handle_t h, const void* device_blob);
