@@ -15,6 +15,8 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
                                   autograd=True its forward is differentiable (HIP backward pass): d_loss.backward() and the
                                   adversarial gradient on the denoised batch, for a stock torch.optim optimizer
     trainer_losses(D, denoised, clean)                  the trainer's d_loss / g_loss / content_loss / adv_loss of one batch
+    Adam(params, lr, betas, eps, weight_decay)          the trainer's optimizer as one kernel per step (cid_adam_step); its state
+                                  interchanges with torch.optim.Adam's
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -38,6 +40,7 @@ _LAZY = {
     "DenoiseDiscriminator": ("discriminator", "DenoiseDiscriminator"),
     "load_discriminator": ("discriminator", "load_discriminator"),
     "trainer_losses": ("discriminator", "trainer_losses"),
+    "Adam": ("optim", "Adam"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

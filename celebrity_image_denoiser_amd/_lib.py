@@ -18,6 +18,20 @@ CID_TAIL_FUSED, CID_TAIL_BANDS, CID_TAIL_TILES = 0, 1, 2
 CID_METRIC_PSNR, CID_METRIC_SSIM, CID_METRIC_MS_SSIM = 1, 2, 4
 CID_DISC_MOMENTUM_NONE = -1.0
 CID_NOISE_GAUSSIAN, CID_NOISE_SALT_PEPPER, CID_NOISE_SPECKLE, CID_NOISE_POISSON, CID_NOISE_UNIFORM = 0, 1, 2, 3, 4
+CID_ADAM_MAX_TENSORS = 32
+
+
+class AdamTensor(ctypes.Structure):
+    """cid_adam_tensor"""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("count", ctypes.c_int64), ("step", ctypes.c_int64)]
+
+
+class AdamHyper(ctypes.Structure):
+    """cid_adam_hyper"""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double)]
+
 
 # every symbol include/cid.h declares: (restype, argtypes)
 _c = ctypes
@@ -102,6 +116,8 @@ SYMBOLS = {
                                 _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "cid_disc_losses": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                    _c.c_void_p, _c.c_void_p]),
+    "cid_adam_step": (_c.c_int, [_c.POINTER(AdamTensor), _c.c_int, _c.POINTER(AdamHyper), _c.c_void_p]),
+    "cid_debug_adam_step_host": (_c.c_int, [_c.POINTER(AdamTensor), _c.c_int, _c.POINTER(AdamHyper)]),
 }
 
 _lib = None

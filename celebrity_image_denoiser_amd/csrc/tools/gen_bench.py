@@ -11,6 +11,10 @@
     pack kernel        k_gen_pack by itself: forced packs queued behind a few forwards, so that the host has enqueued them all before
                        the first one starts and the events around them see the kernels back to back; the blob's bytes over that time
                        against the 8 TB/s of HBM
+    adam               stock torch.optim.Adam(G.parameters(), lr=1e-4).step() on the 24 parameters
+    adam_device        cid.Adam(G.parameters(), lr=1e-4).step(): one cid_adam_step launch; the same process and the same 24 gradients
+    adam kernel        k_adam_step by itself, queued back to back behind a few forwards as `pack kernel` is: 28 bytes per element (four
+                       loads, three stores) over that time against the 8 TB/s of HBM
 
 Cases: B=16 256^2 (the trainer's batch, training.py:504-505) and B=64 128^2.  For each: median ms per call over --reps windows of
 --iters calls [min-max], images/s, algorithmic TFLOP/s and its share of the 157.3 TFLOP/s fp32 MFMA peak; the forward + backward rows
@@ -19,6 +23,7 @@ count 3x the forward's algorithmic FLOPs (forward, data gradient, weight gradien
     python celebrity_image_denoiser_amd/csrc/tools/gen_bench.py [--reps 5] [--iters 20] [--case N,H,W ...] [--no-aten] [--json out.json]
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -30,7 +35,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import celebrity_image_denoiser_amd as cid  # noqa: E402
-from celebrity_image_denoiser_amd import synth  # noqa: E402
+from celebrity_image_denoiser_amd import _lib, synth  # noqa: E402
 from celebrity_image_denoiser_amd.generator import launch_table  # noqa: E402
 
 MFMA_F32_PEAK = 157.3e12
@@ -157,9 +162,60 @@ def main():
     print(f"touch (the in-place change of the 24 parameters alone): {med0:.4f} ms [{min(t0):.4f}-{max(t0):.4f}]", flush=True)
     print(f"pack kernel (k_gen_pack back to back): {medk:.4f} ms [{min(tk):.4f}-{max(tk):.4f}] for the {blob_bytes / 1e6:.1f} MB blob: "
           f"{blob_bytes / (medk * 1e-3) / 1e12:.2f} TB/s written, {blob_bytes / (medk * 1e-3) / HBM_PEAK:.3f} of 8 TB/s", flush=True)
+    adam_rows(args, gen, gen_ag, x, y, rows)
     if args.json:
         with open(args.json, "w") as f:
             json.dump(rows, f, indent=1)
+
+
+def adam_rows(args, gen, gen_ag, x, y, rows):
+    """The optimizer step: stock torch.optim.Adam on `gen`'s parameters, cid.Adam on `gen_ag`'s, both reading the same 24 gradients."""
+    dev = x.device
+    rng = torch.Generator(dev).manual_seed(2)
+    grads = [torch.randn(p.shape, device=dev, generator=rng) * 1e-3 for p in gen.parameters()]
+    for m in (gen, gen_ag):
+        for p, g in zip(m.parameters(), grads):
+            p.grad = g
+    stock = torch.optim.Adam(gen.parameters(), lr=1e-4)
+    device = cid.Adam(gen_ag.parameters(), lr=1e-4)
+    ts = timed(stock.step, args.reps, args.iters)
+    td = timed(device.step, args.reps, args.iters)
+    # the kernel alone through the C ABI with a fixed table, behind ~20 ms of queued work so that the host is ahead of the device
+    params = list(gen_ag.parameters())
+    table = (_lib.AdamTensor * len(params))()
+    for e, p, g in zip(table, params, grads):
+        st = device.state[p]
+        e.param, e.grad, e.exp_avg, e.exp_avg_sq = p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+        e.count, e.step = p.numel(), 1000
+    hp = _lib.AdamHyper(1e-4, 0.9, 0.999, 1e-8, 0.0)
+    L = _lib.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def adam_kernel(n=args.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(8):
+            gen(x, out=y)
+        e0.record()
+        for _ in range(n):
+            if L.cid_adam_step(table, len(params), ctypes.byref(hp), stream) != 0:
+                raise SystemExit("cid_adam_step failed")
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    adam_kernel()
+    tk = [adam_kernel() for _ in range(args.reps)]
+    meds, medd, medk = statistics.median(ts), statistics.median(td), statistics.median(tk)
+    nbytes = 28 * sum(p.numel() for p in params)
+    rows.append({"adam_ms_median": meds, "adam_ms_min": min(ts), "adam_ms_max": max(ts),
+                 "adam_device_ms_median": medd, "adam_device_ms_min": min(td), "adam_device_ms_max": max(td),
+                 "adam_kernel_ms_median": medk, "adam_kernel_ms_min": min(tk), "adam_kernel_ms_max": max(tk),
+                 "adam_bytes": nbytes, "adam_device_over_stock": medd / meds, "adam_kernel_hbm_share": nbytes / (medk * 1e-3) / HBM_PEAK})
+    print(f"adam (torch.optim.Adam(G.parameters(), lr=1e-4).step(), 24 tensors): {meds:.4f} ms [{min(ts):.4f}-{max(ts):.4f}]", flush=True)
+    print(f"adam_device (cid.Adam(G.parameters(), lr=1e-4).step(), one launch): {medd:.4f} ms [{min(td):.4f}-{max(td):.4f}] = "
+          f"{medd / meds:.3f} of the stock step", flush=True)
+    print(f"adam kernel (k_adam_step back to back): {medk:.4f} ms [{min(tk):.4f}-{max(tk):.4f}] for {nbytes / 1e6:.1f} MB moved: "
+          f"{nbytes / (medk * 1e-3) / 1e12:.2f} TB/s, {nbytes / (medk * 1e-3) / HBM_PEAK:.3f} of 8 TB/s", flush=True)
 
 
 if __name__ == "__main__":

@@ -332,3 +332,24 @@ def add_noise_np(clean_u8: np.ndarray, kind: str, seed: int = NOISE_SEED, first_
     if kind == "poisson":
         return add_poisson_noise(clean_u8, seed, first_index)
     return add_salt_pepper_noise(clean_u8, seed=seed, first_index=first_index, **params)
+
+
+def adam_step_np(p, g, m, v, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
+    """One torch.optim.Adam update (default flags: no amsgrad, no maximize, L2 weight decay) of one fp32 tensor -> (p', m', v'):
+    the CPU restatement of k_adam_step / cid_adam_step, the expression tree of include/cid.h in float64 with one rounding to
+    float32 per stored value.  `t` is the tensor's step number including this update (>= 1).  The inputs are not modified."""
+    t = int(t)
+    if t < 1:
+        raise ValueError("adam_step_np: t counts this update, so it is at least 1")
+    lr, beta1, beta2, eps, weight_decay = float(lr), float(beta1), float(beta2), float(eps), float(weight_decay)
+    p64, m64, v64 = (np.asarray(a, dtype=np.float32).astype(np.float64) for a in (p, m, v))
+    g64 = np.asarray(g, dtype=np.float32).astype(np.float64)
+    if weight_decay != 0.0:
+        g64 = g64 + weight_decay * p64
+    m1 = (m64 * beta1 + (1.0 - beta1) * g64).astype(np.float32)
+    v1 = (v64 * beta2 + ((1.0 - beta2) * g64) * g64).astype(np.float32)
+    bc1 = 1.0 - math.pow(beta1, float(t))
+    bc2 = 1.0 - math.pow(beta2, float(t))
+    denom = np.sqrt(v1.astype(np.float64)) / math.sqrt(bc2) + eps
+    p1 = (p64 - (lr / bc1) * (m1.astype(np.float64) / denom)).astype(np.float32)
+    return p1, m1, v1

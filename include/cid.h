@@ -527,10 +527,47 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
                  size_t saved_bytes, const cid_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The trainer's optimizer step — g_optimizer.step() / d_optimizer.step() of training.py:239-240, 417, 426: torch.optim.Adam with default
+ * flags — for up to CID_ADAM_MAX_TENSORS fp32 tensors in ONE kernel on `stream`.  No handle (as cid_quality); asynchronous, no host
+ * synchronisation, no memcpy, no allocation.  `tensors[i]` names one parameter in DEVICE memory: param, exp_avg and exp_avg_sq are
+ * updated in place (`count` contiguous elements each, every element written exactly once), grad is only read; each pointer at least
+ * 4-byte aligned.  `step` is that tensor's step number INCLUDING this update (>= 1; torch counts steps per parameter, so the tensors of
+ * one call may differ).  count == 0 is a no-op entry; a tensor that is not to be updated is left out of the table.  After the call a
+ * generator or discriminator handle needs cid_pack_weights_device / cid_disc_pack_weights_device before its next forward.
+ *
+ * Per element, in double from the fp32 operands, without contraction, each stored value rounded once (round-to-nearest-even):
+ *   g  = (double)grad                      ; if weight_decay != 0:  g = g + weight_decay * (double)p        (L2, not decoupled)
+ *   m' = (float)( (double)m * beta1 + (1 - beta1) * g )
+ *   v' = (float)( (double)v * beta2 + ((1 - beta2) * g) * g )
+ *   bc1 = 1 - beta1^t,  bc2 = 1 - beta2^t                  (host, double, pow(); t = the tensor's `step`)
+ *   p' = (float)( (double)p - (lr / bc1) * ( (double)m' / ( sqrt((double)v') / sqrt(bc2) + eps ) ) )
+ * with 1 - beta1, 1 - beta2, lr / bc1 and sqrt(bc2) formed once on the host in double.  m' and v' need only IEEE multiply and add, so
+ * they are the same bits wherever the tree is evaluated; p' goes through a double sqrt and two double divisions.  A tensor's results
+ * do not depend on which other tensors share the call or on its place in the table.
+ * Outside the tree: amsgrad, maximize, decoupled weight decay (AdamW), tensors that are not fp32, capture-time step counters.
+ * Every argument error is found before anything is launched, in this order:
+ *   CID_ERR_INVALID    null tensors or hp; ntensors outside 1..CID_ADAM_MAX_TENSORS; a null or not 4-byte-aligned pointer in an entry
+ *                      with count > 0; count < 0 (or beyond 2^44) or step < 1; a hyper-parameter that is not finite or out of range
+ *                      (lr < 0, a beta outside [0, 1), eps < 0, weight_decay < 0); any two of the written ranges (param, exp_avg,
+ *                      exp_avg_sq over all entries) overlapping each other or a grad range
+ *   CID_ERR_HIP        launch failure
+ */
+typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; int64_t count; int64_t step; } cid_adam_tensor;
+typedef struct { double lr, beta1, beta2, eps, weight_decay; } cid_adam_hyper;
+#define CID_ADAM_MAX_TENSORS 32
+int cid_adam_step(const cid_adam_tensor* tensors, int ntensors, const cid_adam_hyper* hp, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
 int cid_debug_poison_lds(void* stream);
+/*
+ * Testing aid (no reference counterpart): cid_adam_step with HOST pointers, run on the CPU by the calling thread: the same argument
+ * checks, the same table and the same work-item code as the kernel (csrc/optim_kernels.h is __host__ __device__), one (work item,
+ * lane) after the other.  It holds the index arithmetic and the expression tree against synth.adam_step_np without a GPU.
+ */
+int cid_debug_adam_step_host(const cid_adam_tensor* tensors, int ntensors, const cid_adam_hyper* hp);
 /*
  * Testing aid (no reference counterpart): the four LeakyReLU masks of a cid_disc_forward_saved call exactly as the backward kernels
  * decide them, uint8 (1 where the slope is 1, 0 where it is 0.2): masks[0] [N,64,H,W] (model.1), masks[1] [N,64,H2,W2] (model.4),
