@@ -11,6 +11,7 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     enhance_images(ckpt, in_dir, out_dir)   the reference's directory eval harnesses (denoisegan_eval.py / denoise_eavl_iter.py)
     quality(a, b) / evaluate(denoised, clean)   PSNR / SSIM / MS-SSIM of device batches (the trainer's per-batch evaluation)
     add_noise(clean_u8, kind)     the trainer's five noise kinds on device uint8 batches; evaluate_noise_types(model, clean_u8)
+    resize(src_u8, (width, height)) / resize_images(list, size)   PIL's bicubic Image.resize on device uint8 batches, bit for bit
     DenoiseDiscriminator() / load_discriminator(ckpt)   the trainer's discriminator (eval or train-mode BatchNorm); with
                                   autograd=True its forward is differentiable (HIP backward pass): d_loss.backward() and the
                                   adversarial gradient on the denoised batch, for a stock torch.optim optimizer
@@ -37,6 +38,8 @@ _LAZY = {
     "NOISE_TYPES": ("noise", "NOISE_TYPES"),
     "add_noise": ("noise", "add_noise"),
     "evaluate_noise_types": ("noise", "evaluate_noise_types"),
+    "resize": ("resize", "resize"),
+    "resize_images": ("resize", "resize_images"),
     "DenoiseDiscriminator": ("discriminator", "DenoiseDiscriminator"),
     "load_discriminator": ("discriminator", "load_discriminator"),
     "trainer_losses": ("discriminator", "trainer_losses"),

@@ -19,6 +19,7 @@ CID_METRIC_PSNR, CID_METRIC_SSIM, CID_METRIC_MS_SSIM = 1, 2, 4
 CID_DISC_MOMENTUM_NONE = -1.0
 CID_NOISE_GAUSSIAN, CID_NOISE_SALT_PEPPER, CID_NOISE_SPECKLE, CID_NOISE_POISSON, CID_NOISE_UNIFORM = 0, 1, 2, 3, 4
 CID_ADAM_MAX_TENSORS = 32
+CID_RESAMPLE_BICUBIC = 3
 
 
 class AdamTensor(ctypes.Structure):
@@ -118,6 +119,10 @@ SYMBOLS = {
                                    _c.c_void_p, _c.c_void_p]),
     "cid_adam_step": (_c.c_int, [_c.POINTER(AdamTensor), _c.c_int, _c.POINTER(AdamHyper), _c.c_void_p]),
     "cid_debug_adam_step_host": (_c.c_int, [_c.POINTER(AdamTensor), _c.c_int, _c.POINTER(AdamHyper)]),
+    "cid_resize_plan_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "cid_resize_plan_destroy": (None, [_c.c_void_p]),
+    "cid_resize_plan_table": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
+    "cid_resize": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p]),
 }
 
 _lib = None

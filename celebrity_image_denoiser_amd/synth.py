@@ -353,3 +353,75 @@ def adam_step_np(p, g, m, v, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weigh
     denom = np.sqrt(v1.astype(np.float64)) / math.sqrt(bc2) + eps
     p1 = (p64 - (lr / bc1) * (m1.astype(np.float64) / denom)).astype(np.float32)
     return p1, m1, v1
+
+
+def _resize_cubic(t: np.ndarray) -> np.ndarray:
+    """Pillow's bicubic filter (a = -0.5) in its evaluation order, float64."""
+    a = -0.5
+    t = np.abs(t)
+    inner = ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0
+    outer = (((t - 5.0) * t + 8.0) * t - 4.0) * a
+    return np.where(t < 1.0, inner, np.where(t < 2.0, outer, 0.0))
+
+
+def resize_tables_np(in_size: int, out_size: int):
+    """(ksize, bounds int32 [out, 2] = (xmin, n), coeffs int32 [out, ksize]) of one axis of the bicubic resize: the CPU restatement
+    of cid_resize_plan_table — the arithmetic of include/cid.h (Pillow's precompute_coeffs + normalize_coeffs_8bpc) in float64,
+    every operation rounded on its own (numpy does not contract), casts truncating, the weights summed in index order."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("resize_tables_np: sizes must be >= 1")
+    scale = float(in_size) / float(out_size)
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)          # astype truncates toward zero, like the C cast
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+    n = xmax - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    live = x < n[:, None]
+    w = _resize_cubic(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * (1.0 / fs))
+    w = np.where(live, w, 0.0)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for k in range(ksize):                                                   # w[0] + w[1] + ... in that order (np.sum is pairwise)
+        ww = ww + w[:, k]
+    w = np.where((ww != 0.0)[:, None], w / np.where(ww != 0.0, ww, 1.0)[:, None], w)
+    fixed = np.where(w < 0.0, -0.5 + w * 4194304.0, 0.5 + w * 4194304.0).astype(np.int64)
+    coeffs = np.where(live, fixed, 0).astype(np.int32)
+    bounds = np.stack([xmin, n], axis=1).astype(np.int32)
+    return ksize, bounds, coeffs
+
+
+def _resize_pass_np(img: np.ndarray, axis: int, out_size: int) -> np.ndarray:
+    """One pass of the resize over `axis` of a uint8 [N,H,W,3] array: clamp((2^21 + sum in * k) >> 22, 0, 255) in integers."""
+    in_size = img.shape[axis]
+    ksize, bounds, coeffs = resize_tables_np(in_size, out_size)
+    src = np.moveaxis(img, axis, -1).astype(np.int64)                        # [..., in]
+    acc = np.full(src.shape[:-1] + (out_size,), 1 << 21, dtype=np.int64)
+    for k in range(ksize):
+        idx = np.minimum(bounds[:, 0].astype(np.int64) + k, in_size - 1)     # past n the coefficient is 0
+        acc += src[..., idx] * coeffs[:, k].astype(np.int64)
+    out = np.clip(acc >> 22, 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.moveaxis(out, -1, axis))
+
+
+def resize_bicubic_np(img_u8: np.ndarray, size) -> np.ndarray:
+    """uint8 [H,W,3] or [N,H,W,3] -> the same resized to size = (width, height) as PIL's Image.resize(size, resample=BICUBIC)
+    does, byte for byte, without PIL: the CPU restatement of resize.resize / cid_resize.  Horizontal pass first (if the width
+    changes) into a uint8 intermediate, vertical pass second (if the height changes); a pass whose axis keeps its size is
+    skipped."""
+    img = np.ascontiguousarray(img_u8, dtype=np.uint8)
+    single = img.ndim == 3
+    if single:
+        img = img[None]
+    if img.ndim != 4 or img.shape[3] != 3:
+        raise ValueError("resize_bicubic_np expects uint8 [H,W,3] or [N,H,W,3]")
+    wd, hd = int(size[0]), int(size[1])
+    if img.shape[2] != wd:
+        img = _resize_pass_np(img, 2, wd)
+    if img.shape[1] != hd:
+        img = _resize_pass_np(img, 1, hd)
+    if np.shares_memory(img, img_u8):                                        # neither pass ran: the result is a copy
+        img = img.copy()
+    return img[0] if single else img

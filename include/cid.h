@@ -558,6 +558,55 @@ typedef struct { double lr, beta1, beta2, eps, weight_decay; } cid_adam_hyper;
 int cid_adam_step(const cid_adam_tensor* tensors, int ntensors, const cid_adam_hyper* hp, void* stream);
 
 /*
+ * Bicubic resize — PIL's Image.resize(image_size, resample=BICUBIC) on uint8 RGB, the first step of every reference entry point
+ * (noise_generation.py:61, denoisegan_eval.py, denoise_eavl_iter.py:89, training.py:303-304), on device batches and bit for bit:
+ * Pillow's 8-bit resampler is integer arithmetic (22-bit fixed-point coefficients, a uint8 intermediate between its two passes).
+ * The bit-defined restatement is synth.resize_bicubic_np (tables: synth.resize_tables_np).  No generator handle: no weights.
+ *
+ * Tables of one axis, from inS to outS samples, in double precision without FMA contraction, casts truncating:
+ *   scale = inS / outS;  fs = max(scale, 1.0);  support = 2.0 * fs;  ksize = (int)ceil(support) * 2 + 1
+ *   for xx in 0 .. outS-1:
+ *     center = (xx + 0.5) * scale
+ *     xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), inS);  n = xmax - xmin
+ *     w[x] = cubic((x + xmin - center + 0.5) * (1.0 / fs)),  x = 0 .. n-1
+ *     ww = w[0] + w[1] + ... (in that order);  if ww != 0: w[x] = w[x] / ww
+ *     k[x] = (int)(w[x] < 0 ? -0.5 + w[x] * 4194304.0 : 0.5 + w[x] * 4194304.0)        (22 bits; k[x] = 0 for n <= x < ksize)
+ *     bounds[xx] = (xmin, n)
+ *   cubic(t): a = -0.5; t = |t|;  t < 1: ((a + 2) * t - (a + 3)) * t * t + 1;  t < 2: (((t - 5) * t + 8) * t - 4) * a;  else 0
+ * One pass over an axis, per channel, in int32 (no overflow: a row's absolute coefficients sum to under 1.4 * 2^22, data <= 255):
+ *   out = clamp((2^21 + sum_x in[xmin + x] * k[x]) >> 22, 0, 255)                                     (arithmetic shift)
+ * The horizontal pass runs first, if Ws != Wd, into a uint8 intermediate of Hs x Wd; the vertical pass second, if Hs != Hd.  A pass
+ * whose axis keeps its size is skipped (not run with identity coefficients); with neither the result is a copy.  The rounding of
+ * the intermediate to uint8 is part of the definition.
+ *
+ * cid_resize_plan_create builds both axes' tables on the host, uploads them into device memory the plan owns (on the current
+ * device) and chooses the launch geometry; it may synchronise, and is the only resize call that may.  On a machine without a GPU
+ * the plan is created with its host tables only: cid_resize_plan_table works, cid_resize returns CID_ERR_STATE.
+ *   CID_ERR_INVALID  null `out`, a filter other than CID_RESAMPLE_BICUBIC
+ *   CID_ERR_SHAPE    a side below 1 or above 16384; Hs*Ws*3 or Hd*Wd*3 >= 2^31; a downscale factor inS/outS above 64 on either axis
+ *                    (ksize at most 257: a tile's band of intermediate rows always fits in LDS).  Upscaling is unbounded within the
+ *                    side limit (ksize 5).
+ * cid_resize_plan_table reads a table back from the plan's host copy (no GPU involved): axis 0 is vertical, 1 horizontal; bounds
+ * holds [out*2] ints (xmin, n), coeffs [out*ksize] ints; either may be NULL to query ksize only.  CID_ERR_INVALID for a null plan or
+ * ksize or an unknown axis.
+ * cid_resize: src is device uint8 [N,Hs,Ws,3]; dst is CID_FMT_U8_NHWC [N,Hd,Wd,3] or CID_FMT_F32_NCHW [N,3,Hd,Wd], the latter as
+ * (u/255.0f - 0.5f)/0.5f with true divisions — the forward's uint8 input arithmetic, so the float result fed to cid_forward gives
+ * the bits of the uint8 result fed to cid_forward_ex(CID_FMT_U8_NHWC).  One kernel on `stream` (hipStream_t, NULL = default
+ * stream), asynchronous, no host synchronisation; the intermediate lives in LDS.  dst must not overlap src.  Offsets are 64-bit:
+ * N*Hs*Ws*3 may exceed 2^31.  Checked on the host before the launch:
+ *   CID_ERR_INVALID  null plan, src or dst; unknown format; an fp32 dst that is not 4-byte aligned; N < 1
+ *   CID_ERR_STATE    a plan created without a GPU
+ * Known departure of Pillow itself from this definition (outside the 64x limit): for a 7-pixel-wide source downscaled 200x or more
+ * in height and upscaled in width (800x7, 900x7, 1000x7 -> 4x16), Pillow 12.2's bytes equal a vertical-first evaluation.
+ */
+typedef struct cid_resize_plan_s* cid_resize_plan_t;
+enum { CID_RESAMPLE_BICUBIC = 3 };                      /* Pillow's number for the filter */
+int cid_resize_plan_create(cid_resize_plan_t* out, int Hs, int Ws, int Hd, int Wd, int filter);
+void cid_resize_plan_destroy(cid_resize_plan_t p);
+int cid_resize_plan_table(cid_resize_plan_t p, int axis, int* ksize, int* bounds, int* coeffs);
+int cid_resize(cid_resize_plan_t p, const void* src_u8_nhwc, void* dst, int dst_fmt, int N, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
