@@ -107,129 +107,6 @@ struct BlobLayout {
 };
 const BlobLayout kBlob;
 
-// Index in the packed segment of reference weight element (co, ci, kh, kw) of layer L.
-// GEMM layers: [nb][chunk][tap][group g][ns][lane = 32*h + j][e] with
-//   ci = 32*chunk + 8*g + 4*h + e  and  n' = 64*nb + 32*ns + j  (n' = co, or tap*COUT + co for convT)
-// — lane (h, j) of v_mfma_f32_32x32x2_f32 holds B[k = h][col = j]; e walks the 4 MFMAs of a group.
-size_t packed_index(const LayerDef& L, int co, int ci, int kh, int kw) {
-    switch (L.kind) {
-        case HEAD: {
-            int s, h;
-            head_step_of(ci * 9 + kh * 3 + kw, s, h);   // the head's K order (conv_kernels.h head_step)
-            return (size_t)((co >> 5) * 14 + s) * 64 + h * 32 + (co & 31);
-        }
-        case TAIL: {   // B[k = ci][col = 3*tap + co] of the tail's 64 x 32 product
-            const int col = (kh * 3 + kw) * 3 + co, ck = ci >> 5, g = (ci >> 3) & 3, h = (ci >> 2) & 1, e = ci & 3;
-            return (size_t)((ck * 4 + g) * 64 + h * 32 + col) * 4 + e;
-        }
-        case CONVT:
-            if (L.cin == 128) {   // up1, k_convt_s32: [tap][g][j][mt][lane = 16*kga + row] — A[row][k = kga] of v_mfma_f32_16x16x4_f32 for k-step j
-                const int g = ci >> 4, kga = (ci >> 2) & 3, j = ci & 3, mt = co >> 4, row = co & 15;   // of group g: ci = 16 g + 4 kga + j, co = 16 mt + row
-                return (((((size_t)(kh * 2 + kw) * (L.cin / 16) + g) * 4 + j) * 4 + mt) * 64) + kga * 16 + row;
-            }
-            [[fallthrough]];
-        case CONV: {
-            const int taps = L.kind == CONV ? 9 : 1;
-            const int tap = L.kind == CONV ? kh * 3 + kw : 0;
-            const int np = L.kind == CONV ? co : (kh * 2 + kw) * L.cout + co;
-            const int nb = np >> 6, ns = (np >> 5) & 1, j = np & 31;
-            const int ck = ci >> 5, g = (ci >> 3) & 3, h = (ci >> 2) & 1, e = ci & 3;
-            const int nchunk = L.cin / 32;
-            return ((((size_t)(nb * nchunk + ck) * taps + tap) * 4 + g) * 2 + ns) * 256 + (h * 32 + j) * 4 + e;
-        }
-    }
-    return 0;
-}
-// Index of (co, ci, kh, kw) in the reference tensor: Conv2d [Cout,Cin,3,3]; ConvTranspose2d [Cin,Cout,2,2].
-size_t ref_index(const LayerDef& L, int co, int ci, int kh, int kw) {
-    if (L.kind == CONVT) return (((size_t)ci * L.cout + co) * 2 + kh) * 2 + kw;
-    return (((size_t)co * L.cin + ci) * 3 + kh) * 3 + kw;
-}
-
-// Winograd F(2x2,3x3) filter transform U = G g G^T (reference Conv2d weight [Cout,Cin,3,3] -> 16 values per
-// (co, ci)), in double, rounded once to fp32, laid out for k_wino64_conv:
-//   [nb = co/64][chunk = ci/16][round = (ci/8)%2][a][nt = (co/32)%2][e][lane = 32*h + j][b],  ci = 16*chunk + 8*round + 4*h + e, co = 64*nb + 32*nt + j
-// (one 16-byte quad per lane = the four positions b of k-step e, so a quad's registers free up after 4 MFMAs)
-void pack_winograd_u(const LayerDef& L, const float* w, float* dst) {
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int nchunk = L.cin / 16;
-    for (int co = 0; co < L.cout; ++co)
-        for (int ci = 0; ci < L.cin; ++ci) {
-            const float* g = w + ((size_t)co * L.cin + ci) * 9;
-            double tmp[4][3];
-            for (int a = 0; a < 4; ++a)
-                for (int q = 0; q < 3; ++q) tmp[a][q] = G[a][0] * g[0 * 3 + q] + G[a][1] * g[1 * 3 + q] + G[a][2] * g[2 * 3 + q];
-            const int nb = co >> 5, j = co & 31, ck = ci >> 4, g2 = (ci >> 3) & 1, h = (ci >> 2) & 1, e = ci & 3;
-            for (int a = 0; a < 4; ++a)
-                for (int b = 0; b < 4; ++b) {
-                    const double u = tmp[a][0] * G[b][0] + tmp[a][1] * G[b][1] + tmp[a][2] * G[b][2];
-                    dst[(((((((size_t)(nb >> 1) * nchunk + ck) * 2 + g2) * 4 + a) * 2 + (nb & 1)) * 4 + e) * 64 + h * 32 + j) * 4 + b] = (float)u;
-                }
-        }
-}
-
-// Winograd F(4x2,3x3) filter transform U = G2 g G4^T — rows by the F(2,3) matrix of pack_winograd_u, columns by F(4,3) at the
-// points 0, 3/4, -3/4, 3/2, -3/2, inf (24 values per (co, ci)) —, in double, rounded once to fp32, laid out for k_wino42_conv:
-//   [nb = co/64][unit][a][q = 6*e2 + b][lane = 16*g + j][cg],   ci = 16*(unit/2) + 4*g + 2*((unit%2) ^ (g&1)) + e2,  co = 64*nb + 4*j + cg
-// (one 16-byte quad per lane = the four channel groups of position (a, b) at k-step e2: one V value, four MFMAs)
-void pack_winograd42_u(const LayerDef& L, const float* w, float* dst) {
-    static const double G2[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    static const double G4[6][3] = {{64.0 / 81, 0, 0},
-                                    {-128.0 / 243, -32.0 / 81, -8.0 / 27},
-                                    {-128.0 / 243, 32.0 / 81, -8.0 / 27},
-                                    {32.0 / 243, 16.0 / 81, 8.0 / 27},
-                                    {32.0 / 243, -16.0 / 81, 8.0 / 27},
-                                    {0, 0, 1}};
-    const int nunit = L.cin / 8;
-    for (int co = 0; co < L.cout; ++co)
-        for (int ci = 0; ci < L.cin; ++ci) {
-            const float* g = w + ((size_t)co * L.cin + ci) * 9;
-            double tmp[4][3];
-            for (int a = 0; a < 4; ++a)
-                for (int q = 0; q < 3; ++q) tmp[a][q] = G2[a][0] * g[0 * 3 + q] + G2[a][1] * g[1 * 3 + q] + G2[a][2] * g[2 * 3 + q];
-            const int nb = co >> 6, j = (co >> 2) & 15, cg = co & 3;   // column j of channel group cg = channel 4j + cg: see the kernel's epilogue
-            // lane group gg reads the 8-byte half (ci >> 1) & 1 of its LDS quad for unit s2 = half ^ (gg & 1): odd channel groups take
-            // the halves in the other order, which makes the kernel's ds_read_b64 conflict-free (wino42_kernels.h, xbase / ybase)
-            const int ck = ci >> 4, gg = (ci >> 2) & 3, s2 = ((ci >> 1) & 1) ^ (gg & 1), e2 = ci & 1;
-            const int unit = ck * 2 + s2;
-            for (int a = 0; a < 4; ++a)
-                for (int b = 0; b < 6; ++b) {
-                    const double u = tmp[a][0] * G4[b][0] + tmp[a][1] * G4[b][1] + tmp[a][2] * G4[b][2];
-                    dst[((((((size_t)nb * nunit + unit) * 4 + a) * 12 + (6 * e2 + b)) * 64) + gg * 16 + j) * 4 + cg] = (float)u;
-                }
-        }
-}
-
-// k_convt_t16: [tap][cb][k-step][mt][lane = 16*kga + row][8] halfs — the A operand of v_mfma_f32_16x16x32_f16: A[row][k = 8 kga + e] with
-// ci = 32*kstep + 8*kga + e and row `row` of M tile `mt` = channel 64 cb + 32 (mt >> 1) + 8 (row >> 2) + 4 (mt & 1) + (row & 3).
-size_t packed_index_ht(const LayerDef& L, int co, int ci, int kh, int kw) {
-    const int tap = kh * 2 + kw, cb = co >> 6, c = co & 63;
-    const int mt = ((c >> 5) << 1) | ((c >> 2) & 1), row = (((c >> 3) & 3) << 2) | (c & 3);
-    const int ks = ci >> 5, kga = (ci >> 3) & 3, e = ci & 7;
-    const int CB = L.cout / 64, KS = L.cin / 32;
-    return (((((size_t)(tap * CB + cb) * KS + ks) * 4 + mt) * 64) + kga * 16 + row) * 8 + e;
-}
-
-// k_conv3x3_h16: [nb][32-ch chunk][dx][dy][cg = co%4][lane = 16*kg + (co/4)%16][8] halfs with ci = 32*chunk + 8*kg + e —
-// lane (col, kg) of v_mfma_f32_16x16x32_f16 holds B[k = 8kg..8kg+7][col]; column col of channel group cg is output channel
-// 64 nb + 4 col + cg, so a lane's four accumulator tiles are four consecutive channels (the kernel stores them as 8 bytes);
-// one (chunk, dx) is a 12 KiB LDS-DMA unit.
-size_t packed_index_h16(const LayerDef& L, int co, int ci, int kh, int kw) {
-    const int nb = co >> 6, cg = co & 3, c = (co >> 2) & 15;
-    const int ck = ci >> 5, kg = (ci >> 3) & 3, e = ci & 7;
-    const int nchunk = L.cin / 32;
-    return ((((((size_t)(nb * nchunk + ck) * 3 + kw) * 3 + kh) * 4 + cg) * 64) + kg * 16 + c) * 8 + e;
-}
-
-// conv_algo = "split16" (k_conv3x3_h16<F32IO>): [column block nb][chunk ck of 32 fp32 channels][j = 0..8][kh][channel group cg][lane = 16 kg + col][8] halfs, where sub-chunk
-// j = 0..2 is tap column kw = j of hi_w (met by hi_x), j = 3..5 kw = j - 3 of lo_w (met by hi_x), j = 6..8 kw = j - 6 of hi_w again (met by lo_x); hi_w = half(w), lo_w = half(w - hi_w)
-size_t packed_index_s16(const LayerDef& L, int co, int ci, int kh, int j) {
-    const int nb = co >> 6, cg = co & 3, c = (co >> 2) & 15;
-    const int ck = ci >> 5, kg = (ci >> 3) & 3, e = ci & 7;
-    const int nchunk = L.cin / 32;
-    return ((((((size_t)(nb * nchunk + ck) * 9 + j) * 3 + kh) * 4 + cg) * 64) + kg * 16 + c) * 8 + e;
-}
-
 // The blob's segments in blob order, each with the alignment gap after it: what cid_packed_segment enumerates and what
 // k_gen_pack (gen_pack_kernels.h) fills.  `count` = the elements (fp32 words, or halfs in the half families) that carry data;
 // the rest of the segment is zero.
@@ -271,27 +148,52 @@ const std::vector<SegDef>& blob_segments() {
     return segs;
 }
 
+// The segment table in the form the pack code (gen_pack_kernels.h) reads, with the work items counted; no pointers yet.
+const GenPackArgs& gen_pack_table() {
+    static const GenPackArgs table = [] {
+        const std::vector<SegDef>& segs = blob_segments();
+        static_assert(sizeof(GenPackArgs) <= 4096, "kernel arguments");
+        GenPackArgs a{};
+        a.nseg = (int)segs.size();
+        unsigned items = 0;
+        for (int i = 0; i < a.nseg; ++i) {
+            const LayerDef& L = kLayers[segs[i].layer];
+            const size_t end = i + 1 < a.nseg ? segs[i + 1].off : kBlob.total;
+            const unsigned nq = (unsigned)((end - segs[i].off) / 4);
+            a.seg[i] = GenPackSeg{(unsigned)(segs[i].off / 4), nq, items, (unsigned)segs[i].count, (unsigned short)L.cin, (unsigned short)L.cout,
+                                  (unsigned char)segs[i].fam, (unsigned char)segs[i].src};
+            const unsigned tiles = (nq + 63) / 64, group = (unsigned)gp_group(segs[i].fam);
+            if (group > 1 && (nq % 64 || tiles % group || segs[i].count != (size_t)nq * (segs[i].fam < GP_H_CONV ? 4 : 8))) std::abort();   // a grouped segment is whole groups, no padding
+            items += tiles / group;
+        }
+        a.nitems = items;
+        return a;
+    }();
+    return table;
+}
+
 // k_gen_pack's arguments: the parameter pointers and the segment table.
 GenPackArgs gen_pack_args(const float* const* params, void* blob) {
-    const std::vector<SegDef>& segs = blob_segments();
-    static_assert(sizeof(GenPackArgs) <= 4096, "kernel arguments");
-    GenPackArgs a{};
+    GenPackArgs a = gen_pack_table();
     for (int i = 0; i < CID_NUM_PARAMS; ++i) a.p[i] = params[i];
     a.blob = static_cast<uint4*>(blob);
-    a.nseg = (int)std::min(segs.size(), (size_t)GP_MAX_SEGS);
-    unsigned items = 0;
-    for (int i = 0; i < a.nseg; ++i) {
-        const LayerDef& L = kLayers[segs[i].layer];
-        const size_t end = i + 1 < a.nseg ? segs[i + 1].off : kBlob.total;
-        const unsigned nq = (unsigned)((end - segs[i].off) / 4);
-        a.seg[i] = GenPackSeg{(unsigned)(segs[i].off / 4), nq, items, (unsigned)segs[i].count, (unsigned short)L.cin, (unsigned short)L.cout,
-                              (unsigned char)segs[i].fam, (unsigned char)segs[i].src};
-        const unsigned tiles = (nq + 63) / 64, group = (unsigned)gp_group(segs[i].fam);
-        if (group > 1 && (nq % 64 || tiles % group || segs[i].count != (size_t)nq * (segs[i].fam < GP_H_CONV ? 4 : 8))) std::abort();   // a grouped segment is whole groups, no padding
-        items += tiles / group;
-    }
-    a.nitems = items;
     return a;
+}
+
+// The host pack: the segments that parameter tensor `src` feeds (kTables: the four LDS slot tables, which read no tensor), written
+// into the host blob by the device pack's own code, every work item over its 64 lanes.  A segment's quads run up to the next
+// segment's start, so the alignment gap after it is rewritten as zeros and nothing outside it is touched.
+constexpr int kTables = -1;
+void stage_segments(float* staging, int src, const float* data) {
+    const GenPackArgs& a = gen_pack_table();
+    for (int i = 0; i < a.nseg; ++i) {
+        const GenPackSeg& s = a.seg[i];
+        if (s.fam == GP_TAB ? src != kTables : s.src != src) continue;
+        const unsigned items = (i + 1 < a.nseg ? a.seg[i + 1].t0 : a.nitems) - s.t0;
+        for (unsigned t = 0; t < items; ++t)
+            for (int lane = 0; lane < 64; ++lane)
+                gen_pack_produce(s, data, t, lane, [staging](unsigned q, const unsigned (&v)[4]) { std::memcpy(staging + 4 * (size_t)q, v, 16); });
+    }
 }
 
 struct Dims {
@@ -358,10 +260,7 @@ struct cid_handle_s {
     int tev_forwards = 0, tev_used = 0;
     cid_handle_s() : staging(kBlob.total, 0.f) {
         std::memset(have, 0, sizeof(have));
-        wino_slot_table(32, 1, reinterpret_cast<unsigned*>(staging.data() + kBlob.tab_off[0]));
-        wino_slot_table(16, 2, reinterpret_cast<unsigned*>(staging.data() + kBlob.tab_off[1]));
-        wino42_slot_table<8>(reinterpret_cast<unsigned*>(staging.data() + kBlob.tab42_off[0]));
-        wino42_slot_table<4>(reinterpret_cast<unsigned*>(staging.data() + kBlob.tab42_off[1]));
+        stage_segments(staging.data(), kTables, nullptr);
     }
 };
 
@@ -466,15 +365,6 @@ bool find_key(const char* key, int& layer, int& is_bias) {
         if (k == n + ".bias") { layer = l; is_bias = 1; return true; }
     }
     return false;
-}
-
-template <typename F>
-void for_each_weight(const LayerDef& L, F f) {
-    const int kk = L.kind == CONVT ? 2 : 3;
-    for (int co = 0; co < L.cout; ++co)
-        for (int ci = 0; ci < L.cin; ++ci)
-            for (int kh = 0; kh < kk; ++kh)
-                for (int kw = 0; kw < kk; ++kw) f(co, ci, kh, kw);
 }
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -882,75 +772,7 @@ int cid_set_weight(cid_handle_t h, const char* key, const float* data, const int
         for (int i = 0; i < ndim; ++i) m += (i ? "," : "") + std::to_string(shape[i]);
         return fail(h, CID_ERR_SHAPE, m + "]");
     }
-    if (is_bias) {
-        std::memcpy(h->staging.data() + kBlob.b_off[l], data, sizeof(float) * L.cout);
-        std::memcpy(h->staging.data() + kBlob.raw_b_off[l], data, sizeof(float) * L.cout);
-    } else {
-        float* dst = h->staging.data() + kBlob.w_off[l];
-        for_each_weight(L, [&](int co, int ci, int kh, int kw) { dst[packed_index(L, co, ci, kh, kw)] = data[ref_index(L, co, ci, kh, kw)]; });
-        std::memcpy(h->staging.data() + kBlob.raw_w_off[l], data, sizeof(float) * ref_weight_count(L));
-        if (L.kind == CONV) pack_winograd_u(L, data, h->staging.data() + kBlob.u_off[l]);
-        if (L.kind == CONV) pack_winograd42_u(L, data, h->staging.data() + kBlob.u42_off[l]);
-        if (L.kind == TAIL) {   // half copy for k_conv_tail_h: [k-step s][lane = 32*h + col][e], ci = 16*s + 8*h + e, col = 3*tap + co
-            _Float16* hd = reinterpret_cast<_Float16*>(h->staging.data() + kBlob.h_off[l]);
-            for_each_weight(L, [&](int co, int ci, int kh, int kw) {
-                const int col = (kh * 3 + kw) * 3 + co, s = ci >> 4, hh = (ci >> 3) & 1, e = ci & 7;
-                hd[((size_t)s * 64 + hh * 32 + col) * 8 + e] = (_Float16)data[ref_index(L, co, ci, kh, kw)];
-            });
-            // and for the fused form (h16_zout_epilogue): the A operand of z^T = W2' . X^T on v_mfma_f32_16x16x32_f16, row 3 tap + co
-            // (27 rows, rows 27..31 stay zero): [row tile t][k-step ks][lane = 16 kga + row][e] with ci = 32 ks + 8 kga + e
-            _Float16* hz = reinterpret_cast<_Float16*>(h->staging.data() + kBlob.hz_off);
-            std::memset(hz, 0, 3 * 2 * 64 * 8 * sizeof(_Float16));
-            for_each_weight(L, [&](int co, int ci, int kh, int kw) {
-                const int row = 3 * (kh * 3 + kw) + co, t = row >> 4, ks = ci >> 5, kga = (ci >> 3) & 3, e = ci & 7;
-                hz[(((size_t)t * 2 + ks) * 64 + kga * 16 + (row & 15)) * 8 + e] = (_Float16)data[ref_index(L, co, ci, kh, kw)];
-            });
-            // the same fragments as hi | lo pieces for the split-operand form (h16_zout_epilogue_f32)
-            _Float16* hzs = reinterpret_cast<_Float16*>(h->staging.data() + kBlob.hzs_off);
-            std::memset(hzs, 0, 2 * 2 * 2 * 64 * 8 * sizeof(_Float16));
-            for_each_weight(L, [&](int co, int ci, int kh, int kw) {
-                const int row = 3 * (kh * 3 + kw) + co, t = row >> 4, ks = ci >> 5, kga = (ci >> 3) & 3, e = ci & 7;
-                const float v = data[ref_index(L, co, ci, kh, kw)];
-                const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
-                const size_t at = (((size_t)t * 2 + ks) * 64 + kga * 16 + (row & 15)) * 8 + e;
-                hzs[at] = hi; hzs[4 * 64 * 8 + at] = lo;
-            });
-        }
-        if (L.kind == CONVT) {   // split-operand pieces of a transposed convolution (k_conv3x3_h16<..., 2, ., ., F32IO, PAIR>): piece p = 0 hi_w, 1 lo_w, 2 hi_w again (met by lo_x)
-            _Float16* sp = reinterpret_cast<_Float16*>(h->staging.data() + kBlob.s_off[l]);
-            const int cbs = L.cout / 64, nchunk = L.cin / 32;
-            for_each_weight(L, [&](int co, int ci, int kh, int kw) {
-                const float v = data[ref_index(L, co, ci, kh, kw)];
-                const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
-                const int blk = (kh * 2 + kw) * cbs + (co >> 6), cg = co & 3, c = (co >> 2) & 15, ck = ci >> 5, kg = (ci >> 3) & 3, e = ci & 7;
-                for (int p = 0; p < 3; ++p)
-                    sp[((((((size_t)blk * nchunk + ck) * 3 + p) * 4 + cg) * 64) + kg * 16 + c) * 8 + e] = p == 1 ? lo : hi;
-            });
-        }
-        if (L.kind == CONV) {   // split-operand pieces (conv_algo = "split16")
-            _Float16* sp = reinterpret_cast<_Float16*>(h->staging.data() + kBlob.s_off[l]);
-            for_each_weight(L, [&](int co, int ci, int kh, int kw) {
-                const float v = data[ref_index(L, co, ci, kh, kw)];
-                const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
-                sp[packed_index_s16(L, co, ci, kh, kw)] = hi; sp[packed_index_s16(L, co, ci, kh, 3 + kw)] = lo; sp[packed_index_s16(L, co, ci, kh, 6 + kw)] = hi;
-            });
-        }
-        if (L.kind == CONV || L.kind == CONVT) {
-            _Float16* hd = reinterpret_cast<_Float16*>(h->staging.data() + kBlob.h_off[l]);
-            for_each_weight(L, [&](int co, int ci, int kh, int kw) {
-                hd[L.kind == CONV ? packed_index_h16(L, co, ci, kh, kw) : packed_index_ht(L, co, ci, kh, kw)] = (_Float16)data[ref_index(L, co, ci, kh, kw)];
-            });
-        }
-        if (L.kind == HEAD) {   // k_conv_head_h16: B[k = 3 tap + c][co], rows 27..31 zero; lane (col = (co / 4) % 16, kg) of group co % 4 holds k = 8kg..8kg+7
-            _Float16* hd = reinterpret_cast<_Float16*>(h->staging.data() + kBlob.h_off[l]);
-            for (int co = 0; co < 64; ++co)
-                for (int k = 0; k < 32; ++k) {
-                    const int tap = k / 3, c = k % 3;
-                    const float v = k < 27 ? data[ref_index(L, co, c, tap / 3, tap % 3)] : 0.f;
-                    hd[((co & 3) * 64 + (k >> 3) * 16 + ((co >> 2) & 15)) * 8 + (k & 7)] = (_Float16)v;
-                }
-        }
-    }
+    stage_segments(h->staging.data(), 2 * l + is_bias, data);   // every layout of this tensor, the reference-layout copy included
     h->have[l][is_bias] = true;
     return CID_OK;
 }

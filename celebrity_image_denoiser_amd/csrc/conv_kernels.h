@@ -379,14 +379,6 @@ __host__ __device__ constexpr HeadStep head_step(int s) {
          : s == 12 ? HeadStep{8, 8, 17, 2}
                    : HeadStep{23, -1, 26, 1};
 }
-// Host: (step, lane half) that multiplies element k.
-inline void head_step_of(int k, int& s, int& h) {
-    for (s = 0; s < 14; ++s) {
-        if (head_step(s).k0 == k) { h = 0; return; }
-        if (head_step(s).k1 == k) { h = 1; return; }
-    }
-    s = h = -1;
-}
 
 // f4: the reference server pads an upload with black to a multiple of 4, runs the network on the padded image and
 // crops the padding off the result again (app.py:276-281,384-385,474-480).  Both are index arithmetic in the first and the
@@ -551,7 +543,7 @@ __global__ void __launch_bounds__(THREADS, 4) k_conv_head(const HeadArgs a) {
 // folded in).  HBM-bound on the 64-channel NHWC input it reads once.
 struct TailArgs {
     const void* in;     // NHWC [N,H,W,64]: fp32, or (IN_F16) half from the fp16-storage path
-    const float* w;     // packed [2 chunk][4 group][64 lanes][4]  (cid_api.hip packed_index, TAIL)
+    const float* w;     // packed [2 chunk][4 group][64 lanes][4]  (gen_pack_kernels.h, GP_W_TAIL)
     const float* bias;  // [3]
     void* out;          // fp32 NCHW [N,3,crop.H,crop.W], or (OUT_U8) uint8 NHWC [N,crop.H,crop.W,3]
     Window crop;        // the window of the network output [H, W] the caller's tensor receives

@@ -48,7 +48,7 @@ struct GemmConvArgsH {
 //     one contiguous run of memory), brought in by LDS-DMA into one of two buffers while the other is computed on: ONE barrier per tile;
 //   * LDS holds a pixel's 16-byte slots XOR-swizzled with the pixel index (phys = s ^ (p & 15)), applied on the SOURCE side of the DMA
 //     (lane L always lands at L * 16): the pixel operand is read with conflict-free ds_read_b128 although pixels are 256 / 512 B apart;
-//   * row m = 4 kg + r of M tile mt is channel 32 (mt >> 1) + 8 kg + 4 (mt & 1) + r (packed_index_ht): a lane's two M tiles of a pair
+//   * row m = 4 kg + r of M tile mt is channel 32 (mt >> 1) + 8 kg + 4 (mt & 1) + r (gen_pack_kernels.h, GP_H_CONVT): a lane's two M tiles of a pair
 //     are 8 CONSECUTIVE channels of one pixel, so results leave as 16-byte stores straight from the accumulators (four lanes = 64
 //     contiguous bytes of a pixel), no staging.
 template <int CIN, int COUT>
@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(64 * 4 * (COUT / 64), 2) k_convt_t16(const Gem
 __device__ __forceinline__ int h16_prow(int i) { return ((0xa802 >> (4 * (i >> 2))) & 15) + (i & 1) + 2 * (i & 2); }
 
 // Stores of the 16x16x32 kernels (round 4: straight from the accumulators).  Column j of channel group cg is output channel 4 j + cg of
-// the workgroup's 64 (packed_index_h16 / the head's packing put the weights there): in an accumulator tile, lane (column c16 = lane & 15,
+// the workgroup's 64 (gen_pack_kernels.h, GP_H_CONV / GP_H_HEAD, puts the weights there): in an accumulator tile, lane (column c16 = lane & 15,
 // row group kg = lane >> 4) holds pixels 16 pg + {2,0,8,10}[kg] + (r&1) + 4(r>>1) (r = 0..3) of one output row, and its four channel
 // groups are four CONSECUTIVE channels 4 c16 .. 4 c16 + 3 — 8 bytes as halfs.  A store instruction therefore writes four pixels'
 // whole 128-byte lines (16 lanes each) with no pass through LDS: rounds 2-3 staged every row as fp32 in a wave-private LDS area
@@ -513,7 +513,7 @@ __device__ __forceinline__ void h16_zout_epilogue_f32(const Args& a, f32x4* stag
 //     win — and then found the layout that keeps them: two pad slots between planes 1 and 2 (PLANE_GAP below) put the plane origins at
 //     0, 4, 2, 6 (mod 8) while the read pairs (0,1) and (2,3) stay 4 (mod 16) apart: reads and writes conflict-free, 0.0 % measured on every
 //     launch of the path, 3x3 launches -0.3...-0.8 % (profiles/r04_ab_f16_plane_gap.txt);
-//   * B: packed on the host per lane, [chunk][dx][dy][channel group][lane = 16 kg + col][8] (cid_api.hip packed_index_h16);
+//   * B: packed per lane, [chunk][dx][dy][channel group][lane = 16 kg + col][8] (gen_pack_kernels.h, GP_H_CONV);
 //     one tap column (12 KiB) at a time by LDS-DMA into one of two buffers — no staging registers, and the LDS stays under a
 //     third of the CU's; the halo tile of the next chunk waits in 24 registers over the chunk's last sub-step;
 //   * per sub-step the wave reads its four input rows once (8 A quads) and 12 B quads for 48 MFMAs.

@@ -1,8 +1,10 @@
-// gen_pack_kernels.h — the generator's packed weights blob built on the device from the 24 parameter tensors.
+// gen_pack_kernels.h — the generator's packed weights blob built from the 24 parameter tensors: THE definition of the blob's layouts.
 //
-// k_gen_pack writes what cid_set_weight x 24 + cid_upload_weights produce (cid_api.hip), byte for byte: every segment of BlobLayout,
-// the four LDS slot tables and the alignment gaps (zeros).  A training loop calls it after every optimizer step in place of 24
-// device-to-host copies, the host's fp64 Winograd transforms and one 58.7 MB upload.
+// One piece of source compiled twice.  On the device k_gen_pack writes every segment of BlobLayout (cid_api.hip), the four LDS slot
+// tables and the alignment gaps (zeros); a training loop calls it after every optimizer step in place of 24 device-to-host copies, a
+// host repack and one 58.7 MB upload.  On the host cid_set_weight runs gen_pack_produce over the work items of the segments that one
+// tensor feeds, and cid_handle_s's constructor over those of the tables.  Each family's layout (index order, which MFMA operand a lane
+// holds) is described where its formula stands below; the kernels' comments point here.
 //
 // Gather form: a lane owns 16 bytes of the blob (a "quad": four fp32 words or eight halfs), a wave a "tile" of 64 consecutive quads
 // (1 KiB) of ONE segment: tiles are counted per segment (the last tile of a segment may be partly masked), so that the segment, found by
@@ -10,26 +12,28 @@
 // in scalar registers and the divisions of the decode run on the scalar unit.  A lane inverts its segment's index formula into
 // (co, ci, kh, kw), reads the parameter(s) with 4-byte loads and stores one uint4 per tile.  Every segment starts on a 256-byte
 // boundary and its quads run up to the next one's start, so every byte is written exactly once by construction; there are no
-// atomics and nothing is read from the blob.  The inverse of each formula sits next to a restatement of the host's forward
-// formula; the byte-identity test (tests/test_generator_pack_device.py) holds the two together.
+// atomics and nothing is read from the blob.  Next to each inverse stands the forward formula (the index of element (co, ci, tap) in
+// the segment), which is what the consuming kernel relies on.  tests/golden/gen_pack_digests.json, recorded from the separate scatter
+// pack that the host had before, pins the layout; the byte-identity test (tests/test_generator_pack_device.py) holds the device's
+// arithmetic and stores against the host's run of the same source.
 //
 // The layouts are transposes of the reference tensors, so a wave's 4-byte reads are scattered (one cache line per lane and load) and
 // the kernel is paced by them, not by its stores.  Where several tiles need the same parameters in the same lanes, one wave therefore
 // takes the whole group as one work item and loads once: the 24 tiles (a, b) of a Winograd F(4x2) position group (four filters per
 // lane), the 4 tiles (a) of an F(2x2) one, the hi | lo | hi tiles of a split16 sub-chunk.  Elsewhere a work item is one tile.
 //
-// Arithmetic that has to match the host bit for bit:
-//   * the Winograd filter transforms run in double with the expression trees of pack_winograd_u / pack_winograd42_u (same constants,
-//     same association, the products by 0 and 1 included), rounded once to fp32.  The host is built without FMA; device code is
-//     contracted by default, so the transform functions switch contraction off.
+// Arithmetic that has to come out the same on the host and on the device, bit for bit:
+//   * the Winograd filter transforms U = G g G^T run in double (rows first, then columns, the products by 0 and 1 included), rounded
+//     once to fp32.  The host is built without FMA; device code is contracted by default, so the transform functions switch
+//     contraction off.
 //   * half pieces: hi = (_Float16)v, lo = (_Float16)(v - (float)hi), round-to-nearest-even, fp16 subnormals kept.
 // Outside the contract (cid.h): fp32-subnormal, |v| > 65504 and non-finite parameter values.
 //
 // The source reads with 4-byte loads (the ABI promises no more alignment); the compiler merges a lane's consecutive ones into wider
 // global loads, which need no more than 4-byte alignment on gfx950.
 //
-// All of the decode is __host__ __device__, so a host build can run gen_pack_item over every (work item, lane) and compare with the
-// host pack without a GPU: tools/gen_pack_emu.hip does, and also checks that every quad is produced exactly once.
+// tools/gen_pack_emu.hip runs all of it on the CPU: every quad is produced exactly once over all work items, and staging tensor by
+// tensor in either order gives the whole-blob gather and touches no other tensor's segments.
 #pragma once
 #include "wino42_kernels.h"
 
@@ -44,20 +48,20 @@ enum GenPackFamily : unsigned char {
     GP_W_HEAD,       // down1.0 for k_conv_head (head_step order)
     GP_W_TAIL,       // upconv1.2 for k_conv_tail: [chunk][group][lane][4], columns 27..31 zero
     GP_W_CONVT_S32,  // up1 for k_convt_s32
-    GP_W_GEMM,       // 3x3 layers for k_gemm_conv (packed_index)
+    GP_W_GEMM,       // 3x3 layers for k_gemm_conv
     GP_W_GEMM_T,     // up2 for k_gemm_conv, MODE 2
     GP_U,            // Winograd F(2x2,3x3) U
     GP_U42,          // Winograd F(4x2,3x3) U
-    GP_TAB,          // LDS slot tables: src = 0, 1 (wino_slot_table 32x1, 16x2), 2, 3 (wino42_slot_table<8>, <4>)
+    GP_TAB,          // LDS slot tables: src = 0, 1 (wino_slot_entry 32x1, 16x2), 2, 3 (wino42_slot_entry<8>, <4>)
     // 2-byte elements
-    GP_H_CONV,       // packed_index_h16
-    GP_H_CONVT,      // packed_index_ht
+    GP_H_CONV,       // 3x3 layers for k_conv3x3_h16
+    GP_H_CONVT,      // up2, up1 for k_convt_t16
     GP_H_TAIL,       // k_conv_tail_h: [s][lane][8]
     GP_H_HEAD,       // k_conv_head_h16: [co & 3][k >> 3][(co >> 2) & 15][8], rows 27..31 zero
     GP_HZ,           // fused last layer's A fragments
     GP_HZS,          // the same as hi | lo pieces
-    GP_S_CONV,       // split16 pieces of a 3x3 layer (packed_index_s16)
-    GP_S_CONVT,      // split16 pieces of a transposed convolution
+    GP_S_CONV,       // split16 pieces of a 3x3 layer: hi | lo | hi
+    GP_S_CONVT,      // split16 pieces of a transposed convolution: hi | lo | hi
 };
 
 // One segment of the blob: the nq quads [q0, next segment's q0), work items [t0, t0 + ceil(nq / 64) / gp_group(fam)).  Elements (words or
@@ -80,7 +84,7 @@ struct GenPackArgs {
 __host__ __device__ inline double gp_g2(int a, int k) {
     return a == 0 ? (k == 0 ? 1.0 : 0.0) : a == 3 ? (k == 2 ? 1.0 : 0.0) : (a == 2 && k == 1) ? -0.5 : 0.5;
 }
-// G of F(4,3) at the points 0, 3/4, -3/4, 3/2, -3/2, inf: the constants as pack_winograd42_u writes them
+// G of F(4,3) at the points 0, 3/4, -3/4, 3/2, -3/2, inf (tests/test_host.py checks them against the kernel's B4^T and A4^T)
 __host__ __device__ inline double gp_g4(int b, int k) {
     switch (b * 3 + k) {
         case 0: return 64.0 / 81;
@@ -131,22 +135,26 @@ __host__ __device__ inline unsigned gp_word(const GenPackSeg& s, const float* w,
     if (i >= s.count) return 0u;
     switch (s.fam) {
         case GP_COPY: return gp_bits(w[i]);
-        case GP_W_HEAD: {   // ((co >> 5) * 14 + step) * 64 + h * 32 + (co & 31), k = ci * 9 + tap on half h of step `step`
+        case GP_W_HEAD: {   // ((co >> 5) * 14 + step) * 64 + h * 32 + (co & 31), k = ci * 9 + tap on lane half h of MFMA step `step`: the head's K order
+                            // (conv_kernels.h head_step); a half with no element (-1) holds a zero weight
             const int j = i & 31, h = (i >> 5) & 1, r = i >> 6, step = r % 14, co = 32 * (r / 14) + j;
             const HeadStep hs = head_step(step);
             const int kk = h ? hs.k1 : hs.k0;
             return kk < 0 ? 0u : gp_bits(w[co * 27 + kk]);
         }
-        case GP_W_TAIL: {   // ((ck * 4 + g) * 64 + h * 32 + col) * 4 + e, ci = 32 ck + 8 g + 4 h + e, col = 3 tap + co
+        case GP_W_TAIL: {   // ((ck * 4 + g) * 64 + h * 32 + col) * 4 + e, ci = 32 ck + 8 g + 4 h + e, col = 3 tap + co: B[k = ci][col] of the tail's
+                            // 64 x 32 product, columns 27..31 zero
             const int e = i & 3, col = (i >> 2) & 31, h = (i >> 7) & 1, g = (i >> 8) & 3, ck = i >> 10;
             return col >= 27 ? 0u : gp_bits(w[gp_ref3(s, col % 3, 32 * ck + 8 * g + 4 * h + e, col / 3)]);
         }
-        case GP_W_CONVT_S32: {   // ((((tap * (cin / 16) + g) * 4 + j) * 4 + mt) * 64) + kga * 16 + row, ci = 16 g + 4 kga + j, co = 16 mt + row
+        case GP_W_CONVT_S32: {   // ((((tap * (cin / 16) + g) * 4 + j) * 4 + mt) * 64) + kga * 16 + row, ci = 16 g + 4 kga + j, co = 16 mt + row:
+                                 // lane 16 kga + row holds A[row][k = kga] of v_mfma_f32_16x16x4_f32 for k-step j of group g
             const int row = 4 * (lane & 3) + k, kga = (lane >> 2) & 3, mt = lane >> 4, j = t & 3, r = t >> 2, ng = s.cin / 16, g = r % ng, tap = r / ng;
             return gp_bits(w[gp_reft(s, 16 * mt + row, 16 * g + 4 * kga + j, tap)]);
         }
         case GP_W_GEMM:
-        case GP_W_GEMM_T: {   // ((((nb * nchunk + ck) * taps + tap) * 4 + g) * 2 + ns) * 256 + (h * 32 + j) * 4 + e
+        case GP_W_GEMM_T: {   // ((((nb * nchunk + ck) * taps + tap) * 4 + g) * 2 + ns) * 256 + (h * 32 + j) * 4 + e, ci = 32 ck + 8 g + 4 h + e,
+                              // n' = 64 nb + 32 ns + j: lane (h, j) of v_mfma_f32_32x32x2_f32 holds B[k = h][col = j]; e walks the 4 MFMAs of group g
             const bool tr = s.fam == GP_W_GEMM_T;
             const int e = k, j = lane & 31, h = lane >> 5, ns = t & 1, g = (t >> 1) & 3, r = t >> 3;
             const int taps = tr ? 1 : 9, nchunk = s.cin / 32, tap = r % taps, r2 = r / taps, ck = r2 % nchunk, nb = r2 / nchunk;
@@ -165,6 +173,11 @@ __host__ __device__ inline unsigned gp_half(const GenPackSeg& s, const float* w,
     float v;
     bool lo = false;
     switch (s.fam) {
+        // k_conv3x3_h16: lane (col c, kg) of v_mfma_f32_16x16x32_f16 holds B[k = 8 kg .. 8 kg + 7][col] with ci = 32 ck + 8 kg + e; column c of
+        // channel group cg is output channel 64 nb + 4 c + cg, so a lane's four accumulator tiles are four consecutive channels (the
+        // kernel stores them as 8 bytes); one (chunk, kw) is a 12 KiB LDS-DMA unit.  split16 (k_conv3x3_h16<F32IO>): sub-chunk j = 0..2
+        // is tap column kw = j of hi_w (met by hi_x), 3..5 of lo_w (met by hi_x), 6..8 of hi_w again (met by lo_x); hi_w = half(w),
+        // lo_w = half(w - hi_w)
         case GP_H_CONV:     // ((((((nb * nchunk + ck) * 3 + kw) * 3 + kh) * 4 + cg) * 64) + kg * 16 + c) * 8 + e
         case GP_S_CONV: {   // ((((((nb * nchunk + ck) * 9 + j) * 3 + kh) * 4 + cg) * 64) + kg * 16 + c) * 8 + e, j = 3 piece + kw
             const int cg = t & 3, nj = s.fam == GP_S_CONV ? 9 : 3, nchunk = s.cin / 32;
@@ -176,7 +189,9 @@ __host__ __device__ inline unsigned gp_half(const GenPackSeg& s, const float* w,
             v = w[gp_ref3(s, 64 * nb + 4 * l16 + cg, 32 * ck + 8 * l4 + e, 3 * kh + kw)];
             break;
         }
-        case GP_H_CONVT: {   // (((((tap * CB + cb) * KS + ks) * 4 + mt) * 64) + kga * 16 + row) * 8 + e, channel of (mt, row): packed_index_ht
+        // k_convt_t16: the A operand of v_mfma_f32_16x16x32_f16, A[row][k = 8 kga + e] with ci = 32 ks + 8 kga + e; row `row` of M tile mt is
+        // channel 64 cb + 32 (mt >> 1) + 8 (row >> 2) + 4 (mt & 1) + (row & 3), so a lane's two M tiles of a pair are eight consecutive channels
+        case GP_H_CONVT: {   // (((((tap * CB + cb) * KS + ks) * 4 + mt) * 64) + kga * 16 + row) * 8 + e
             const int mt = t & 3, KS = s.cin / 32, CB = s.cout / 64;
             int r = t >> 2;
             const int ks = r % KS; r /= KS;
@@ -185,7 +200,8 @@ __host__ __device__ inline unsigned gp_half(const GenPackSeg& s, const float* w,
             v = w[gp_reft(s, 64 * cb + c, 32 * ks + 8 * l4 + e, tap)];
             break;
         }
-        case GP_S_CONVT: {   // ((((((blk * nchunk + ck) * 3 + p) * 4 + cg) * 64) + kg * 16 + c) * 8 + e, blk = tap * (cout / 64) + co / 64
+        case GP_S_CONVT: {   // ((((((blk * nchunk + ck) * 3 + p) * 4 + cg) * 64) + kg * 16 + c) * 8 + e, blk = tap * (cout / 64) + co / 64; piece p = 0 hi_w,
+                             // 1 lo_w, 2 hi_w again (met by lo_x), lanes as GP_H_CONV (k_conv3x3_h16<..., 2, ., ., F32IO, PAIR>)
             const int cg = t & 3, nchunk = s.cin / 32, cbs = s.cout / 64;
             int r = t >> 2;
             const int p = r % 3; r /= 3;
@@ -194,20 +210,22 @@ __host__ __device__ inline unsigned gp_half(const GenPackSeg& s, const float* w,
             v = w[gp_reft(s, 64 * (blk % cbs) + 4 * l16 + cg, 32 * ck + 8 * l4 + e, blk / cbs)];
             break;
         }
-        case GP_H_TAIL: {   // (s * 64 + hh * 32 + col) * 8 + e, ci = 16 s + 8 hh + e, col = 3 tap + co
+        case GP_H_TAIL: {   // (s * 64 + hh * 32 + col) * 8 + e, ci = 16 s + 8 hh + e, col = 3 tap + co: k_conv_tail_h's [k-step s][lane = 32 hh + col][e]
             const int col = lane & 31, hh = lane >> 5, st = t;
             if (col >= 27) return 0u;
             v = w[gp_ref3(s, col % 3, 16 * st + 8 * hh + e, col / 3)];
             break;
         }
-        case GP_H_HEAD: {   // ((co & 3) * 64 + (k >> 3) * 16 + ((co >> 2) & 15)) * 8 + (k & 7), k = 3 tap + c
+        case GP_H_HEAD: {   // ((co & 3) * 64 + (k >> 3) * 16 + ((co >> 2) & 15)) * 8 + (k & 7), k = 3 tap + c: k_conv_head_h16's B[k][co], rows 27..31
+                            // zero; lane (col = (co / 4) % 16, kg) of group co % 4 holds k = 8 kg .. 8 kg + 7
             const int k = 8 * l4 + e, co = 4 * l16 + (int)t;
             if (k >= 27) return 0u;
             v = w[gp_ref3(s, co, k % 3, k / 3)];
             break;
         }
         case GP_HZ:
-        case GP_HZS: {   // [piece][row tile rt][k-step ks][lane = 16 kga + row][e], row 16 rt + row = 3 tap + co, ci = 32 ks + 8 kga + e
+        case GP_HZS: {   // [piece][row tile rt][k-step ks][lane = 16 kga + row][e], row 16 rt + row = 3 tap + co, ci = 32 ks + 8 kga + e: the A operand of
+                         // z^T = W2' . X^T on v_mfma_f32_16x16x32_f16 (h16_zout_epilogue), 27 rows, rows 27..31 zero; GP_HZS: hi | lo pieces
             const int ks = t & 1, rt = (t >> 1) & 1, row = 16 * rt + l16;
             lo = s.fam == GP_HZS && (t >> 2) == 1;
             if (row >= 27) return 0u;
@@ -221,7 +239,9 @@ __host__ __device__ inline unsigned gp_half(const GenPackSeg& s, const float* w,
 }
 
 // Work items of the grouped families: emit(q, words) stores the quad at blob offset 16 q.
-// GP_U: [co / 64][ci / 16][(ci / 8) % 2][a][(co / 32) % 2][e][lane = 32 h + j][b], ci = 16 ck + 8 g2 + 4 h + e; item t = the same without a
+// GP_U: Winograd F(2x2,3x3) filter transform U = G g G^T, 16 values per (co, ci), laid out for k_wino64_conv:
+// [co / 64][ci / 16][(ci / 8) % 2][a][(co / 32) % 2][e][lane = 32 h + j][b], ci = 16 ck + 8 g2 + 4 h + e, co = 64 nb + 32 nt + j (one quad per lane =
+// the four positions b of k-step e, so a quad's registers free up after 4 MFMAs); item t = the same without a
 template <class Emit>
 __host__ __device__ inline void gp_item_u(const GenPackSeg& s, const float* w, unsigned t, int lane, Emit&& emit) {
     const int j = lane & 31, h = lane >> 5, e = t & 3, nt = (t >> 2) & 1, g2 = (t >> 3) & 1;
@@ -241,7 +261,11 @@ __host__ __device__ inline void gp_item_u(const GenPackSeg& s, const float* w, u
         emit(s.q0 + 64 * tile + lane, out);
     }
 }
-// GP_U42: [co / 64][unit][a][q = 6 e2 + b][lane = 16 gg + j][cg], ci = 16 (unit / 2) + 4 gg + 2 ((unit % 2) ^ (gg & 1)) + e2, co = 64 nb + 4 j + cg;
+// GP_U42: Winograd F(4x2,3x3) filter transform U = G2 g G4^T, rows by F(2,3), columns by F(4,3): 24 values per (co, ci), laid out for k_wino42_conv:
+// [co / 64][unit][a][q = 6 e2 + b][lane = 16 gg + j][cg], ci = 16 (unit / 2) + 4 gg + 2 ((unit % 2) ^ (gg & 1)) + e2, co = 64 nb + 4 j + cg (one quad per
+// lane = the four channel groups of position (a, b) at k-step e2: one V value, four MFMAs; column j of channel group cg = channel 4 j + cg: see
+// the kernel's epilogue).  Lane group gg reads the 8-byte half (ci >> 1) & 1 of its LDS quad for unit % 2 = half ^ (gg & 1): odd lane groups
+// take the halves in the other order, which makes the kernel's ds_read_b64 conflict-free (wino42_kernels.h, xbase / ybase).
 // item t = (nb * nunit + unit) * 2 + e2
 template <class Emit>
 __host__ __device__ inline void gp_item_u42(const GenPackSeg& s, const float* w, unsigned t, int lane, Emit&& emit) {
@@ -299,18 +323,21 @@ __host__ __device__ inline void gp_item_s_conv(const GenPackSeg& s, const float*
     }
 }
 
-// Work item `item` (wave-uniform) as seen by lane `lane`: emit(q, words) for each of the lane's quads.
-template <class Emit>
-__host__ __device__ inline void gen_pack_item(const GenPackArgs& a, unsigned item, int lane, Emit&& emit) {
-    int lo = 0, hi = a.nseg - 1;   // the last segment that starts at or before the item
+// The last segment that starts at or before work item `item`.
+__host__ __device__ inline int gen_pack_find(const GenPackArgs& a, unsigned item) {
+    int lo = 0, hi = a.nseg - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (a.seg[mid].t0 <= item) lo = mid;
         else hi = mid - 1;
     }
-    const GenPackSeg s = a.seg[lo];
-    const float* w = s.fam == GP_TAB ? nullptr : a.p[s.src];
-    const unsigned t = item - s.t0;
+    return lo;
+}
+
+// Work item t (wave-uniform) of segment s as seen by lane `lane`: emit(q, words) for each of the lane's quads.  w = the segment's
+// parameter tensor (GP_TAB reads none).
+template <class Emit>
+__host__ __device__ inline void gen_pack_produce(const GenPackSeg& s, const float* w, unsigned t, int lane, Emit&& emit) {
     if (s.fam == GP_U42) return gp_item_u42(s, w, t, lane, emit);
     if (s.fam == GP_U) return gp_item_u(s, w, t, lane, emit);
     if (s.fam == GP_S_CONV) return gp_item_s_conv(s, w, t, lane, emit);
@@ -325,6 +352,15 @@ __host__ __device__ inline void gen_pack_item(const GenPackArgs& a, unsigned ite
         for (int k = 0; k < 4; ++k) out[k] = gp_half(s, w, t, lane, 2 * k) | gp_half(s, w, t, lane, 2 * k + 1) << 16;
     }
     emit(s.q0 + r, out);
+}
+
+// Work item `item` of the whole blob: search, then produce.
+template <class Emit>
+__host__ __device__ inline void gen_pack_item(const GenPackArgs& a, unsigned item, int lane, Emit&& emit) {
+    const GenPackSeg s = a.seg[gen_pack_find(a, item)];
+    const float* w = s.fam == GP_TAB ? nullptr : a.p[s.src];
+    const unsigned t = item - s.t0;
+    gen_pack_produce(s, w, t, lane, emit);
 }
 
 __global__ void __launch_bounds__(GP_THREADS) k_gen_pack(const GenPackArgs a) {

@@ -9,7 +9,7 @@
 // every entry of B4^T and A4^T is a dyadic rational (exact in fp32), and of the point sets tried this one has the smallest error
 // on this network (tools/emulate_f43_winograd.py, both directions at F(4,3): 2.8e-6 on the He-gain weights against 1.3e-6 for
 // direct fp32 and 5.8e-6 for the textbook points 0, +-1, +-2).  U is computed on the host in double and rounded once
-// (cid_api.hip pack_winograd42_u).
+// (gen_pack_kernels.h, GP_U42).
 //
 // Why not F(4x4,3x3) (2.25 multiplies per pixel): with a row of the 6x6 tile per wave it needs six waves of ~170 registers; hipcc
 // needs 225-256 for that loop, so only one such workgroup fits a CU and two of its SIMDs carry two waves against one on the
@@ -241,7 +241,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
     // (two channel groups g x 16 tiles) touch only every other 8-byte slot — a 2-way conflict by construction, the 33-41 %
     // SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE of round 2.  With odd channel groups on the other half the 16 tiles of g even cover
     // the 16 even slots (10 tc mod 32, + 16 tr for TC = 8, + 24 tr for TC = 4) and those of g odd the 16 odd ones: conflict-free.
-    // Unit (chunk, s2) therefore holds channels 4g + 2 (s2 ^ (g & 1)) + e2 of the chunk (pack_winograd42_u packs U to match);
+    // Unit (chunk, s2) therefore holds channels 4g + 2 (s2 ^ (g & 1)) + e2 of the chunk (gen_pack_kernels.h, GP_U42, packs U to match);
     // the half flips at every unit, one v_xor per base.
     int xbase = 2 * (WPS * ((2 * tr + xrow) * RS + tc) + g) + (g & 1), ybase = 2 * (WPS * ((2 * tr + yrow) * RS + tc) + g) + (g & 1);
     auto col_off = [](int c) { return 2 * WPS * ((c & 3) * QS + (c >> 2)); };   // patch column c of the tile: plane c mod 4, pixel tc + c / 4
@@ -427,7 +427,7 @@ __global__ void __launch_bounds__(THREADS, 2) k_wino42_conv(const WinoArgs a) {
     const int lane = lane_e, m16 = lane_e & 15, g = lane_e >> 4;
     // Wave w finishes tile quarter r = w: the tiles 4g + w (g = lane >> 4) for all four channel groups.  Its bias values are
     // requested here; the column transform and the exchange cover their latency.
-    // MFMA column j = m16 of channel group cg is output channel 64 nb + 4 m16 + cg (pack_winograd42_u): a lane's four groups are four
+    // MFMA column j = m16 of channel group cg is output channel 64 nb + 4 m16 + cg (gen_pack_kernels.h, GP_U42): a lane's four groups are four
     // CONSECUTIVE channels, so its results leave as 16-byte quads straight from registers — no transposing pass through LDS
     const f32x4 bias4 = *reinterpret_cast<const f32x4*>(a.bias + nb * WN2 + 4 * m16);
     if (has_next) load_slot_entries();   // for the offsets formed at the tile boundary; older than the epilogue's stores, so its wait skips them

@@ -59,7 +59,7 @@ inline int wino_slot_table(int TC, int BTR, unsigned* out /* may be null */) {
 
 struct WinoArgs {
     const float* in;    // NHWC [N, Hin, Win, in_ps]
-    const float* u;     // packed U: [nb][chunk][round][a][nt][e][lane][b]  (cid_api.hip pack_winograd_u)
+    const float* u;     // packed U: [nb][chunk][round][a][nt][e][lane][b]  (gen_pack_kernels.h, GP_U)
     const float* bias;  // [COUT]
     const unsigned* slot_tab;   // per LDS slot of the raw tile: (row << 20 | column << 8 | channel group), ~0u = deliver zeros (host: wino_slot_table)
     float* out;         // [N, Hs, Ws, out_ps] (+ out_coff)

@@ -4,8 +4,14 @@ The contract is byte identity with the host pack (cid_set_weight x 24 + cid_expo
 parameter values: DenoiseGenerator(autograd=True).pack_weights() takes the device path, pack_weights_host() and an
 autograd=False module's pack_weights() are the host path and serve as the reference.  Allowed differing bytes: zero.  A
 mismatch is reported per blob segment (cid_packed_segment).
+
+Both packs compile csrc/gen_pack_kernels.h, so byte identity holds the device's arithmetic and stores against the host's and says
+nothing about the layout: tests/golden/gen_pack_digests.json, recorded from the host's former separate pack code, pins that.
 """
 import ctypes
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -22,6 +28,7 @@ TABLES = ("tab:32", "tab:16", "tab42:8", "tab42:4")
 # one near the top of the half range, and one that a half holds exactly (lo piece 0)
 EDGE_VALUES = (0.0, -0.0, 1.0, -1.0, 2.0 ** -20, -(2.0 ** -20), 1e-6, 3.0e4, 341.0 / 1024.0)
 BOUNDARIES = (4, 8, 16, 32, 64)   # the ci / co index formulas split on these
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gen_pack_digests.json")
 
 
 def segments():
@@ -164,6 +171,59 @@ def test_the_weight_sets_tell_every_segment_apart():
         if v.size >= 2 * len(EDGE_VALUES):
             for x in EDGE_VALUES:
                 assert (v.view(np.uint32) == np.float32(x).view(np.uint32)).any(), (k, x)
+
+
+@pytest.mark.parametrize("kind", WSETS)
+def test_host_pack_has_the_recorded_layout(kind):
+    """The host and the device pack are one piece of source, so the layout is pinned by digests recorded from the scatter pack that
+    cid_set_weight had before (tests/golden/make_gen_pack_digests.py): every segment and the whole blob, no segment left out."""
+    with open(DIGESTS) as f:
+        gold = json.load(f)
+    segs = segments()[0]
+    assert list(gold["ranges"].items()) == [(n, f"{off}+{size}") for n, off, size in segs]      # the same names, order and ranges
+    assert list(gold["sets"][kind]["segments"]) == [n for n, _, _ in segs]
+    blob = host_blob(kind).numpy().tobytes()
+    assert len(blob) == gold["bytes"]
+    bad = [n for n, off, size in segs if hashlib.sha256(blob[off:off + size]).hexdigest() != gold["sets"][kind]["segments"][n]]
+    assert not bad, f"{kind}: segments that differ from the recorded layout: {bad}"
+    assert hashlib.sha256(blob).hexdigest() == gold["sets"][kind]["blob"]
+
+
+def test_staging_order_does_not_matter_and_a_tensor_owns_its_segments():
+    """Through the C ABI: the 24 tensors staged in key order and in reverse order export the same bytes, and setting down2.0.weight
+    again with other values changes exactly the segments it feeds."""
+    L = _lib.lib()
+    sd = {k: v.numpy() for k, v in state_dict("edge").items()}
+    keys = [L.cid_param_key(i).decode() for i in range(24)]
+    assert sorted(keys) == sorted(sd)
+
+    def stage(h, k, v):
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        assert L.cid_set_weight(h, k.encode(), v.ctypes.data, (ctypes.c_int64 * v.ndim)(*v.shape), v.ndim) == 0
+
+    def export(h):
+        out = np.empty(L.cid_packed_weights_bytes(), np.uint8)
+        assert L.cid_export_packed(h, out.ctypes.data, out.nbytes) == 0
+        return out
+
+    hs = [ctypes.c_void_p(), ctypes.c_void_p()]
+    try:
+        for h, order in zip(hs, (keys, keys[::-1])):
+            assert L.cid_create(ctypes.byref(h)) == 0
+            for k in order:
+                stage(h, k, sd[k])
+        fwd = export(hs[0])
+        assert np.array_equal(fwd, export(hs[1]))
+        assert np.array_equal(fwd, host_blob("edge").numpy())
+        stage(hs[0], "down2.0.weight", sd["down2.0.weight"] * np.float32(1.5) + np.float32(0.25))
+        again = export(hs[0])
+    finally:
+        for h in hs:
+            L.cid_destroy(h)
+    changed = {n for n, off, size in segments()[0] if not np.array_equal(fwd[off:off + size], again[off:off + size])}
+    want = {n for n, _, _ in segments()[0] if n.endswith(":down2.0") and not n.startswith(("b:", "raw_b:"))}
+    assert want == {p + ":down2.0" for p in ("w", "raw_w", "u", "u42", "h", "s16")}
+    assert changed == want
 
 
 # ------------------------------------------------------------------------------------------------------------ GPU

@@ -239,7 +239,7 @@ def test_host_pipeline_refuses_cpu_model():
 
 
 def test_winograd_f4x2_transform_constants():
-    """The constants k_wino42_conv hard-codes (csrc/wino42_kernels.h: B4^T rows, A4^T in w42_out4, G4 in pack_winograd42_u;
+    """The constants k_wino42_conv hard-codes (csrc/wino42_kernels.h: B4^T rows, A4^T in w42_out4, G4 in gen_pack_kernels.h gp_g4;
     interpolation points 0, +-3/4, +-3/2, inf) and the F(2,3) matrices of the vertical direction compute a 3x3 correlation
     exactly: Y(2x4) = A2^T [ (G2 g G4^T) . (B2^T d B4) ] A4 against the direct sum, in float64, for random g and d.  Every
     entry of B4^T and A4^T is a dyadic rational, i.e. exact in fp32 (the kernel's transforms add no coefficient rounding)."""
