@@ -18,6 +18,8 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     trainer_losses(D, denoised, clean)                  the trainer's d_loss / g_loss / content_loss / adv_loss of one batch
     Adam(params, lr, betas, eps, weight_decay)          the trainer's optimizer as one kernel per step (cid_adam_step); its state
                                   interchanges with torch.optim.Adam's
+    ESRGANGenerator(num_residuals=8) / load_esrgan(ckpt)   the server's ESRGAN model (eval mode); enhance(model, x) -> the raw
+                                  fp32 output, enhance_u8(model, u8) -> the server's uint8 view
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -44,6 +46,10 @@ _LAZY = {
     "load_discriminator": ("discriminator", "load_discriminator"),
     "trainer_losses": ("discriminator", "trainer_losses"),
     "Adam": ("optim", "Adam"),
+    "ESRGANGenerator": ("esrgan", "ESRGANGenerator"),
+    "load_esrgan": ("esrgan", "load_esrgan"),
+    "enhance": ("esrgan", "enhance"),
+    "enhance_u8": ("esrgan", "enhance_u8"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

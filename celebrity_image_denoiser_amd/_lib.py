@@ -123,6 +123,20 @@ SYMBOLS = {
     "cid_resize_plan_destroy": (None, [_c.c_void_p]),
     "cid_resize_plan_table": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
     "cid_resize": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p]),
+    "cid_esr_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int]),
+    "cid_esr_destroy": (None, [_c.c_void_p]),
+    "cid_esr_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_esr_param_key": (_c.c_char_p, [_c.c_void_p, _c.c_int]),
+    "cid_esr_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_esr_set_bn_eps": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_double]),
+    "cid_esr_missing_weights": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int)]),
+    "cid_esr_packed_weights_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "cid_esr_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_esr_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_esr_forward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                   _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_esr_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
+                                      _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
 }
 
 _lib = None
@@ -165,6 +179,13 @@ def lib() -> ctypes.CDLL:
 def check(handle, code: int):
     if code != CID_OK:
         msg = lib().cid_last_error(handle)
+        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
+
+
+def check_esr(handle, code: int):
+    """check() for a cid_esr_t handle."""
+    if code != CID_OK:
+        msg = lib().cid_esr_last_error(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
 
 

@@ -15,6 +15,7 @@
 #include "gen_pack_kernels.h"
 #include "optim_kernels.h"
 #include "resize_kernels.h"
+#include "esrgan_kernels.h"
 
 #include <dlfcn.h>
 
@@ -2777,6 +2778,299 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
             hipLaunchKernelGGL(k_gen_dgrad_head, grid, dim3(G_THREADS), 0, s, a);
             if (hipPeekAtLastError() != hipSuccess) return herr("down1.0 data gradient");
         }
+    }
+    return CID_OK;
+}
+
+}  // extern "C"
+
+// ---- the server's ESRGANGenerator (cid_esr_*): weight staging, BatchNorm folding, workspace plan and launch sequence; kernels in
+// esrgan_kernels.h ----
+namespace {
+
+constexpr int kEsrMaxBlocks = CID_ESR_MAX_RESIDUALS;
+constexpr size_t kEsrHeadSeg = (size_t)E_HEAD_K * 64 + 128;      // weights, bias[64], slope (padded to 64)
+constexpr size_t kEsrConvSeg = (size_t)E_CONV_W + 256;           // weights, bias[64], s[64], t[64], slope (padded to 64)
+constexpr size_t kEsrTailSeg = (size_t)E_TAIL_W + 64;            // weights, bias[3] (padded to 64)
+
+enum EsrKind { ESR_W, ESR_VEC, ESR_COUNT };                      // a convolution weight, a vector, num_batches_tracked
+struct EsrKey { std::string name; EsrKind kind; int64_t shape[4]; int ndim; size_t count; };
+
+std::vector<EsrKey> esr_keys(int R) {
+    std::vector<EsrKey> k;
+    const auto w = [&](const std::string& n, int co, int ci, int ks) { k.push_back({n, ESR_W, {co, ci, ks, ks}, 4, (size_t)co * ci * ks * ks}); };
+    const auto v = [&](const std::string& n, int c) { k.push_back({n, ESR_VEC, {c, 0, 0, 0}, 1, (size_t)c}); };
+    w("initial.0.weight", 64, 3, 9);
+    v("initial.0.bias", 64);
+    v("initial.1.weight", 1);
+    for (int i = 0; i < R; ++i) {
+        const std::string b = "residuals." + std::to_string(i) + ".block.";
+        for (int c = 0; c < 2; ++c) {
+            const std::string conv = b + std::to_string(3 * c) + ".", bn = b + std::to_string(3 * c + 1) + ".";
+            w(conv + "weight", 64, 64, 3);
+            v(conv + "bias", 64);
+            v(bn + "weight", 64);
+            v(bn + "bias", 64);
+            v(bn + "running_mean", 64);
+            v(bn + "running_var", 64);
+            k.push_back({bn + "num_batches_tracked", ESR_COUNT, {0, 0, 0, 0}, 0, 1});
+            if (c == 0) v(b + "2.weight", 1);
+        }
+    }
+    w("final.weight", 3, 64, 9);
+    v("final.bias", 3);
+    return k;
+}
+
+struct EsrPlan {
+    size_t x1, mid, cur, total;   // byte offsets of the three C8 tensors; `cur` ends as the tensor the tail reads
+    int ctiles_x, ctiles, ttiles_x, ttiles;
+};
+
+int esr_plan(int N, int H, int W, EsrPlan& p) {
+    if (N < 1 || H < 1 || W < 1) return CID_ERR_SHAPE;
+    if ((long long)H * W > 0x7fffffffLL) return CID_ERR_SHAPE;   // a pixel index inside one image is an int
+    const size_t t = align256((size_t)N * 64 * H * W * sizeof(float));
+    p.x1 = 0;
+    p.mid = t;
+    p.cur = 2 * t;
+    p.total = 3 * t;
+    p.ctiles_x = (W + D_TW - 1) / D_TW;
+    p.ctiles = ((H + DiscGeom<64, 64, 1>::TH - 1) / DiscGeom<64, 64, 1>::TH) * p.ctiles_x;
+    p.ttiles_x = (W + E_TAIL_TW - 1) / E_TAIL_TW;
+    p.ttiles = ((H + E_TAIL_TH - 1) / E_TAIL_TH) * p.ttiles_x;
+    return CID_OK;
+}
+
+}  // namespace
+
+struct cid_esr_s {
+    int R = 0;
+    std::vector<EsrKey> keys;
+    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
+    std::vector<char> have;
+    double eps[2 * kEsrMaxBlocks];
+    std::vector<float> staging;
+    const float* dev_blob = nullptr;
+    std::string err;
+    size_t blob_floats() const { return kEsrHeadSeg + 2 * (size_t)R * kEsrConvSeg + kEsrTailSeg; }
+    int find(const std::string& k) const {
+        for (size_t i = 0; i < keys.size(); ++i)
+            if (keys[i].name == k) return (int)i;
+        return -1;
+    }
+};
+
+namespace {
+int efail(cid_esr_t h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+// The blob from the staged tensors: the kernels' weight layouts, and each BatchNorm folded to y = s*z + t with
+// s = gamma / sqrt(running_var + eps), t = beta - running_mean * s, derived in fp64 and rounded once to fp32.
+void esr_pack(cid_esr_t h) {
+    h->staging.assign(h->blob_floats(), 0.f);
+    float* b = h->staging.data();
+    const auto get = [&](const std::string& k) -> const float* { return h->raw[h->find(k)].data(); };
+    {   // head: [ci][kh][kw][co]
+        const float* w = get("initial.0.weight");
+        for (int co = 0; co < 64; ++co)
+            for (int k = 0; k < E_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * E_HEAD_K + k];
+        std::memcpy(b + E_HEAD_K * 64, get("initial.0.bias"), 64 * sizeof(float));
+        b[E_HEAD_K * 64 + 64] = get("initial.1.weight")[0];
+    }
+    for (int i = 0; i < h->R; ++i)
+        for (int c = 0; c < 2; ++c) {
+            float* seg = b + kEsrHeadSeg + (size_t)(2 * i + c) * kEsrConvSeg;
+            const std::string blk = "residuals." + std::to_string(i) + ".block.";
+            const std::string conv = blk + std::to_string(3 * c) + ".", bn = blk + std::to_string(3 * c + 1) + ".";
+            const float* w = get(conv + "weight");
+            for (int co = 0; co < 64; ++co)
+                for (int ci = 0; ci < 64; ++ci)
+                    for (int tap = 0; tap < 9; ++tap)
+                        seg[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 64 + co] = w[((size_t)co * 64 + ci) * 9 + tap];
+            std::memcpy(seg + E_CONV_BIAS, get(conv + "bias"), 64 * sizeof(float));
+            const float *gamma = get(bn + "weight"), *beta = get(bn + "bias"), *mean = get(bn + "running_mean"), *var = get(bn + "running_var");
+            for (int ch = 0; ch < 64; ++ch) {
+                const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + h->eps[2 * i + c]);
+                seg[E_CONV_S + ch] = (float)s;
+                seg[E_CONV_T + ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
+            }
+            seg[E_CONV_SLOPE] = c == 0 ? get(blk + "2.weight")[0] : 0.f;
+        }
+    {   // tail: [ci][kh][co * 9 + kw]
+        float* seg = b + kEsrHeadSeg + 2 * (size_t)h->R * kEsrConvSeg;
+        const float* w = get("final.weight");
+        for (int co = 0; co < 3; ++co)
+            for (int ci = 0; ci < 64; ++ci)
+                for (int kh = 0; kh < 9; ++kh)
+                    for (int kw = 0; kw < 9; ++kw)
+                        seg[((size_t)ci * 9 + kh) * E_TAIL_WROW + co * 9 + kw] = w[(((size_t)co * 64 + ci) * 9 + kh) * 9 + kw];
+        std::memcpy(seg + E_TAIL_W, get("final.bias"), 3 * sizeof(float));
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int cid_esr_create(cid_esr_t* out, int num_residuals) {
+    if (!out) return CID_ERR_INVALID;
+    *out = nullptr;
+    if (num_residuals < 0 || num_residuals > kEsrMaxBlocks) return CID_ERR_INVALID;
+    cid_esr_s* h = new (std::nothrow) cid_esr_s();
+    if (!h) return CID_ERR_INVALID;
+    h->R = num_residuals;
+    h->keys = esr_keys(num_residuals);
+    h->raw.resize(h->keys.size());
+    h->have.assign(h->keys.size(), 0);
+    std::fill(h->eps, h->eps + 2 * kEsrMaxBlocks, 1e-5);
+    *out = h;
+    return CID_OK;
+}
+
+void cid_esr_destroy(cid_esr_t h) { delete h; }
+
+const char* cid_esr_last_error(cid_esr_t h) { return h ? h->err.c_str() : "null handle"; }
+
+const char* cid_esr_param_key(cid_esr_t h, int i) {
+    if (!h || i < 0 || (size_t)i >= h->keys.size()) return nullptr;
+    return h->keys[i].name.c_str();
+}
+
+int cid_esr_set_weight(cid_esr_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
+    if (!h) return CID_ERR_INVALID;
+    if (!key || !data || (!shape && ndim > 0)) return efail(h, CID_ERR_INVALID, "cid_esr_set_weight: null argument");
+    const int i = h->find(key);
+    if (i < 0) return efail(h, CID_ERR_KEY, std::string("cid_esr_set_weight: unexpected key '") + key + "'");
+    const EsrKey& k = h->keys[i];
+    if (k.kind == ESR_COUNT) {   // num_batches_tracked: part of the state_dict, unused in eval mode
+        if (ndim != 0) return efail(h, CID_ERR_SHAPE, "cid_esr_set_weight: size mismatch for " + k.name);
+        h->have[i] = 1;
+        return CID_OK;
+    }
+    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return efail(h, CID_ERR_SHAPE, "cid_esr_set_weight: size mismatch for " + k.name);
+    const float* f = static_cast<const float*>(data);
+    h->raw[i].assign(f, f + k.count);
+    h->have[i] = 1;
+    return CID_OK;
+}
+
+int cid_esr_set_bn_eps(cid_esr_t h, int block, int which, double eps) {
+    if (!h) return CID_ERR_INVALID;
+    if (block < 0 || block >= h->R || (which != 0 && which != 1)) return efail(h, CID_ERR_INVALID, "cid_esr_set_bn_eps: no such BatchNorm");
+    if (!std::isfinite(eps) || eps < 0.0) return efail(h, CID_ERR_INVALID, "cid_esr_set_bn_eps: eps must be finite and >= 0");
+    h->eps[2 * block + which] = eps;
+    return CID_OK;
+}
+
+int cid_esr_missing_weights(cid_esr_t h, int* count) {
+    if (!h || !count) return CID_ERR_INVALID;
+    int m = 0;
+    for (size_t i = 0; i < h->keys.size(); ++i) m += h->keys[i].kind != ESR_COUNT && !h->have[i];
+    *count = m;
+    return CID_OK;
+}
+
+size_t cid_esr_packed_weights_bytes(cid_esr_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
+
+int cid_esr_upload_weights(cid_esr_t h, void* device_blob, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!device_blob) return efail(h, CID_ERR_INVALID, "cid_esr_upload_weights: null device pointer");
+    if ((uintptr_t)device_blob & 255) return efail(h, CID_ERR_WORKSPACE, "cid_esr_upload_weights: blob must be 256-byte aligned");
+    for (size_t i = 0; i < h->keys.size(); ++i)
+        if (h->keys[i].kind != ESR_COUNT && !h->have[i]) return efail(h, CID_ERR_STATE, "cid_esr_upload_weights: " + h->keys[i].name + " not set");
+    esr_pack(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
+    if (e != hipSuccess) return efail(h, CID_ERR_HIP, std::string("cid_esr_upload_weights: ") + hipGetErrorString(e));
+    h->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_esr_workspace_bytes(int N, int H, int W, size_t* bytes) {
+    if (!bytes) return CID_ERR_INVALID;
+    EsrPlan p;
+    const int rc = esr_plan(N, H, W, p);
+    if (rc == CID_OK) *bytes = p.total;
+    return rc;
+}
+
+int cid_esr_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
+    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
+    EsrPlan p;
+    const int rc = esr_plan(N, H, W, p);
+    if (rc != CID_OK) return rc;
+    const std::string s(stage);
+    if (s == "x1") *offset_bytes = p.x1;
+    else if (s == "tail_in") *offset_bytes = p.cur;
+    else return CID_ERR_KEY;
+    *C = 64;
+    *Hs = H;
+    *Ws = W;
+    *channel_block = 8;
+    return CID_OK;
+}
+
+int cid_esr_forward(cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!in || !out || !workspace) return efail(h, CID_ERR_INVALID, "cid_esr_forward: null pointer");
+    if ((in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) || (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC))
+        return efail(h, CID_ERR_INVALID, "cid_esr_forward: unknown format");
+    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
+        return efail(h, CID_ERR_INVALID, "cid_esr_forward: misaligned fp32 operand");
+    EsrPlan p;
+    if (esr_plan(N, H, W, p) != CID_OK) return efail(h, CID_ERR_SHAPE, "cid_esr_forward: input shape not accepted (N, H, W >= 1, H*W < 2^31)");
+    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
+        return efail(h, CID_ERR_WORKSPACE, "cid_esr_forward: workspace smaller than cid_esr_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return efail(h, CID_ERR_STATE, "cid_esr_forward: weights not uploaded");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto herr = [&](const char* what) { return efail(h, CID_ERR_HIP, std::string("cid_esr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    char* ws = static_cast<char*>(workspace);
+    float *x1 = reinterpret_cast<float*>(ws + p.x1), *mid = reinterpret_cast<float*>(ws + p.mid), *cur = reinterpret_cast<float*>(ws + p.cur);
+    const float* blob = h->dev_blob;
+    const int R = h->R;
+
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        const unsigned imgs = (unsigned)std::min(kDiscChunk, N - n0);
+        const EsrHeadArgs a{in, x1, R == 0 ? cur : nullptr, blob, H, W, n0};
+        const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), imgs);
+        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_esr_head<true>, grid, dim3(D_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_esr_head<false>, grid, dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("head");
+    }
+    for (int i = 0; i < R; ++i)
+        for (int c = 0; c < 2; ++c)
+            for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+                EsrConvArgs a{};
+                a.w = blob + kEsrHeadSeg + (size_t)(2 * i + c) * kEsrConvSeg;
+                a.H = H;
+                a.W = W;
+                a.tiles_x = p.ctiles_x;
+                a.n0 = n0;
+                const dim3 grid((unsigned)p.ctiles, (unsigned)std::min(kDiscChunk, N - n0)), block(D_THREADS);
+                if (c == 0) {   // block.0-2: the block's input (x1 for the first block) -> mid
+                    a.in = i == 0 ? x1 : cur;
+                    a.out = mid;
+                    hipLaunchKernelGGL(k_esr_conv<EPI_PRELU>, grid, block, 0, s, a);
+                } else {        // block.3-4 and the residual sum -> cur (in place from the second block on)
+                    a.in = mid;
+                    a.out = cur;
+                    a.res = i == 0 ? x1 : cur;
+                    a.x1 = x1;
+                    if (i == R - 1) hipLaunchKernelGGL(k_esr_conv<EPI_SUM>, grid, block, 0, s, a);
+                    else hipLaunchKernelGGL(k_esr_conv<EPI_RES>, grid, block, 0, s, a);
+                }
+                if (hipPeekAtLastError() != hipSuccess) return herr("trunk");
+            }
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        const EsrTailArgs a{cur, out, blob + kEsrHeadSeg + 2 * (size_t)R * kEsrConvSeg, H, W, p.ttiles_x, n0};
+        const dim3 grid((unsigned)p.ttiles, (unsigned)std::min(kDiscChunk, N - n0));
+        if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_esr_tail<true>, grid, dim3(E_TAIL_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_esr_tail<false>, grid, dim3(E_TAIL_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("tail");
     }
     return CID_OK;
 }

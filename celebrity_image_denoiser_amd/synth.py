@@ -425,3 +425,74 @@ def resize_bicubic_np(img_u8: np.ndarray, size) -> np.ndarray:
     if np.shares_memory(img, img_u8):                                        # neither pass ran: the result is a copy
         img = img.copy()
     return img[0] if single else img
+
+
+# ---- the server's ESRGANGenerator (backend/app.py:188-218): parameter shapes and synthetic weights ----
+
+def esrgan_param_shapes(num_residuals: int = 8) -> "OrderedDict[str, tuple]":
+    """state_dict key -> (shape, dtype name) of ESRGANGenerator(num_residuals), in the module's own order, BatchNorm buffers and
+    num_batches_tracked included."""
+    out: "OrderedDict[str, tuple]" = OrderedDict()
+    f = "float32"
+    out["initial.0.weight"] = ((64, 3, 9, 9), f)
+    out["initial.0.bias"] = ((64,), f)
+    out["initial.1.weight"] = ((1,), f)
+    for i in range(num_residuals):
+        b = f"residuals.{i}.block."
+        for c in (0, 3):
+            out[f"{b}{c}.weight"] = ((64, 64, 3, 3), f)
+            out[f"{b}{c}.bias"] = ((64,), f)
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                out[f"{b}{c + 1}.{k}"] = ((64,), f)
+            out[f"{b}{c + 1}.num_batches_tracked"] = ((), "int64")
+            if c == 0:
+                out[f"{b}2.weight"] = ((1,), f)
+    out["final.weight"] = ((3, 64, 9, 9), f)
+    out["final.bias"] = ((3,), f)
+    return out
+
+
+def make_esrgan_state_dict(kind: str = "default", num_residuals: int = 8, seed: int = WEIGHT_SEED) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights keyed like the reference's ESRGANGenerator state_dict, from the hash streams.
+
+    Convolution weights and biases are U(+-sqrt(1/fan_in)) for kind="default" and U(+-sqrt(6/fan_in)) for kind="hot"; BatchNorm
+    gamma in [0.6, 1.4], beta in +-0.1, running_mean in +-0.3, running_var in [0.5, 1.5], far enough from a fresh BatchNorm that a
+    swapped or unused buffer shows; PReLU slopes in [0.05, 0.45].  In "hot" the slope of initial.1 is -0.3 and that of the last
+    block's PReLU 1.5 (with no block, only the first): learned slopes may leave [0, 1], which a max-form PReLU gets wrong."""
+    if kind not in ("default", "hot"):
+        raise ValueError(f"unknown weight set {kind!r}")
+    shapes = esrgan_param_shapes(num_residuals)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for key, (shape, dtype) in shapes.items():
+        if dtype == "int64":
+            sd[key] = np.array(7, dtype=np.int64)
+            continue
+        n = int(np.prod(shape))
+        u = hash_uniform(seed, _fnv1a64("esrgan:" + kind + ":" + key), n)
+        layer, leaf = key.rsplit(".", 1)
+        wshape = shapes[layer + ".weight"][0]
+        if len(wshape) == 4:                                   # a convolution's weight or bias
+            fan_in = wshape[1] * wshape[2] * wshape[3]
+            bound = math.sqrt((1.0 if kind == "default" else 6.0) / fan_in)
+            v = (2.0 * u - 1.0) * bound
+        elif wshape == (1,):                                   # a PReLU slope
+            v = 0.05 + 0.4 * u
+        elif leaf == "weight":
+            v = 0.6 + 0.8 * u
+        elif leaf == "bias":
+            v = (2.0 * u - 1.0) * 0.1
+        elif leaf == "running_mean":
+            v = (2.0 * u - 1.0) * 0.3
+        else:                                                  # running_var
+            v = 0.5 + u
+        sd[key] = v.astype(np.float32).reshape(shape)
+    if kind == "hot":
+        sd["initial.1.weight"][...] = -0.3
+        if num_residuals > 0:
+            sd[f"residuals.{num_residuals - 1}.block.2.weight"][...] = 1.5
+    return sd
+
+
+def esrgan_inputs_u8(n: int, h: int, w: int, first_index: int = 0) -> np.ndarray:
+    """uint8 [n,h,w,3] inputs for the ESRGAN tests: the noisy face-like fields of make_batch."""
+    return add_gaussian_noise(clean_images_u8(n, h, w, first_index), 25.0, first_index)

@@ -607,6 +607,58 @@ int cid_resize_plan_table(cid_resize_plan_t p, int axis, int* ksize, int* bounds
 int cid_resize(cid_resize_plan_t p, const void* src_u8_nhwc, void* dst, int dst_fmt, int N, void* stream);
 
 /*
+ * The server's second model — ESRGANGenerator(num_residuals = 8) (backend/app.py:188-218; the same class in
+ * backend/trainingcode/esrgan_code/models.py:6-34), the "esrgan" branch of /enhance (app.py:387-397).  Eval mode, fp32:
+ *
+ *   x1  = PReLU(Conv2d(3, 64, 9, padding=4)(x))                                         initial.0, initial.1 (one slope)
+ *   x  <- x + BatchNorm(Conv3x3(PReLU(BatchNorm(Conv3x3(x)))))   R times, from x1        residuals.i.block.{0,1,2,3,4}
+ *   out = Conv2d(64, 3, 9, padding=4)(x1 + x2)                                           final; no tanh, no clamp
+ *
+ * Its own handle and blob, as the discriminator has.  cid_esr_create fixes R = num_residuals (0 <= R <= CID_ESR_MAX_RESIDUALS,
+ * CID_ERR_INVALID otherwise); with R = 0 the reference's empty nn.Sequential is the identity and out = final(x1 + x1).
+ * cid_esr_param_key(h, i) enumerates the module's state_dict keys in its order (5 + 15 R of them, BatchNorm buffers and
+ * num_batches_tracked included; NULL past the end).  cid_esr_set_weight takes each of them as host fp32 in the reference layout
+ * (Conv2d [Cout,Cin,k,k]; bias, BatchNorm weight / bias / running_mean / running_var [C]; a PReLU slope [1]); a num_batches_tracked
+ * key (ndim 0) is accepted and ignored.  Unknown key -> CID_ERR_KEY, wrong shape -> CID_ERR_SHAPE.  cid_esr_set_bn_eps gives the eps
+ * of BatchNorm `which` (0: block.1, 1: block.4) of residual block `block` (default 1e-5, nn.BatchNorm2d's).
+ * cid_esr_missing_weights counts the tensors still unset (num_batches_tracked never counts).  cid_esr_upload_weights packs the
+ * blob (cid_esr_packed_weights_bytes(h), 256-byte aligned, caller-owned device memory), copies it and attaches it; it needs every
+ * tensor (CID_ERR_STATE otherwise) and waits for its copy, as cid_disc_upload_weights does.  Each BatchNorm is folded there into
+ * y = fmaf(s, z, t) with s = gamma / sqrt(running_var + eps) and t = beta - running_mean * s, derived in fp64 and rounded once to
+ * fp32: train-mode BatchNorm is out of scope.  PReLU is v > 0 ? v : a * v for any slope a.
+ *
+ * cid_esr_forward: in is fp32 [N,3,H,W] in [0,1] (CID_FMT_F32_NCHW; the server feeds ToTensor() alone) or uint8 [N,H,W,3]
+ * (CID_FMT_U8_NHWC), read as (float)u / 255.0f with a true division: a uint8 image and its /255 fp32 copy give identical bits.
+ * out is the raw fp32 [N,3,H,W], or uint8 [N,H,W,3] as the server's clamp(0,1) -> ToPILImage view (app.py:251-254):
+ * (uint8)(clamp(v, 0, 1) * 255.0f), a truncation.  Any H, W >= 1.  1 + 2 R + 1 launches on `stream` (hipStream_t, NULL = default
+ * stream), no host synchronisation; the trunk runs on exact-fp32 MFMA, head and tail on the VALU.  Every sum has a fixed order and
+ * an image's tiles depend only on (H, W): an image's result is bit-identical in any batch.  Checked on the host before any launch:
+ *   CID_ERR_INVALID    null pointer, unknown format, misaligned fp32 operand
+ *   CID_ERR_SHAPE      N < 1, H < 1, W < 1, H*W >= 2^31
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_esr_workspace_bytes(N, H, W) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_esr_stage_view (testing aid): where the last forward of an [N,3,H,W] input left `stage` in its workspace: "x1", or "tail_in",
+ * the tensor the last launch read (x1 + x2).  Both are fp32 with C channels in blocks of *channel_block = 8: element (n, c, y, x) is
+ * at (((n * (C/8) + c/8) * Hs + y) * Ws + x) * 8 + c % 8 floats past offset_bytes.  Unknown stage -> CID_ERR_KEY.
+ */
+typedef struct cid_esr_s* cid_esr_t;
+#define CID_ESR_MAX_RESIDUALS 16
+int cid_esr_create(cid_esr_t* out, int num_residuals);
+void cid_esr_destroy(cid_esr_t h);
+const char* cid_esr_last_error(cid_esr_t h);
+const char* cid_esr_param_key(cid_esr_t h, int i);
+int cid_esr_set_weight(cid_esr_t h, const char* key, const void* host_data, const int64_t* shape, int ndim);
+int cid_esr_set_bn_eps(cid_esr_t h, int block, int which, double eps);
+int cid_esr_missing_weights(cid_esr_t h, int* count);
+size_t cid_esr_packed_weights_bytes(cid_esr_t h);
+int cid_esr_upload_weights(cid_esr_t h, void* device_blob, void* stream);
+int cid_esr_workspace_bytes(int N, int H, int W, size_t* bytes);
+int cid_esr_forward(cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int cid_esr_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
