@@ -20,6 +20,8 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
                                   interchanges with torch.optim.Adam's
     ESRGANGenerator(num_residuals=8) / load_esrgan(ckpt)   the server's ESRGAN model (eval mode); enhance(model, x) -> the raw
                                   fp32 output, enhance_u8(model, u8) -> the server's uint8 view
+    SRGANGenerator(scale_factor=4) / load_srgan(ckpt)      the server's SRGAN model (eval mode): super_resolve(model, x) -> fp32 at
+                                  scale times the size, super_resolve_u8(model, u8) -> the server's padded uint8 view
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -50,6 +52,10 @@ _LAZY = {
     "load_esrgan": ("esrgan", "load_esrgan"),
     "enhance": ("esrgan", "enhance"),
     "enhance_u8": ("esrgan", "enhance_u8"),
+    "SRGANGenerator": ("srgan", "SRGANGenerator"),
+    "load_srgan": ("srgan", "load_srgan"),
+    "super_resolve": ("srgan", "super_resolve"),
+    "super_resolve_u8": ("srgan", "super_resolve_u8"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

@@ -20,6 +20,7 @@ CID_DISC_MOMENTUM_NONE = -1.0
 CID_NOISE_GAUSSIAN, CID_NOISE_SALT_PEPPER, CID_NOISE_SPECKLE, CID_NOISE_POISSON, CID_NOISE_UNIFORM = 0, 1, 2, 3, 4
 CID_ADAM_MAX_TENSORS = 32
 CID_RESAMPLE_BICUBIC = 3
+CID_SR_RAW = 1
 
 
 class AdamTensor(ctypes.Structure):
@@ -137,6 +138,20 @@ SYMBOLS = {
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "cid_esr_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
                                       _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "cid_sr_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int]),
+    "cid_sr_destroy": (None, [_c.c_void_p]),
+    "cid_sr_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_sr_param_key": (_c.c_char_p, [_c.c_void_p, _c.c_int]),
+    "cid_sr_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_sr_set_bn_eps": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_double]),
+    "cid_sr_missing_weights": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int)]),
+    "cid_sr_packed_weights_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "cid_sr_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_sr_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_sr_forward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                  _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_sr_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
+                                     _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
 }
 
 _lib = None
@@ -186,6 +201,13 @@ def check_esr(handle, code: int):
     """check() for a cid_esr_t handle."""
     if code != CID_OK:
         msg = lib().cid_esr_last_error(handle) if handle else None
+        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
+
+
+def check_sr(handle, code: int):
+    """check() for a cid_sr_t handle."""
+    if code != CID_OK:
+        msg = lib().cid_sr_last_error(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
 
 

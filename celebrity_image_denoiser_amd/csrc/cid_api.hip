@@ -16,6 +16,7 @@
 #include "optim_kernels.h"
 #include "resize_kernels.h"
 #include "esrgan_kernels.h"
+#include "srgan_kernels.h"
 
 #include <dlfcn.h>
 
@@ -3070,6 +3071,366 @@ int cid_esr_forward(cid_esr_t h, const void* in, int in_fmt, void* out, int out_
         const dim3 grid((unsigned)p.ttiles, (unsigned)std::min(kDiscChunk, N - n0));
         if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_esr_tail<true>, grid, dim3(E_TAIL_THREADS), 0, s, a);
         else hipLaunchKernelGGL(k_esr_tail<false>, grid, dim3(E_TAIL_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("tail");
+    }
+    return CID_OK;
+}
+
+}  // extern "C"
+
+// ---- the server's SRGANGenerator (cid_sr_*): weight staging, BatchNorm folding, workspace plan and launch sequence; kernels in
+// srgan_kernels.h (head, upscale stage, tail) and esrgan_kernels.h (trunk) ----
+namespace {
+
+constexpr int kSrBlocks = 5;
+constexpr size_t kSrUpSeg = (size_t)S_UP_W + 256 + 64;           // weights, bias[256] in packed order, slope (padded to 64)
+
+std::vector<EsrKey> sr_keys(int stages) {
+    std::vector<EsrKey> k;
+    const auto w = [&](const std::string& n, int co, int ci, int ks) { k.push_back({n, ESR_W, {co, ci, ks, ks}, 4, (size_t)co * ci * ks * ks}); };
+    const auto v = [&](const std::string& n, int c) { k.push_back({n, ESR_VEC, {c, 0, 0, 0}, 1, (size_t)c}); };
+    w("initial.0.weight", 64, 3, 9);
+    v("initial.0.bias", 64);
+    v("initial.1.weight", 1);
+    for (int i = 0; i < kSrBlocks; ++i) {
+        const std::string b = "res_blocks." + std::to_string(i) + ".";
+        for (int c = 0; c < 2; ++c) {
+            const std::string conv = b + std::to_string(3 * c) + ".", bn = b + std::to_string(3 * c + 1) + ".";
+            w(conv + "weight", 64, 64, 3);
+            v(conv + "bias", 64);
+            v(bn + "weight", 64);
+            v(bn + "bias", 64);
+            v(bn + "running_mean", 64);
+            v(bn + "running_var", 64);
+            k.push_back({bn + "num_batches_tracked", ESR_COUNT, {0, 0, 0, 0}, 0, 1});
+            if (c == 0) v(b + "2.weight", 1);
+        }
+    }
+    w("mid.weight", 64, 64, 3);
+    v("mid.bias", 64);
+    for (int u = 0; u < stages; ++u) {
+        w("upscale." + std::to_string(3 * u) + ".weight", 256, 64, 3);
+        v("upscale." + std::to_string(3 * u) + ".bias", 256);
+        v("upscale." + std::to_string(3 * u + 2) + ".weight", 1);
+    }
+    w("final.weight", 3, 64, 9);
+    v("final.bias", 3);
+    return k;
+}
+
+int sr_stages(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }
+
+struct SrPlan {
+    int stages;
+    size_t x0, mid, cur, up[3], total;   // byte offsets of the C8 tensors; `mid` ends as the trunk's result, up[k] is stage k's output
+    int ctiles_x, ctiles;                // trunk tiles (16 x 16) of the padded image
+};
+
+int sr_plan(int N, int Hp, int Wp, int scale, SrPlan& p) {
+    p.stages = sr_stages(scale);
+    if (p.stages < 0) return CID_ERR_INVALID;
+    if (N < 1 || Hp < 1 || Wp < 1) return CID_ERR_SHAPE;
+    if ((long long)Hp * Wp > 0x7fffffffLL / ((long long)scale * scale)) return CID_ERR_SHAPE;   // a pixel index inside one image is an int
+    const size_t t = align256((size_t)N * 64 * Hp * Wp * sizeof(float));
+    p.x0 = 0;
+    p.mid = t;
+    p.cur = 2 * t;
+    size_t at = 3 * t;
+    for (int u = 0; u < p.stages; ++u) {
+        p.up[u] = at;
+        at += align256((size_t)N * 64 * ((size_t)Hp << (u + 1)) * ((size_t)Wp << (u + 1)) * sizeof(float));
+    }
+    p.total = at;
+    p.ctiles_x = (Wp + D_TW - 1) / D_TW;
+    p.ctiles = ((Hp + DiscGeom<64, 64, 1>::TH - 1) / DiscGeom<64, 64, 1>::TH) * p.ctiles_x;
+    return CID_OK;
+}
+
+}  // namespace
+
+struct cid_sr_s {
+    int scale = 1, stages = 0;
+    std::vector<EsrKey> keys;
+    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
+    std::vector<char> have;
+    double eps[2 * kSrBlocks];
+    std::vector<float> staging;
+    const float* dev_blob = nullptr;
+    std::string err;
+    // head, ten block convolutions, mid, the upscale stages, tail
+    size_t up_off(int u) const { return kEsrHeadSeg + (2 * (size_t)kSrBlocks + 1) * kEsrConvSeg + (size_t)u * kSrUpSeg; }
+    size_t tail_off() const { return up_off(stages); }
+    size_t blob_floats() const { return tail_off() + kEsrTailSeg; }
+    int find(const std::string& k) const {
+        for (size_t i = 0; i < keys.size(); ++i)
+            if (keys[i].name == k) return (int)i;
+        return -1;
+    }
+};
+
+namespace {
+int sfail(cid_sr_t h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+// One 3x3 64 -> 64 convolution into k_esr_conv's segment layout.
+void sr_pack_conv64(float* seg, const float* w, const float* bias) {
+    for (int co = 0; co < 64; ++co)
+        for (int ci = 0; ci < 64; ++ci)
+            for (int tap = 0; tap < 9; ++tap) seg[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 64 + co] = w[((size_t)co * 64 + ci) * 9 + tap];
+    std::memcpy(seg + E_CONV_BIAS, bias, 64 * sizeof(float));
+}
+
+// The blob from the staged tensors: the kernels' weight layouts, each BatchNorm folded to y = s*z + t in fp64 as esr_pack does, `mid`
+// with the identity fold (s, t) = (1, 0), and each upscale stage's columns in the order of s_up_conv_channel.
+void sr_pack(cid_sr_t h) {
+    h->staging.assign(h->blob_floats(), 0.f);
+    float* b = h->staging.data();
+    const auto get = [&](const std::string& k) -> const float* { return h->raw[h->find(k)].data(); };
+    {   // head: [ci][kh][kw][co]
+        const float* w = get("initial.0.weight");
+        for (int co = 0; co < 64; ++co)
+            for (int k = 0; k < E_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * E_HEAD_K + k];
+        std::memcpy(b + E_HEAD_K * 64, get("initial.0.bias"), 64 * sizeof(float));
+        b[E_HEAD_K * 64 + 64] = get("initial.1.weight")[0];
+    }
+    for (int i = 0; i < kSrBlocks; ++i)
+        for (int c = 0; c < 2; ++c) {
+            float* seg = b + kEsrHeadSeg + (size_t)(2 * i + c) * kEsrConvSeg;
+            const std::string blk = "res_blocks." + std::to_string(i) + ".";
+            const std::string conv = blk + std::to_string(3 * c) + ".", bn = blk + std::to_string(3 * c + 1) + ".";
+            sr_pack_conv64(seg, get(conv + "weight"), get(conv + "bias"));
+            const float *gamma = get(bn + "weight"), *beta = get(bn + "bias"), *mean = get(bn + "running_mean"), *var = get(bn + "running_var");
+            for (int ch = 0; ch < 64; ++ch) {
+                const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + h->eps[2 * i + c]);
+                seg[E_CONV_S + ch] = (float)s;
+                seg[E_CONV_T + ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
+            }
+            seg[E_CONV_SLOPE] = c == 0 ? get(blk + "2.weight")[0] : 0.f;
+        }
+    {   // mid: bias only; fmaf(1, z, 0) = z
+        float* seg = b + kEsrHeadSeg + 2 * (size_t)kSrBlocks * kEsrConvSeg;
+        sr_pack_conv64(seg, get("mid.weight"), get("mid.bias"));
+        for (int ch = 0; ch < 64; ++ch) seg[E_CONV_S + ch] = 1.f;
+    }
+    for (int u = 0; u < h->stages; ++u) {   // [half][chunk][tap][ci % 8][128 packed columns]
+        float* seg = b + h->up_off(u);
+        const float* w = get("upscale." + std::to_string(3 * u) + ".weight");
+        const float* bias = get("upscale." + std::to_string(3 * u) + ".bias");
+        for (int J = 0; J < 256; ++J) {
+            const int cc = s_up_conv_channel(J);
+            for (int ci = 0; ci < 64; ++ci)
+                for (int tap = 0; tap < 9; ++tap)
+                    seg[(size_t)(J / 128) * (64 * 9 * 128) + ((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 128 + J % 128] = w[((size_t)cc * 64 + ci) * 9 + tap];
+            seg[S_UP_BIAS + J] = bias[cc];
+        }
+        seg[S_UP_SLOPE] = get("upscale." + std::to_string(3 * u + 2) + ".weight")[0];
+    }
+    {   // tail: [ci][kh][co * 9 + kw]
+        float* seg = b + h->tail_off();
+        const float* w = get("final.weight");
+        for (int co = 0; co < 3; ++co)
+            for (int ci = 0; ci < 64; ++ci)
+                for (int kh = 0; kh < 9; ++kh)
+                    for (int kw = 0; kw < 9; ++kw)
+                        seg[((size_t)ci * 9 + kh) * E_TAIL_WROW + co * 9 + kw] = w[(((size_t)co * 64 + ci) * 9 + kh) * 9 + kw];
+        std::memcpy(seg + E_TAIL_W, get("final.bias"), 3 * sizeof(float));
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int cid_sr_create(cid_sr_t* out, int scale_factor) {
+    if (!out) return CID_ERR_INVALID;
+    *out = nullptr;
+    if (sr_stages(scale_factor) < 0) return CID_ERR_INVALID;
+    cid_sr_s* h = new (std::nothrow) cid_sr_s();
+    if (!h) return CID_ERR_INVALID;
+    h->scale = scale_factor;
+    h->stages = sr_stages(scale_factor);
+    h->keys = sr_keys(h->stages);
+    h->raw.resize(h->keys.size());
+    h->have.assign(h->keys.size(), 0);
+    std::fill(h->eps, h->eps + 2 * kSrBlocks, 1e-5);
+    *out = h;
+    return CID_OK;
+}
+
+void cid_sr_destroy(cid_sr_t h) { delete h; }
+
+const char* cid_sr_last_error(cid_sr_t h) { return h ? h->err.c_str() : "null handle"; }
+
+const char* cid_sr_param_key(cid_sr_t h, int i) {
+    if (!h || i < 0 || (size_t)i >= h->keys.size()) return nullptr;
+    return h->keys[i].name.c_str();
+}
+
+int cid_sr_set_weight(cid_sr_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
+    if (!h) return CID_ERR_INVALID;
+    if (!key || !data || (!shape && ndim > 0)) return sfail(h, CID_ERR_INVALID, "cid_sr_set_weight: null argument");
+    const int i = h->find(key);
+    if (i < 0) return sfail(h, CID_ERR_KEY, std::string("cid_sr_set_weight: unexpected key '") + key + "'");
+    const EsrKey& k = h->keys[i];
+    if (k.kind == ESR_COUNT) {   // num_batches_tracked: part of the state_dict, unused in eval mode
+        if (ndim != 0) return sfail(h, CID_ERR_SHAPE, "cid_sr_set_weight: size mismatch for " + k.name);
+        h->have[i] = 1;
+        return CID_OK;
+    }
+    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return sfail(h, CID_ERR_SHAPE, "cid_sr_set_weight: size mismatch for " + k.name);
+    const float* f = static_cast<const float*>(data);
+    h->raw[i].assign(f, f + k.count);
+    h->have[i] = 1;
+    return CID_OK;
+}
+
+int cid_sr_set_bn_eps(cid_sr_t h, int block, int which, double eps) {
+    if (!h) return CID_ERR_INVALID;
+    if (block < 0 || block >= kSrBlocks || (which != 0 && which != 1)) return sfail(h, CID_ERR_INVALID, "cid_sr_set_bn_eps: no such BatchNorm");
+    if (!std::isfinite(eps) || eps < 0.0) return sfail(h, CID_ERR_INVALID, "cid_sr_set_bn_eps: eps must be finite and >= 0");
+    h->eps[2 * block + which] = eps;
+    return CID_OK;
+}
+
+int cid_sr_missing_weights(cid_sr_t h, int* count) {
+    if (!h || !count) return CID_ERR_INVALID;
+    int m = 0;
+    for (size_t i = 0; i < h->keys.size(); ++i) m += h->keys[i].kind != ESR_COUNT && !h->have[i];
+    *count = m;
+    return CID_OK;
+}
+
+size_t cid_sr_packed_weights_bytes(cid_sr_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
+
+int cid_sr_upload_weights(cid_sr_t h, void* device_blob, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!device_blob) return sfail(h, CID_ERR_INVALID, "cid_sr_upload_weights: null device pointer");
+    if ((uintptr_t)device_blob & 255) return sfail(h, CID_ERR_WORKSPACE, "cid_sr_upload_weights: blob must be 256-byte aligned");
+    for (size_t i = 0; i < h->keys.size(); ++i)
+        if (h->keys[i].kind != ESR_COUNT && !h->have[i]) return sfail(h, CID_ERR_STATE, "cid_sr_upload_weights: " + h->keys[i].name + " not set");
+    sr_pack(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
+    if (e != hipSuccess) return sfail(h, CID_ERR_HIP, std::string("cid_sr_upload_weights: ") + hipGetErrorString(e));
+    h->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_sr_workspace_bytes(int N, int Hp, int Wp, int scale_factor, size_t* bytes) {
+    if (!bytes) return CID_ERR_INVALID;
+    SrPlan p;
+    const int rc = sr_plan(N, Hp, Wp, scale_factor, p);
+    if (rc == CID_OK) *bytes = p.total;
+    return rc;
+}
+
+int cid_sr_stage_view(const char* stage, int N, int Hp, int Wp, int scale_factor, size_t* offset_bytes, int* C, int* Hs, int* Ws,
+                      int* channel_block) {
+    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
+    SrPlan p;
+    const int rc = sr_plan(N, Hp, Wp, scale_factor, p);
+    if (rc != CID_OK) return rc;
+    const std::string s(stage);
+    int shift = 0;
+    if (s == "x0") *offset_bytes = p.x0;
+    else if (s == "trunk") *offset_bytes = p.mid;
+    else if (s == "up1" && p.stages >= 2) *offset_bytes = p.up[0], shift = 1;
+    else if (s == "up2" && p.stages >= 3) *offset_bytes = p.up[1], shift = 2;
+    else if (s == "tail_in") *offset_bytes = p.stages ? p.up[p.stages - 1] : p.mid, shift = p.stages;
+    else return CID_ERR_KEY;
+    *C = 64;
+    *Hs = Hp << shift;
+    *Ws = Wp << shift;
+    *channel_block = 8;
+    return CID_OK;
+}
+
+int cid_sr_forward(cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, int pad_left, int pad_top,
+                   int pad_right, int pad_bottom, unsigned flags, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!in || !out || !workspace) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: null pointer");
+    if ((in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) || (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC))
+        return sfail(h, CID_ERR_INVALID, "cid_sr_forward: unknown format");
+    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
+        return sfail(h, CID_ERR_INVALID, "cid_sr_forward: misaligned fp32 operand");
+    if (flags & ~(unsigned)CID_SR_RAW) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: unknown flags");
+    if ((flags & CID_SR_RAW) && out_fmt != CID_FMT_F32_NCHW) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: CID_SR_RAW needs an fp32 output");
+    for (const int pad : {pad_left, pad_top, pad_right, pad_bottom})
+        if (pad < 0 || pad > 4096) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: pads must lie in [0, 4096]");
+    if (N < 1 || H < 1 || W < 1 || H > 0x7fffffff - 8192 || W > 0x7fffffff - 8192)
+        return sfail(h, CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (N, H, W >= 1)");
+    const int Hp = H + pad_top + pad_bottom, Wp = W + pad_left + pad_right;
+    SrPlan p;
+    if (sr_plan(N, Hp, Wp, h->scale, p) != CID_OK)
+        return sfail(h, CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (scale^2 * Hp * Wp < 2^31)");
+    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
+        return sfail(h, CID_ERR_WORKSPACE, "cid_sr_forward: workspace smaller than cid_sr_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return sfail(h, CID_ERR_STATE, "cid_sr_forward: weights not uploaded");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto herr = [&](const char* what) { return sfail(h, CID_ERR_HIP, std::string("cid_sr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    char* ws = static_cast<char*>(workspace);
+    float *x0 = reinterpret_cast<float*>(ws + p.x0), *mid = reinterpret_cast<float*>(ws + p.mid), *cur = reinterpret_cast<float*>(ws + p.cur);
+    const float* blob = h->dev_blob;
+
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        const SrHeadArgs a{in, x0, blob, H, W, Hp, Wp, pad_left, pad_top, n0};
+        const dim3 grid((unsigned)(((long long)Hp * Wp + D_THREADS - 1) / D_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
+        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_sr_head<true>, grid, dim3(D_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_sr_head<false>, grid, dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("head");
+    }
+    // launches 0 .. 9: the blocks' convolutions (x0 or cur -> mid -> cur); launch 10: mid(cur) + x0 -> mid
+    for (int l = 0; l <= 2 * kSrBlocks; ++l)
+        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+            EsrConvArgs a{};
+            a.w = blob + kEsrHeadSeg + (size_t)l * kEsrConvSeg;
+            a.H = Hp;
+            a.W = Wp;
+            a.tiles_x = p.ctiles_x;
+            a.n0 = n0;
+            const dim3 grid((unsigned)p.ctiles, (unsigned)std::min(kDiscChunk, N - n0)), block(D_THREADS);
+            if (l == 2 * kSrBlocks) {
+                a.in = cur;
+                a.out = mid;
+                a.res = x0;
+                hipLaunchKernelGGL(k_esr_conv<EPI_RES>, grid, block, 0, s, a);
+            } else if (l % 2 == 0) {
+                a.in = l == 0 ? x0 : cur;
+                a.out = mid;
+                hipLaunchKernelGGL(k_esr_conv<EPI_PRELU>, grid, block, 0, s, a);
+            } else {
+                a.in = mid;
+                a.out = cur;
+                hipLaunchKernelGGL(k_esr_conv<EPI_BN>, grid, block, 0, s, a);
+            }
+            if (hipPeekAtLastError() != hipSuccess) return herr("trunk");
+        }
+    const float* u = mid;
+    int Hu = Hp, Wu = Wp;
+    for (int k = 0; k < p.stages; ++k) {
+        float* dst = reinterpret_cast<float*>(ws + p.up[k]);
+        const int tiles_x = (Wu + D_TW - 1) / D_TW;
+        const int tiles = ((Hu + DiscGeom<64, 128, 1>::TH - 1) / DiscGeom<64, 128, 1>::TH) * tiles_x;
+        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+            const SrUpArgs a{u, dst, blob + h->up_off(k), Hu, Wu, tiles_x, n0};
+            const dim3 grid((unsigned)tiles, (unsigned)std::min(kDiscChunk, N - n0), 2);
+            hipLaunchKernelGGL(k_sr_up, grid, dim3(D_THREADS), 0, s, a);
+            if (hipPeekAtLastError() != hipSuccess) return herr("upscale");
+        }
+        u = dst;
+        Hu *= 2;
+        Wu *= 2;
+    }
+    const int ttiles_x = (Wu + E_TAIL_TW - 1) / E_TAIL_TW;
+    const int ttiles = ((Hu + E_TAIL_TH - 1) / E_TAIL_TH) * ttiles_x;
+    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        const EsrTailArgs a{u, out, blob + h->tail_off(), Hu, Wu, ttiles_x, n0};
+        const dim3 grid((unsigned)ttiles, (unsigned)std::min(kDiscChunk, N - n0));
+        if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_sr_tail<SR_OUT_U8>, grid, dim3(E_TAIL_THREADS), 0, s, a);
+        else if (flags & CID_SR_RAW) hipLaunchKernelGGL(k_sr_tail<SR_OUT_RAW>, grid, dim3(E_TAIL_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_sr_tail<SR_OUT_F32>, grid, dim3(E_TAIL_THREADS), 0, s, a);
         if (hipPeekAtLastError() != hipSuccess) return herr("tail");
     }
     return CID_OK;

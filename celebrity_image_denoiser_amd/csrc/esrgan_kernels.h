@@ -17,6 +17,7 @@
 //         EPI_PRELU  out = prelu(y)                 block.0-2
 //         EPI_RES    out = res + y                  block.3-4 (res = the block's input; out may be the same buffer)
 //         EPI_SUM    out = x1 + (res + y)           block.3-4 of the last block: the tensor the tail reads
+//         EPI_BN     out = y                        the SRGAN generator's blocks, which have no skip (srgan_kernels.h)
 //     PReLU is v > 0 ? v : a * v (a learned slope may be negative or above 1).  Halo positions outside the image are zero.
 //   * k_esr_tail<U8>: the 9x9 64 -> 3 convolution + bias on the VALU.  COUT = 3 would fill 3 of an MFMA tile's 16 rows, so the
 //     kernel keeps 8 consecutive pixels x 3 channels in registers per thread instead: one 16-float row segment read from LDS
@@ -103,7 +104,7 @@ __global__ void __launch_bounds__(D_THREADS) k_esr_head(const EsrHeadArgs a) {
 constexpr int E_CONV_W = 64 * 64 * 9;   // packed weights of one trunk convolution
 // one trunk segment of the blob: weights, then bias[64], s[64], t[64], slope
 constexpr int E_CONV_BIAS = E_CONV_W, E_CONV_S = E_CONV_W + 64, E_CONV_T = E_CONV_W + 128, E_CONV_SLOPE = E_CONV_W + 192;
-enum { EPI_PRELU = 0, EPI_RES = 1, EPI_SUM = 2 };
+enum { EPI_PRELU = 0, EPI_RES = 1, EPI_SUM = 2, EPI_BN = 3 };
 
 struct EsrConvArgs {
     const float* in;      // C8, 64 channels
@@ -204,7 +205,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_esr_conv(const EsrConvArgs a) 
                 if (EPI == EPI_PRELU) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) y[r] = e_prelu(y[r], slope);
-                } else {
+                } else if (EPI != EPI_BN) {
                     y = *reinterpret_cast<const d_f32x4*>(a.res + at) + y;
                     if (EPI == EPI_SUM) y = *reinterpret_cast<const d_f32x4*>(a.x1 + at) + y;
                 }
@@ -233,18 +234,15 @@ struct EsrTailArgs {
     int n0;
 };
 
-template <bool U8>
-__global__ void __launch_bounds__(E_TAIL_THREADS) k_esr_tail(const EsrTailArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[4 * E_TAIL_PLANE];
+// The convolution itself, shared with the SRGAN generator's tail (srgan_kernels.h): acc[co][j] = bias + the 5184-term sum of output
+// pixel (ty * 16 + ry, tx * 64 + cx + j), channel co.  `lds` holds 4 * E_TAIL_PLANE floats.
+__device__ __forceinline__ void e_tail_sums(const EsrTailArgs& a, float* lds, int ty, int tx, size_t n, float (&acc)[3][E_TAIL_PX]) {
     const int tid = threadIdx.x;
     const int ry = tid >> 3, cx = (tid & 7) * E_TAIL_PX;   // this thread's row and first column inside the tile
-    const int t = blockIdx.x, ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-    const size_t n = (size_t)a.n0 + blockIdx.y;
     const int iy0 = ty * E_TAIL_TH - 4, ix0 = tx * E_TAIL_TW - 4;
     const size_t plane = (size_t)a.H * a.W;
     const EsrConstF wc = (EsrConstF)a.w;
 
-    float acc[3][E_TAIL_PX];
 #pragma unroll
     for (int co = 0; co < 3; ++co)
 #pragma unroll
@@ -299,6 +297,18 @@ __global__ void __launch_bounds__(E_TAIL_THREADS) k_esr_tail(const EsrTailArgs a
 #pragma unroll
             for (int j = 0; j < E_TAIL_PX; ++j) acc[co][j] += part[co][j];
     }
+}
+
+template <bool U8>
+__global__ void __launch_bounds__(E_TAIL_THREADS) k_esr_tail(const EsrTailArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[4 * E_TAIL_PLANE];
+    const int tid = threadIdx.x;
+    const int ry = tid >> 3, cx = (tid & 7) * E_TAIL_PX;
+    const int t = blockIdx.x, ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const size_t n = (size_t)a.n0 + blockIdx.y;
+    const size_t plane = (size_t)a.H * a.W;
+    float acc[3][E_TAIL_PX];
+    e_tail_sums(a, lds, ty, tx, n, acc);
 
     const int oy = ty * E_TAIL_TH + ry;
     if (oy >= a.H) return;

@@ -1,0 +1,226 @@
+"""Times the SRGAN forward (SRGANGenerator, cid_sr_forward) on the GPU with device events after a warm-up, next to the same network
+restated with the module's own stock nn containers on ATen/MIOpen fp32 in the same process.
+
+Cases: B=4 256^2 (few large images) and B=64 64^2 (many small ones), scale 4: the outputs are 1024^2 and 256^2.  Each case runs in a
+process of its own (this script starts one child per case).  For each: median ms per call over --reps windows of --iters calls
+[min-max], images/s, algorithmic TFLOP/s (2 * 1,407,168 MACs per input pixel at scale 4: head, eleven trunk convolutions, the upscale
+stages and the tail at 16 times the pixels) and its share of the 157.3 TFLOP/s fp32 MFMA peak.
+
+--trace starts ONE `rocprofv3 --kernel-trace` run (no counters in it) of a few forwards of the given case and prints per launch the
+count, the mean and the minimum time, and the fp32-MFMA bound of the trunk and upscale launches.
+
+    python celebrity_image_denoiser_amd/csrc/tools/srgan_bench.py [--reps 5] [--iters 10] [--case N,H,W ...] [--scale 4]
+                                                                  [--no-aten] [--no-u8] [--json out.json] [--trace N,H,W]
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, ROOT)
+
+MFMA_F32_PEAK = 157.3e12
+CASES = ((4, 256, 256), (64, 64, 64))
+
+
+def sr_macs_per_pixel(scale):
+    stages = scale.bit_length() - 1
+    up = sum(4 ** k * 64 * 576 * 4 for k in range(stages))           # stage k: 64 -> 256 at 4^k times the pixels
+    return 243 * 64 + 11 * 64 * 576 + up + scale * scale * 5184 * 3
+
+
+def sr_flops(n, h, w, scale):
+    return 2.0 * n * h * w * sr_macs_per_pixel(scale)
+
+
+def aten_forward(m, x):
+    """The reference's forward (app.py:180-186) on the module's stock containers."""
+    import torch
+
+    x0 = m.initial(x)
+    return torch.tanh(m.final(m.upscale(m.mid(m.res_blocks(x0)) + x0)))
+
+
+def timed(fn, reps, iters):
+    import torch
+
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / iters)
+    return out
+
+
+def summary(t, n, flops):
+    med = statistics.median(t)
+    return {"ms_median": med, "ms_min": min(t), "ms_max": max(t), "images_per_s": n / med * 1e3,
+            "tflops": flops / med / 1e9, "mfma_share": flops / med / 1e-3 / MFMA_F32_PEAK}
+
+
+def fmt(name, r):
+    return (f"{name} {r['ms_median']:.3f} ms [{r['ms_min']:.3f}-{r['ms_max']:.3f}] {r['images_per_s']:.0f} img/s "
+            f"{r['tflops']:.1f} TF/s {100 * r['mfma_share']:.0f}% of 157.3")
+
+
+def setup(n, h, w, scale):
+    import torch
+
+    import celebrity_image_denoiser_amd as cid
+    from celebrity_image_denoiser_amd import synth
+
+    if not torch.cuda.is_available():
+        raise SystemExit("srgan_bench needs a GPU")
+    dev = "cuda:0"
+    model = cid.load_srgan(synth.make_srgan_state_dict("default", scale), scale_factor=scale, device=dev, strict=True)
+    u8 = torch.from_numpy(synth.srgan_inputs_u8(min(n, 16), h, w)).to(dev).repeat((n + 15) // 16, 1, 1, 1)[:n].contiguous()
+    x = ((u8.to(torch.float32).div(255.0) - 0.5) / 0.5).permute(0, 3, 1, 2).contiguous()
+    return model, u8, x
+
+
+def run_case(n, h, w, args):
+    import torch
+
+    model, u8, x = setup(n, h, w, args.scale)
+    flops = sr_flops(n, h, w, args.scale)
+    row = {"N": n, "H": h, "W": w, "scale": args.scale, "gflop": flops / 1e9}
+    row["hip"] = summary(timed(lambda: model(x), args.reps, args.iters), n, flops)
+    line = f"B={n:3d} {h}x{w} x{args.scale} {flops / 1e9:.0f} GFLOP | " + fmt("hip", row["hip"])
+    if not args.no_u8:
+        row["hip_u8"] = summary(timed(lambda: model(u8), args.reps, args.iters), n, flops)
+        line += " | " + fmt("hip u8", row["hip_u8"])
+    if not args.no_aten:
+        with torch.no_grad():
+            row["aten"] = summary(timed(lambda: aten_forward(model, x), args.reps, args.iters), n, flops)
+        line += " | " + fmt("aten", row["aten"]) + f" | hip/aten {row['hip']['ms_median'] / row['aten']['ms_median']:.2f}"
+    print(line, flush=True)
+    return row
+
+
+def run_traced(n, h, w, args):
+    """The child of --trace: a few plain forwards, nothing else."""
+    import torch
+
+    model, _, x = setup(n, h, w, args.scale)
+    for _ in range(args.trace_calls):
+        model(x)
+    torch.cuda.synchronize()
+
+
+def short_name(k):
+    k = k.split("(")[0].replace("void ", "").replace("cid::", "")
+    for a, b in (("k_esr_conv<0>", "k_esr_conv<EPI_PRELU>"), ("k_esr_conv<1>", "k_esr_conv<EPI_RES>"), ("k_esr_conv<3>", "k_esr_conv<EPI_BN>"),
+                 ("k_sr_tail<0>", "k_sr_tail<F32>"), ("k_sr_tail<1>", "k_sr_tail<U8>"), ("k_sr_tail<2>", "k_sr_tail<RAW>")):
+        k = k.replace(a, b)
+    return k
+
+
+def trace(n, h, w, args):
+    """One rocprofv3 --kernel-trace run of this script's traced child; per kernel: launches, mean and min ms, in launch order."""
+    with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR", "/tmp")) as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
+               "--traced-child", f"{n},{h},{w}", "--scale", str(args.scale), "--trace-calls", str(args.trace_calls)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode:
+            raise SystemExit(f"rocprofv3 failed ({r.returncode}):\n{r.stderr[-2000:]}")
+        files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+        if not files:
+            raise SystemExit("rocprofv3 wrote no kernel trace")
+        rows = []
+        for f in files:
+            with open(f, newline="") as fh:
+                rows += list(csv.DictReader(fh))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    # the warm-up forward inside load/pack is not one: only model(x) launches kernels of these names; keep the last trace_calls - 1
+    # forwards (the first one pays for code loading)
+    per = {}
+    for r in rows:
+        name = short_name(r["Kernel_Name"])
+        if "k_sr_" in name or "k_esr_" in name:
+            per.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
+    stages = args.scale.bit_length() - 1
+    bound = lambda macs: 2.0 * macs / MFMA_F32_PEAK * 1e3   # noqa: E731
+    print(f"per launch at B={n} {h}x{w} x{args.scale} (one rocprofv3 --kernel-trace run of {args.trace_calls} forwards, the first dropped; mean / min ms)")
+    total = 0.0
+    out = {}
+    for name, t in per.items():
+        calls = len(t) // args.trace_calls           # launches of this kernel per forward
+        t = t[calls:]                                # drop the first forward
+        mean, mn = statistics.mean(t), min(t)
+        line = f"{name:24s} {len(t):3d} launches   {mean:.3f} / {mn:.3f}"
+        if "k_esr_conv" in name:
+            b = bound(n * h * w * 64 * 576)
+            line += f"   fp32-MFMA bound {b:.3f} ms, share {b / mean:.2f}"
+            total += mean * calls
+        elif "k_sr_up" in name:
+            # the stages differ in size: group by position within a forward
+            for k in range(stages):
+                tk = t[k::stages]
+                b = bound(n * h * w * 4 ** k * 64 * 576 * 4)
+                print(f"{'k_sr_up (stage %d)' % (k + 1):24s} {len(tk):3d} launches   {statistics.mean(tk):.3f} / {min(tk):.3f}   fp32-MFMA bound {b:.3f} ms, share "
+                      f"{b / statistics.mean(tk):.2f}")
+                out[f"k_sr_up.{k + 1}"] = statistics.mean(tk)
+                total += statistics.mean(tk)
+            continue
+        else:
+            total += mean * calls
+        out[name] = mean
+        print(line)
+    tail = [v for k, v in out.items() if "k_sr_tail" in k]
+    if tail and total > 0:
+        print(f"sum of one forward's launches {total:.3f} ms; the tail's share {tail[0] / total:.2f}")
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--case", action="append", default=None, help="N,H,W (repeatable); default: the two cases above, one process each")
+    ap.add_argument("--scale", type=int, default=4)
+    ap.add_argument("--no-aten", action="store_true", help="skip the ATen/MIOpen baseline")
+    ap.add_argument("--no-u8", action="store_true", help="skip the uint8 -> uint8 path")
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--trace", default=None, help="N,H,W: per-launch times of this case from one rocprofv3 --kernel-trace run")
+    ap.add_argument("--trace-calls", type=int, default=4)
+    ap.add_argument("--traced-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    shape = lambda s: tuple(int(v) for v in s.split(","))   # noqa: E731
+    if args.traced_child:
+        run_traced(*shape(args.traced_child), args)
+        return
+    rows = []
+    if args.child:
+        rows = [run_case(*shape(c), args) for c in args.case]
+    elif args.case or not args.trace:
+        for c in ([shape(c) for c in args.case] if args.case else CASES):
+            # each case in a process of its own: allocator state and clocks of one do not reach the next
+            with tempfile.NamedTemporaryFile(suffix=".json") as tf:
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case", ",".join(map(str, c)), "--scale", str(args.scale),
+                       "--reps", str(args.reps), "--iters", str(args.iters), "--json", tf.name]
+                cmd += ["--no-aten"] * args.no_aten + ["--no-u8"] * args.no_u8
+                subprocess.run(cmd, check=True)
+                rows += json.load(open(tf.name))
+    if args.trace:
+        rows.append({"trace": args.trace, "per_launch_ms": trace(*shape(args.trace), args)})
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -496,3 +496,86 @@ def make_esrgan_state_dict(kind: str = "default", num_residuals: int = 8, seed: 
 def esrgan_inputs_u8(n: int, h: int, w: int, first_index: int = 0) -> np.ndarray:
     """uint8 [n,h,w,3] inputs for the ESRGAN tests: the noisy face-like fields of make_batch."""
     return add_gaussian_noise(clean_images_u8(n, h, w, first_index), 25.0, first_index)
+
+
+# ---- the server's SRGANGenerator (backend/app.py:145-186): parameter shapes and synthetic weights ----
+
+def _srgan_stages(scale_factor: int) -> int:
+    s = int(scale_factor)
+    if s < 1 or s & (s - 1):
+        raise ValueError(f"scale_factor must be a power of two (got {scale_factor})")
+    return s.bit_length() - 1
+
+
+def srgan_param_shapes(scale_factor: int = 4) -> "OrderedDict[str, tuple]":
+    """state_dict key -> (shape, dtype name) of SRGANGenerator(scale_factor), in the module's own order, BatchNorm buffers and
+    num_batches_tracked included."""
+    out: "OrderedDict[str, tuple]" = OrderedDict()
+    f = "float32"
+    out["initial.0.weight"] = ((64, 3, 9, 9), f)
+    out["initial.0.bias"] = ((64,), f)
+    out["initial.1.weight"] = ((1,), f)
+    for i in range(5):
+        b = f"res_blocks.{i}."
+        for c in (0, 3):
+            out[f"{b}{c}.weight"] = ((64, 64, 3, 3), f)
+            out[f"{b}{c}.bias"] = ((64,), f)
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                out[f"{b}{c + 1}.{k}"] = ((64,), f)
+            out[f"{b}{c + 1}.num_batches_tracked"] = ((), "int64")
+            if c == 0:
+                out[f"{b}2.weight"] = ((1,), f)
+    out["mid.weight"] = ((64, 64, 3, 3), f)
+    out["mid.bias"] = ((64,), f)
+    for u in range(_srgan_stages(scale_factor)):
+        out[f"upscale.{3 * u}.weight"] = ((256, 64, 3, 3), f)
+        out[f"upscale.{3 * u}.bias"] = ((256,), f)
+        out[f"upscale.{3 * u + 2}.weight"] = ((1,), f)
+    out["final.weight"] = ((3, 64, 9, 9), f)
+    out["final.bias"] = ((3,), f)
+    return out
+
+
+def make_srgan_state_dict(kind: str = "default", scale_factor: int = 4, seed: int = WEIGHT_SEED) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights keyed like the reference's SRGANGenerator state_dict, from the hash streams "srgan:<kind>:<key>", with the
+    distributions of make_esrgan_state_dict: convolutions U(+-sqrt(g/fan_in)), g = 1 for "default" and 6 for "hot"; BatchNorm gamma
+    in [0.6, 1.4], beta in +-0.1, running_mean in +-0.3, running_var in [0.5, 1.5]; PReLU slopes in [0.05, 0.45].  In "hot" the
+    slope of initial.1 is -0.3, that of the last block's PReLU (res_blocks.4.2) 1.5 and that of the first upscale stage -0.3."""
+    if kind not in ("default", "hot"):
+        raise ValueError(f"unknown weight set {kind!r}")
+    shapes = srgan_param_shapes(scale_factor)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for key, (shape, dtype) in shapes.items():
+        if dtype == "int64":
+            sd[key] = np.array(7, dtype=np.int64)
+            continue
+        n = int(np.prod(shape))
+        u = hash_uniform(seed, _fnv1a64("srgan:" + kind + ":" + key), n)
+        layer, leaf = key.rsplit(".", 1)
+        wshape = shapes[layer + ".weight"][0]
+        if len(wshape) == 4:                                   # a convolution's weight or bias
+            fan_in = wshape[1] * wshape[2] * wshape[3]
+            bound = math.sqrt((1.0 if kind == "default" else 6.0) / fan_in)
+            v = (2.0 * u - 1.0) * bound
+        elif wshape == (1,):                                   # a PReLU slope
+            v = 0.05 + 0.4 * u
+        elif leaf == "weight":
+            v = 0.6 + 0.8 * u
+        elif leaf == "bias":
+            v = (2.0 * u - 1.0) * 0.1
+        elif leaf == "running_mean":
+            v = (2.0 * u - 1.0) * 0.3
+        else:                                                  # running_var
+            v = 0.5 + u
+        sd[key] = v.astype(np.float32).reshape(shape)
+    if kind == "hot":
+        sd["initial.1.weight"][...] = -0.3
+        sd["res_blocks.4.2.weight"][...] = 1.5
+        if "upscale.2.weight" in sd:
+            sd["upscale.2.weight"][...] = -0.3
+    return sd
+
+
+def srgan_inputs_u8(n: int, h: int, w: int, first_index: int = 0) -> np.ndarray:
+    """uint8 [n,h,w,3] inputs for the SRGAN tests: the noisy face-like fields of make_batch."""
+    return add_gaussian_noise(clean_images_u8(n, h, w, first_index), 25.0, first_index)

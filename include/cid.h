@@ -659,6 +659,62 @@ int cid_esr_forward(cid_esr_t h, const void* in, int in_fmt, void* out, int out_
 int cid_esr_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block);
 
 /*
+ * The server's third model — SRGANGenerator(scale_factor = 4) (backend/app.py:145-186; the same class in
+ * backend/trainingcode/srgan_code/sr_ganTrainGNew.py:19-51), the "srgan" branch of /enhance.  Eval mode, fp32:
+ *
+ *   x0  = PReLU(Conv2d(3, 64, 9, padding=4)(x))                                          initial.0, initial.1
+ *   r   = five times  b <- BatchNorm(Conv3x3(PReLU(BatchNorm(Conv3x3(b))))), from x0      res_blocks.i.{0,1,2,3,4}; NO skip per block
+ *   t   = Conv3x3(r) + x0                                                                mid (bias, no BatchNorm)
+ *   u  <- PReLU(PixelShuffle(2)(Conv2d(64, 256, 3, padding=1)(u)))  log2(scale) times     upscale.{3k, 3k+2}, from t
+ *   out = tanh(Conv2d(64, 3, 9, padding=4)(u))                                           final
+ *
+ * PixelShuffle(2) is out[n, c, 2y+i, 2x+j] = in[n, 4c + 2i + j, y, x].  Its own handle and blob, mirroring cid_esr_* one for one.
+ * cid_sr_create fixes scale_factor = 1, 2, 4 or 8 (0 to 3 upscale stages; anything else -> CID_ERR_INVALID).  cid_sr_param_key
+ * enumerates the module's state_dict keys in its order (82 + 3 * stages of them).  cid_sr_set_weight, cid_sr_set_bn_eps (block 0..4;
+ * which 0: res_blocks.i.1, 1: res_blocks.i.4), cid_sr_missing_weights, cid_sr_packed_weights_bytes and cid_sr_upload_weights behave
+ * as their cid_esr_* namesakes, errors included; each BatchNorm is folded into y = fmaf(s, z, t) in fp64 at upload, and `mid` runs
+ * with (s, t) = (1, 0).  PReLU is v > 0 ? v : a * v for any slope a.
+ *
+ * cid_sr_forward: in is the UNPADDED image, fp32 [N,3,H,W] already normalised to [-1,1] (CID_FMT_F32_NCHW) or uint8 [N,H,W,3]
+ * (CID_FMT_U8_NHWC), read as ((float)u / 255.0f - 0.5f) / 0.5f with true divisions (ToTensor + Normalize(0.5, 0.5)): a uint8 image
+ * and its normalised fp32 copy give identical bits.  The server's Pad(fill=0) is index arithmetic, as in cid_forward_padded: the
+ * network runs on Hp x Wp = (H + pad_top + pad_bottom) x (W + pad_left + pad_right), the band around the image reads as -1.0 and no
+ * padded copy exists.  Pads must lie in [0, 4096].  out is the WHOLE padded result, as the server shows it (app.py:481-485 crops only
+ * the input's picture): fp32 [N,3,s*Hp,s*Wp] = tanh(.), or uint8 [N,s*Hp,s*Wp,3] as the server's view
+ * (uint8)(clamp(tanhf(v) * 0.5f + 0.5f, 0, 1) * 255.0f), a truncation.  flags & CID_SR_RAW gives the fp32 sums before tanh instead
+ * (a testing aid).  Any H, W >= 1.  1 + 11 + stages + 1 launches on `stream`, no host synchronisation; trunk and upscale stages run on
+ * exact-fp32 MFMA, head and tail on the VALU; the 256-channel tensor before a PixelShuffle is never stored.  Every sum has a fixed
+ * order and an image's tiles depend only on the padded size: an image's result is bit-identical in any batch.  Checked on the host
+ * before any launch:
+ *   CID_ERR_INVALID    null pointer, unknown format, misaligned fp32 operand, unknown flags, CID_SR_RAW with a uint8 output,
+ *                      a pad outside [0, 4096]
+ *   CID_ERR_SHAPE      N < 1, H < 1, W < 1, s^2 * Hp * Wp >= 2^31
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_sr_workspace_bytes(N, Hp, Wp, scale_factor) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_sr_stage_view (testing aid): where the last forward over a padded Hp x Wp input left `stage` in its workspace: "x0", "trunk"
+ * (= mid(r) + x0), "up1" (the first upscale stage's output; with two or more stages), "up2" (with three) and "tail_in" (the last
+ * stage's output, or "trunk" at scale 1).  All are fp32 with 64 channels in blocks of 8, laid out as cid_esr_stage_view describes,
+ * of size *Hs x *Ws.  Unknown or absent stage -> CID_ERR_KEY; a scale that is not 1, 2, 4 or 8 -> CID_ERR_INVALID.
+ */
+typedef struct cid_sr_s* cid_sr_t;
+enum { CID_SR_RAW = 1 };
+int cid_sr_create(cid_sr_t* out, int scale_factor);
+void cid_sr_destroy(cid_sr_t h);
+const char* cid_sr_last_error(cid_sr_t h);
+const char* cid_sr_param_key(cid_sr_t h, int i);
+int cid_sr_set_weight(cid_sr_t h, const char* key, const void* host_data, const int64_t* shape, int ndim);
+int cid_sr_set_bn_eps(cid_sr_t h, int block, int which, double eps);
+int cid_sr_missing_weights(cid_sr_t h, int* count);
+size_t cid_sr_packed_weights_bytes(cid_sr_t h);
+int cid_sr_upload_weights(cid_sr_t h, void* device_blob, void* stream);
+int cid_sr_workspace_bytes(int N, int Hp, int Wp, int scale_factor, size_t* bytes);
+int cid_sr_forward(cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, int pad_left, int pad_top,
+                   int pad_right, int pad_bottom, unsigned flags, void* workspace, size_t workspace_bytes, void* stream);
+int cid_sr_stage_view(const char* stage, int N, int Hp, int Wp, int scale_factor, size_t* offset_bytes, int* C, int* Hs, int* Ws,
+                      int* channel_block);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
