@@ -22,6 +22,9 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
                                   fp32 output, enhance_u8(model, u8) -> the server's uint8 view
     SRGANGenerator(scale_factor=4) / load_srgan(ckpt)      the server's SRGAN model (eval mode): super_resolve(model, x) -> fp32 at
                                   scale times the size, super_resolve_u8(model, u8) -> the server's padded uint8 view
+    CGANGenerator(n_classes=10) / load_cgan(ckpt)          the server's class-conditional cGAN model (eval mode): latent(n, seed) draws
+                                  its input on the device, generate(model, labels, seed=s) -> fp32 [N,3,64,64], generate_u8 -> the
+                                  server's uint8 view
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -56,6 +59,11 @@ _LAZY = {
     "load_srgan": ("srgan", "load_srgan"),
     "super_resolve": ("srgan", "super_resolve"),
     "super_resolve_u8": ("srgan", "super_resolve_u8"),
+    "CGANGenerator": ("cgan", "CGANGenerator"),
+    "load_cgan": ("cgan", "load_cgan"),
+    "latent": ("cgan", "latent"),
+    "generate": ("cgan", "generate"),
+    "generate_u8": ("cgan", "generate_u8"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

@@ -21,6 +21,7 @@ CID_NOISE_GAUSSIAN, CID_NOISE_SALT_PEPPER, CID_NOISE_SPECKLE, CID_NOISE_POISSON,
 CID_ADAM_MAX_TENSORS = 32
 CID_RESAMPLE_BICUBIC = 3
 CID_SR_RAW = 1
+CID_CG_RAW = 1
 
 
 class AdamTensor(ctypes.Structure):
@@ -152,6 +153,21 @@ SYMBOLS = {
                                   _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "cid_sr_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
                                      _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "cid_cg_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int]),
+    "cid_cg_destroy": (None, [_c.c_void_p]),
+    "cid_cg_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_cg_param_key": (_c.c_char_p, [_c.c_void_p, _c.c_int]),
+    "cid_cg_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_cg_set_bn_eps": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_double]),
+    "cid_cg_missing_weights": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int)]),
+    "cid_cg_packed_weights_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "cid_cg_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_cg_workspace_bytes": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_cg_latent": (_c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "cid_cg_forward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_uint, _c.c_void_p,
+                                  _c.c_size_t, _c.c_void_p]),
+    "cid_cg_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
+                                     _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
 }
 
 _lib = None
@@ -208,6 +224,13 @@ def check_sr(handle, code: int):
     """check() for a cid_sr_t handle."""
     if code != CID_OK:
         msg = lib().cid_sr_last_error(handle) if handle else None
+        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
+
+
+def check_cg(handle, code: int):
+    """check() for a cid_cg_t handle."""
+    if code != CID_OK:
+        msg = lib().cid_cg_last_error(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
 
 

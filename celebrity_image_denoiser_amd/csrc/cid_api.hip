@@ -17,6 +17,7 @@
 #include "resize_kernels.h"
 #include "esrgan_kernels.h"
 #include "srgan_kernels.h"
+#include "cgan_kernels.h"
 
 #include <dlfcn.h>
 
@@ -3431,6 +3432,311 @@ int cid_sr_forward(cid_sr_t h, const void* in, int in_fmt, void* out, int out_fm
         if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_sr_tail<SR_OUT_U8>, grid, dim3(E_TAIL_THREADS), 0, s, a);
         else if (flags & CID_SR_RAW) hipLaunchKernelGGL(k_sr_tail<SR_OUT_RAW>, grid, dim3(E_TAIL_THREADS), 0, s, a);
         else hipLaunchKernelGGL(k_sr_tail<SR_OUT_F32>, grid, dim3(E_TAIL_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("tail");
+    }
+    return CID_OK;
+}
+
+}  // extern "C"
+
+// ---- the server's CGANGenerator (cid_cg_*): weight staging, BatchNorm folding, workspace plan and launch sequence; kernels in
+// cgan_kernels.h ----
+namespace {
+
+constexpr int kCgMaxClasses = 1 << 20;
+constexpr int kCgMaxN = 1 << 18;          // every grid and every int index of the kernels stays below 2^31
+const int kCgBn[4] = {0, 3, 6, 9};        // model.<i> of the four BatchNorms
+const int kCgUp[3] = {2, 5, 8};           // model.<i> of the three transposed convolutions
+const int kCgCin[3] = {128, 128, 64}, kCgCout[3] = {128, 64, 32};
+
+std::vector<EsrKey> cg_keys(int n_classes) {
+    std::vector<EsrKey> k;
+    const auto v = [&](const std::string& n, int c) { k.push_back({n, ESR_VEC, {c, 0, 0, 0}, 1, (size_t)c}); };
+    const auto bn = [&](int i, int c) {
+        const std::string b = "model." + std::to_string(i) + ".";
+        v(b + "weight", c);
+        v(b + "bias", c);
+        v(b + "running_mean", c);
+        v(b + "running_var", c);
+        k.push_back({b + "num_batches_tracked", ESR_COUNT, {0, 0, 0, 0}, 0, 1});
+    };
+    k.push_back({"label_emb.weight", ESR_W, {n_classes, CG_LATENT, 0, 0}, 2, (size_t)n_classes * CG_LATENT});
+    k.push_back({"l1.weight", ESR_W, {CG_FEAT, 2 * CG_LATENT, 0, 0}, 2, (size_t)CG_FEAT * 2 * CG_LATENT});
+    v("l1.bias", CG_FEAT);
+    bn(0, 128);
+    for (int u = 0; u < 3; ++u) {
+        const std::string c = "model." + std::to_string(kCgUp[u]) + ".";
+        k.push_back({c + "weight", ESR_W, {kCgCin[u], kCgCout[u], 4, 4}, 4, (size_t)kCgCin[u] * kCgCout[u] * 16});
+        v(c + "bias", kCgCout[u]);
+        bn(kCgBn[u + 1], kCgCout[u]);
+    }
+    k.push_back({"model.11.weight", ESR_W, {3, 32, 3, 3}, 4, 3 * 32 * 9});
+    v("model.11.bias", 3);
+    return k;
+}
+
+size_t cg_align64(size_t floats) { return (floats + 63) & ~(size_t)63; }
+
+struct CgPlan {
+    size_t l1, t[3], total;   // byte offsets of the C8 tensors: l1's [N,128,8,8] and the three stages' outputs
+};
+
+int cg_plan(int N, CgPlan& p) {
+    if (N < 1 || N > kCgMaxN) return CID_ERR_SHAPE;
+    size_t at = 0;
+    p.l1 = at;
+    at += align256((size_t)N * CG_FEAT * sizeof(float));
+    for (int u = 0; u < 3; ++u) {
+        p.t[u] = at;
+        at += align256((size_t)N * kCgCout[u] * (256u << (2 * u)) * sizeof(float));
+    }
+    p.total = at;
+    return CID_OK;
+}
+
+}  // namespace
+
+struct cid_cg_s {
+    int n_classes = 10;
+    std::vector<EsrKey> keys;
+    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
+    std::vector<char> have;
+    double eps[4];
+    std::vector<float> staging;
+    const float* dev_blob = nullptr;
+    std::string err;
+    // the linear, the three stages (weights, bias, s, t), the tail, the embedding table
+    size_t up_off(int u) const {
+        size_t at = cg_align64(CG_LIN_SEG);
+        for (int i = 0; i < u; ++i) at += cg_align64((size_t)16 * kCgCin[i] * kCgCout[i] + 3 * kCgCout[i]);
+        return at;
+    }
+    size_t tail_off() const { return up_off(3); }
+    size_t emb_off() const { return tail_off() + CG_TAIL_SEG; }
+    size_t blob_floats() const { return emb_off() + cg_align64((size_t)n_classes * CG_LATENT); }
+    int find(const std::string& k) const {
+        for (size_t i = 0; i < keys.size(); ++i)
+            if (keys[i].name == k) return (int)i;
+        return -1;
+    }
+};
+
+namespace {
+int cgfail(cid_cg_t h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+// The blob from the staged tensors: the kernels' weight layouts, each BatchNorm folded to y = s*v + t in fp64 as sr_pack does.
+void cg_pack(cid_cg_t h) {
+    h->staging.assign(h->blob_floats(), 0.f);
+    float* b = h->staging.data();
+    const auto get = [&](const std::string& k) -> const float* { return h->raw[h->find(k)].data(); };
+    const auto fold = [&](int which, int C, float* s_out, float* t_out) {
+        const std::string bn = "model." + std::to_string(kCgBn[which]) + ".";
+        const float *gamma = get(bn + "weight"), *beta = get(bn + "bias"), *mean = get(bn + "running_mean"), *var = get(bn + "running_var");
+        for (int ch = 0; ch < C; ++ch) {
+            const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + h->eps[which]);
+            s_out[ch] = (float)s;
+            t_out[ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
+        }
+    };
+    {   // linear: [tile][lane][52]: lane (l16, kq) holds row l16's weights of k = 4 s + kq
+        const float *w = get("l1.weight"), *bias = get("l1.bias");
+        for (int tile = 0; tile < CG_LIN_TILES; ++tile)
+            for (int row = 0; row < 16; ++row) {
+                const int j = cg_lin_feature(tile, row);
+                for (int kq = 0; kq < 4; ++kq)
+                    for (int s = 0; s < CG_LIN_STEPS; ++s)
+                        b[((size_t)tile * 64 + kq * 16 + row) * CG_LIN_LSTR + s] = w[(size_t)j * (2 * CG_LATENT) + 4 * s + kq];
+                b[CG_LIN_BIAS + tile * 16 + row] = bias[j];
+            }
+        fold(0, 128, b + CG_LIN_S, b + CG_LIN_T);
+    }
+    for (int u = 0; u < 3; ++u) {
+        float* seg = b + h->up_off(u);
+        const int CI = kCgCin[u], CO = kCgCout[u];
+        const std::string c = "model." + std::to_string(kCgUp[u]) + ".";
+        const float* w = get(c + "weight");
+        for (int ci = 0; ci < CI; ++ci)
+            for (int co = 0; co < CO; ++co)
+                for (int ky = 0; ky < 4; ++ky)
+                    for (int kx = 0; kx < 4; ++kx) seg[cg_up_windex(CO, ci, co, ky, kx)] = w[(((size_t)ci * CO + co) * 4 + ky) * 4 + kx];
+        float* tail = seg + (size_t)16 * CI * CO;
+        std::memcpy(tail, get(c + "bias"), CO * sizeof(float));
+        fold(u + 1, CO, tail + CO, tail + 2 * CO);
+    }
+    {   // tail: [ci][tap][co], then the biases
+        float* seg = b + h->tail_off();
+        const float* w = get("model.11.weight");
+        for (int co = 0; co < 3; ++co)
+            for (int ci = 0; ci < 32; ++ci)
+                for (int tap = 0; tap < 9; ++tap) seg[(ci * 9 + tap) * 3 + co] = w[((size_t)co * 32 + ci) * 9 + tap];
+        std::memcpy(seg + CG_TAIL_W, get("model.11.bias"), 3 * sizeof(float));
+    }
+    std::memcpy(b + h->emb_off(), get("label_emb.weight"), (size_t)h->n_classes * CG_LATENT * sizeof(float));
+}
+}  // namespace
+
+extern "C" {
+
+int cid_cg_create(cid_cg_t* out, int n_classes) {
+    if (!out) return CID_ERR_INVALID;
+    *out = nullptr;
+    if (n_classes < 1 || n_classes > kCgMaxClasses) return CID_ERR_INVALID;
+    cid_cg_s* h = new (std::nothrow) cid_cg_s();
+    if (!h) return CID_ERR_INVALID;
+    h->n_classes = n_classes;
+    h->keys = cg_keys(n_classes);
+    h->raw.resize(h->keys.size());
+    h->have.assign(h->keys.size(), 0);
+    std::fill(h->eps, h->eps + 4, 1e-5);
+    *out = h;
+    return CID_OK;
+}
+
+void cid_cg_destroy(cid_cg_t h) { delete h; }
+
+const char* cid_cg_last_error(cid_cg_t h) { return h ? h->err.c_str() : "null handle"; }
+
+const char* cid_cg_param_key(cid_cg_t h, int i) {
+    if (!h || i < 0 || (size_t)i >= h->keys.size()) return nullptr;
+    return h->keys[i].name.c_str();
+}
+
+int cid_cg_set_weight(cid_cg_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
+    if (!h) return CID_ERR_INVALID;
+    if (!key || !data || (!shape && ndim > 0)) return cgfail(h, CID_ERR_INVALID, "cid_cg_set_weight: null argument");
+    const int i = h->find(key);
+    if (i < 0) return cgfail(h, CID_ERR_KEY, std::string("cid_cg_set_weight: unexpected key '") + key + "'");
+    const EsrKey& k = h->keys[i];
+    if (k.kind == ESR_COUNT) {   // num_batches_tracked: part of the state_dict, unused in eval mode
+        if (ndim != 0) return cgfail(h, CID_ERR_SHAPE, "cid_cg_set_weight: size mismatch for " + k.name);
+        h->have[i] = 1;
+        return CID_OK;
+    }
+    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return cgfail(h, CID_ERR_SHAPE, "cid_cg_set_weight: size mismatch for " + k.name);
+    const float* f = static_cast<const float*>(data);
+    h->raw[i].assign(f, f + k.count);
+    h->have[i] = 1;
+    return CID_OK;
+}
+
+int cid_cg_set_bn_eps(cid_cg_t h, int which, double eps) {
+    if (!h) return CID_ERR_INVALID;
+    if (which < 0 || which > 3) return cgfail(h, CID_ERR_INVALID, "cid_cg_set_bn_eps: no such BatchNorm");
+    if (!std::isfinite(eps) || eps < 0.0) return cgfail(h, CID_ERR_INVALID, "cid_cg_set_bn_eps: eps must be finite and >= 0");
+    h->eps[which] = eps;
+    return CID_OK;
+}
+
+int cid_cg_missing_weights(cid_cg_t h, int* count) {
+    if (!h || !count) return CID_ERR_INVALID;
+    int m = 0;
+    for (size_t i = 0; i < h->keys.size(); ++i) m += h->keys[i].kind != ESR_COUNT && !h->have[i];
+    *count = m;
+    return CID_OK;
+}
+
+size_t cid_cg_packed_weights_bytes(cid_cg_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
+
+int cid_cg_upload_weights(cid_cg_t h, void* device_blob, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!device_blob) return cgfail(h, CID_ERR_INVALID, "cid_cg_upload_weights: null device pointer");
+    if ((uintptr_t)device_blob & 255) return cgfail(h, CID_ERR_WORKSPACE, "cid_cg_upload_weights: blob must be 256-byte aligned");
+    for (size_t i = 0; i < h->keys.size(); ++i)
+        if (h->keys[i].kind != ESR_COUNT && !h->have[i]) return cgfail(h, CID_ERR_STATE, "cid_cg_upload_weights: " + h->keys[i].name + " not set");
+    cg_pack(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
+    if (e != hipSuccess) return cgfail(h, CID_ERR_HIP, std::string("cid_cg_upload_weights: ") + hipGetErrorString(e));
+    h->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_cg_workspace_bytes(int N, size_t* bytes) {
+    if (!bytes) return CID_ERR_INVALID;
+    CgPlan p;
+    const int rc = cg_plan(N, p);
+    if (rc == CID_OK) *bytes = p.total;
+    return rc;
+}
+
+int cid_cg_stage_view(const char* stage, int N, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
+    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
+    CgPlan p;
+    const int rc = cg_plan(N, p);
+    if (rc != CID_OK) return rc;
+    const std::string s(stage);
+    int u = -1;
+    if (s == "l1") *offset_bytes = p.l1;
+    else if (s == "t1") u = 0;
+    else if (s == "t2") u = 1;
+    else if (s == "t3") u = 2;
+    else return CID_ERR_KEY;
+    if (u >= 0) *offset_bytes = p.t[u];
+    *C = u < 0 ? 128 : kCgCout[u];
+    *Hs = *Ws = u < 0 ? 8 : 16 << u;
+    *channel_block = 8;
+    return CID_OK;
+}
+
+int cid_cg_latent(uint64_t seed, uint64_t first_index, int N, float* z_out, void* stream) {
+    if (!z_out || ((uintptr_t)z_out & 3)) return CID_ERR_INVALID;
+    if (N < 1 || N > kCgMaxN) return CID_ERR_SHAPE;
+    const CgLatentArgs a{z_out, (long long)N * CG_LATENT, seed + first_index};
+    hipLaunchKernelGGL(k_cg_latent, dim3((unsigned)((a.count + D_THREADS - 1) / D_THREADS)), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    return hipPeekAtLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
+}
+
+int cid_cg_forward(cid_cg_t h, const float* z, const int64_t* labels, void* out, int out_fmt, int N, unsigned flags, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!z || !labels || !out || !workspace) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: null pointer");
+    if (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: unknown format");
+    if (((uintptr_t)z & 3) || ((uintptr_t)labels & 7) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
+        return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: misaligned operand");
+    if (flags & ~(unsigned)CID_CG_RAW) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: unknown flags");
+    if ((flags & CID_CG_RAW) && out_fmt != CID_FMT_F32_NCHW) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: CID_CG_RAW needs an fp32 output");
+    CgPlan p;
+    if (cg_plan(N, p) != CID_OK) return cgfail(h, CID_ERR_SHAPE, "cid_cg_forward: batch size not accepted (1 <= N <= 2^18)");
+    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
+        return cgfail(h, CID_ERR_WORKSPACE, "cid_cg_forward: workspace smaller than cid_cg_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return cgfail(h, CID_ERR_STATE, "cid_cg_forward: weights not uploaded");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto herr = [&](const char* what) { return cgfail(h, CID_ERR_HIP, std::string("cid_cg_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    char* ws = static_cast<char*>(workspace);
+    const float* blob = h->dev_blob;
+    float* l1 = reinterpret_cast<float*>(ws + p.l1);
+    float* t[3] = {reinterpret_cast<float*>(ws + p.t[0]), reinterpret_cast<float*>(ws + p.t[1]), reinterpret_cast<float*>(ws + p.t[2])};
+
+    {
+        const CgLinearArgs a{z, reinterpret_cast<const long long*>(labels), l1, blob, blob + h->emb_off(), N, h->n_classes};
+        hipLaunchKernelGGL(k_cg_linear, dim3(CG_LIN_TILES), dim3(64), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("linear");
+    }
+    {
+        const CgUpArgs a{l1, t[0], blob + h->up_off(0)};
+        hipLaunchKernelGGL((k_cg_up<128, 128, 8>), dim3((unsigned)N * CgUpGeom<128, 128, 8>::TILES), dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("up 1");
+    }
+    {
+        const CgUpArgs a{t[0], t[1], blob + h->up_off(1)};
+        hipLaunchKernelGGL((k_cg_up<128, 64, 16>), dim3((unsigned)N * CgUpGeom<128, 64, 16>::TILES), dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("up 2");
+    }
+    {
+        const CgUpArgs a{t[1], t[2], blob + h->up_off(2)};
+        hipLaunchKernelGGL((k_cg_up<64, 32, 32>), dim3((unsigned)N * CgUpGeom<64, 32, 32>::TILES), dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return herr("up 3");
+    }
+    {
+        const CgTailArgs a{t[2], out, blob + h->tail_off(), (long long)N * 4096};
+        const dim3 grid((unsigned)(a.count / D_THREADS));
+        if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_cg_tail<CG_OUT_U8>, grid, dim3(D_THREADS), 0, s, a);
+        else if (flags & CID_CG_RAW) hipLaunchKernelGGL(k_cg_tail<CG_OUT_RAW>, grid, dim3(D_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_cg_tail<CG_OUT_F32>, grid, dim3(D_THREADS), 0, s, a);
         if (hipPeekAtLastError() != hipSuccess) return herr("tail");
     }
     return CID_OK;

@@ -22,6 +22,8 @@
 
 #include <cstdint>
 
+#include "hash_streams.h"
+
 namespace cid {
 
 constexpr int NOISE_THREADS = 256;
@@ -30,10 +32,6 @@ constexpr int NOISE_MAX_GRID_Y = 65535;   // images per grid row; larger batches
 constexpr int NOISE_POISSON_KMAX = 1023;  // inversion cut-off (never reached for lambda <= 255 but by rounding)
 
 enum NoiseKind { NK_GAUSSIAN = 0, NK_SALT_PEPPER = 1, NK_SPECKLE = 2, NK_POISSON = 3, NK_UNIFORM = 4 };
-
-constexpr uint64_t fnv1a64(const char* s, uint64_t h = 0xCBF29CE484222325ull) {
-    return *s ? fnv1a64(s + 1, (h ^ (uint64_t)(unsigned char)*s) * 0x100000001B3ull) : h;
-}
 
 // stream ids: gaussian keeps synth.add_gaussian_noise's 1 and 2; the other kinds hash their names clear of them
 constexpr uint64_t NS_GAUSS_U1 = 1, NS_GAUSS_U2 = 2;
@@ -65,27 +63,9 @@ struct NoiseScatterArgs {
     uint8_t value;            // 255 salt, 0 pepper
 };
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ double unit_double(uint64_t z) {
-#pragma clang fp contract(off)
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
 // np.clip(v, 0, 255).astype(np.uint8): clip, then truncate toward zero
 __device__ __forceinline__ uint8_t clip_u8(double v) {
     return (uint8_t)(v < 0.0 ? 0 : (v > 255.0 ? 255 : (int)v));
-}
-
-// sqrt(-2*log(1-u1)) * cos((2*pi)*u2), numpy's evaluation order
-__device__ __forceinline__ double box_muller(double u1, double u2) {
-#pragma clang fp contract(off)
-    return sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
 }
 
 template <int KIND>

@@ -579,3 +579,83 @@ def make_srgan_state_dict(kind: str = "default", scale_factor: int = 4, seed: in
 def srgan_inputs_u8(n: int, h: int, w: int, first_index: int = 0) -> np.ndarray:
     """uint8 [n,h,w,3] inputs for the SRGAN tests: the noisy face-like fields of make_batch."""
     return add_gaussian_noise(clean_images_u8(n, h, w, first_index), 25.0, first_index)
+
+
+# ---- the server's CGANGenerator (backend/app.py:105-143): parameter shapes, synthetic weights and the latent's streams ----
+
+CGAN_LATENT_DIM = 100
+CGAN_Z_STREAMS = (_fnv1a64("cgan:z:u1"), _fnv1a64("cgan:z:u2"))   # u1, u2 of the latent's Box-Muller (cid_cg_latent)
+CGAN_HOT_GAIN = 14.0
+
+
+def cgan_param_shapes(n_classes: int = 10) -> "OrderedDict[str, tuple]":
+    """state_dict key -> (shape, dtype name) of CGANGenerator(n_classes), in the module's own order, BatchNorm buffers and
+    num_batches_tracked included.  ConvTranspose2d weights are [Cin, Cout, 4, 4]."""
+    if int(n_classes) < 1:
+        raise ValueError(f"n_classes must be positive (got {n_classes})")
+    out: "OrderedDict[str, tuple]" = OrderedDict()
+    f = "float32"
+
+    def bn(i, c):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            out[f"model.{i}.{k}"] = ((c,), f)
+        out[f"model.{i}.num_batches_tracked"] = ((), "int64")
+
+    out["label_emb.weight"] = ((int(n_classes), CGAN_LATENT_DIM), f)
+    out["l1.weight"] = ((8192, 2 * CGAN_LATENT_DIM), f)
+    out["l1.bias"] = ((8192,), f)
+    bn(0, 128)
+    for i, cin, cout in ((2, 128, 128), (5, 128, 64), (8, 64, 32)):
+        out[f"model.{i}.weight"] = ((cin, cout, 4, 4), f)
+        out[f"model.{i}.bias"] = ((cout,), f)
+        bn(i + 1, cout)
+    out["model.11.weight"] = ((3, 32, 3, 3), f)
+    out["model.11.bias"] = ((3,), f)
+    return out
+
+
+def make_cgan_state_dict(kind: str = "default", n_classes: int = 10, seed: int = WEIGHT_SEED) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights keyed like the reference's CGANGenerator state_dict, from the hash streams "cgan:<kind>:<key>".
+    "default" has the scale of PyTorch's initialisation: linear and convolutions U(+-1/sqrt(fan_in)) with torch's fan_in rule
+    (shape[1] * kernel area, also for ConvTranspose2d), the embedding Box-Muller N(0, 1), BatchNorm gamma 1, beta 0, running_mean 0,
+    running_var 1.  "hot": linear and convolutions U(+-sqrt(g/fan_in)) with g = CGAN_HOT_GAIN, which saturates tanh in part of the
+    output; BatchNorm gamma in [0.6, 1.4], beta in +-0.1, running_mean in +-0.3, running_var in [0.5, 1.5]."""
+    if kind not in ("default", "hot"):
+        raise ValueError(f"unknown weight set {kind!r}")
+    shapes = cgan_param_shapes(n_classes)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for key, (shape, dtype) in shapes.items():
+        if dtype == "int64":
+            sd[key] = np.array(7, dtype=np.int64)
+            continue
+        n = int(np.prod(shape))
+        stream = _fnv1a64("cgan:" + kind + ":" + key)
+        u = hash_uniform(seed, stream, n)
+        layer, leaf = key.rsplit(".", 1)
+        wshape = shapes[layer + ".weight"][0]
+        if key == "label_emb.weight":
+            v = _box_muller(u, hash_uniform(seed, _fnv1a64("cgan:" + kind + ":" + key + ":u2"), n))
+        elif len(wshape) >= 2:                                 # the linear's or a convolution's weight or bias
+            fan_in = int(np.prod(wshape[1:]))
+            bound = math.sqrt((1.0 if kind == "default" else CGAN_HOT_GAIN) / fan_in)
+            v = (2.0 * u - 1.0) * bound
+        elif kind == "default":                                # BatchNorm as constructed
+            v = np.full(n, 1.0 if leaf in ("weight", "running_var") else 0.0)
+        elif leaf == "weight":
+            v = 0.6 + 0.8 * u
+        elif leaf == "bias":
+            v = (2.0 * u - 1.0) * 0.1
+        elif leaf == "running_mean":
+            v = (2.0 * u - 1.0) * 0.3
+        else:                                                  # running_var
+            v = 0.5 + u
+        sd[key] = v.astype(np.float32).reshape(shape)
+    return sd
+
+
+def cgan_latent_np(n: int, seed: int, first_index: int = 0) -> np.ndarray:
+    """fp32 [n,100]: row i is Box-Muller in float64 of the two streams CGAN_Z_STREAMS under seed (seed + first_index + i), rounded to
+    fp32: the restatement of cid_cg_latent.  A row depends on (seed + first_index + i) alone."""
+    z = _box_muller(_image_uniforms(seed, first_index, n, CGAN_Z_STREAMS[0], CGAN_LATENT_DIM),
+                    _image_uniforms(seed, first_index, n, CGAN_Z_STREAMS[1], CGAN_LATENT_DIM))
+    return z.astype(np.float32)

@@ -715,6 +715,63 @@ int cid_sr_stage_view(const char* stage, int N, int Hp, int Wp, int scale_factor
                       int* channel_block);
 
 /*
+ * The server's fourth model — CGANGenerator(n_classes = 10, latent_dim = 100) (backend/app.py:105-143), the "cgan" branch of /enhance,
+ * label-conditioned branch (cond a 1-D integer tensor).  Eval mode, fp32; the output is always 64 x 64:
+ *
+ *   x    = cat(z [N,100], label_emb[label] [N,100])                                       label_emb
+ *   a0   = ReLU(BatchNorm(l1(x).view(N,128,8,8)))                                          l1, model.0, model.1
+ *   a_k  = ReLU(BatchNorm(ConvTranspose2d(C, C', 4, stride=2, padding=1)(a_{k-1})))        model.{2,3,4}, {5,6,7}, {8,9,10}
+ *                                                                                         128 -> 128 -> 64 -> 32 channels, 8 -> 64 pixels
+ *   out  = tanh(Conv2d(32, 3, 3, padding=1)(a_3))                                          model.11
+ *
+ * The reference hard-codes view(-1, 100, 1, 1), so latent_dim is 100 and only n_classes is a parameter.  Its image-conditioned branch
+ * (a 4-D cond, app.py:139-143) feeds 6 channels to BatchNorm2d(128) and raises for every input; it is not built.  Its own handle and
+ * blob, mirroring cid_sr_* one for one.  cid_cg_create fixes n_classes (1 .. 2^20; anything else -> CID_ERR_INVALID).
+ * cid_cg_param_key enumerates the module's 31 state_dict keys in its order; ConvTranspose2d weights are [Cin,Cout,4,4] as PyTorch
+ * stores them.  cid_cg_set_weight, cid_cg_set_bn_eps (which 0..3: model.0, model.3, model.6, model.9), cid_cg_missing_weights,
+ * cid_cg_packed_weights_bytes and cid_cg_upload_weights behave as their cid_sr_* namesakes, errors included; each BatchNorm is folded
+ * into y = fmaf(s, v, t) in fp64 at upload.  ReLU is v < 0 ? 0 : v.
+ *
+ * cid_cg_latent: the input the server draws with torch.randn(N,100,1,1) (app.py:428), from the counter-based hash streams of
+ * cid_add_noise: z_out[i, e] (fp32 [N,100], device) = (float)box_muller(u1, u2) with u1, u2 element e of the streams
+ * fnv1a64("cgan:z:u1") and fnv1a64("cgan:z:u2") under seed (seed + first_index + i), so image i's latent does not depend on the batch
+ * it is drawn in.  One launch.  CID_ERR_INVALID: null or misaligned pointer; CID_ERR_SHAPE: N outside [1, 2^18].
+ *
+ * cid_cg_forward: z is fp32 [N,100] and labels int64 [N], both on the device; out is fp32 [N,3,64,64] = tanh(.) (CID_FMT_F32_NCHW), or
+ * uint8 [N,64,64,3] (CID_FMT_U8_NHWC) as the server's view (uint8)(clamp(tanhf(v) * 0.5f + 0.5f, 0, 1) * 255.0f), a truncation
+ * (app.py:435, 472).  flags & CID_CG_RAW gives the fp32 sums before tanh instead (a testing aid).  The labels are read on the device
+ * and NOT range-checked on the host (that would need a synchronisation): a label outside [0, n_classes) never indexes out of bounds;
+ * that image's whole output is NaN (fp32) or 0 (uint8) and no other image changes.  1 + 3 + 1 launches on `stream`, no host
+ * synchronisation: the linear and the three transposed convolutions run on exact-fp32 MFMA (each transposed convolution as four 2 x 2
+ * convolutions, one per output parity), the tail on the VALU.  In the linear the images are the GEMM's columns; every sum has a fixed
+ * order: an image's result is bit-identical in any batch and at any position in it.  Checked on the host before any launch:
+ *   CID_ERR_INVALID    null pointer, unknown format, misaligned operand, unknown flags, CID_CG_RAW with a uint8 output
+ *   CID_ERR_SHAPE      N outside [1, 2^18]
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_cg_workspace_bytes(N) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_cg_stage_view (testing aid): where the last forward over N images left `stage` in its workspace: "l1" (a0, 128 channels, 8 x 8),
+ * "t1" (128, 16 x 16), "t2" (64, 32 x 32), "t3" (32, 64 x 64), all after BatchNorm and ReLU, fp32 in channel blocks of 8, laid out as
+ * cid_esr_stage_view describes.  Unknown stage -> CID_ERR_KEY.
+ */
+typedef struct cid_cg_s* cid_cg_t;
+enum { CID_CG_RAW = 1 };
+int cid_cg_create(cid_cg_t* out, int n_classes);
+void cid_cg_destroy(cid_cg_t h);
+const char* cid_cg_last_error(cid_cg_t h);
+const char* cid_cg_param_key(cid_cg_t h, int i);
+int cid_cg_set_weight(cid_cg_t h, const char* key, const void* host_data, const int64_t* shape, int ndim);
+int cid_cg_set_bn_eps(cid_cg_t h, int which, double eps);
+int cid_cg_missing_weights(cid_cg_t h, int* count);
+size_t cid_cg_packed_weights_bytes(cid_cg_t h);
+int cid_cg_upload_weights(cid_cg_t h, void* device_blob, void* stream);
+int cid_cg_workspace_bytes(int N, size_t* bytes);
+int cid_cg_latent(uint64_t seed, uint64_t first_index, int N, float* z_out, void* stream);
+int cid_cg_forward(cid_cg_t h, const float* z, const int64_t* labels, void* out, int out_fmt, int N, unsigned flags, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int cid_cg_stage_view(const char* stage, int N, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
