@@ -330,7 +330,8 @@ def test_eval_parity(kind, shape):
         assert float(ref64.min()) > 0.02 and float(ref64.max()) < 0.98
 
 
-def _check_train(kind, shape, momentum, calls=2):
+def _check_train(kind, shape, momentum, calls=2, make=images):
+    """Train-mode parity of `calls` successive calls; make(n, h, w, first_index=...) -> (u8, fp32) batches (default: images)."""
     from celebrity_image_denoiser_amd import discriminator
 
     m = _module(kind, True)
@@ -338,7 +339,7 @@ def _check_train(kind, shape, momentum, calls=2):
         m.model[i[0]].momentum = momentum
     sd = cast(weights(kind), torch.float64)
     for call in range(calls):
-        u8, x = images(*shape, first_index=sum(shape) + 31 * call)
+        u8, x = make(*shape, first_index=sum(shape) + 31 * call)
         p = m(x.to(DEV))
         torch.cuda.synchronize()
         ref = restate(sd, x.double(), True, momentum)

@@ -44,9 +44,10 @@ class _MaskedLeaky(torch.autograd.Function):
         return g * torch.where(mask, 1.0, 0.2).to(g.dtype), None
 
 
-def ref_backward(sd, x, training, target, dtype, masks=None):
-    """Gradients of BCE(D(x), target) in `dtype` on the CPU.  masks: four bool tensors for LeakyReLU's backward, or None for the
-    run's own (y > 0).  -> (param grads by state_dict key, input grad, the four pre-activations y, probabilities)"""
+def ref_backward(sd, x, training, target, dtype, masks=None, grad_prob=None):
+    """Gradients of BCE(D(x), target) in `dtype` on the CPU, or, with `grad_prob`, of sum(D(x) * grad_prob) (an upstream gradient
+    handed in as cid_disc_backward takes it; `target` is not read).  masks: four bool tensors for LeakyReLU's backward, or None
+    for the run's own (y > 0).  -> (param grads by state_dict key, input grad, the four pre-activations y, probabilities)"""
     P = {k: sd[k].to(dtype).clone().requires_grad_(True) for k in PARAMS}
     xx = x.to(dtype).clone().requires_grad_(True)
     ys = []
@@ -68,7 +69,10 @@ def ref_backward(sd, x, training, target, dtype, masks=None):
     y = act(bn(conv(y, 5), 6))
     y = act(bn(conv(y, 8, 2), 9))
     p = torch.sigmoid(F.conv2d(F.adaptive_avg_pool2d(y, 1), P["model.12.weight"], P["model.12.bias"]).view(-1))
-    F.binary_cross_entropy(p, torch.full_like(p, target)).backward()
+    if grad_prob is not None:
+        p.backward(grad_prob.to(dtype))
+    else:
+        F.binary_cross_entropy(p, torch.full_like(p, target)).backward()
     return {k: P[k].grad for k in PARAMS}, xx.grad, ys, p.detach()
 
 
@@ -312,7 +316,13 @@ PARITY_CASES = [(s, t) for t in (True, False) for s in ((16, 256, 256), (16, 128
 @pytest.mark.parametrize("loss", ("real1", "fake0"))
 def test_gradient_parity(kind, shape, training, loss):
     """BCE(D(clean), 1) and BCE(D(perturbed), 0), each on its own: all 16 parameter gradients and the input gradient."""
-    x = images(*shape, first_index=sum(shape))[1]
+    gradient_parity(kind, shape, training, loss)
+
+
+def gradient_parity(kind, shape, training, loss, x=None):
+    """One case of test_gradient_parity, on images(*shape) or on the fp32 CPU batch `x` -> (e_hip, e_aten)."""
+    if x is None:
+        x = images(*shape, first_index=sum(shape))[1]
     target = 1.0
     if loss == "fake0":
         x = (x + 0.05 * torch.sin(torch.arange(x.numel(), dtype=torch.float32).reshape(x.shape))).clamp(-1, 1)
@@ -340,6 +350,7 @@ def test_gradient_parity(kind, shape, training, loss):
     for k in PARAMS + ["input"]:
         assert all(bool(torch.isfinite(t).all()) for t in ([got[k]] if k != "input" else [gx]))
         assert e_hip[k] <= max(TOL, 2 * e_aten[k]), (k, e_hip[k], e_aten[k])
+    return e_hip, e_aten
 
 
 @pytest.mark.gpu

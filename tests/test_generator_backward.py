@@ -190,12 +190,14 @@ def stage(buf, name, n, h, w):
     return flat.view(n, hs.value, ws.value, ps.value)[..., coff.value:coff.value + c.value].permute(0, 3, 1, 2).contiguous()
 
 
-def saved_masks_and_argmax(saved, n, h, w):
-    """The nine ReLU masks and the two pool routings as cid_backward decides them, from the saved buffer (CPU tensors)."""
-    masks = [(stage(saved, s, n, h, w) > 0).cpu() for s in RELU_STAGES]
+def saved_masks_and_argmax(saved, n, h, w, idx=None):
+    """The nine ReLU masks and the two pool routings as cid_backward decides them, from the saved buffer (CPU tensors); of the
+    images `idx` (a device index tensor) only, if given."""
+    pick = (lambda t: t) if idx is None else (lambda t: t[idx])
+    masks = [(pick(stage(saved, s, n, h, w)) > 0).cpu() for s in RELU_STAGES]
     argmax = []
     for e_name, p_name in (("down1", "pool1"), ("down2", "pool2")):
-        e, p = stage(saved, e_name, n, h, w), stage(saved, p_name, n, h, w)
+        e, p = pick(stage(saved, e_name, n, h, w)), pick(stage(saved, p_name, n, h, w))
         a = torch.full(p.shape, 3, dtype=torch.int64, device=e.device)
         for k in (2, 1, 0):   # the FIRST equal element in scan order wins
             a = torch.where(e[:, :, k // 2::2, k % 2::2] == p, torch.full_like(a, k), a)
