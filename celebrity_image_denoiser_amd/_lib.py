@@ -22,6 +22,8 @@ CID_ADAM_MAX_TENSORS = 32
 CID_RESAMPLE_BICUBIC = 3
 CID_SR_RAW = 1
 CID_CG_RAW = 1
+CID_LPIPS_UNIT_VIEW = 1
+CID_LPIPS_NUM_WEIGHTS = 17
 
 
 class AdamTensor(ctypes.Structure):
@@ -168,6 +170,19 @@ SYMBOLS = {
                                   _c.c_size_t, _c.c_void_p]),
     "cid_cg_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
                                      _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "cid_lpips_create": (_c.c_int, [_c.POINTER(_c.c_void_p)]),
+    "cid_lpips_destroy": (None, [_c.c_void_p]),
+    "cid_lpips_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_lpips_param_key": (_c.c_char_p, [_c.c_void_p, _c.c_int]),
+    "cid_lpips_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_lpips_missing_weights": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int)]),
+    "cid_lpips_packed_weights_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "cid_lpips_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_lpips_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_lpips_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
+                                        _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "cid_lpips": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_uint,
+                             _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
 }
 
 _lib = None
@@ -231,6 +246,13 @@ def check_cg(handle, code: int):
     """check() for a cid_cg_t handle."""
     if code != CID_OK:
         msg = lib().cid_cg_last_error(handle) if handle else None
+        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
+
+
+def check_lpips(handle, code: int):
+    """check() for a cid_lpips_t handle."""
+    if code != CID_OK:
+        msg = lib().cid_lpips_last_error(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
 
 

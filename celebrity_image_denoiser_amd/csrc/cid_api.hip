@@ -18,6 +18,7 @@
 #include "esrgan_kernels.h"
 #include "srgan_kernels.h"
 #include "cgan_kernels.h"
+#include "lpips_kernels.h"
 
 #include <dlfcn.h>
 
@@ -3738,6 +3739,262 @@ int cid_cg_forward(cid_cg_t h, const float* z, const int64_t* labels, void* out,
         else if (flags & CID_CG_RAW) hipLaunchKernelGGL(k_cg_tail<CG_OUT_RAW>, grid, dim3(D_THREADS), 0, s, a);
         else hipLaunchKernelGGL(k_cg_tail<CG_OUT_F32>, grid, dim3(D_THREADS), 0, s, a);
         if (hipPeekAtLastError() != hipSuccess) return herr("tail");
+    }
+    return CID_OK;
+}
+
+}  // extern "C"
+
+// ---- LPIPS(net='alex') (cid_lpips_*): weight staging, workspace plan and launch sequence; kernels in lpips_kernels.h ----
+namespace {
+
+constexpr int kLpMaxN = 1 << 20;
+constexpr int kLpMinSide = 31;
+const int kLpSlice[5] = {0, 3, 6, 8, 10};            // net.slice<k+1>.<i>
+const int kLpCin[5] = {3, 64, 192, 384, 256}, kLpKs[5] = {11, 5, 3, 3, 3};
+
+std::vector<EsrKey> lp_keys() {
+    std::vector<EsrKey> k;
+    k.push_back({"scaling_layer.shift", ESR_W, {1, 3, 1, 1}, 4, 3});
+    k.push_back({"scaling_layer.scale", ESR_W, {1, 3, 1, 1}, 4, 3});
+    for (int l = 0; l < LP_TAPS; ++l) {
+        const std::string c = "net.slice" + std::to_string(l + 1) + "." + std::to_string(kLpSlice[l]) + ".";
+        const int co = lp_channels(l), ci = kLpCin[l], ks = kLpKs[l];
+        k.push_back({c + "weight", ESR_W, {co, ci, ks, ks}, 4, (size_t)co * ci * ks * ks});
+        k.push_back({c + "bias", ESR_VEC, {co, 0, 0, 0}, 1, (size_t)co});
+    }
+    for (int l = 0; l < LP_TAPS; ++l)
+        k.push_back({"lin" + std::to_string(l) + ".model.1.weight", ESR_W, {1, lp_channels(l), 1, 1}, 4, (size_t)lp_channels(l)});
+    return k;
+}
+
+const std::vector<EsrKey>& lp_key_table() {
+    static const std::vector<EsrKey> k = lp_keys();
+    return k;
+}
+
+// blob segments (floats, 64-float aligned): the head, relu2 ... relu5 (packed weights then biases), the five lin vectors
+size_t lp_conv_off(int l) {   // l = 1 .. 4; l = 5: the lin segment
+    size_t at = LP_HEAD_SEG;
+    for (int i = 1; i < l; ++i) at += cg_align64((size_t)lp_channels(i) * kLpCin[i] * kLpKs[i] * kLpKs[i] + lp_channels(i));
+    return at;
+}
+size_t lp_blob_floats() { return lp_conv_off(5) + LP_LIN_SEG; }
+
+struct LpPlan {
+    int Hs[LP_TAPS], Ws[LP_TAPS];   // sizes of relu1 ... relu5
+    size_t tap[LP_TAPS], total;     // byte offsets of the C8 tensors (2 N images each)
+};
+
+int lp_plan(int N, int H, int W, LpPlan& p) {
+    if (N < 1 || N > kLpMaxN || H < kLpMinSide || W < kLpMinSide || (long long)H * W >= (1ll << 31)) return CID_ERR_SHAPE;
+    p.Hs[0] = (H - 7) / 4 + 1, p.Ws[0] = (W - 7) / 4 + 1;
+    p.Hs[1] = (p.Hs[0] - 3) / 2 + 1, p.Ws[1] = (p.Ws[0] - 3) / 2 + 1;
+    p.Hs[2] = (p.Hs[1] - 3) / 2 + 1, p.Ws[2] = (p.Ws[1] - 3) / 2 + 1;
+    p.Hs[3] = p.Hs[4] = p.Hs[2], p.Ws[3] = p.Ws[4] = p.Ws[2];
+    // what a workgroup of the GEMM kernel stages must fit its LDS planes
+    if (lp_stage_bound(p.Hs[1], p.Ws[1], 2) > LP_XPOS || lp_stage_bound(p.Hs[2], p.Ws[2], 1) > LP_XPOS) return CID_ERR_SHAPE;
+    size_t at = 0;
+    for (int k = 0; k < LP_TAPS; ++k) {
+        p.tap[k] = at;
+        at += align256((size_t)2 * N * lp_channels(k) * p.Hs[k] * p.Ws[k] * sizeof(float));
+    }
+    p.total = at;
+    return CID_OK;
+}
+
+}  // namespace
+
+struct cid_lpips_s {
+    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
+    std::vector<char> have;
+    std::vector<float> staging;
+    const float* dev_blob = nullptr;
+    std::string err;
+};
+
+namespace {
+int lpfail(cid_lpips_t h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+int lp_find(const std::string& k) {
+    const auto& keys = lp_key_table();
+    for (size_t i = 0; i < keys.size(); ++i)
+        if (keys[i].name == k) return (int)i;
+    return -1;
+}
+
+void lp_pack(cid_lpips_t h) {
+    h->staging.assign(lp_blob_floats(), 0.f);
+    float* b = h->staging.data();
+    const auto get = [&](const std::string& k) -> const float* { return h->raw[lp_find(k)].data(); };
+    {   // head: [k][64], bias, shift, scale
+        const float *w = get("net.slice1.0.weight");
+        for (int co = 0; co < 64; ++co)
+            for (int k = 0; k < LP_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * LP_HEAD_K + k];
+        std::memcpy(b + LP_HEAD_B, get("net.slice1.0.bias"), 64 * sizeof(float));
+        std::memcpy(b + LP_HEAD_SS, get("scaling_layer.shift"), 3 * sizeof(float));
+        std::memcpy(b + LP_HEAD_SS + 4, get("scaling_layer.scale"), 3 * sizeof(float));
+    }
+    for (int l = 1; l < LP_TAPS; ++l) {
+        float* seg = b + lp_conv_off(l);
+        const int CO = lp_channels(l), CI = kLpCin[l], KS = kLpKs[l];
+        const std::string c = "net.slice" + std::to_string(l + 1) + "." + std::to_string(kLpSlice[l]) + ".";
+        const float* w = get(c + "weight");
+        for (int co = 0; co < CO; ++co)
+            for (int ci = 0; ci < CI; ++ci)
+                for (int kh = 0; kh < KS; ++kh)
+                    for (int kw = 0; kw < KS; ++kw) seg[lp_conv_windex(CI, KS, co, ci, kh, kw)] = w[(((size_t)co * CI + ci) * KS + kh) * KS + kw];
+        std::memcpy(seg + (size_t)CO * CI * KS * KS, get(c + "bias"), CO * sizeof(float));
+    }
+    for (int l = 0; l < LP_TAPS; ++l)
+        std::memcpy(b + lp_conv_off(5) + lp_lin_off(l), get("lin" + std::to_string(l) + ".model.1.weight"), lp_channels(l) * sizeof(float));
+}
+
+template <int CIN, int COUT, int KS, bool POOL>
+void lp_conv_launch(const float* in, float* out, const float* w, int N, int Hs, int Ws, int Ho, int Wo, hipStream_t s) {
+    const LpConvArgs a{in, out, w, (long long)2 * N * Ho * Wo, Hs, Ws, Ho, Wo};
+    const dim3 grid((unsigned)((a.total + LP_NT - 1) / LP_NT), COUT / LP_MT);
+    hipLaunchKernelGGL((k_lpips_conv<CIN, COUT, KS, POOL>), grid, dim3(D_THREADS), 0, s, a);
+}
+}  // namespace
+
+extern "C" {
+
+int cid_lpips_create(cid_lpips_t* out) {
+    if (!out) return CID_ERR_INVALID;
+    *out = nullptr;
+    cid_lpips_s* h = new (std::nothrow) cid_lpips_s();
+    if (!h) return CID_ERR_INVALID;
+    h->raw.resize(lp_key_table().size());
+    h->have.assign(lp_key_table().size(), 0);
+    *out = h;
+    return CID_OK;
+}
+
+void cid_lpips_destroy(cid_lpips_t h) { delete h; }
+
+const char* cid_lpips_last_error(cid_lpips_t h) { return h ? h->err.c_str() : "null handle"; }
+
+const char* cid_lpips_param_key(cid_lpips_t h, int i) {
+    if (!h || i < 0 || (size_t)i >= lp_key_table().size()) return nullptr;
+    return lp_key_table()[i].name.c_str();
+}
+
+int cid_lpips_set_weight(cid_lpips_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
+    if (!h) return CID_ERR_INVALID;
+    if (!key || !data || (!shape && ndim > 0)) return lpfail(h, CID_ERR_INVALID, "cid_lpips_set_weight: null argument");
+    const int i = lp_find(key);
+    if (i < 0) return lpfail(h, CID_ERR_KEY, std::string("cid_lpips_set_weight: unexpected key '") + key + "'");
+    const EsrKey& k = lp_key_table()[i];
+    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return lpfail(h, CID_ERR_SHAPE, "cid_lpips_set_weight: size mismatch for " + k.name);
+    const float* f = static_cast<const float*>(data);
+    h->raw[i].assign(f, f + k.count);
+    h->have[i] = 1;
+    return CID_OK;
+}
+
+int cid_lpips_missing_weights(cid_lpips_t h, int* count) {
+    if (!h || !count) return CID_ERR_INVALID;
+    int m = 0;
+    for (size_t i = 0; i < h->have.size(); ++i) m += !h->have[i];
+    *count = m;
+    return CID_OK;
+}
+
+size_t cid_lpips_packed_weights_bytes(cid_lpips_t h) { return h ? lp_blob_floats() * sizeof(float) : 0; }
+
+int cid_lpips_upload_weights(cid_lpips_t h, void* device_blob, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!device_blob) return lpfail(h, CID_ERR_INVALID, "cid_lpips_upload_weights: null device pointer");
+    if ((uintptr_t)device_blob & 255) return lpfail(h, CID_ERR_WORKSPACE, "cid_lpips_upload_weights: blob must be 256-byte aligned");
+    for (size_t i = 0; i < h->have.size(); ++i)
+        if (!h->have[i]) return lpfail(h, CID_ERR_STATE, "cid_lpips_upload_weights: " + lp_key_table()[i].name + " not set");
+    lp_pack(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
+    if (e != hipSuccess) return lpfail(h, CID_ERR_HIP, std::string("cid_lpips_upload_weights: ") + hipGetErrorString(e));
+    h->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_lpips_workspace_bytes(int N, int H, int W, size_t* bytes) {
+    if (!bytes) return CID_ERR_INVALID;
+    LpPlan p;
+    const int rc = lp_plan(N, H, W, p);
+    if (rc == CID_OK) *bytes = p.total;
+    return rc;
+}
+
+int cid_lpips_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
+    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
+    LpPlan p;
+    const int rc = lp_plan(N, H, W, p);
+    if (rc != CID_OK) return rc;
+    const std::string s(stage);
+    if (s.size() != 5 || s.compare(0, 4, "relu") != 0 || s[4] < '1' || s[4] > '5') return CID_ERR_KEY;
+    const int k = s[4] - '1';
+    *offset_bytes = p.tap[k];
+    *C = lp_channels(k);
+    *Hs = p.Hs[k];
+    *Ws = p.Ws[k];
+    *channel_block = 8;
+    return CID_OK;
+}
+
+int cid_lpips(cid_lpips_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
+              double* layers, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!a || !b || !out || !workspace) return lpfail(h, CID_ERR_INVALID, "cid_lpips: null pointer");
+    if ((fmt_a != CID_FMT_F32_NCHW && fmt_a != CID_FMT_U8_NHWC) || (fmt_b != CID_FMT_F32_NCHW && fmt_b != CID_FMT_U8_NHWC))
+        return lpfail(h, CID_ERR_INVALID, "cid_lpips: unknown format");
+    if ((fmt_a == CID_FMT_F32_NCHW && ((uintptr_t)a & 3)) || (fmt_b == CID_FMT_F32_NCHW && ((uintptr_t)b & 3)) || ((uintptr_t)out & 7) ||
+        ((uintptr_t)layers & 7))
+        return lpfail(h, CID_ERR_INVALID, "cid_lpips: misaligned operand");
+    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return lpfail(h, CID_ERR_INVALID, "cid_lpips: unknown flags");
+    LpPlan p;
+    if (lp_plan(N, H, W, p) != CID_OK)
+        return lpfail(h, CID_ERR_SHAPE, "cid_lpips: shape not accepted (1 <= N <= 2^20, H and W >= 31 and within the kernels' tile limit)");
+    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
+        return lpfail(h, CID_ERR_WORKSPACE, "cid_lpips: workspace smaller than cid_lpips_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return lpfail(h, CID_ERR_STATE, "cid_lpips: weights not uploaded");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto herr = [&](const char* what) { return lpfail(h, CID_ERR_HIP, std::string("cid_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    char* ws = static_cast<char*>(workspace);
+    const float* blob = h->dev_blob;
+    float* t[LP_TAPS];
+    for (int k = 0; k < LP_TAPS; ++k) t[k] = reinterpret_cast<float*>(ws + p.tap[k]);
+
+    for (long long n0 = 0; n0 < 2ll * N; n0 += kDiscChunk) {
+        const LpHeadArgs ha{a, b, t[0], blob, H, W, p.Hs[0], p.Ws[0], N, (int)n0, fmt_a == CID_FMT_U8_NHWC, fmt_b == CID_FMT_U8_NHWC,
+                            (flags & CID_LPIPS_UNIT_VIEW) != 0};
+        const dim3 grid((unsigned)((p.Hs[0] * p.Ws[0] + LP_HEAD_PIX - 1) / LP_HEAD_PIX), (unsigned)std::min<long long>(kDiscChunk, 2ll * N - n0));
+        hipLaunchKernelGGL(k_lpips_head, grid, dim3(LP_HEAD_PIX), 0, s, ha);
+        if (hipPeekAtLastError() != hipSuccess) return herr("head");
+    }
+    lp_conv_launch<64, 192, 5, true>(t[0], t[1], blob + lp_conv_off(1), N, p.Hs[0], p.Ws[0], p.Hs[1], p.Ws[1], s);
+    if (hipPeekAtLastError() != hipSuccess) return herr("relu2");
+    lp_conv_launch<192, 384, 3, true>(t[1], t[2], blob + lp_conv_off(2), N, p.Hs[1], p.Ws[1], p.Hs[2], p.Ws[2], s);
+    if (hipPeekAtLastError() != hipSuccess) return herr("relu3");
+    lp_conv_launch<384, 256, 3, false>(t[2], t[3], blob + lp_conv_off(3), N, p.Hs[2], p.Ws[2], p.Hs[3], p.Ws[3], s);
+    if (hipPeekAtLastError() != hipSuccess) return herr("relu4");
+    lp_conv_launch<256, 256, 3, false>(t[3], t[4], blob + lp_conv_off(4), N, p.Hs[3], p.Ws[3], p.Hs[4], p.Ws[4], s);
+    if (hipPeekAtLastError() != hipSuccess) return herr("relu5");
+    {
+        LpDistArgs da;
+        for (int k = 0; k < LP_TAPS; ++k) {
+            da.tap[k] = t[k];
+            da.P[k] = p.Hs[k] * p.Ws[k];
+        }
+        da.lin = blob + lp_conv_off(5);
+        da.out = out;
+        da.layers = layers;
+        da.N = N;
+        hipLaunchKernelGGL(k_lpips_dist, dim3((unsigned)N), dim3(D_THREADS), 0, s, da);
+        if (hipPeekAtLastError() != hipSuccess) return herr("distance");
     }
     return CID_OK;
 }

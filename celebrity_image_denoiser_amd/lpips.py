@@ -1,0 +1,250 @@
+"""LPIPS(net='alex') — the third number of the reference trainers' evaluation (training.py:282,389) — on the GPU.
+
+    LPIPS()                               nn.Module with the package's state_dict names (scaling_layer.*, net.slice*.*, lin*.*, and
+                                          the lins.* aliases); forward(in0, in1, retPerLayer=False, normalize=False) -> fp32 [N,1,1,1]
+    load_lpips(lin_ckpt, backbone=None)   -> LPIPS from a full LPIPS state dict, or from the package's lin*-only weight file together
+                                          with a torchvision AlexNet state dict
+    metrics.lpips(a, b, model)            float64 [N] on the device (metrics.py)
+
+The definition is stated once, in the header comment of include/cid.h (cid_lpips).  Everything numeric runs in HIP kernels behind
+cid_lpips_*; there is no CPU fallback.  No weights ship with this package: synth.make_lpips_state_dict draws portable synthetic
+ones, and INTEGRATION.md says how to obtain and pass the real ones.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Mapping, Optional, Union
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+CHANNELS = (64, 192, 384, 256, 256)
+MIN_SIDE = 31
+# net.slice<k+1>.<index>: torchvision's alexnet.features indices of the five convolutions
+_CONVS = ((1, 0, 3, 64, 11, 4, 2), (2, 3, 64, 192, 5, 1, 2), (3, 6, 192, 384, 3, 1, 1), (4, 8, 384, 256, 3, 1, 1),
+          (5, 10, 256, 256, 3, 1, 1))
+
+
+class _ScalingLayer(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.register_buffer("shift", torch.tensor([-.030, -.088, -.188])[None, :, None, None])
+        self.register_buffer("scale", torch.tensor([.458, .448, .450])[None, :, None, None])
+
+
+class _LinLayer(nn.Module):
+    def __init__(self, chn_in: int):
+        super().__init__()
+        self.model = nn.Sequential(nn.Dropout(), nn.Conv2d(chn_in, 1, 1, stride=1, padding=0, bias=False))
+
+
+def operand(x, what: str = "lpips"):
+    """(CID format, (N, H, W)) of an fp32 [N,3,H,W] or uint8 [N,H,W,3] tensor."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise RuntimeError(f"{what}() expects 4-d torch tensors: float32 [N,3,H,W] or uint8 [N,H,W,3]")
+    if x.dtype == torch.float32 and x.shape[1] == 3:
+        return _lib.CID_FMT_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
+    if x.dtype == torch.uint8 and x.shape[3] == 3:
+        return _lib.CID_FMT_U8_NHWC, (x.shape[0], x.shape[1], x.shape[2])
+    raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3], got {x.dtype} {list(x.shape)}")
+
+
+class LPIPS(nn.Module):
+    """lpips.LPIPS(net='alex') as a parameter container plus the HIP forward.  `scaling_layer`, `net`, `lin0` ... `lin4` and `lins`
+    are stock layers, so state_dict keys, .to() and load_state_dict() behave as in the package.  Eval mode only (dropout is inert).
+    Asynchronous on the current stream, without autograd history.  Weight changes are found by the tensors' version counters and
+    repacked at the next call (after writes through `.data` call pack_weights(force=True))."""
+
+    def __init__(self):
+        super().__init__()
+        self.scaling_layer = _ScalingLayer()
+        self.net = nn.Module()
+        for k, idx, cin, cout, ks, stride, pad in _CONVS:
+            seq = nn.Sequential()
+            seq.add_module(str(idx), nn.Conv2d(cin, cout, ks, stride=stride, padding=pad))
+            self.net.add_module(f"slice{k}", seq)
+        for k, c in enumerate(CHANNELS):
+            setattr(self, f"lin{k}", _LinLayer(c))
+        self.lins = nn.ModuleList([getattr(self, f"lin{k}") for k in range(5)])
+        for p in self.parameters():
+            p.requires_grad_(False)
+        self.eval()
+        self._cid = ctypes.c_void_p()
+        _lib.check_lpips(None, _lib.lib().cid_lpips_create(ctypes.byref(self._cid)))
+        self._blob = None          # packed weights on the device (uint8 tensor, owns the memory)
+        self._packed_sig = None
+        self._ws = None            # workspace (uint8 tensor, grow-only)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_cid", None):
+                _lib.lib().cid_lpips_destroy(self._cid)
+                self._cid = None
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ weights
+    def _device(self) -> torch.device:
+        return next(self.parameters()).device
+
+    def _tensors(self):
+        return [(k, t) for k, t in self.state_dict(keep_vars=True).items() if not k.startswith("lins.")]
+
+    def _signature(self):
+        return tuple((k, t.data_ptr(), t._version, str(t.device)) for k, t in self._tensors())
+
+    def pack_weights(self, force: bool = False) -> torch.Tensor:
+        """Pack the state_dict into the kernels' layout on the module's GPU (if anything changed since the last call)."""
+        sig = self._signature()
+        if not force and self._blob is not None and sig == self._packed_sig:
+            return self._blob
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("LPIPS runs only on an AMD GPU (HIP kernels behind libcid.so); move it with .to('cuda') first. "
+                               "There is no CPU fallback.")
+        L = _lib.lib()
+        for key, t in self._tensors():
+            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+            shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+            _lib.check_lpips(self._cid, L.cid_lpips_set_weight(self._cid, key.encode(), a.ctypes.data, shape, a.ndim))
+        blob = torch.empty(L.cid_lpips_packed_weights_bytes(self._cid), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check_lpips(self._cid, L.cid_lpips_upload_weights(self._cid, blob.data_ptr(), stream))
+        self._blob, self._packed_sig = blob, sig
+        return blob
+
+    # ------------------------------------------------------------------ forward
+    def _ensure_workspace(self, n: int, h: int, w: int, device: torch.device) -> None:
+        need = ctypes.c_size_t()
+        rc = _lib.lib().cid_lpips_workspace_bytes(n, h, w, ctypes.byref(need))
+        if rc == 2:   # CID_ERR_SHAPE
+            raise ValueError(f"image size {h}x{w} (N={n}) not accepted: LPIPS needs H, W >= {MIN_SIDE} (AlexNet's maps 7 -> 3 -> 1) "
+                             "and sides of at most 1024")
+        _lib.check_lpips(self._cid, rc)
+        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
+            if self._ws is not None:
+                torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
+            self._ws = None
+            self._ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+
+    def distances(self, a: torch.Tensor, b: torch.Tensor, unit_view: bool = False, per_layer: bool = False):
+        """cid_lpips on the current stream: float64 [N] on the device, with per_layer also float64 [N,5] = d_0 ... d_4.  Each operand
+        is float32 [N,3,H,W] or uint8 [N,H,W,3] (read as (u/255-0.5)/0.5); unit_view applies v*0.5+0.5 to both (the trainers' call)."""
+        if self.training:
+            raise RuntimeError("LPIPS is in train mode: the metric is defined in eval mode (dropout inert); call .eval()")
+        fa, shape_a = operand(a)
+        fb, shape_b = operand(b)
+        if shape_a != shape_b:
+            raise ValueError("Input images must have the same dimensions.")
+        if not (a.is_cuda and b.is_cuda):
+            raise RuntimeError("got a CPU tensor: LPIPS is GPU-only (hand-written HIP kernels); there is no CPU fallback")
+        dev = self._device()
+        if a.device != dev or b.device != dev:
+            raise RuntimeError(f"operands on {a.device} and {b.device} but module parameters on {dev}")
+        n, h, w = shape_a
+        if n < 1:
+            raise RuntimeError(f"empty input {list(a.shape)}")
+        self._ensure_workspace(n, h, w, dev)
+        self.pack_weights()
+        a, b = a.contiguous(), b.contiguous()
+        out = torch.empty((n,), dtype=torch.float64, device=dev)
+        layers = torch.empty((n, 5), dtype=torch.float64, device=dev) if per_layer else None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check_lpips(self._cid, _lib.lib().cid_lpips(
+                self._cid, a.data_ptr(), fa, b.data_ptr(), fb, n, h, w, _lib.CID_LPIPS_UNIT_VIEW if unit_view else 0, out.data_ptr(),
+                layers.data_ptr() if per_layer else None, self._ws.data_ptr(), self._ws.numel(), stream))
+        return (out, layers) if per_layer else out
+
+    def forward(self, in0: torch.Tensor, in1: torch.Tensor, retPerLayer: bool = False, normalize: bool = False):
+        """The package's call: fp32 [N,1,1,1]; with retPerLayer also the list of the five layer tensors ([N,1,1,1] each).
+        normalize=True takes [0,1] inputs (2*x - 1 first): an fp32 copy is made, since the kernels' own input view is the opposite
+        one."""
+        if normalize:
+            in0, in1 = (2.0 * t - 1.0 if t.dtype == torch.float32 else t for t in (in0, in1))
+            if in0.dtype != torch.float32 or in1.dtype != torch.float32:
+                raise RuntimeError("normalize=True needs float32 operands in [0,1]")
+        if retPerLayer:
+            d, layers = self.distances(in0, in1, per_layer=True)
+            return d.to(torch.float32).view(-1, 1, 1, 1), [layers[:, k].to(torch.float32).view(-1, 1, 1, 1) for k in range(5)]
+        return self.distances(in0, in1).to(torch.float32).view(-1, 1, 1, 1)
+
+    def stage(self, name: str, n: int, h: int, w: int) -> torch.Tensor:
+        """What the last call over n pairs of h x w images left in the workspace, as fp32 [2 n,C,Hs,Ws] (a copy): "relu1" ... "relu5";
+        operand a's n images, then operand b's (cid_lpips_stage_view)."""
+        off, c, hs, ws, cb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = _lib.lib().cid_lpips_stage_view(name.encode(), n, h, w, ctypes.byref(off), ctypes.byref(c), ctypes.byref(hs),
+                                             ctypes.byref(ws), ctypes.byref(cb))
+        if rc != _lib.CID_OK:
+            raise KeyError(f"no stored stage {name!r} for {n} pairs of {h}x{w} (cid_lpips_stage_view -> {rc})")
+        count = 2 * n * c.value * hs.value * ws.value
+        t = self._ws[off.value:off.value + 4 * count].view(torch.float32)
+        t = t.view(2 * n, c.value // cb.value, hs.value, ws.value, cb.value).permute(0, 1, 4, 2, 3)
+        return t.reshape(2 * n, c.value, hs.value, ws.value).clone()
+
+
+_FEATURES = {f"features.{idx}.": f"net.slice{k}.{idx}." for k, idx, *_ in _CONVS}
+
+
+def lpips_state_dict(lin_sd: Mapping, backbone_sd: Optional[Mapping] = None) -> dict:
+    """The module's state dict from either layout: a full LPIPS state dict, or the package's lin*-only file plus a torchvision
+    AlexNet state dict (features.N.* -> net.sliceK.N.*, classifier.* dropped).  "module." prefixes are stripped; lins.* aliases are
+    filled from lin* (or the other way round)."""
+    from .api import extract_state_dict
+
+    out = {}
+    for k, v in extract_state_dict(lin_sd).items():
+        out[k] = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+    if backbone_sd is not None:
+        for k, v in extract_state_dict(backbone_sd).items():
+            if k.startswith("classifier."):
+                continue
+            for old, new in _FEATURES.items():
+                if k.startswith(old):
+                    out[new + k[len(old):]] = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+                    break
+            else:
+                raise KeyError(f"unexpected key {k!r} in the AlexNet state dict (expected features.{{0,3,6,8,10}}.* and classifier.*)")
+    for k in range(5):
+        a, b = f"lin{k}.model.1.weight", f"lins.{k}.model.1.weight"
+        if a in out and b not in out:
+            out[b] = out[a]
+        elif b in out and a not in out:
+            out[a] = out[b]
+    return out
+
+
+def load_lpips(lin_ckpt: Union[str, Mapping], backbone: Union[str, Mapping, None] = None,
+               device: Optional[Union[str, torch.device]] = None, strict: bool = True) -> LPIPS:
+    """Build an LPIPS on `device` (default: current GPU).  `lin_ckpt` is a full LPIPS state dict, or the package's weight file
+    (lin* keys only) with `backbone` a torchvision AlexNet state dict; each a path (read with the torch-free reader) or a mapping.
+    The module's own shift / scale buffers stand in when a file leaves them out.  strict=True raises for any other missing or
+    unexpected key, as load_state_dict does."""
+    from .api import _read_checkpoint_file
+
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError("celebrity_image_denoiser_amd.load_lpips: an AMD GPU is required (no CPU fallback)")
+    model = build_lpips(lin_ckpt, backbone, strict, _read_checkpoint_file)
+    model.to(device).eval()
+    model.pack_weights()
+    return model
+
+
+def build_lpips(lin_ckpt, backbone=None, strict: bool = True, reader=None) -> LPIPS:
+    """load_lpips without the move to the GPU: the module on the CPU, weights loaded (the loader's key handling, testable anywhere)."""
+    if reader is None:
+        from .api import _read_checkpoint_file as reader
+    lin_sd = reader(lin_ckpt) if isinstance(lin_ckpt, str) else lin_ckpt
+    back_sd = reader(backbone) if isinstance(backbone, str) else backbone
+    sd = lpips_state_dict(lin_sd, back_sd)
+    model = LPIPS()
+    for k, v in model.scaling_layer.state_dict(prefix="scaling_layer.").items():
+        sd.setdefault(k, v)
+    model.load_state_dict(sd, strict=strict)
+    return model

@@ -99,14 +99,33 @@ def quality(a, b, metrics=("psnr", "ssim", "ms_ssim")):
     return {m: out[:, _COLUMNS[m]].contiguous() for m in names}
 
 
-def evaluate(denoised_hr, clean_hr, ms_ssim: bool = True):
-    """Drop-in for the reference's DenoiseGANTrainer.evaluate (training.py:378-392): (psnr, ssim, lpips, msssim) as Python
-    floats, batch means of the per-image values, after one device-to-host copy of N x 3 doubles.
+def lpips(a, b, model, unit_view: bool = False):
+    """Per-image LPIPS(net='alex') of two device batches under `model` (lpips.LPIPS), computed by HIP kernels (cid_lpips,
+    include/cid.h): float64 tensor [N] on the inputs' GPU.  Operands as in quality(): float32 [N,3,H,W] in [-1,1] or uint8
+    [N,H,W,3] (read as (u/255-0.5)/0.5), each its own format.  unit_view=True feeds x*0.5+0.5 instead, as the reference trainers do
+    (training.py:389).  H, W >= 31, else ValueError."""
+    from .lpips import LPIPS
 
-    lpips is always 0.0: LPIPS needs pretrained AlexNet weights and is not computed; 0.0 is the value the trainer itself reports
-    when its LPIPS model is unavailable (training.py:284-287,385).  With ms_ssim=False msssim is 0.0 as well; with ms_ssim=True
-    images of min(H, W) <= 160 raise ValueError (pytorch_msssim's size assertion)."""
+    if not isinstance(model, LPIPS):
+        raise TypeError("lpips() needs a celebrity_image_denoiser_amd.lpips.LPIPS model (load_lpips)")
+    return model.distances(a, b, unit_view=unit_view)
+
+
+_lpips = lpips   # evaluate() has a parameter of that name
+
+
+def evaluate(denoised_hr, clean_hr, ms_ssim: bool = True, lpips=None):
+    """Drop-in for the reference's DenoiseGANTrainer.evaluate (training.py:378-392): (psnr, ssim, lpips, msssim) as Python
+    floats, batch means of the per-image values, after one device-to-host copy of N x 3 doubles (and N more with LPIPS).
+
+    `lpips` is an lpips.LPIPS model (load_lpips): the third value is then the batch mean of the trainer's own call, the model on
+    x*0.5+0.5 (training.py:389).  Without a model it is 0.0, the value the trainer itself reports when its LPIPS model is
+    unavailable (training.py:284-287,385).  With ms_ssim=False msssim is 0.0 as well; with ms_ssim=True images of
+    min(H, W) <= 160 raise ValueError (pytorch_msssim's size assertion)."""
     metrics = ("psnr", "ssim", "ms_ssim") if ms_ssim else ("psnr", "ssim")
     out, _ = _quality_table(denoised_hr, clean_hr, metrics)
+    lp = 0.0
+    if lpips is not None:
+        lp = float(_lpips(denoised_hr, clean_hr, lpips, unit_view=True).cpu().numpy().mean())
     means = out.cpu().numpy().mean(axis=0)
-    return float(means[0]), float(means[1]), 0.0, float(means[2]) if ms_ssim else 0.0
+    return float(means[0]), float(means[1]), lp, float(means[2]) if ms_ssim else 0.0

@@ -63,7 +63,7 @@ def add_noise(clean_u8, kind: str, *, seed: int = synth.NOISE_SEED, first_index:
 
 
 def evaluate_noise_types(model, clean_u8, kinds=NOISE_TYPES, seed: int = synth.NOISE_SEED, first_index: int = 0,
-                         max_batch: int = None, discriminator=None) -> dict:
+                         max_batch: int = None, discriminator=None, lpips=None) -> dict:
     """How well `model` denoises each noise kind, all on the GPU: per kind, add_noise -> model.forward_u8(noisy, out_u8=False) ->
     metrics.quality(denoised, clean_u8), plus metrics.quality(noisy, clean_u8) for the input's own PSNR.
 
@@ -74,7 +74,10 @@ def evaluate_noise_types(model, clean_u8, kinds=NOISE_TYPES, seed: int = synth.N
 
     With a `discriminator` (discriminator.DenoiseDiscriminator), each kind's dict also holds "d_loss" and "g_loss": the trainer's
     two per-epoch numbers (training.py:455) from discriminator.trainer_losses(discriminator, denoised, clean), here per noise kind
-    on held-out images; with max_batch they are averaged over the chunks weighted by chunk size."""
+    on held-out images; with max_batch they are averaged over the chunks weighted by chunk size.
+
+    With an `lpips` model (lpips.LPIPS), each kind's dict also holds "lpips": the batch mean of the trainer's call on the denoised and
+    the clean images (metrics.lpips(..., unit_view=True), training.py:389)."""
     import numpy as np
     import torch
 
@@ -98,7 +101,7 @@ def evaluate_noise_types(model, clean_u8, kinds=NOISE_TYPES, seed: int = synth.N
         from .discriminator import trainer_losses
     result = {}
     for kind in kinds:
-        vals = {m: [] for m in ("psnr_noisy",) + names}
+        vals = {m: [] for m in ("psnr_noisy",) + names + (("lpips",) if lpips is not None else ())}
         losses = {"d_loss": 0.0, "g_loss": 0.0}
         for i0 in range(0, n, step):
             clean = clean_u8[i0:i0 + step]
@@ -108,6 +111,8 @@ def evaluate_noise_types(model, clean_u8, kinds=NOISE_TYPES, seed: int = synth.N
             vals["psnr_noisy"].append(metrics.quality(noisy, clean, ("psnr",))["psnr"].cpu().numpy())
             for m in names:
                 vals[m].append(q[m].cpu().numpy())
+            if lpips is not None:
+                vals["lpips"].append(metrics.lpips(denoised, clean, lpips, unit_view=True).cpu().numpy())
             if discriminator is not None:
                 lo = trainer_losses(discriminator, denoised, clean)
                 for m in losses:

@@ -659,3 +659,56 @@ def cgan_latent_np(n: int, seed: int, first_index: int = 0) -> np.ndarray:
     z = _box_muller(_image_uniforms(seed, first_index, n, CGAN_Z_STREAMS[0], CGAN_LATENT_DIM),
                     _image_uniforms(seed, first_index, n, CGAN_Z_STREAMS[1], CGAN_LATENT_DIM))
     return z.astype(np.float32)
+
+
+# ---- LPIPS(net='alex') (include/cid.h, cid_lpips): portable synthetic weights ----
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)
+LPIPS_SHIFT = (-.030, -.088, -.188)
+LPIPS_SCALE = (.458, .448, .450)
+
+
+def lpips_param_shapes() -> "OrderedDict[str, tuple]":
+    """state_dict key -> shape of lpips.LPIPS(net='alex') in the module's own order, the lins.* aliases of lin* last."""
+    out: "OrderedDict[str, tuple]" = OrderedDict()
+    out["scaling_layer.shift"] = (1, 3, 1, 1)
+    out["scaling_layer.scale"] = (1, 3, 1, 1)
+    for k, idx, cin, cout, ks in ((1, 0, 3, 64, 11), (2, 3, 64, 192, 5), (3, 6, 192, 384, 3), (4, 8, 384, 256, 3), (5, 10, 256, 256, 3)):
+        out[f"net.slice{k}.{idx}.weight"] = (cout, cin, ks, ks)
+        out[f"net.slice{k}.{idx}.bias"] = (cout,)
+    for k, c in enumerate(LPIPS_CHANNELS):
+        out[f"lin{k}.model.1.weight"] = (1, c, 1, 1)
+    for k, c in enumerate(LPIPS_CHANNELS):
+        out[f"lins.{k}.model.1.weight"] = (1, c, 1, 1)
+    return out
+
+
+def make_lpips_state_dict(kind: str = "default", seed: int = WEIGHT_SEED) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights keyed like lpips.LPIPS(net='alex'), from the hash streams "lpips:<kind>:<key>".  No pretrained weights ship
+    with this package; these keep the activations alive through the five ReLUs so that every tap carries signal.
+    Convolutions are He-uniform, U(+-sqrt(6 / fan_in)); biases U(+-0.05) ("default") or U(+-0.5) ("hot", which also doubles the
+    weights' gain: larger, sparser activations).  lin weights are non-negative, u / sum(u) * (1 + 0.25 (2 v - 1)) per layer: they sum
+    to about 1.  shift / scale are the package's constants.  lins.* repeat lin*."""
+    if kind not in ("default", "hot"):
+        raise ValueError(f"unknown weight set {kind!r}")
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for key, shape in lpips_param_shapes().items():
+        n = int(np.prod(shape))
+        if key == "scaling_layer.shift":
+            v = np.array(LPIPS_SHIFT)
+        elif key == "scaling_layer.scale":
+            v = np.array(LPIPS_SCALE)
+        elif key.startswith("lins."):
+            sd[key] = sd["lin" + key[len("lins."):]]
+            continue
+        else:
+            u = hash_uniform(seed, _fnv1a64("lpips:" + kind + ":" + key), n)
+            if key.startswith("lin"):
+                g = hash_uniform(seed, _fnv1a64("lpips:" + kind + ":" + key + ":gain"), 1)[0]
+                v = u / u.sum() * (1.0 + 0.25 * (2.0 * g - 1.0))
+            elif key.endswith(".weight"):
+                fan_in = shape[1] * shape[2] * shape[3]
+                v = (2.0 * u - 1.0) * math.sqrt((6.0 if kind == "default" else 12.0) / fan_in)
+            else:
+                v = (2.0 * u - 1.0) * (0.05 if kind == "default" else 0.5)
+        sd[key] = v.astype(np.float32).reshape(shape)
+    return sd

@@ -299,8 +299,8 @@ int cid_broadcast_weights(cid_handle_t h, void* comm, int root, int rank, void* 
 
 /*
  * Image-quality metrics of denoised batches — the reference denoise trainer's evaluation, DenoiseGANTrainer.evaluate
- * (backend/trainingcode/denoise_gan_code/training.py:378-392, once per batch at :432), on device tensors.  LPIPS (:282) is not
- * provided: it needs pretrained AlexNet weights.  No handle: no weights are involved.
+ * (backend/trainingcode/denoise_gan_code/training.py:378-392, once per batch at :432), on device tensors.  LPIPS (:282) has weights
+ * and therefore its own handle: cid_lpips below.  No handle here: no weights are involved.
  *
  * For each image pair (a, b) of a batch (3 channels, H x W), three per-image values:
  *   PSNR     skimage peak_signal_noise_ratio(a, b, data_range=2.0) on float32 inputs (training.py:380): d = a - b and d*d in fp32,
@@ -770,6 +770,74 @@ int cid_cg_latent(uint64_t seed, uint64_t first_index, int N, float* z_out, void
 int cid_cg_forward(cid_cg_t h, const float* z, const int64_t* labels, void* out, int out_fmt, int N, unsigned flags, void* workspace,
                    size_t workspace_bytes, void* stream);
 int cid_cg_stage_view(const char* stage, int N, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block);
+
+/*
+ * LPIPS — lpips.LPIPS(net='alex') of lpips 0.1.4 (version='0.1', lpips=True, spatial=False, eval mode), the third number of the
+ * reference trainers' evaluation (denoise_gan_code/training.py:282,389; srgan_code/sr_ganTrainGNew.py:264,372;
+ * cgan_code/training5barrev.py:20,140).  THE DEFINITION (kept here and nowhere else):
+ *
+ *   1. forward(in0, in1, normalize=False): with normalize=True each input becomes 2*x - 1 first.  Inputs are meant to lie in [-1,1].
+ *   2. Scaling layer: (x - shift) / scale per channel, shift = (-.030, -.088, -.188), scale = (.458, .448, .450).  The zero padding of
+ *      the first convolution applies to the SCALED tensor: a padded position is 0, not (0 - shift) / scale.
+ *   3. torchvision AlexNet `features`, five taps, each taken after a ReLU:
+ *        relu1  Conv2d(3,64,11,stride 4,pad 2) + ReLU
+ *        relu2  MaxPool2d(3,2) -> Conv2d(64,192,5,pad 2) + ReLU
+ *        relu3  MaxPool2d(3,2) -> Conv2d(192,384,3,pad 1) + ReLU
+ *        relu4  Conv2d(384,256,3,pad 1) + ReLU
+ *        relu5  Conv2d(256,256,3,pad 1) + ReLU
+ *      Pools have no padding and use floor mode: H1 = (H-7)/4 + 1, H2 = (H1-3)/2 + 1, H3 = (H2-3)/2 + 1 (integer division; the same
+ *      for W); relu3, relu4 and relu5 are H3 x W3.  The smallest accepted side is 31 (maps 7 -> 3 -> 1).
+ *   4. Per tap k and tower: xhat = x / (sqrt(sum_c x^2) + 1e-10) per pixel.
+ *   5. Layer distance d_k = mean over pixels of sum_c w_k[c] * (xhat0 - xhat1)^2; w_k is the 1x1 `lin` convolution (no bias, no
+ *      clamp, dropout inert in eval mode).
+ *   6. d = d_0 + ... + d_4, one value per image pair (the package returns it as fp32 [N,1,1,1]).
+ *
+ * The three trainers call it on x*0.5+0.5 with normalize=False, so the network sees [0,1] images where it expects [-1,1];
+ * CID_LPIPS_UNIT_VIEW reproduces that call (v*0.5f+0.5f on both operands before the scaling layer) and does not correct it.
+ *
+ * State-dict names (cid_lpips_param_key order, 17 tensors, fp32): scaling_layer.shift, scaling_layer.scale ([1,3,1,1]);
+ * net.slice1.0, net.slice2.3, net.slice3.6, net.slice4.8, net.slice5.10 .weight / .bias ([Cout,Cin,k,k] / [Cout]);
+ * lin0.model.1.weight ... lin4.model.1.weight ([1,C,1,1], C = 64, 192, 384, 256, 256).  The module repeats the five lin tensors
+ * under lins.<k>.model.1.weight; those aliases are the caller's to drop.  The package's weight file holds only the lin* keys, the
+ * backbone is torchvision's alexnet state dict (features.{0,3,6,8,10}.*).
+ *
+ * Its own handle and blob, mirroring cid_cg_* one for one: cid_lpips_set_weight (CID_ERR_KEY for any other name, CID_ERR_SHAPE for a
+ * size mismatch), cid_lpips_missing_weights, cid_lpips_packed_weights_bytes and cid_lpips_upload_weights (needs all 17 tensors,
+ * CID_ERR_STATE otherwise) behave as their namesakes.
+ *
+ * cid_lpips: a and b are fp32 [N,3,H,W] (CID_FMT_F32_NCHW, read as they are) or uint8 [N,H,W,3] (CID_FMT_U8_NHWC, read as
+ * (u/255 - 0.5)/0.5 like cid_quality: a uint8 image and its normalised fp32 copy give identical bits), each its own format.
+ * out is device double [N]; layers, if not NULL, device double [N][5] = d_0 ... d_4.  Both towers run as one batch of 2 N images:
+ * 1 + 4 + 1 launches on `stream`, no host synchronisation.  relu1 is computed on the VALU, relu2 ... relu5 on the exact-fp32 MFMA with
+ * the max-pools taken while the operand is staged (no pooled tensor exists); from the stored fp32 taps on, everything (channel sums
+ * of squares, sqrt, + 1e-10, the divisions, the weighted squared differences, the pixel mean, the layer sum) is double in a fixed
+ * order, so the distance's only error is the taps'.  No atomics; every sum's order depends on (H, W) and the pixel alone: an image
+ * pair's result is bit-identical in any batch and at any position in it, d(x, x) is exactly 0 and d(a, b) == d(b, a) bit for bit.
+ * Checked on the host before any launch:
+ *   CID_ERR_INVALID    null pointer (layers may be NULL), unknown format, misaligned fp32 operand / out / layers, unknown flags
+ *   CID_ERR_SHAPE      N outside [1, 2^20], H or W < 31, H*W >= 2^31, or a map too wide for the convolution kernel's LDS tile
+ *                      (sides up to 1024 are accepted)
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_lpips_workspace_bytes(N, H, W) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_lpips_stage_view (testing aid): where the last call over N pairs left `stage` = "relu1" ... "relu5" in its workspace: fp32 in
+ * channel blocks of 8 as cid_esr_stage_view describes, 2 N images (operand a's N, then operand b's N).  Unknown stage -> CID_ERR_KEY.
+ */
+typedef struct cid_lpips_s* cid_lpips_t;
+enum { CID_LPIPS_UNIT_VIEW = 1 };
+#define CID_LPIPS_NUM_WEIGHTS 17
+int cid_lpips_create(cid_lpips_t* out);
+void cid_lpips_destroy(cid_lpips_t h);
+const char* cid_lpips_last_error(cid_lpips_t h);
+const char* cid_lpips_param_key(cid_lpips_t h, int i);
+int cid_lpips_set_weight(cid_lpips_t h, const char* key, const void* host_data, const int64_t* shape, int ndim);
+int cid_lpips_missing_weights(cid_lpips_t h, int* count);
+size_t cid_lpips_packed_weights_bytes(cid_lpips_t h);
+int cid_lpips_upload_weights(cid_lpips_t h, void* device_blob, void* stream);
+int cid_lpips_workspace_bytes(int N, int H, int W, size_t* bytes);
+int cid_lpips_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block);
+int cid_lpips(cid_lpips_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
+              double* layers, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
