@@ -25,8 +25,11 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     CGANGenerator(n_classes=10) / load_cgan(ckpt)          the server's class-conditional cGAN model (eval mode): latent(n, seed) draws
                                   its input on the device, generate(model, labels, seed=s) -> fp32 [N,3,64,64], generate_u8 -> the
                                   server's uint8 view
-    LPIPS() / load_lpips(lin_ckpt, backbone)               lpips.LPIPS(net='alex'), the trainers' third metric: metrics.lpips(a, b, model)
-                                  -> float64 [N]; evaluate(denoised, clean, lpips=model) fills the third value
+    LPIPS(net) / load_lpips(lin_ckpt, backbone, net=net)   lpips.LPIPS(net='alex'), the trainers' third metric, or net='vgg', the ESRGAN
+                                  trainer's: metrics.lpips(a, b, model) -> float64 [N]; evaluate(denoised, clean, lpips=model) fills
+                                  the third value
+    VGGPerceptualLoss() / load_vgg_loss(backbone)          the SRGAN and denoise trainers' content loss, MSE of vgg16.features[:16]
+                                  (forward value only, no autograd history)
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.
@@ -68,6 +71,8 @@ _LAZY = {
     "generate_u8": ("cgan", "generate_u8"),
     "LPIPS": ("lpips", "LPIPS"),
     "load_lpips": ("lpips", "load_lpips"),
+    "VGGPerceptualLoss": ("lpips", "VGGPerceptualLoss"),
+    "load_vgg_loss": ("lpips", "load_vgg_loss"),
     "HostPipeline": ("pipeline", "HostPipeline"),
     "denoise_host_batches": ("pipeline", "denoise_host_batches"),
     "GraphedForward": ("pipeline", "GraphedForward"),

@@ -24,6 +24,9 @@ CID_SR_RAW = 1
 CID_CG_RAW = 1
 CID_LPIPS_UNIT_VIEW = 1
 CID_LPIPS_NUM_WEIGHTS = 17
+CID_VGG_LPIPS, CID_VGG_CONTENT = 0, 1
+CID_VGG_NUM_WEIGHTS = 33
+CID_VGG_MAX_SIDE = 512
 
 
 class AdamTensor(ctypes.Structure):
@@ -183,6 +186,21 @@ SYMBOLS = {
                                         _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "cid_lpips": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_uint,
                              _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_vgg_create": (_c.c_int, [_c.POINTER(_c.c_void_p)]),
+    "cid_vgg_destroy": (None, [_c.c_void_p]),
+    "cid_vgg_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_vgg_param_key": (_c.c_char_p, [_c.c_void_p, _c.c_int]),
+    "cid_vgg_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_vgg_missing_weights": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int)]),
+    "cid_vgg_packed_weights_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "cid_vgg_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_vgg_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_vgg_stage_view": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
+                                      _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "cid_vgg_lpips": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_uint,
+                                 _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_vgg_content_loss": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_uint,
+                                        _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
 }
 
 _lib = None
@@ -253,6 +271,13 @@ def check_lpips(handle, code: int):
     """check() for a cid_lpips_t handle."""
     if code != CID_OK:
         msg = lib().cid_lpips_last_error(handle) if handle else None
+        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
+
+
+def check_vgg(handle, code: int):
+    """check() for a cid_vgg_t handle."""
+    if code != CID_OK:
+        msg = lib().cid_vgg_last_error(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
 
 

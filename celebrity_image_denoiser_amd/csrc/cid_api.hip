@@ -19,6 +19,7 @@
 #include "srgan_kernels.h"
 #include "cgan_kernels.h"
 #include "lpips_kernels.h"
+#include "vgg_kernels.h"
 
 #include <dlfcn.h>
 
@@ -3993,9 +3994,345 @@ int cid_lpips(cid_lpips_t h, const void* a, int fmt_a, const void* b, int fmt_b,
         da.out = out;
         da.layers = layers;
         da.N = N;
-        hipLaunchKernelGGL(k_lpips_dist, dim3((unsigned)N), dim3(D_THREADS), 0, s, da);
+        hipLaunchKernelGGL(k_lpips_dist<LpAlexTaps>, dim3((unsigned)N), dim3(D_THREADS), 0, s, da);
         if (hipPeekAtLastError() != hipSuccess) return herr("distance");
     }
+    return CID_OK;
+}
+
+}  // extern "C"
+
+// ---- VGG16 features (cid_vgg_*): LPIPS(net='vgg') and the content loss; kernels in vgg_kernels.h and lpips_kernels.h ----
+namespace {
+
+static_assert(VG_MAX_SIDE == CID_VGG_MAX_SIDE, "vgg_kernels.h and cid.h agree on the largest side");
+constexpr int kVgMinSide[2] = {16, 4};               // by form: CID_VGG_LPIPS, CID_VGG_CONTENT
+const int kVgIdx[VG_CONVS] = {0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28};   // torchvision's features indices
+const int kVgSlice[VG_CONVS] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5};
+const int kVgCin[VG_CONVS] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
+const int kVgCout[VG_CONVS] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+constexpr int kVgContentConvs = 7;                   // slice1 ... slice3
+
+std::string vg_conv_name(int l) { return "net.slice" + std::to_string(kVgSlice[l]) + "." + std::to_string(kVgIdx[l]) + "."; }
+
+std::vector<EsrKey> vg_keys() {
+    std::vector<EsrKey> k;
+    k.push_back({"scaling_layer.shift", ESR_W, {1, 3, 1, 1}, 4, 3});
+    k.push_back({"scaling_layer.scale", ESR_W, {1, 3, 1, 1}, 4, 3});
+    for (int l = 0; l < VG_CONVS; ++l) {
+        k.push_back({vg_conv_name(l) + "weight", ESR_W, {kVgCout[l], kVgCin[l], 3, 3}, 4, (size_t)kVgCout[l] * kVgCin[l] * 9});
+        k.push_back({vg_conv_name(l) + "bias", ESR_VEC, {kVgCout[l], 0, 0, 0}, 1, (size_t)kVgCout[l]});
+    }
+    for (int l = 0; l < LP_TAPS; ++l)
+        k.push_back({"lin" + std::to_string(l) + ".model.1.weight", ESR_W, {1, VgTaps::channels(l), 1, 1}, 4, (size_t)VgTaps::channels(l)});
+    return k;
+}
+
+const std::vector<EsrKey>& vg_key_table() {
+    static const std::vector<EsrKey> k = vg_keys();
+    return k;
+}
+
+// blob segments (floats, 64-float aligned): the head, convolutions 1 ... 12 (packed weights then biases), the five lin vectors
+size_t vg_conv_off(int l) {   // l = 1 .. 12; l = 13: the lin segment
+    size_t at = VG_HEAD_SEG;
+    for (int i = 1; i < l; ++i) at += cg_align64((size_t)kVgCout[i] * kVgCin[i] * 9 + kVgCout[i]);
+    return at;
+}
+size_t vg_blob_floats() { return vg_conv_off(VG_CONVS) + VG_LIN_SEG; }
+
+struct VgPlan {
+    int Hs[LP_TAPS], Ws[LP_TAPS];    // sizes of relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+    size_t s0, s1;                   // byte offsets of the two scratch tensors (the convolutions between the taps)
+    size_t tap[LP_TAPS], total;      // byte offsets of the taps (C8, 2 N images each); the content form has the first three
+};
+
+int vg_plan(int what, int N, int H, int W, VgPlan& p) {
+    if (what != CID_VGG_LPIPS && what != CID_VGG_CONTENT) return CID_ERR_INVALID;
+    if (N < 1 || N > kLpMaxN || H < kVgMinSide[what] || W < kVgMinSide[what] || H > VG_MAX_SIDE || W > VG_MAX_SIDE) return CID_ERR_SHAPE;
+    // the head's grid.x runs over the whole batch's pixels
+    if (((long long)2 * N * H * W + VG_HEAD_PIX - 1) / VG_HEAD_PIX > 0x7fffffffll) return CID_ERR_SHAPE;
+    const int taps = what == CID_VGG_LPIPS ? LP_TAPS : 3;
+    p.Hs[0] = H, p.Ws[0] = W;
+    for (int k = 1; k < LP_TAPS; ++k) p.Hs[k] = p.Hs[k - 1] / 2, p.Ws[k] = p.Ws[k - 1] / 2;
+    for (int k = 0; k < taps; ++k)
+        if (vg_stage_bound(p.Hs[k], p.Ws[k]) > (k < 1 ? VG_XPOS_WIDE : LP_XPOS)) return CID_ERR_SHAPE;   // cannot happen up to VG_MAX_SIDE
+    size_t at = 0;
+    p.s0 = at;
+    at += align256((size_t)2 * N * 64 * H * W * sizeof(float));
+    p.s1 = at;
+    at += align256((size_t)2 * N * 256 * p.Hs[2] * p.Ws[2] * sizeof(float));
+    for (int k = 0; k < LP_TAPS; ++k) {
+        p.tap[k] = at;
+        if (k < taps) at += align256((size_t)2 * N * VgTaps::channels(k) * p.Hs[k] * p.Ws[k] * sizeof(float));
+    }
+    p.total = at;
+    return CID_OK;
+}
+
+}  // namespace
+
+struct cid_vgg_s {
+    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
+    std::vector<char> have;
+    std::vector<float> staging;
+    const float* dev_blob = nullptr;
+    bool full = false;                     // the uploaded blob holds all 33 tensors (else slice1 ... slice3 only)
+    std::string err;
+};
+
+namespace {
+int vgfail(cid_vgg_t h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+int vg_find(const std::string& k) {
+    const auto& keys = vg_key_table();
+    for (size_t i = 0; i < keys.size(); ++i)
+        if (keys[i].name == k) return (int)i;
+    return -1;
+}
+
+void vg_pack(cid_vgg_t h, bool full) {
+    h->staging.assign(vg_blob_floats(), 0.f);
+    float* b = h->staging.data();
+    const auto get = [&](const std::string& k) -> const float* { return h->raw[vg_find(k)].data(); };
+    {   // head: [k][64], bias, shift, scale
+        const float* w = get(vg_conv_name(0) + "weight");
+        for (int co = 0; co < 64; ++co)
+            for (int k = 0; k < VG_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * VG_HEAD_K + k];
+        std::memcpy(b + VG_HEAD_B, get(vg_conv_name(0) + "bias"), 64 * sizeof(float));
+        if (full) {
+            std::memcpy(b + VG_HEAD_SS, get("scaling_layer.shift"), 3 * sizeof(float));
+            std::memcpy(b + VG_HEAD_SS + 4, get("scaling_layer.scale"), 3 * sizeof(float));
+        }
+    }
+    for (int l = 1; l < (full ? VG_CONVS : kVgContentConvs); ++l) {
+        float* seg = b + vg_conv_off(l);
+        const int CO = kVgCout[l], CI = kVgCin[l];
+        const float* w = get(vg_conv_name(l) + "weight");
+        for (int co = 0; co < CO; ++co)
+            for (int ci = 0; ci < CI; ++ci)
+                for (int t = 0; t < 9; ++t) seg[lp_conv_windex(CI, 3, co, ci, t / 3, t % 3)] = w[((size_t)co * CI + ci) * 9 + t];
+        std::memcpy(seg + (size_t)CO * CI * 9, get(vg_conv_name(l) + "bias"), CO * sizeof(float));
+    }
+    if (full)
+        for (int l = 0; l < LP_TAPS; ++l)
+            std::memcpy(b + vg_conv_off(VG_CONVS) + VgTaps::lin_off(l), get("lin" + std::to_string(l) + ".model.1.weight"),
+                        VgTaps::channels(l) * sizeof(float));
+}
+
+// One trunk convolution from an Hs x Ws tensor; the plane size follows the output map's width.  Only the launch that can meet a
+// map wider than 339 (relu1_2, at the image's own size) has a wide instantiation.
+template <int CIN, int COUT, bool POOL, bool CAN_BE_WIDE>
+void vg_conv_launch(const float* in, float* out, const float* w, int N, int Hs, int Ws, hipStream_t s) {
+    const int Ho = POOL ? Hs / 2 : Hs, Wo = POOL ? Ws / 2 : Ws;
+    const LpConvArgs a{in, out, w, (long long)2 * N * Ho * Wo, Hs, Ws, Ho, Wo};
+    const dim3 grid((unsigned)((a.total + LP_NT - 1) / LP_NT), COUT / LP_MT);
+    if (vg_stage_bound(Ho, Wo) <= LP_XPOS) {
+        hipLaunchKernelGGL((k_lpips_conv<CIN, COUT, 3, POOL, 2, LP_XPOS>), grid, dim3(D_THREADS), 0, s, a);
+    } else if constexpr (CAN_BE_WIDE) {
+        hipLaunchKernelGGL((k_lpips_conv<CIN, COUT, 3, POOL, 2, VG_XPOS_WIDE>), grid, dim3(D_THREADS), 0, s, a);
+    }
+}
+
+// the checks cid_vgg_lpips and cid_vgg_content_loss share
+int vg_check(cid_vgg_t h, const char* fn, int what, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags,
+             const void* out, const void* layers, const void* workspace, size_t workspace_bytes, VgPlan& p) {
+    const std::string f(fn);
+    if (!a || !b || !out || !workspace) return vgfail(h, CID_ERR_INVALID, f + ": null pointer");
+    if ((fmt_a != CID_FMT_F32_NCHW && fmt_a != CID_FMT_U8_NHWC) || (fmt_b != CID_FMT_F32_NCHW && fmt_b != CID_FMT_U8_NHWC))
+        return vgfail(h, CID_ERR_INVALID, f + ": unknown format");
+    if ((fmt_a == CID_FMT_F32_NCHW && ((uintptr_t)a & 3)) || (fmt_b == CID_FMT_F32_NCHW && ((uintptr_t)b & 3)) || ((uintptr_t)out & 7) ||
+        ((uintptr_t)layers & 7))
+        return vgfail(h, CID_ERR_INVALID, f + ": misaligned operand");
+    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return vgfail(h, CID_ERR_INVALID, f + ": unknown flags");
+    if (vg_plan(what, N, H, W, p) != CID_OK)
+        return vgfail(h, CID_ERR_SHAPE, f + ": shape not accepted (1 <= N <= 2^20, " + std::to_string(kVgMinSide[what]) + " <= H, W <= " +
+                                            std::to_string(VG_MAX_SIDE) + ", 2 N H W < 2^37)");
+    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
+        return vgfail(h, CID_ERR_WORKSPACE, f + ": workspace smaller than cid_vgg_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return vgfail(h, CID_ERR_STATE, f + ": weights not uploaded");
+    if (what == CID_VGG_LPIPS && !h->full) return vgfail(h, CID_ERR_STATE, f + ": the handle holds slice1 ... slice3 only (content loss)");
+    return CID_OK;
+}
+
+// head and trunk up to tap `last` (2: relu3_3, 4: relu5_3); returns the name of the launch that failed, or null
+const char* vg_features(cid_vgg_t h, const VgPlan& p, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, bool unit,
+                        bool scaled, int last, char* ws, hipStream_t s) {
+    const float* blob = h->dev_blob;
+    float *s0 = reinterpret_cast<float*>(ws + p.s0), *s1 = reinterpret_cast<float*>(ws + p.s1), *t[LP_TAPS];
+    for (int k = 0; k < LP_TAPS; ++k) t[k] = reinterpret_cast<float*>(ws + p.tap[k]);
+    const auto bad = [] { return hipPeekAtLastError() != hipSuccess; };
+    {
+        const VgHeadArgs ha{a, b, s0, blob, (long long)2 * N * H * W, H, W, N, fmt_a == CID_FMT_U8_NHWC, fmt_b == CID_FMT_U8_NHWC, unit, scaled};
+        hipLaunchKernelGGL(k_vgg_head, dim3((unsigned)((ha.total + VG_HEAD_PIX - 1) / VG_HEAD_PIX)), dim3(VG_HEAD_PIX), 0, s, ha);
+        if (bad()) return "relu1_1";
+    }
+    vg_conv_launch<64, 64, false, true>(s0, t[0], blob + vg_conv_off(1), N, p.Hs[0], p.Ws[0], s);
+    if (bad()) return "relu1_2";
+    vg_conv_launch<64, 128, true, false>(t[0], s0, blob + vg_conv_off(2), N, p.Hs[0], p.Ws[0], s);
+    if (bad()) return "relu2_1";
+    vg_conv_launch<128, 128, false, false>(s0, t[1], blob + vg_conv_off(3), N, p.Hs[1], p.Ws[1], s);
+    if (bad()) return "relu2_2";
+    vg_conv_launch<128, 256, true, false>(t[1], s0, blob + vg_conv_off(4), N, p.Hs[1], p.Ws[1], s);
+    if (bad()) return "relu3_1";
+    vg_conv_launch<256, 256, false, false>(s0, s1, blob + vg_conv_off(5), N, p.Hs[2], p.Ws[2], s);
+    if (bad()) return "relu3_2";
+    vg_conv_launch<256, 256, false, false>(s1, t[2], blob + vg_conv_off(6), N, p.Hs[2], p.Ws[2], s);
+    if (bad()) return "relu3_3";
+    if (last == 2) return nullptr;
+    vg_conv_launch<256, 512, true, false>(t[2], s0, blob + vg_conv_off(7), N, p.Hs[2], p.Ws[2], s);
+    if (bad()) return "relu4_1";
+    vg_conv_launch<512, 512, false, false>(s0, s1, blob + vg_conv_off(8), N, p.Hs[3], p.Ws[3], s);
+    if (bad()) return "relu4_2";
+    vg_conv_launch<512, 512, false, false>(s1, t[3], blob + vg_conv_off(9), N, p.Hs[3], p.Ws[3], s);
+    if (bad()) return "relu4_3";
+    vg_conv_launch<512, 512, true, false>(t[3], s0, blob + vg_conv_off(10), N, p.Hs[3], p.Ws[3], s);
+    if (bad()) return "relu5_1";
+    vg_conv_launch<512, 512, false, false>(s0, s1, blob + vg_conv_off(11), N, p.Hs[4], p.Ws[4], s);
+    if (bad()) return "relu5_2";
+    vg_conv_launch<512, 512, false, false>(s1, t[4], blob + vg_conv_off(12), N, p.Hs[4], p.Ws[4], s);
+    if (bad()) return "relu5_3";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int cid_vgg_create(cid_vgg_t* out) {
+    if (!out) return CID_ERR_INVALID;
+    *out = nullptr;
+    cid_vgg_s* h = new (std::nothrow) cid_vgg_s();
+    if (!h) return CID_ERR_INVALID;
+    h->raw.resize(vg_key_table().size());
+    h->have.assign(vg_key_table().size(), 0);
+    *out = h;
+    return CID_OK;
+}
+
+void cid_vgg_destroy(cid_vgg_t h) { delete h; }
+
+const char* cid_vgg_last_error(cid_vgg_t h) { return h ? h->err.c_str() : "null handle"; }
+
+const char* cid_vgg_param_key(cid_vgg_t h, int i) {
+    if (!h || i < 0 || (size_t)i >= vg_key_table().size()) return nullptr;
+    return vg_key_table()[i].name.c_str();
+}
+
+int cid_vgg_set_weight(cid_vgg_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
+    if (!h) return CID_ERR_INVALID;
+    if (!key || !data || (!shape && ndim > 0)) return vgfail(h, CID_ERR_INVALID, "cid_vgg_set_weight: null argument");
+    const int i = vg_find(key);
+    if (i < 0) return vgfail(h, CID_ERR_KEY, std::string("cid_vgg_set_weight: unexpected key '") + key + "'");
+    const EsrKey& k = vg_key_table()[i];
+    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return vgfail(h, CID_ERR_SHAPE, "cid_vgg_set_weight: size mismatch for " + k.name);
+    const float* f = static_cast<const float*>(data);
+    h->raw[i].assign(f, f + k.count);
+    h->have[i] = 1;
+    return CID_OK;
+}
+
+int cid_vgg_missing_weights(cid_vgg_t h, int* count) {
+    if (!h || !count) return CID_ERR_INVALID;
+    int m = 0;
+    for (size_t i = 0; i < h->have.size(); ++i) m += !h->have[i];
+    *count = m;
+    return CID_OK;
+}
+
+size_t cid_vgg_packed_weights_bytes(cid_vgg_t h) { return h ? vg_blob_floats() * sizeof(float) : 0; }
+
+int cid_vgg_upload_weights(cid_vgg_t h, void* device_blob, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    if (!device_blob) return vgfail(h, CID_ERR_INVALID, "cid_vgg_upload_weights: null device pointer");
+    // all 33 tensors, or exactly the 14 of slice1 ... slice3 (key table entries 2 ... 15)
+    int set = 0, content = 0;
+    for (size_t i = 0; i < h->have.size(); ++i) {
+        set += h->have[i] != 0;
+        content += h->have[i] && i >= 2 && i < 2 + 2 * (size_t)kVgContentConvs;
+    }
+    const bool full = set == CID_VGG_NUM_WEIGHTS;
+    if (!full && !(set == 2 * kVgContentConvs && content == set)) {
+        std::string first;
+        for (size_t i = 0; i < h->have.size() && first.empty(); ++i)
+            if (!h->have[i]) first = vg_key_table()[i].name;
+        return vgfail(h, CID_ERR_STATE, "cid_vgg_upload_weights: needs all " + std::to_string(CID_VGG_NUM_WEIGHTS) +
+                                            " tensors or exactly the 14 of slice1 ... slice3; " + std::to_string(set) + " set, first missing " + first);
+    }
+    if ((uintptr_t)device_blob & 255) return vgfail(h, CID_ERR_WORKSPACE, "cid_vgg_upload_weights: blob must be 256-byte aligned");
+    vg_pack(h, full);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
+    if (e != hipSuccess) return vgfail(h, CID_ERR_HIP, std::string("cid_vgg_upload_weights: ") + hipGetErrorString(e));
+    h->dev_blob = static_cast<const float*>(device_blob);
+    h->full = full;
+    return CID_OK;
+}
+
+int cid_vgg_workspace_bytes(int what, int N, int H, int W, size_t* bytes) {
+    if (!bytes) return CID_ERR_INVALID;
+    VgPlan p;
+    const int rc = vg_plan(what, N, H, W, p);
+    if (rc == CID_OK) *bytes = p.total;
+    return rc;
+}
+
+int cid_vgg_stage_view(int what, const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
+    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
+    VgPlan p;
+    const int rc = vg_plan(what, N, H, W, p);
+    if (rc != CID_OK) return rc;
+    const std::string s(stage);
+    if (s.size() != 5 || s.compare(0, 4, "relu") != 0 || s[4] < '1' || s[4] > (what == CID_VGG_LPIPS ? '5' : '3')) return CID_ERR_KEY;
+    const int k = s[4] - '1';
+    *offset_bytes = p.tap[k];
+    *C = VgTaps::channels(k);
+    *Hs = p.Hs[k];
+    *Ws = p.Ws[k];
+    *channel_block = 8;
+    return CID_OK;
+}
+
+int cid_vgg_lpips(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
+                  double* layers, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    VgPlan p;
+    const int rc = vg_check(h, "cid_vgg_lpips", CID_VGG_LPIPS, a, fmt_a, b, fmt_b, N, H, W, flags, out, layers, workspace, workspace_bytes, p);
+    if (rc != CID_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto herr = [&](const char* what) { return vgfail(h, CID_ERR_HIP, std::string("cid_vgg_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    char* ws = static_cast<char*>(workspace);
+    if (const char* failed = vg_features(h, p, a, fmt_a, b, fmt_b, N, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0, true, 4, ws, s)) return herr(failed);
+    LpDistArgs da;
+    for (int k = 0; k < LP_TAPS; ++k) {
+        da.tap[k] = reinterpret_cast<const float*>(ws + p.tap[k]);
+        da.P[k] = p.Hs[k] * p.Ws[k];
+    }
+    da.lin = h->dev_blob + vg_conv_off(VG_CONVS);
+    da.out = out;
+    da.layers = layers;
+    da.N = N;
+    hipLaunchKernelGGL(k_lpips_dist<VgTaps>, dim3((unsigned)N), dim3(D_THREADS), 0, s, da);
+    if (hipPeekAtLastError() != hipSuccess) return herr("distance");
+    return CID_OK;
+}
+
+int cid_vgg_content_loss(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return CID_ERR_INVALID;
+    VgPlan p;
+    const int rc = vg_check(h, "cid_vgg_content_loss", CID_VGG_CONTENT, a, fmt_a, b, fmt_b, N, H, W, flags, out, nullptr, workspace, workspace_bytes, p);
+    if (rc != CID_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto herr = [&](const char* what) { return vgfail(h, CID_ERR_HIP, std::string("cid_vgg_content_loss: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    char* ws = static_cast<char*>(workspace);
+    if (const char* failed = vg_features(h, p, a, fmt_a, b, fmt_b, N, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0, false, 2, ws, s)) return herr(failed);
+    const VgContentArgs ca{reinterpret_cast<const float*>(ws + p.tap[2]), out, (long long)256 * p.Hs[2] * p.Ws[2], N};
+    hipLaunchKernelGGL(k_vgg_content, dim3((unsigned)N), dim3(D_THREADS), 0, s, ca);
+    if (hipPeekAtLastError() != hipSuccess) return herr("loss");
     return CID_OK;
 }
 

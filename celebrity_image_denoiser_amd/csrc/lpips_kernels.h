@@ -123,9 +123,7 @@ __global__ void __launch_bounds__(LP_HEAD_PIX) k_lpips_head(const LpHeadArgs a) 
 constexpr int LP_NT = 128;                 // GEMM columns (output pixels of the batch sequence) per workgroup
 constexpr int LP_MT = 64;                  // output channels per workgroup
 constexpr int LP_XPOS = 2048;              // staged positions per plane, at most (the host checks lp_stage_bound against it)
-constexpr int LP_XSTR = LP_XPOS + 16;      // plane stride = 16 mod 64: the 4 planes of a k-step sit 16 banks apart
 constexpr int LP_WSTR = LP_MT + 16;        // weight row stride, 16 mod 64 likewise
-constexpr int LP_X_ITERS = LP_XPOS / D_THREADS;
 
 // Positions a workgroup stages per plane: an upper bound over every run of LP_NT consecutive columns of maps Ho x Wo with halo `pad`.
 // The first and the last image of a run are staged over the rows the run touches, the images between them whole; every staged row
@@ -154,15 +152,18 @@ struct LpConvArgs {
     float* out;          // C8, COUT channels, Ho x Wo
     const float* w;      // packed weights, then COUT biases
     long long total;     // 2 N * Ho * Wo columns
-    int Hs, Ws;          // the previous tap's size; with POOL, Ho = (Hs - 3) / 2 + 1, else Ho = Hs
+    int Hs, Ws;          // the previous tap's size; with POOL, Ho = (Hs - PK) / 2 + 1, else Ho = Hs
     int Ho, Wo;
 };
 
-template <int CIN, int COUT, int KS, bool POOL>
+// PK is the pool's window (stride 2, no padding, floor mode): 3 for AlexNet, 2 for VGG (vgg_kernels.h).  XPOS is the plane size: a
+// launch that stages more than LP_XPOS positions takes a wider plane (vgg_kernels.h).
+template <int CIN, int COUT, int KS, bool POOL, int PK = 3, int XPOS = LP_XPOS>
 __global__ void __launch_bounds__(D_THREADS, 2) k_lpips_conv(const LpConvArgs a) {
     constexpr int PAD = KS / 2, TAPS = KS * KS, CHUNKS = CIN / 4, WROWS = TAPS * 4;
-    static_assert(CIN % 8 == 0 && COUT % LP_MT == 0, "channel blocks");
-    __shared__ float lds_x[4 * LP_XSTR];
+    constexpr int XSTR = XPOS + 16, X_ITERS = XPOS / D_THREADS;   // plane stride = 16 mod 64: the 4 planes of a k-step sit 16 banks apart
+    static_assert(CIN % 8 == 0 && COUT % LP_MT == 0 && XPOS % 64 == 0 && XPOS % D_THREADS == 0, "channel blocks, bank offset");
+    __shared__ float lds_x[4 * XSTR];
     __shared__ __attribute__((aligned(16))) float lds_w[WROWS * LP_WSTR];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -182,9 +183,9 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_lpips_conv(const LpConvArgs a)
 
     // where this thread's staged positions come from: float offset of (image, channel block 0, pixel), or -1 for the zero halo
     const size_t plane = (size_t)a.Hs * a.Ws * 8;
-    long long x_off[LP_X_ITERS];
+    long long x_off[X_ITERS];
 #pragma unroll
-    for (int it = 0; it < LP_X_ITERS; ++it) {
+    for (int it = 0; it < X_ITERS; ++it) {
         const int idx = it * D_THREADS + tid;
         x_off[it] = -1;
         if (idx < npos) {
@@ -208,7 +209,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_lpips_conv(const LpConvArgs a)
 #pragma unroll
     for (int pt = 0; pt < 4; ++pt) {
         const long long q = q0 + wn * 64 + pt * 16 + l16;
-        xb[pt] = kq * LP_XSTR;
+        xb[pt] = kq * XSTR;
         ob[pt] = -1;
         if (q < a.total) {
             const long long n = q / P;
@@ -233,7 +234,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_lpips_conv(const LpConvArgs a)
         __syncthreads();   // every wave is done with the previous chunk
         const size_t coff = (size_t)(chunk >> 1) * plane + (chunk & 1) * 4;
 #pragma unroll
-        for (int it = 0; it < LP_X_ITERS; ++it) {
+        for (int it = 0; it < X_ITERS; ++it) {
             const int idx = it * D_THREADS + tid;
             if (idx < npos) {
                 d_f32x4 v = d_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -242,15 +243,15 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_lpips_conv(const LpConvArgs a)
                     v = *reinterpret_cast<const d_f32x4*>(s);
                     if (POOL) {
 #pragma unroll
-                        for (int t = 1; t < 9; ++t) {
-                            const d_f32x4 u = *reinterpret_cast<const d_f32x4*>(s + ((size_t)(t / 3) * a.Ws + t % 3) * 8);
+                        for (int t = 1; t < PK * PK; ++t) {
+                            const d_f32x4 u = *reinterpret_cast<const d_f32x4*>(s + ((size_t)(t / PK) * a.Ws + t % PK) * 8);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) v[e] = lp_max(v[e], u[e]);
                         }
                     }
                 }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) lds_x[e * LP_XSTR + idx] = v[e];
+                for (int e = 0; e < 4; ++e) lds_x[e * XSTR + idx] = v[e];
             }
         }
         {
@@ -316,6 +317,13 @@ struct LpDistArgs {
     int N;
 };
 
+struct LpAlexTaps {
+    static __host__ __device__ constexpr int channels(int k) { return lp_channels(k); }
+    static __host__ __device__ constexpr int lin_off(int k) { return lp_lin_off(k); }
+};
+
+// NET names the five taps' channel counts and where their lin weights start; the arithmetic is the same for every network.
+template <class NET = LpAlexTaps>
 __global__ void __launch_bounds__(D_THREADS) k_lpips_dist(const LpDistArgs a) {
     __shared__ double red[D_THREADS];
     const int tid = threadIdx.x;
@@ -323,10 +331,10 @@ __global__ void __launch_bounds__(D_THREADS) k_lpips_dist(const LpDistArgs a) {
     double total = 0.0;
 #pragma unroll
     for (int k = 0; k < LP_TAPS; ++k) {
-        const int CB = lp_channels(k) / 8, P = a.P[k];
+        const int CB = NET::channels(k) / 8, P = a.P[k];
         const float* x0 = a.tap[k] + n * CB * (size_t)P * 8;
         const float* x1 = a.tap[k] + (n + (size_t)a.N) * CB * (size_t)P * 8;
-        const float* w = a.lin + lp_lin_off(k);
+        const float* w = a.lin + NET::lin_off(k);
         double part = 0.0;
         for (int p = tid; p < P; p += D_THREADS) {
             double s0 = 0.0, s1 = 0.0;

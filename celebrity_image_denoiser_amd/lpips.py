@@ -1,13 +1,17 @@
-"""LPIPS(net='alex') — the third number of the reference trainers' evaluation (training.py:282,389) — on the GPU.
+"""LPIPS — the third number of the reference trainers' evaluation (training.py:282,389; net='alex') and the ESRGAN trainer's
+perceptual metric (esrgan_train.py:65,133; net='vgg') — and the trainers' VGGPerceptualLoss, on the GPU.
 
-    LPIPS()                               nn.Module with the package's state_dict names (scaling_layer.*, net.slice*.*, lin*.*, and
+    LPIPS(net="alex")                     nn.Module with the package's state_dict names (scaling_layer.*, net.slice*.*, lin*.*, and
                                           the lins.* aliases); forward(in0, in1, retPerLayer=False, normalize=False) -> fp32 [N,1,1,1]
-    load_lpips(lin_ckpt, backbone=None)   -> LPIPS from a full LPIPS state dict, or from the package's lin*-only weight file together
-                                          with a torchvision AlexNet state dict
+    load_lpips(lin_ckpt, backbone=None, net="alex")   -> LPIPS from a full LPIPS state dict, or from the package's lin*-only weight
+                                          file together with a torchvision AlexNet / vgg16 state dict
     metrics.lpips(a, b, model)            float64 [N] on the device (metrics.py)
+    VGGPerceptualLoss()                   the trainers' content loss: MSE of vgg16.features[:16]; forward(x, y) -> fp32 scalar,
+                                          per_image(x, y) -> float64 [N]; no autograd history
+    load_vgg_loss(backbone)               -> VGGPerceptualLoss from a torchvision vgg16 (or features-only) state dict
 
-The definition is stated once, in the header comment of include/cid.h (cid_lpips).  Everything numeric runs in HIP kernels behind
-cid_lpips_*; there is no CPU fallback.  No weights ship with this package: synth.make_lpips_state_dict draws portable synthetic
+The definitions are stated once, in the header comments of include/cid.h (cid_lpips, cid_vgg_lpips, cid_vgg_content_loss).
+Everything numeric runs in HIP kernels behind cid_lpips_* and cid_vgg_*; there is no CPU fallback.  No weights ship with this package: synth.make_lpips_state_dict draws portable synthetic
 ones, and INTEGRATION.md says how to obtain and pass the real ones.
 """
 from __future__ import annotations
@@ -26,6 +30,13 @@ MIN_SIDE = 31
 # net.slice<k+1>.<index>: torchvision's alexnet.features indices of the five convolutions
 _CONVS = ((1, 0, 3, 64, 11, 4, 2), (2, 3, 64, 192, 5, 1, 2), (3, 6, 192, 384, 3, 1, 1), (4, 8, 384, 256, 3, 1, 1),
           (5, 10, 256, 256, 3, 1, 1))
+VGG_CHANNELS = (64, 128, 256, 512, 512)
+VGG_MIN_SIDE, VGG_LOSS_MIN_SIDE, VGG_MAX_SIDE = 16, 4, _lib.CID_VGG_MAX_SIDE
+# torchvision's vgg16.features indices of the thirteen convolutions, by slice
+_VGG_CONVS = tuple((k, idx, cin, cout, 3, 1, 1) for k, idx, cin, cout in (
+    (1, 0, 3, 64), (1, 2, 64, 64), (2, 5, 64, 128), (2, 7, 128, 128), (3, 10, 128, 256), (3, 12, 256, 256), (3, 14, 256, 256),
+    (4, 17, 256, 512), (4, 19, 512, 512), (4, 21, 512, 512), (5, 24, 512, 512), (5, 26, 512, 512), (5, 28, 512, 512)))
+_NETS = {"alex": (_CONVS, CHANNELS, "lpips"), "vgg": (_VGG_CONVS, VGG_CHANNELS, "vgg")}
 
 
 class _ScalingLayer(nn.Module):
@@ -52,28 +63,37 @@ def operand(x, what: str = "lpips"):
     raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3], got {x.dtype} {list(x.shape)}")
 
 
+def _shape_error(rc: int, what: str, n: int, h: int, w: int, why: str) -> None:
+    if rc == 2:   # CID_ERR_SHAPE
+        raise ValueError(f"image size {h}x{w} (N={n}) not accepted: {what} needs {why}")
+
+
 class LPIPS(nn.Module):
-    """lpips.LPIPS(net='alex') as a parameter container plus the HIP forward.  `scaling_layer`, `net`, `lin0` ... `lin4` and `lins`
+    """lpips.LPIPS(net='alex' or 'vgg') as a parameter container plus the HIP forward.  `scaling_layer`, `net`, `lin0` ... `lin4` and `lins`
     are stock layers, so state_dict keys, .to() and load_state_dict() behave as in the package.  Eval mode only (dropout is inert).
     Asynchronous on the current stream, without autograd history.  Weight changes are found by the tensors' version counters and
     repacked at the next call (after writes through `.data` call pack_weights(force=True))."""
 
-    def __init__(self):
+    def __init__(self, net: str = "alex"):
         super().__init__()
+        if net not in _NETS:
+            raise ValueError(f"unknown net {net!r}: 'alex' or 'vgg'")
+        self.pnet_type = net
+        convs, self.chns, self._abi = _NETS[net]
         self.scaling_layer = _ScalingLayer()
         self.net = nn.Module()
-        for k, idx, cin, cout, ks, stride, pad in _CONVS:
-            seq = nn.Sequential()
-            seq.add_module(str(idx), nn.Conv2d(cin, cout, ks, stride=stride, padding=pad))
-            self.net.add_module(f"slice{k}", seq)
-        for k, c in enumerate(CHANNELS):
+        for k in range(1, 6):
+            self.net.add_module(f"slice{k}", nn.Sequential())
+        for k, idx, cin, cout, ks, stride, pad in convs:
+            getattr(self.net, f"slice{k}").add_module(str(idx), nn.Conv2d(cin, cout, ks, stride=stride, padding=pad))
+        for k, c in enumerate(self.chns):
             setattr(self, f"lin{k}", _LinLayer(c))
         self.lins = nn.ModuleList([getattr(self, f"lin{k}") for k in range(5)])
         for p in self.parameters():
             p.requires_grad_(False)
         self.eval()
         self._cid = ctypes.c_void_p()
-        _lib.check_lpips(None, _lib.lib().cid_lpips_create(ctypes.byref(self._cid)))
+        self._check(self._fn("create")(ctypes.byref(self._cid)), handle=False)
         self._blob = None          # packed weights on the device (uint8 tensor, owns the memory)
         self._packed_sig = None
         self._ws = None            # workspace (uint8 tensor, grow-only)
@@ -81,10 +101,21 @@ class LPIPS(nn.Module):
     def __del__(self):
         try:
             if getattr(self, "_cid", None):
-                _lib.lib().cid_lpips_destroy(self._cid)
+                self._fn("destroy")(self._cid)
                 self._cid = None
         except Exception:
             pass
+
+    # ------------------------------------------------------------------ the C ABI family of this net: cid_lpips_* or cid_vgg_*
+    def _fn(self, name: str):
+        return getattr(_lib.lib(), f"cid_{self._abi}_{name}")
+
+    def _check(self, rc: int, handle: bool = True) -> None:
+        (_lib.check_vgg if self._abi == "vgg" else _lib.check_lpips)(self._cid if handle else None, rc)
+
+    def _form(self) -> tuple:
+        """The leading `what` argument of cid_vgg_workspace_bytes / cid_vgg_stage_view; cid_lpips_* has none."""
+        return (_lib.CID_VGG_LPIPS,) if self._abi == "vgg" else ()
 
     # ------------------------------------------------------------------ weights
     def _device(self) -> torch.device:
@@ -105,26 +136,26 @@ class LPIPS(nn.Module):
         if dev.type != "cuda":
             raise RuntimeError("LPIPS runs only on an AMD GPU (HIP kernels behind libcid.so); move it with .to('cuda') first. "
                                "There is no CPU fallback.")
-        L = _lib.lib()
         for key, t in self._tensors():
             a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
             shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-            _lib.check_lpips(self._cid, L.cid_lpips_set_weight(self._cid, key.encode(), a.ctypes.data, shape, a.ndim))
-        blob = torch.empty(L.cid_lpips_packed_weights_bytes(self._cid), dtype=torch.uint8, device=dev)
+            self._check(self._fn("set_weight")(self._cid, key.encode(), a.ctypes.data, shape, a.ndim))
+        blob = torch.empty(self._fn("packed_weights_bytes")(self._cid), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_lpips(self._cid, L.cid_lpips_upload_weights(self._cid, blob.data_ptr(), stream))
+            self._check(self._fn("upload_weights")(self._cid, blob.data_ptr(), stream))
         self._blob, self._packed_sig = blob, sig
         return blob
 
     # ------------------------------------------------------------------ forward
     def _ensure_workspace(self, n: int, h: int, w: int, device: torch.device) -> None:
         need = ctypes.c_size_t()
-        rc = _lib.lib().cid_lpips_workspace_bytes(n, h, w, ctypes.byref(need))
-        if rc == 2:   # CID_ERR_SHAPE
-            raise ValueError(f"image size {h}x{w} (N={n}) not accepted: LPIPS needs H, W >= {MIN_SIDE} (AlexNet's maps 7 -> 3 -> 1) "
-                             "and sides of at most 1024")
-        _lib.check_lpips(self._cid, rc)
+        rc = self._fn("workspace_bytes")(*self._form(), n, h, w, ctypes.byref(need))
+        if self._abi == "vgg":
+            _shape_error(rc, "LPIPS(net='vgg')", n, h, w, f"{VGG_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE} (four 2x2 pools down to 1x1)")
+        else:
+            _shape_error(rc, "LPIPS", n, h, w, f"H, W >= {MIN_SIDE} (AlexNet's maps 7 -> 3 -> 1) and sides of at most 1024")
+        self._check(rc)
         if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
             if self._ws is not None:
                 torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
@@ -136,18 +167,8 @@ class LPIPS(nn.Module):
         is float32 [N,3,H,W] or uint8 [N,H,W,3] (read as (u/255-0.5)/0.5); unit_view applies v*0.5+0.5 to both (the trainers' call)."""
         if self.training:
             raise RuntimeError("LPIPS is in train mode: the metric is defined in eval mode (dropout inert); call .eval()")
-        fa, shape_a = operand(a)
-        fb, shape_b = operand(b)
-        if shape_a != shape_b:
-            raise ValueError("Input images must have the same dimensions.")
-        if not (a.is_cuda and b.is_cuda):
-            raise RuntimeError("got a CPU tensor: LPIPS is GPU-only (hand-written HIP kernels); there is no CPU fallback")
         dev = self._device()
-        if a.device != dev or b.device != dev:
-            raise RuntimeError(f"operands on {a.device} and {b.device} but module parameters on {dev}")
-        n, h, w = shape_a
-        if n < 1:
-            raise RuntimeError(f"empty input {list(a.shape)}")
+        (fa, fb), (n, h, w) = _check_pair(a, b, dev, "LPIPS")
         self._ensure_workspace(n, h, w, dev)
         self.pack_weights()
         a, b = a.contiguous(), b.contiguous()
@@ -155,7 +176,7 @@ class LPIPS(nn.Module):
         layers = torch.empty((n, 5), dtype=torch.float64, device=dev) if per_layer else None
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_lpips(self._cid, _lib.lib().cid_lpips(
+            self._check((_lib.lib().cid_vgg_lpips if self._abi == "vgg" else _lib.lib().cid_lpips)(
                 self._cid, a.data_ptr(), fa, b.data_ptr(), fb, n, h, w, _lib.CID_LPIPS_UNIT_VIEW if unit_view else 0, out.data_ptr(),
                 layers.data_ptr() if per_layer else None, self._ws.data_ptr(), self._ws.numel(), stream))
         return (out, layers) if per_layer else out
@@ -177,25 +198,178 @@ class LPIPS(nn.Module):
         """What the last call over n pairs of h x w images left in the workspace, as fp32 [2 n,C,Hs,Ws] (a copy): "relu1" ... "relu5";
         operand a's n images, then operand b's (cid_lpips_stage_view)."""
         off, c, hs, ws, cb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        rc = _lib.lib().cid_lpips_stage_view(name.encode(), n, h, w, ctypes.byref(off), ctypes.byref(c), ctypes.byref(hs),
-                                             ctypes.byref(ws), ctypes.byref(cb))
+        rc = self._fn("stage_view")(*self._form(), name.encode(), n, h, w, ctypes.byref(off), ctypes.byref(c), ctypes.byref(hs),
+                                    ctypes.byref(ws), ctypes.byref(cb))
         if rc != _lib.CID_OK:
-            raise KeyError(f"no stored stage {name!r} for {n} pairs of {h}x{w} (cid_lpips_stage_view -> {rc})")
-        count = 2 * n * c.value * hs.value * ws.value
-        t = self._ws[off.value:off.value + 4 * count].view(torch.float32)
-        t = t.view(2 * n, c.value // cb.value, hs.value, ws.value, cb.value).permute(0, 1, 4, 2, 3)
-        return t.reshape(2 * n, c.value, hs.value, ws.value).clone()
+            raise KeyError(f"no stored stage {name!r} for {n} pairs of {h}x{w} (cid_{self._abi}_stage_view -> {rc})")
+        return _stage_tensor(self._ws, off.value, n, c.value, hs.value, ws.value, cb.value)
 
 
-_FEATURES = {f"features.{idx}.": f"net.slice{k}.{idx}." for k, idx, *_ in _CONVS}
+def _stage_tensor(ws: torch.Tensor, off: int, n: int, c: int, hs: int, wsz: int, cb: int) -> torch.Tensor:
+    count = 2 * n * c * hs * wsz
+    t = ws[off:off + 4 * count].view(torch.float32)
+    t = t.view(2 * n, c // cb, hs, wsz, cb).permute(0, 1, 4, 2, 3)
+    return t.reshape(2 * n, c, hs, wsz).clone()
 
 
-def lpips_state_dict(lin_sd: Mapping, backbone_sd: Optional[Mapping] = None) -> dict:
+def _check_pair(a, b, dev, what: str):
+    """The operand checks distances() and per_image() share: ((fmt_a, fmt_b), (n, h, w))."""
+    fa, shape_a = operand(a)
+    fb, shape_b = operand(b)
+    if shape_a != shape_b:
+        raise ValueError("Input images must have the same dimensions.")
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError(f"got a CPU tensor: {what} is GPU-only (hand-written HIP kernels); there is no CPU fallback")
+    if a.device != dev or b.device != dev:
+        raise RuntimeError(f"operands on {a.device} and {b.device} but module parameters on {dev}")
+    if shape_a[0] < 1:
+        raise RuntimeError(f"empty input {list(a.shape)}")
+    return (fa, fb), shape_a
+
+
+_VGG_LOSS_IDX = (0, 2, 5, 7, 10, 12, 14)
+
+
+class VGGPerceptualLoss(nn.Module):
+    """The reference trainers' VGGPerceptualLoss (sr_ganTrainGNew.py:83-94, training.py:101-111): MSELoss of vgg16.features[:16] on
+    the two operands as they are, with the reference's parameter names slice.{0,2,5,7,10,12,14}.weight / .bias, frozen, eval mode.
+    The forward runs in HIP kernels (cid_vgg_content_loss) on the current stream and has NO autograd history: the backward through
+    VGG is not implemented, so the value can be logged or compared but not trained through."""
+
+    def __init__(self):
+        super().__init__()
+        self.slice = nn.Sequential()
+        for k, idx, cin, cout, ks, stride, pad in _VGG_CONVS[:7]:
+            self.slice.add_module(str(idx), nn.Conv2d(cin, cout, ks, stride=stride, padding=pad))
+        for p in self.parameters():
+            p.requires_grad_(False)
+        self.eval()
+        self._cid = ctypes.c_void_p()
+        _lib.check_vgg(None, _lib.lib().cid_vgg_create(ctypes.byref(self._cid)))
+        self._blob = None
+        self._packed_sig = None
+        self._ws = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_cid", None):
+                _lib.lib().cid_vgg_destroy(self._cid)
+                self._cid = None
+        except Exception:
+            pass
+
+    def _signature(self):
+        return tuple((k, t.data_ptr(), t._version, str(t.device)) for k, t in self.state_dict(keep_vars=True).items())
+
+    def pack_weights(self, force: bool = False) -> torch.Tensor:
+        """Pack the state_dict into the kernels' layout on the module's GPU (if anything changed since the last call)."""
+        sig = self._signature()
+        if not force and self._blob is not None and sig == self._packed_sig:
+            return self._blob
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("VGGPerceptualLoss runs only on an AMD GPU (HIP kernels behind libcid.so); move it with .to('cuda') "
+                               "first. There is no CPU fallback.")
+        L = _lib.lib()
+        slice_of = {idx: k for k, idx, *_ in _VGG_CONVS}
+        for key, t in self.state_dict(keep_vars=True).items():
+            _, idx, leaf = key.split(".")
+            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+            shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+            name = f"net.slice{slice_of[int(idx)]}.{idx}.{leaf}"
+            _lib.check_vgg(self._cid, L.cid_vgg_set_weight(self._cid, name.encode(), a.ctypes.data, shape, a.ndim))
+        blob = torch.empty(L.cid_vgg_packed_weights_bytes(self._cid), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check_vgg(self._cid, L.cid_vgg_upload_weights(self._cid, blob.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        self._blob, self._packed_sig = blob, sig
+        return blob
+
+    def per_image(self, x: torch.Tensor, y: torch.Tensor, unit_view: bool = False) -> torch.Tensor:
+        """cid_vgg_content_loss on the current stream: float64 [N] on the device, the mean squared difference of relu3_3 per pair."""
+        if self.training:
+            raise RuntimeError("VGGPerceptualLoss is in train mode: the reference keeps it in eval mode; call .eval()")
+        dev = next(self.parameters()).device
+        (fx, fy), (n, h, w) = _check_pair(x, y, dev, "VGGPerceptualLoss")
+        need = ctypes.c_size_t()
+        rc = _lib.lib().cid_vgg_workspace_bytes(_lib.CID_VGG_CONTENT, n, h, w, ctypes.byref(need))
+        _shape_error(rc, "VGGPerceptualLoss", n, h, w, f"{VGG_LOSS_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE}")
+        _lib.check_vgg(self._cid, rc)
+        if self._ws is None or self._ws.numel() < need.value or self._ws.device != dev:
+            if self._ws is not None:
+                torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
+            self._ws = None
+            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        self.pack_weights()
+        x, y = x.detach().contiguous(), y.detach().contiguous()
+        out = torch.empty((n,), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check_vgg(self._cid, _lib.lib().cid_vgg_content_loss(
+                self._cid, x.data_ptr(), fx, y.data_ptr(), fy, n, h, w, _lib.CID_LPIPS_UNIT_VIEW if unit_view else 0, out.data_ptr(),
+                self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        return out
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """The reference's call: the fp32 scalar MSELoss()(slice(x), slice(y)), the mean of per_image.  No autograd history."""
+        return self.per_image(x, y).mean().to(torch.float32)
+
+    def stage(self, name: str, n: int, h: int, w: int) -> torch.Tensor:
+        """ "relu1" ... "relu3" (relu1_2, relu2_2, relu3_3) of the last call, fp32 [2 n,C,Hs,Ws] (a copy): x's n images, then y's."""
+        off, c, hs, ws, cb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = _lib.lib().cid_vgg_stage_view(_lib.CID_VGG_CONTENT, name.encode(), n, h, w, ctypes.byref(off), ctypes.byref(c),
+                                           ctypes.byref(hs), ctypes.byref(ws), ctypes.byref(cb))
+        if rc != _lib.CID_OK:
+            raise KeyError(f"no stored stage {name!r} for {n} pairs of {h}x{w} (cid_vgg_stage_view -> {rc})")
+        return _stage_tensor(self._ws, off.value, n, c.value, hs.value, ws.value, cb.value)
+
+
+def vgg_loss_state_dict(backbone_sd: Mapping) -> dict:
+    """slice.N.* from a torchvision vgg16 state dict (features.N.*, later features and classifier.* dropped), a features-only one
+    (N.*) or the class's own (slice.N.*).  Any other key raises KeyError."""
+    from .api import extract_state_dict
+
+    out = {}
+    for k, v in extract_state_dict(backbone_sd).items():
+        parts = k.split(".")
+        if parts[0] in ("features", "slice"):
+            parts = parts[1:]
+        elif parts[0] == "classifier":
+            continue
+        if len(parts) != 2 or not parts[0].isdigit() or parts[1] not in ("weight", "bias") or int(parts[0]) not in [c[1] for c in _VGG_CONVS]:
+            raise KeyError(f"unexpected key {k!r} in the vgg16 state dict (expected features.N.weight / .bias and classifier.*)")
+        if int(parts[0]) in _VGG_LOSS_IDX:
+            out[f"slice.{parts[0]}.{parts[1]}"] = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+    return out
+
+
+def build_vgg_loss(backbone, reader=None) -> VGGPerceptualLoss:
+    """load_vgg_loss without the move to the GPU."""
+    if reader is None:
+        from .api import _read_checkpoint_file as reader
+    model = VGGPerceptualLoss()
+    model.load_state_dict(vgg_loss_state_dict(reader(backbone) if isinstance(backbone, str) else backbone), strict=True)
+    return model
+
+
+def load_vgg_loss(backbone: Union[str, Mapping], device: Optional[Union[str, torch.device]] = None) -> VGGPerceptualLoss:
+    """A VGGPerceptualLoss on `device` (default: current GPU) from a torchvision vgg16 state dict or a features-only one, a path or
+    a mapping."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError("celebrity_image_denoiser_amd.load_vgg_loss: an AMD GPU is required (no CPU fallback)")
+    model = build_vgg_loss(backbone)
+    model.to(device).eval()
+    model.pack_weights()
+    return model
+
+
+def lpips_state_dict(lin_sd: Mapping, backbone_sd: Optional[Mapping] = None, net: str = "alex") -> dict:
     """The module's state dict from either layout: a full LPIPS state dict, or the package's lin*-only file plus a torchvision
-    AlexNet state dict (features.N.* -> net.sliceK.N.*, classifier.* dropped).  "module." prefixes are stripped; lins.* aliases are
+    AlexNet / vgg16 state dict (features.N.* -> net.sliceK.N.*, classifier.* dropped).  "module." prefixes are stripped; lins.* aliases are
     filled from lin* (or the other way round)."""
     from .api import extract_state_dict
 
+    features = {f"features.{idx}.": f"net.slice{k}.{idx}." for k, idx, *_ in _NETS[net][0]}
     out = {}
     for k, v in extract_state_dict(lin_sd).items():
         out[k] = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
@@ -203,12 +377,14 @@ def lpips_state_dict(lin_sd: Mapping, backbone_sd: Optional[Mapping] = None) -> 
         for k, v in extract_state_dict(backbone_sd).items():
             if k.startswith("classifier."):
                 continue
-            for old, new in _FEATURES.items():
+            for old, new in features.items():
                 if k.startswith(old):
                     out[new + k[len(old):]] = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
                     break
             else:
-                raise KeyError(f"unexpected key {k!r} in the AlexNet state dict (expected features.{{0,3,6,8,10}}.* and classifier.*)")
+                name = "AlexNet" if net == "alex" else "vgg16"
+                want = ",".join(str(c[1]) for c in _NETS[net][0])
+                raise KeyError(f"unexpected key {k!r} in the {name} state dict (expected features.{{{want}}}.* and classifier.*)")
     for k in range(5):
         a, b = f"lin{k}.model.1.weight", f"lins.{k}.model.1.weight"
         if a in out and b not in out:
@@ -219,9 +395,9 @@ def lpips_state_dict(lin_sd: Mapping, backbone_sd: Optional[Mapping] = None) -> 
 
 
 def load_lpips(lin_ckpt: Union[str, Mapping], backbone: Union[str, Mapping, None] = None,
-               device: Optional[Union[str, torch.device]] = None, strict: bool = True) -> LPIPS:
+               device: Optional[Union[str, torch.device]] = None, strict: bool = True, net: str = "alex") -> LPIPS:
     """Build an LPIPS on `device` (default: current GPU).  `lin_ckpt` is a full LPIPS state dict, or the package's weight file
-    (lin* keys only) with `backbone` a torchvision AlexNet state dict; each a path (read with the torch-free reader) or a mapping.
+    (lin* keys only) with `backbone` a torchvision AlexNet (net="alex") or vgg16 (net="vgg") state dict; each a path (read with the torch-free reader) or a mapping.
     The module's own shift / scale buffers stand in when a file leaves them out.  strict=True raises for any other missing or
     unexpected key, as load_state_dict does."""
     from .api import _read_checkpoint_file
@@ -230,20 +406,20 @@ def load_lpips(lin_ckpt: Union[str, Mapping], backbone: Union[str, Mapping, None
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     if device is None or torch.device(device).type != "cuda":
         raise RuntimeError("celebrity_image_denoiser_amd.load_lpips: an AMD GPU is required (no CPU fallback)")
-    model = build_lpips(lin_ckpt, backbone, strict, _read_checkpoint_file)
+    model = build_lpips(lin_ckpt, backbone, strict, _read_checkpoint_file, net=net)
     model.to(device).eval()
     model.pack_weights()
     return model
 
 
-def build_lpips(lin_ckpt, backbone=None, strict: bool = True, reader=None) -> LPIPS:
+def build_lpips(lin_ckpt, backbone=None, strict: bool = True, reader=None, net: str = "alex") -> LPIPS:
     """load_lpips without the move to the GPU: the module on the CPU, weights loaded (the loader's key handling, testable anywhere)."""
     if reader is None:
         from .api import _read_checkpoint_file as reader
     lin_sd = reader(lin_ckpt) if isinstance(lin_ckpt, str) else lin_ckpt
     back_sd = reader(backbone) if isinstance(backbone, str) else backbone
-    sd = lpips_state_dict(lin_sd, back_sd)
-    model = LPIPS()
+    model = LPIPS(net)
+    sd = lpips_state_dict(lin_sd, back_sd, net)
     for k, v in model.scaling_layer.state_dict(prefix="scaling_layer.").items():
         sd.setdefault(k, v)
     model.load_state_dict(sd, strict=strict)

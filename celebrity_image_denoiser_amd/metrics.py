@@ -100,10 +100,10 @@ def quality(a, b, metrics=("psnr", "ssim", "ms_ssim")):
 
 
 def lpips(a, b, model, unit_view: bool = False):
-    """Per-image LPIPS(net='alex') of two device batches under `model` (lpips.LPIPS), computed by HIP kernels (cid_lpips,
-    include/cid.h): float64 tensor [N] on the inputs' GPU.  Operands as in quality(): float32 [N,3,H,W] in [-1,1] or uint8
+    """Per-image LPIPS of two device batches under `model` (lpips.LPIPS, net='alex' or 'vgg'), computed by HIP kernels (cid_lpips /
+    cid_vgg_lpips, include/cid.h): float64 tensor [N] on the inputs' GPU.  Operands as in quality(): float32 [N,3,H,W] in [-1,1] or uint8
     [N,H,W,3] (read as (u/255-0.5)/0.5), each its own format.  unit_view=True feeds x*0.5+0.5 instead, as the reference trainers do
-    (training.py:389).  H, W >= 31, else ValueError."""
+    (training.py:389).  H, W >= 31 (net='alex') or 16 <= H, W <= 512 (net='vgg'), else ValueError."""
     from .lpips import LPIPS
 
     if not isinstance(model, LPIPS):

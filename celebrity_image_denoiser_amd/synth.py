@@ -665,33 +665,44 @@ def cgan_latent_np(n: int, seed: int, first_index: int = 0) -> np.ndarray:
 LPIPS_CHANNELS = (64, 192, 384, 256, 256)
 LPIPS_SHIFT = (-.030, -.088, -.188)
 LPIPS_SCALE = (.458, .448, .450)
+LPIPS_VGG_CHANNELS = (64, 128, 256, 512, 512)
+# (slice, torchvision vgg16.features index, Cin, Cout, kernel)
+LPIPS_VGG_CONVS = ((1, 0, 3, 64, 3), (1, 2, 64, 64, 3), (2, 5, 64, 128, 3), (2, 7, 128, 128, 3), (3, 10, 128, 256, 3), (3, 12, 256, 256, 3),
+                   (3, 14, 256, 256, 3), (4, 17, 256, 512, 3), (4, 19, 512, 512, 3), (4, 21, 512, 512, 3), (5, 24, 512, 512, 3),
+                   (5, 26, 512, 512, 3), (5, 28, 512, 512, 3))
 
 
-def lpips_param_shapes() -> "OrderedDict[str, tuple]":
-    """state_dict key -> shape of lpips.LPIPS(net='alex') in the module's own order, the lins.* aliases of lin* last."""
+def lpips_param_shapes(net: str = "alex") -> "OrderedDict[str, tuple]":
+    """state_dict key -> shape of lpips.LPIPS(net=net) in the module's own order, the lins.* aliases of lin* last."""
+    if net not in ("alex", "vgg"):
+        raise ValueError(f"unknown net {net!r}")
     out: "OrderedDict[str, tuple]" = OrderedDict()
     out["scaling_layer.shift"] = (1, 3, 1, 1)
     out["scaling_layer.scale"] = (1, 3, 1, 1)
-    for k, idx, cin, cout, ks in ((1, 0, 3, 64, 11), (2, 3, 64, 192, 5), (3, 6, 192, 384, 3), (4, 8, 384, 256, 3), (5, 10, 256, 256, 3)):
+    convs = LPIPS_VGG_CONVS if net == "vgg" else ((1, 0, 3, 64, 11), (2, 3, 64, 192, 5), (3, 6, 192, 384, 3), (4, 8, 384, 256, 3), (5, 10, 256, 256, 3))
+    channels = LPIPS_VGG_CHANNELS if net == "vgg" else LPIPS_CHANNELS
+    for k, idx, cin, cout, ks in convs:
         out[f"net.slice{k}.{idx}.weight"] = (cout, cin, ks, ks)
         out[f"net.slice{k}.{idx}.bias"] = (cout,)
-    for k, c in enumerate(LPIPS_CHANNELS):
+    for k, c in enumerate(channels):
         out[f"lin{k}.model.1.weight"] = (1, c, 1, 1)
-    for k, c in enumerate(LPIPS_CHANNELS):
+    for k, c in enumerate(channels):
         out[f"lins.{k}.model.1.weight"] = (1, c, 1, 1)
     return out
 
 
-def make_lpips_state_dict(kind: str = "default", seed: int = WEIGHT_SEED) -> "OrderedDict[str, np.ndarray]":
-    """Synthetic weights keyed like lpips.LPIPS(net='alex'), from the hash streams "lpips:<kind>:<key>".  No pretrained weights ship
-    with this package; these keep the activations alive through the five ReLUs so that every tap carries signal.
+def make_lpips_state_dict(kind: str = "default", seed: int = WEIGHT_SEED, net: str = "alex") -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights keyed like lpips.LPIPS(net=net), from the hash streams "lpips:<kind>:<key>" (net="alex") or
+    "lpips_vgg:<kind>:<key>" (net="vgg").  No pretrained weights ship
+    with this package; these keep the activations alive through the ReLUs so that every tap carries signal.
     Convolutions are He-uniform, U(+-sqrt(6 / fan_in)); biases U(+-0.05) ("default") or U(+-0.5) ("hot", which also doubles the
     weights' gain: larger, sparser activations).  lin weights are non-negative, u / sum(u) * (1 + 0.25 (2 v - 1)) per layer: they sum
     to about 1.  shift / scale are the package's constants.  lins.* repeat lin*."""
     if kind not in ("default", "hot"):
         raise ValueError(f"unknown weight set {kind!r}")
+    stream = ("lpips_vgg:" if net == "vgg" else "lpips:") + kind + ":"
     sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
-    for key, shape in lpips_param_shapes().items():
+    for key, shape in lpips_param_shapes(net).items():
         n = int(np.prod(shape))
         if key == "scaling_layer.shift":
             v = np.array(LPIPS_SHIFT)
@@ -701,9 +712,9 @@ def make_lpips_state_dict(kind: str = "default", seed: int = WEIGHT_SEED) -> "Or
             sd[key] = sd["lin" + key[len("lins."):]]
             continue
         else:
-            u = hash_uniform(seed, _fnv1a64("lpips:" + kind + ":" + key), n)
+            u = hash_uniform(seed, _fnv1a64(stream + key), n)
             if key.startswith("lin"):
-                g = hash_uniform(seed, _fnv1a64("lpips:" + kind + ":" + key + ":gain"), 1)[0]
+                g = hash_uniform(seed, _fnv1a64(stream + key + ":gain"), 1)[0]
                 v = u / u.sum() * (1.0 + 0.25 * (2.0 * g - 1.0))
             elif key.endswith(".weight"):
                 fan_in = shape[1] * shape[2] * shape[3]
@@ -712,3 +723,12 @@ def make_lpips_state_dict(kind: str = "default", seed: int = WEIGHT_SEED) -> "Or
                 v = (2.0 * u - 1.0) * (0.05 if kind == "default" else 0.5)
         sd[key] = v.astype(np.float32).reshape(shape)
     return sd
+
+
+def vgg_loss_state_dict(lpips_vgg_sd) -> "OrderedDict[str, np.ndarray]":
+    """The reference VGGPerceptualLoss's state dict (slice.N.*) cut from a make_lpips_state_dict(net="vgg") one: slice1 ... slice3."""
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for k, idx, *_ in LPIPS_VGG_CONVS[:7]:
+        for leaf in ("weight", "bias"):
+            out[f"slice.{idx}.{leaf}"] = lpips_vgg_sd[f"net.slice{k}.{idx}.{leaf}"]
+    return out

@@ -840,6 +840,76 @@ int cid_lpips(cid_lpips_t h, const void* a, int fmt_a, const void* b, int fmt_b,
               double* layers, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * VGG16 features — what the reference's trainers build on torchvision's vgg16: lpips.LPIPS(net='vgg') of lpips 0.1.4, the ESRGAN
+ * trainer's perceptual metric (esrgan_code/esrgan_train.py:65,133), and VGGPerceptualLoss, the content loss of the SRGAN and denoise
+ * trainers (srgan_code/sr_ganTrainGNew.py:83-94,217,405; denoise_gan_code/training.py:101-111).  Forward only, eval mode, fp32.
+ * THE DEFINITION (kept here and nowhere else):
+ *
+ *   1. The backbone is torchvision vgg16 `features`, every convolution Conv2d(Cin,Cout,3,pad 1) + ReLU, every pool MaxPool2d(2,2)
+ *      without padding, floor mode (an odd last row or column is dropped).  By `features` index:
+ *        slice1   0: 3->64     2: 64->64                          relu1_2   H1 x W1 = H x W
+ *        slice2   pool,  5: 64->128    7: 128->128                relu2_2   H2 = H1 / 2
+ *        slice3   pool, 10: 128->256  12: 256->256  14: 256->256  relu3_3   H3 = H2 / 2
+ *        slice4   pool, 17: 256->512  19: 512->512  21: 512->512  relu4_3   H4 = H3 / 2
+ *        slice5   pool, 24: 512->512  26: 512->512  28: 512->512  relu5_3   H5 = H4 / 2      (integer division; the same for W)
+ *   2. cid_vgg_lpips is LPIPS as cid_lpips defines it (items 1, 2 and 4 - 6 there: normalize, the scaling layer with the zero padding
+ *      applied to the SCALED tensor, unit vectors per pixel, d_k with the 1x1 `lin` weights, d = d_0 + ... + d_4) over the five taps
+ *      relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 of 64, 128, 256, 512, 512 channels.  The smallest accepted side is 16 (H5 = 1).
+ *      CID_LPIPS_UNIT_VIEW has cid_lpips's meaning.
+ *   3. cid_vgg_content_loss is MSELoss()(features[:16](a), features[:16](b)) per image pair: out[n] = mean over the 256 * H3 * W3
+ *      values of (relu3_3(a_n) - relu3_3(b_n))^2.  The operands enter the first convolution as they are read: no scaling layer and no
+ *      ImageNet normalisation, which is what the reference's class does with its [-1,1] tensors.  The trainer's scalar is the mean
+ *      of out.  The smallest accepted side is 4 (H3 = 1).  CID_LPIPS_UNIT_VIEW applies v*0.5f+0.5f first here too.
+ *
+ * State-dict names (cid_vgg_param_key order, 33 tensors, fp32): scaling_layer.shift, scaling_layer.scale ([1,3,1,1]);
+ * net.slice1.{0,2}, net.slice2.{5,7}, net.slice3.{10,12,14}, net.slice4.{17,19,21}, net.slice5.{24,26,28} .weight / .bias
+ * ([Cout,Cin,3,3] / [Cout]); lin0.model.1.weight ... lin4.model.1.weight ([1,C,1,1], C = 64, 128, 256, 512, 512).  The lins.* aliases
+ * are the caller's to drop.  The package's weight file holds only the lin* keys; the backbone is torchvision's vgg16 state dict
+ * (features.N.* -> net.sliceK.N.*).  The reference's VGGPerceptualLoss names the same first seven convolutions slice.N.*.
+ *
+ * The handle mirrors cid_lpips_* one for one, with one difference: cid_vgg_upload_weights accepts either all 33 tensors or exactly
+ * the 14 tensors of net.slice1 ... net.slice3; the second form serves cid_vgg_content_loss only (cid_vgg_lpips returns
+ * CID_ERR_STATE on it).  Any other set of tensors is CID_ERR_STATE.
+ *
+ * Operands, out, layers, flags and guarantees are cid_lpips's: a and b are fp32 [N,3,H,W] or uint8 [N,H,W,3] (read as
+ * (u/255 - 0.5)/0.5; the same bits as the normalised fp32 copy), out is device double [N], layers (cid_vgg_lpips only, may be NULL)
+ * device double [N][5].  Both towers run as one batch of 2 N images: 1 + 12 + 1 launches on `stream` (1 + 6 + 1 for the content
+ * loss), no host synchronisation.  The first convolution runs on the VALU, the other twelve on the exact-fp32 MFMA with the pools
+ * taken while the operand is staged (no pooled tensor exists); from the stored fp32 taps on everything is double in a fixed order.
+ * No atomics, and no launch dimension other than grid.x grows with N; every sum's order depends on (H, W) and the pixel alone: an
+ * image pair's result is bit-identical in any batch and at any position in it, the value of (x, x) is exactly 0 and (a, b) gives
+ * the bits of (b, a).  `what` selects the form a workspace or a view is for: CID_VGG_LPIPS or CID_VGG_CONTENT.
+ * THE LARGEST ACCEPTED SIDE IS 512 (H and W each): the convolution kernel stages whole rows of a map in LDS, and its widest plane
+ * holds the rows a run of columns touches in a map up to 512 wide.  Checked on the host before any launch:
+ *   CID_ERR_INVALID    null pointer (layers may be NULL), unknown format or form, misaligned fp32 operand / out / layers, unknown flags
+ *   CID_ERR_SHAPE      N outside [1, 2^20], H or W < 16 (cid_vgg_lpips) or < 4 (cid_vgg_content_loss), H or W > 512,
+ *                      or more than (2^31 - 1) * 64 pixels in the 2 N images
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_vgg_workspace_bytes(what, N, H, W) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded, or cid_vgg_lpips on a handle that holds slice1 ... slice3 only
+ *
+ * cid_vgg_stage_view (testing aid): where the last call left `stage` = "relu1" ... "relu5" (the five taps above; "relu1" ... "relu3"
+ * for CID_VGG_CONTENT) in its workspace, in the layout cid_lpips_stage_view describes.  Unknown stage -> CID_ERR_KEY.
+ */
+typedef struct cid_vgg_s* cid_vgg_t;
+enum { CID_VGG_LPIPS = 0, CID_VGG_CONTENT = 1 };
+#define CID_VGG_NUM_WEIGHTS 33
+#define CID_VGG_MAX_SIDE 512
+int cid_vgg_create(cid_vgg_t* out);
+void cid_vgg_destroy(cid_vgg_t h);
+const char* cid_vgg_last_error(cid_vgg_t h);
+const char* cid_vgg_param_key(cid_vgg_t h, int i);
+int cid_vgg_set_weight(cid_vgg_t h, const char* key, const void* host_data, const int64_t* shape, int ndim);
+int cid_vgg_missing_weights(cid_vgg_t h, int* count);
+size_t cid_vgg_packed_weights_bytes(cid_vgg_t h);
+int cid_vgg_upload_weights(cid_vgg_t h, void* device_blob, void* stream);
+int cid_vgg_workspace_bytes(int what, int N, int H, int W, size_t* bytes);
+int cid_vgg_stage_view(int what, const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block);
+int cid_vgg_lpips(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
+                  double* layers, void* workspace, size_t workspace_bytes, void* stream);
+int cid_vgg_content_loss(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
  * kernels, so a forward enqueued after it exposes any kernel that reads LDS words it has not written.
  */
