@@ -246,43 +246,23 @@ def check(handle, code: int):
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
 
 
-def check_esr(handle, code: int):
-    """check() for a cid_esr_t handle."""
+def check_abi(abi: str, handle, code: int):
+    """check() for the handle of the family cid_<abi>_*: "esr", "sr", "cg", "lpips", "vgg" or "disc"."""
     if code != CID_OK:
-        msg = lib().cid_esr_last_error(handle) if handle else None
-        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
-
-
-def check_sr(handle, code: int):
-    """check() for a cid_sr_t handle."""
-    if code != CID_OK:
-        msg = lib().cid_sr_last_error(handle) if handle else None
-        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
-
-
-def check_cg(handle, code: int):
-    """check() for a cid_cg_t handle."""
-    if code != CID_OK:
-        msg = lib().cid_cg_last_error(handle) if handle else None
-        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
-
-
-def check_lpips(handle, code: int):
-    """check() for a cid_lpips_t handle."""
-    if code != CID_OK:
-        msg = lib().cid_lpips_last_error(handle) if handle else None
-        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
-
-
-def check_vgg(handle, code: int):
-    """check() for a cid_vgg_t handle."""
-    if code != CID_OK:
-        msg = lib().cid_vgg_last_error(handle) if handle else None
+        msg = getattr(lib(), f"cid_{abi}_last_error")(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
 
 
 def check_disc(handle, code: int):
     """check() for a cid_disc_t handle."""
-    if code != CID_OK:
-        msg = lib().cid_disc_last_error(handle) if handle else None
-        raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
+    check_abi("disc", handle, code)
+
+
+def check_lpips(handle, code: int):
+    """check() for a cid_lpips_t handle (the tests call it)."""
+    check_abi("lpips", handle, code)
+
+
+def check_vgg(handle, code: int):
+    """check() for a cid_vgg_t handle (the tests call it)."""
+    check_abi("vgg", handle, code)

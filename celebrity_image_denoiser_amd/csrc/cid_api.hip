@@ -35,6 +35,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "weight_store.h"
+
 namespace {
 
 using namespace cid;
@@ -2797,33 +2799,88 @@ constexpr size_t kEsrHeadSeg = (size_t)E_HEAD_K * 64 + 128;      // weights, bia
 constexpr size_t kEsrConvSeg = (size_t)E_CONV_W + 256;           // weights, bias[64], s[64], t[64], slope (padded to 64)
 constexpr size_t kEsrTailSeg = (size_t)E_TAIL_W + 64;            // weights, bias[3] (padded to 64)
 
-enum EsrKind { ESR_W, ESR_VEC, ESR_COUNT };                      // a convolution weight, a vector, num_batches_tracked
-struct EsrKey { std::string name; EsrKind kind; int64_t shape[4]; int ndim; size_t count; };
+// The key tables and pack steps below stand on WeightStore (weight_store.h).  What SRGAN shares with ESRGAN is written once here.
+void keys_head9(KeyTable& k) {
+    k.conv("initial.0.", 64, 3, 9);
+    k.tensor("initial.1.weight", {1});
+}
 
-std::vector<EsrKey> esr_keys(int R) {
-    std::vector<EsrKey> k;
-    const auto w = [&](const std::string& n, int co, int ci, int ks) { k.push_back({n, ESR_W, {co, ci, ks, ks}, 4, (size_t)co * ci * ks * ks}); };
-    const auto v = [&](const std::string& n, int c) { k.push_back({n, ESR_VEC, {c, 0, 0, 0}, 1, (size_t)c}); };
-    w("initial.0.weight", 64, 3, 9);
-    v("initial.0.bias", 64);
-    v("initial.1.weight", 1);
-    for (int i = 0; i < R; ++i) {
-        const std::string b = "residuals." + std::to_string(i) + ".block.";
-        for (int c = 0; c < 2; ++c) {
-            const std::string conv = b + std::to_string(3 * c) + ".", bn = b + std::to_string(3 * c + 1) + ".";
-            w(conv + "weight", 64, 64, 3);
-            v(conv + "bias", 64);
-            v(bn + "weight", 64);
-            v(bn + "bias", 64);
-            v(bn + "running_mean", 64);
-            v(bn + "running_var", 64);
-            k.push_back({bn + "num_batches_tracked", ESR_COUNT, {0, 0, 0, 0}, 0, 1});
-            if (c == 0) v(b + "2.weight", 1);
-        }
+// <blk>0 conv, <blk>1 BatchNorm, <blk>2 PReLU, <blk>3 conv, <blk>4 BatchNorm
+void keys_res_block(KeyTable& k, const std::string& blk) {
+    for (int c = 0; c < 2; ++c) {
+        k.conv(blk + std::to_string(3 * c) + ".", 64, 64, 3);
+        k.batchnorm(blk + std::to_string(3 * c + 1) + ".", 64);
+        if (c == 0) k.tensor(blk + "2.weight", {1});
     }
-    w("final.weight", 3, 64, 9);
-    v("final.bias", 3);
+}
+
+KeyTable esr_keys(int R) {
+    KeyTable k;
+    keys_head9(k);
+    for (int i = 0; i < R; ++i) keys_res_block(k, "residuals." + std::to_string(i) + ".block.");
+    k.conv("final.", 3, 64, 9);
     return k;
+}
+
+// The BatchNorm under the key prefix `bn` folded to y = s*z + t with s = gamma / sqrt(running_var + eps), t = beta - running_mean * s,
+// derived in fp64 and rounded once to fp32.
+void pack_bn_fold(const WeightStore& w, const std::string& bn, double eps, int C, float* s_out, float* t_out) {
+    const float *gamma = w.get(bn + "weight"), *beta = w.get(bn + "bias"), *mean = w.get(bn + "running_mean"), *var = w.get(bn + "running_var");
+    for (int ch = 0; ch < C; ++ch) {
+        const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + eps);
+        s_out[ch] = (float)s;
+        t_out[ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
+    }
+}
+
+// A 64-channel convolution's [co][K] weights as the [k][64] rows a head kernel reads.
+void pack_k64(float* dst, const float* w, int K) {
+    for (int co = 0; co < 64; ++co)
+        for (int k = 0; k < K; ++k) dst[(size_t)k * 64 + co] = w[(size_t)co * K + k];
+}
+
+// initial.*, the 9x9 head: [ci][kh][kw][co], bias, the PReLU's slope
+void pack_head9(const WeightStore& w, float* seg) {
+    pack_k64(seg, w.get("initial.0.weight"), E_HEAD_K);
+    std::memcpy(seg + E_HEAD_K * 64, w.get("initial.0.bias"), 64 * sizeof(float));
+    seg[E_HEAD_K * 64 + 64] = w.get("initial.1.weight")[0];
+}
+
+// One 3x3 64 -> 64 convolution into k_esr_conv's segment layout.
+void pack_conv64(float* seg, const float* w, const float* bias) {
+    for (int co = 0; co < 64; ++co)
+        for (int ci = 0; ci < 64; ++ci)
+            for (int tap = 0; tap < 9; ++tap) seg[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 64 + co] = w[((size_t)co * 64 + ci) * 9 + tap];
+    std::memcpy(seg + E_CONV_BIAS, bias, 64 * sizeof(float));
+}
+
+// Convolution c (0, 1) of the residual block under `blk` with its BatchNorm folded; the first one carries the block's PReLU slope.
+void pack_res_conv(const WeightStore& w, float* seg, const std::string& blk, int c, double eps) {
+    const std::string conv = blk + std::to_string(3 * c) + ".", bn = blk + std::to_string(3 * c + 1) + ".";
+    pack_conv64(seg, w.get(conv + "weight"), w.get(conv + "bias"));
+    pack_bn_fold(w, bn, eps, 64, seg + E_CONV_S, seg + E_CONV_T);
+    seg[E_CONV_SLOPE] = c == 0 ? w.get(blk + "2.weight")[0] : 0.f;
+}
+
+// final.*, the 9x9 tail: [ci][kh][co * 9 + kw], bias
+void pack_tail9(const WeightStore& w, float* seg) {
+    const float* f = w.get("final.weight");
+    for (int co = 0; co < 3; ++co)
+        for (int ci = 0; ci < 64; ++ci)
+            for (int kh = 0; kh < 9; ++kh)
+                for (int kw = 0; kw < 9; ++kw)
+                    seg[((size_t)ci * 9 + kh) * E_TAIL_WROW + co * 9 + kw] = f[(((size_t)co * 64 + ci) * 9 + kh) * 9 + kw];
+    std::memcpy(seg + E_TAIL_W, w.get("final.bias"), 3 * sizeof(float));
+}
+
+// The argument checks cid_esr_forward and cid_sr_forward share.
+int check_image_io(WeightStore* h, const std::string& fn, const void* in, int in_fmt, const void* out, int out_fmt, const void* workspace) {
+    if (!in || !out || !workspace) return h->fail(CID_ERR_INVALID, fn + ": null pointer");
+    if ((in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) || (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC))
+        return h->fail(CID_ERR_INVALID, fn + ": unknown format");
+    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
+        return h->fail(CID_ERR_INVALID, fn + ": misaligned fp32 operand");
+    return CID_OK;
 }
 
 struct EsrPlan {
@@ -2848,71 +2905,19 @@ int esr_plan(int N, int H, int W, EsrPlan& p) {
 
 }  // namespace
 
-struct cid_esr_s {
+struct cid_esr_s : WeightStore {
     int R = 0;
-    std::vector<EsrKey> keys;
-    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
-    std::vector<char> have;
     double eps[2 * kEsrMaxBlocks];
-    std::vector<float> staging;
-    const float* dev_blob = nullptr;
-    std::string err;
     size_t blob_floats() const { return kEsrHeadSeg + 2 * (size_t)R * kEsrConvSeg + kEsrTailSeg; }
-    int find(const std::string& k) const {
-        for (size_t i = 0; i < keys.size(); ++i)
-            if (keys[i].name == k) return (int)i;
-        return -1;
-    }
 };
 
 namespace {
-int efail(cid_esr_t h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
-// The blob from the staged tensors: the kernels' weight layouts, and each BatchNorm folded to y = s*z + t with
-// s = gamma / sqrt(running_var + eps), t = beta - running_mean * s, derived in fp64 and rounded once to fp32.
-void esr_pack(cid_esr_t h) {
-    h->staging.assign(h->blob_floats(), 0.f);
-    float* b = h->staging.data();
-    const auto get = [&](const std::string& k) -> const float* { return h->raw[h->find(k)].data(); };
-    {   // head: [ci][kh][kw][co]
-        const float* w = get("initial.0.weight");
-        for (int co = 0; co < 64; ++co)
-            for (int k = 0; k < E_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * E_HEAD_K + k];
-        std::memcpy(b + E_HEAD_K * 64, get("initial.0.bias"), 64 * sizeof(float));
-        b[E_HEAD_K * 64 + 64] = get("initial.1.weight")[0];
-    }
-    for (int i = 0; i < h->R; ++i)
-        for (int c = 0; c < 2; ++c) {
-            float* seg = b + kEsrHeadSeg + (size_t)(2 * i + c) * kEsrConvSeg;
-            const std::string blk = "residuals." + std::to_string(i) + ".block.";
-            const std::string conv = blk + std::to_string(3 * c) + ".", bn = blk + std::to_string(3 * c + 1) + ".";
-            const float* w = get(conv + "weight");
-            for (int co = 0; co < 64; ++co)
-                for (int ci = 0; ci < 64; ++ci)
-                    for (int tap = 0; tap < 9; ++tap)
-                        seg[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 64 + co] = w[((size_t)co * 64 + ci) * 9 + tap];
-            std::memcpy(seg + E_CONV_BIAS, get(conv + "bias"), 64 * sizeof(float));
-            const float *gamma = get(bn + "weight"), *beta = get(bn + "bias"), *mean = get(bn + "running_mean"), *var = get(bn + "running_var");
-            for (int ch = 0; ch < 64; ++ch) {
-                const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + h->eps[2 * i + c]);
-                seg[E_CONV_S + ch] = (float)s;
-                seg[E_CONV_T + ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
-            }
-            seg[E_CONV_SLOPE] = c == 0 ? get(blk + "2.weight")[0] : 0.f;
-        }
-    {   // tail: [ci][kh][co * 9 + kw]
-        float* seg = b + kEsrHeadSeg + 2 * (size_t)h->R * kEsrConvSeg;
-        const float* w = get("final.weight");
-        for (int co = 0; co < 3; ++co)
-            for (int ci = 0; ci < 64; ++ci)
-                for (int kh = 0; kh < 9; ++kh)
-                    for (int kw = 0; kw < 9; ++kw)
-                        seg[((size_t)ci * 9 + kh) * E_TAIL_WROW + co * 9 + kw] = w[(((size_t)co * 64 + ci) * 9 + kh) * 9 + kw];
-        std::memcpy(seg + E_TAIL_W, get("final.bias"), 3 * sizeof(float));
-    }
+// The blob from the staged tensors: the head, the 2 R block convolutions, the tail.
+void esr_pack(const cid_esr_s* h, float* b) {
+    pack_head9(*h, b);
+    for (int l = 0; l < 2 * h->R; ++l)
+        pack_res_conv(*h, b + kEsrHeadSeg + (size_t)l * kEsrConvSeg, "residuals." + std::to_string(l / 2) + ".block.", l % 2, h->eps[l]);
+    pack_tail9(*h, b + kEsrHeadSeg + 2 * (size_t)h->R * kEsrConvSeg);
 }
 }  // namespace
 
@@ -2924,10 +2929,8 @@ int cid_esr_create(cid_esr_t* out, int num_residuals) {
     if (num_residuals < 0 || num_residuals > kEsrMaxBlocks) return CID_ERR_INVALID;
     cid_esr_s* h = new (std::nothrow) cid_esr_s();
     if (!h) return CID_ERR_INVALID;
+    h->init("cid_esr", esr_keys(num_residuals));
     h->R = num_residuals;
-    h->keys = esr_keys(num_residuals);
-    h->raw.resize(h->keys.size());
-    h->have.assign(h->keys.size(), 0);
     std::fill(h->eps, h->eps + 2 * kEsrMaxBlocks, 1e-5);
     *out = h;
     return CID_OK;
@@ -2937,60 +2940,27 @@ void cid_esr_destroy(cid_esr_t h) { delete h; }
 
 const char* cid_esr_last_error(cid_esr_t h) { return h ? h->err.c_str() : "null handle"; }
 
-const char* cid_esr_param_key(cid_esr_t h, int i) {
-    if (!h || i < 0 || (size_t)i >= h->keys.size()) return nullptr;
-    return h->keys[i].name.c_str();
-}
+const char* cid_esr_param_key(cid_esr_t h, int i) { return h ? h->key(i) : nullptr; }
 
 int cid_esr_set_weight(cid_esr_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    if (!h) return CID_ERR_INVALID;
-    if (!key || !data || (!shape && ndim > 0)) return efail(h, CID_ERR_INVALID, "cid_esr_set_weight: null argument");
-    const int i = h->find(key);
-    if (i < 0) return efail(h, CID_ERR_KEY, std::string("cid_esr_set_weight: unexpected key '") + key + "'");
-    const EsrKey& k = h->keys[i];
-    if (k.kind == ESR_COUNT) {   // num_batches_tracked: part of the state_dict, unused in eval mode
-        if (ndim != 0) return efail(h, CID_ERR_SHAPE, "cid_esr_set_weight: size mismatch for " + k.name);
-        h->have[i] = 1;
-        return CID_OK;
-    }
-    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return efail(h, CID_ERR_SHAPE, "cid_esr_set_weight: size mismatch for " + k.name);
-    const float* f = static_cast<const float*>(data);
-    h->raw[i].assign(f, f + k.count);
-    h->have[i] = 1;
-    return CID_OK;
+    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
 }
 
 int cid_esr_set_bn_eps(cid_esr_t h, int block, int which, double eps) {
     if (!h) return CID_ERR_INVALID;
-    if (block < 0 || block >= h->R || (which != 0 && which != 1)) return efail(h, CID_ERR_INVALID, "cid_esr_set_bn_eps: no such BatchNorm");
-    if (!std::isfinite(eps) || eps < 0.0) return efail(h, CID_ERR_INVALID, "cid_esr_set_bn_eps: eps must be finite and >= 0");
-    h->eps[2 * block + which] = eps;
-    return CID_OK;
+    return h->set_bn_eps(block >= 0 && block < h->R && (which == 0 || which == 1) ? &h->eps[2 * block + which] : nullptr, eps);
 }
 
 int cid_esr_missing_weights(cid_esr_t h, int* count) {
     if (!h || !count) return CID_ERR_INVALID;
-    int m = 0;
-    for (size_t i = 0; i < h->keys.size(); ++i) m += h->keys[i].kind != ESR_COUNT && !h->have[i];
-    *count = m;
+    *count = h->missing();
     return CID_OK;
 }
 
 size_t cid_esr_packed_weights_bytes(cid_esr_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
 
 int cid_esr_upload_weights(cid_esr_t h, void* device_blob, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return efail(h, CID_ERR_INVALID, "cid_esr_upload_weights: null device pointer");
-    if ((uintptr_t)device_blob & 255) return efail(h, CID_ERR_WORKSPACE, "cid_esr_upload_weights: blob must be 256-byte aligned");
-    for (size_t i = 0; i < h->keys.size(); ++i)
-        if (h->keys[i].kind != ESR_COUNT && !h->have[i]) return efail(h, CID_ERR_STATE, "cid_esr_upload_weights: " + h->keys[i].name + " not set");
-    esr_pack(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return efail(h, CID_ERR_HIP, std::string("cid_esr_upload_weights: ") + hipGetErrorString(e));
-    h->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
+    return h ? h->upload(device_blob, stream, h->blob_floats(), [h](float* b) { esr_pack(h, b); }) : CID_ERR_INVALID;
 }
 
 int cid_esr_workspace_bytes(int N, int H, int W, size_t* bytes) {
@@ -3020,18 +2990,14 @@ int cid_esr_stage_view(const char* stage, int N, int H, int W, size_t* offset_by
 int cid_esr_forward(cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, void* workspace,
                     size_t workspace_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!in || !out || !workspace) return efail(h, CID_ERR_INVALID, "cid_esr_forward: null pointer");
-    if ((in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) || (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC))
-        return efail(h, CID_ERR_INVALID, "cid_esr_forward: unknown format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
-        return efail(h, CID_ERR_INVALID, "cid_esr_forward: misaligned fp32 operand");
+    if (const int rc = check_image_io(h, "cid_esr_forward", in, in_fmt, out, out_fmt, workspace)) return rc;
     EsrPlan p;
-    if (esr_plan(N, H, W, p) != CID_OK) return efail(h, CID_ERR_SHAPE, "cid_esr_forward: input shape not accepted (N, H, W >= 1, H*W < 2^31)");
+    if (esr_plan(N, H, W, p) != CID_OK) return h->fail(CID_ERR_SHAPE, "cid_esr_forward: input shape not accepted (N, H, W >= 1, H*W < 2^31)");
     if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return efail(h, CID_ERR_WORKSPACE, "cid_esr_forward: workspace smaller than cid_esr_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return efail(h, CID_ERR_STATE, "cid_esr_forward: weights not uploaded");
+        return h->fail(CID_ERR_WORKSPACE, "cid_esr_forward: workspace smaller than cid_esr_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_esr_forward: weights not uploaded");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return efail(h, CID_ERR_HIP, std::string("cid_esr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_esr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
     char* ws = static_cast<char*>(workspace);
     float *x1 = reinterpret_cast<float*>(ws + p.x1), *mid = reinterpret_cast<float*>(ws + p.mid), *cur = reinterpret_cast<float*>(ws + p.cur);
     const float* blob = h->dev_blob;
@@ -3088,36 +3054,16 @@ namespace {
 constexpr int kSrBlocks = 5;
 constexpr size_t kSrUpSeg = (size_t)S_UP_W + 256 + 64;           // weights, bias[256] in packed order, slope (padded to 64)
 
-std::vector<EsrKey> sr_keys(int stages) {
-    std::vector<EsrKey> k;
-    const auto w = [&](const std::string& n, int co, int ci, int ks) { k.push_back({n, ESR_W, {co, ci, ks, ks}, 4, (size_t)co * ci * ks * ks}); };
-    const auto v = [&](const std::string& n, int c) { k.push_back({n, ESR_VEC, {c, 0, 0, 0}, 1, (size_t)c}); };
-    w("initial.0.weight", 64, 3, 9);
-    v("initial.0.bias", 64);
-    v("initial.1.weight", 1);
-    for (int i = 0; i < kSrBlocks; ++i) {
-        const std::string b = "res_blocks." + std::to_string(i) + ".";
-        for (int c = 0; c < 2; ++c) {
-            const std::string conv = b + std::to_string(3 * c) + ".", bn = b + std::to_string(3 * c + 1) + ".";
-            w(conv + "weight", 64, 64, 3);
-            v(conv + "bias", 64);
-            v(bn + "weight", 64);
-            v(bn + "bias", 64);
-            v(bn + "running_mean", 64);
-            v(bn + "running_var", 64);
-            k.push_back({bn + "num_batches_tracked", ESR_COUNT, {0, 0, 0, 0}, 0, 1});
-            if (c == 0) v(b + "2.weight", 1);
-        }
-    }
-    w("mid.weight", 64, 64, 3);
-    v("mid.bias", 64);
+KeyTable sr_keys(int stages) {
+    KeyTable k;
+    keys_head9(k);
+    for (int i = 0; i < kSrBlocks; ++i) keys_res_block(k, "res_blocks." + std::to_string(i) + ".");
+    k.conv("mid.", 64, 64, 3);
     for (int u = 0; u < stages; ++u) {
-        w("upscale." + std::to_string(3 * u) + ".weight", 256, 64, 3);
-        v("upscale." + std::to_string(3 * u) + ".bias", 256);
-        v("upscale." + std::to_string(3 * u + 2) + ".weight", 1);
+        k.conv("upscale." + std::to_string(3 * u) + ".", 256, 64, 3);
+        k.tensor("upscale." + std::to_string(3 * u + 2) + ".weight", {1});
     }
-    w("final.weight", 3, 64, 9);
-    v("final.bias", 3);
+    k.conv("final.", 3, 64, 9);
     return k;
 }
 
@@ -3151,95 +3097,41 @@ int sr_plan(int N, int Hp, int Wp, int scale, SrPlan& p) {
 
 }  // namespace
 
-struct cid_sr_s {
+struct cid_sr_s : WeightStore {
     int scale = 1, stages = 0;
-    std::vector<EsrKey> keys;
-    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
-    std::vector<char> have;
     double eps[2 * kSrBlocks];
-    std::vector<float> staging;
-    const float* dev_blob = nullptr;
-    std::string err;
     // head, ten block convolutions, mid, the upscale stages, tail
     size_t up_off(int u) const { return kEsrHeadSeg + (2 * (size_t)kSrBlocks + 1) * kEsrConvSeg + (size_t)u * kSrUpSeg; }
     size_t tail_off() const { return up_off(stages); }
     size_t blob_floats() const { return tail_off() + kEsrTailSeg; }
-    int find(const std::string& k) const {
-        for (size_t i = 0; i < keys.size(); ++i)
-            if (keys[i].name == k) return (int)i;
-        return -1;
-    }
 };
 
 namespace {
-int sfail(cid_sr_t h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
-// One 3x3 64 -> 64 convolution into k_esr_conv's segment layout.
-void sr_pack_conv64(float* seg, const float* w, const float* bias) {
-    for (int co = 0; co < 64; ++co)
+// Upscale stage u: [half][chunk][tap][ci % 8][128 packed columns], the columns in the order of s_up_conv_channel; bias; slope.
+void sr_pack_up(const cid_sr_s* h, float* seg, int u) {
+    const float* w = h->get("upscale." + std::to_string(3 * u) + ".weight");
+    const float* bias = h->get("upscale." + std::to_string(3 * u) + ".bias");
+    for (int J = 0; J < 256; ++J) {
+        const int cc = s_up_conv_channel(J);
         for (int ci = 0; ci < 64; ++ci)
-            for (int tap = 0; tap < 9; ++tap) seg[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 64 + co] = w[((size_t)co * 64 + ci) * 9 + tap];
-    std::memcpy(seg + E_CONV_BIAS, bias, 64 * sizeof(float));
+            for (int tap = 0; tap < 9; ++tap)
+                seg[(size_t)(J / 128) * (64 * 9 * 128) + ((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 128 + J % 128] = w[((size_t)cc * 64 + ci) * 9 + tap];
+        seg[S_UP_BIAS + J] = bias[cc];
+    }
+    seg[S_UP_SLOPE] = h->get("upscale." + std::to_string(3 * u + 2) + ".weight")[0];
 }
 
-// The blob from the staged tensors: the kernels' weight layouts, each BatchNorm folded to y = s*z + t in fp64 as esr_pack does, `mid`
-// with the identity fold (s, t) = (1, 0), and each upscale stage's columns in the order of s_up_conv_channel.
-void sr_pack(cid_sr_t h) {
-    h->staging.assign(h->blob_floats(), 0.f);
-    float* b = h->staging.data();
-    const auto get = [&](const std::string& k) -> const float* { return h->raw[h->find(k)].data(); };
-    {   // head: [ci][kh][kw][co]
-        const float* w = get("initial.0.weight");
-        for (int co = 0; co < 64; ++co)
-            for (int k = 0; k < E_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * E_HEAD_K + k];
-        std::memcpy(b + E_HEAD_K * 64, get("initial.0.bias"), 64 * sizeof(float));
-        b[E_HEAD_K * 64 + 64] = get("initial.1.weight")[0];
-    }
-    for (int i = 0; i < kSrBlocks; ++i)
-        for (int c = 0; c < 2; ++c) {
-            float* seg = b + kEsrHeadSeg + (size_t)(2 * i + c) * kEsrConvSeg;
-            const std::string blk = "res_blocks." + std::to_string(i) + ".";
-            const std::string conv = blk + std::to_string(3 * c) + ".", bn = blk + std::to_string(3 * c + 1) + ".";
-            sr_pack_conv64(seg, get(conv + "weight"), get(conv + "bias"));
-            const float *gamma = get(bn + "weight"), *beta = get(bn + "bias"), *mean = get(bn + "running_mean"), *var = get(bn + "running_var");
-            for (int ch = 0; ch < 64; ++ch) {
-                const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + h->eps[2 * i + c]);
-                seg[E_CONV_S + ch] = (float)s;
-                seg[E_CONV_T + ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
-            }
-            seg[E_CONV_SLOPE] = c == 0 ? get(blk + "2.weight")[0] : 0.f;
-        }
-    {   // mid: bias only; fmaf(1, z, 0) = z
-        float* seg = b + kEsrHeadSeg + 2 * (size_t)kSrBlocks * kEsrConvSeg;
-        sr_pack_conv64(seg, get("mid.weight"), get("mid.bias"));
-        for (int ch = 0; ch < 64; ++ch) seg[E_CONV_S + ch] = 1.f;
-    }
-    for (int u = 0; u < h->stages; ++u) {   // [half][chunk][tap][ci % 8][128 packed columns]
-        float* seg = b + h->up_off(u);
-        const float* w = get("upscale." + std::to_string(3 * u) + ".weight");
-        const float* bias = get("upscale." + std::to_string(3 * u) + ".bias");
-        for (int J = 0; J < 256; ++J) {
-            const int cc = s_up_conv_channel(J);
-            for (int ci = 0; ci < 64; ++ci)
-                for (int tap = 0; tap < 9; ++tap)
-                    seg[(size_t)(J / 128) * (64 * 9 * 128) + ((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 128 + J % 128] = w[((size_t)cc * 64 + ci) * 9 + tap];
-            seg[S_UP_BIAS + J] = bias[cc];
-        }
-        seg[S_UP_SLOPE] = get("upscale." + std::to_string(3 * u + 2) + ".weight")[0];
-    }
-    {   // tail: [ci][kh][co * 9 + kw]
-        float* seg = b + h->tail_off();
-        const float* w = get("final.weight");
-        for (int co = 0; co < 3; ++co)
-            for (int ci = 0; ci < 64; ++ci)
-                for (int kh = 0; kh < 9; ++kh)
-                    for (int kw = 0; kw < 9; ++kw)
-                        seg[((size_t)ci * 9 + kh) * E_TAIL_WROW + co * 9 + kw] = w[(((size_t)co * 64 + ci) * 9 + kh) * 9 + kw];
-        std::memcpy(seg + E_TAIL_W, get("final.bias"), 3 * sizeof(float));
-    }
+// The blob from the staged tensors: the head, the ten block convolutions, `mid` with the identity fold (s, t) = (1, 0), the upscale
+// stages, the tail.
+void sr_pack(const cid_sr_s* h, float* b) {
+    pack_head9(*h, b);
+    for (int l = 0; l < 2 * kSrBlocks; ++l)
+        pack_res_conv(*h, b + kEsrHeadSeg + (size_t)l * kEsrConvSeg, "res_blocks." + std::to_string(l / 2) + ".", l % 2, h->eps[l]);
+    float* mid = b + kEsrHeadSeg + 2 * (size_t)kSrBlocks * kEsrConvSeg;   // bias only; fmaf(1, z, 0) = z
+    pack_conv64(mid, h->get("mid.weight"), h->get("mid.bias"));
+    std::fill(mid + E_CONV_S, mid + E_CONV_S + 64, 1.f);
+    for (int u = 0; u < h->stages; ++u) sr_pack_up(h, b + h->up_off(u), u);
+    pack_tail9(*h, b + h->tail_off());
 }
 }  // namespace
 
@@ -3253,9 +3145,7 @@ int cid_sr_create(cid_sr_t* out, int scale_factor) {
     if (!h) return CID_ERR_INVALID;
     h->scale = scale_factor;
     h->stages = sr_stages(scale_factor);
-    h->keys = sr_keys(h->stages);
-    h->raw.resize(h->keys.size());
-    h->have.assign(h->keys.size(), 0);
+    h->init("cid_sr", sr_keys(h->stages));
     std::fill(h->eps, h->eps + 2 * kSrBlocks, 1e-5);
     *out = h;
     return CID_OK;
@@ -3265,60 +3155,27 @@ void cid_sr_destroy(cid_sr_t h) { delete h; }
 
 const char* cid_sr_last_error(cid_sr_t h) { return h ? h->err.c_str() : "null handle"; }
 
-const char* cid_sr_param_key(cid_sr_t h, int i) {
-    if (!h || i < 0 || (size_t)i >= h->keys.size()) return nullptr;
-    return h->keys[i].name.c_str();
-}
+const char* cid_sr_param_key(cid_sr_t h, int i) { return h ? h->key(i) : nullptr; }
 
 int cid_sr_set_weight(cid_sr_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    if (!h) return CID_ERR_INVALID;
-    if (!key || !data || (!shape && ndim > 0)) return sfail(h, CID_ERR_INVALID, "cid_sr_set_weight: null argument");
-    const int i = h->find(key);
-    if (i < 0) return sfail(h, CID_ERR_KEY, std::string("cid_sr_set_weight: unexpected key '") + key + "'");
-    const EsrKey& k = h->keys[i];
-    if (k.kind == ESR_COUNT) {   // num_batches_tracked: part of the state_dict, unused in eval mode
-        if (ndim != 0) return sfail(h, CID_ERR_SHAPE, "cid_sr_set_weight: size mismatch for " + k.name);
-        h->have[i] = 1;
-        return CID_OK;
-    }
-    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return sfail(h, CID_ERR_SHAPE, "cid_sr_set_weight: size mismatch for " + k.name);
-    const float* f = static_cast<const float*>(data);
-    h->raw[i].assign(f, f + k.count);
-    h->have[i] = 1;
-    return CID_OK;
+    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
 }
 
 int cid_sr_set_bn_eps(cid_sr_t h, int block, int which, double eps) {
     if (!h) return CID_ERR_INVALID;
-    if (block < 0 || block >= kSrBlocks || (which != 0 && which != 1)) return sfail(h, CID_ERR_INVALID, "cid_sr_set_bn_eps: no such BatchNorm");
-    if (!std::isfinite(eps) || eps < 0.0) return sfail(h, CID_ERR_INVALID, "cid_sr_set_bn_eps: eps must be finite and >= 0");
-    h->eps[2 * block + which] = eps;
-    return CID_OK;
+    return h->set_bn_eps(block >= 0 && block < kSrBlocks && (which == 0 || which == 1) ? &h->eps[2 * block + which] : nullptr, eps);
 }
 
 int cid_sr_missing_weights(cid_sr_t h, int* count) {
     if (!h || !count) return CID_ERR_INVALID;
-    int m = 0;
-    for (size_t i = 0; i < h->keys.size(); ++i) m += h->keys[i].kind != ESR_COUNT && !h->have[i];
-    *count = m;
+    *count = h->missing();
     return CID_OK;
 }
 
 size_t cid_sr_packed_weights_bytes(cid_sr_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
 
 int cid_sr_upload_weights(cid_sr_t h, void* device_blob, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return sfail(h, CID_ERR_INVALID, "cid_sr_upload_weights: null device pointer");
-    if ((uintptr_t)device_blob & 255) return sfail(h, CID_ERR_WORKSPACE, "cid_sr_upload_weights: blob must be 256-byte aligned");
-    for (size_t i = 0; i < h->keys.size(); ++i)
-        if (h->keys[i].kind != ESR_COUNT && !h->have[i]) return sfail(h, CID_ERR_STATE, "cid_sr_upload_weights: " + h->keys[i].name + " not set");
-    sr_pack(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return sfail(h, CID_ERR_HIP, std::string("cid_sr_upload_weights: ") + hipGetErrorString(e));
-    h->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
+    return h ? h->upload(device_blob, stream, h->blob_floats(), [h](float* b) { sr_pack(h, b); }) : CID_ERR_INVALID;
 }
 
 int cid_sr_workspace_bytes(int N, int Hp, int Wp, int scale_factor, size_t* bytes) {
@@ -3353,26 +3210,22 @@ int cid_sr_stage_view(const char* stage, int N, int Hp, int Wp, int scale_factor
 int cid_sr_forward(cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, int pad_left, int pad_top,
                    int pad_right, int pad_bottom, unsigned flags, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!in || !out || !workspace) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: null pointer");
-    if ((in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) || (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC))
-        return sfail(h, CID_ERR_INVALID, "cid_sr_forward: unknown format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
-        return sfail(h, CID_ERR_INVALID, "cid_sr_forward: misaligned fp32 operand");
-    if (flags & ~(unsigned)CID_SR_RAW) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: unknown flags");
-    if ((flags & CID_SR_RAW) && out_fmt != CID_FMT_F32_NCHW) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: CID_SR_RAW needs an fp32 output");
+    if (const int rc = check_image_io(h, "cid_sr_forward", in, in_fmt, out, out_fmt, workspace)) return rc;
+    if (flags & ~(unsigned)CID_SR_RAW) return h->fail(CID_ERR_INVALID, "cid_sr_forward: unknown flags");
+    if ((flags & CID_SR_RAW) && out_fmt != CID_FMT_F32_NCHW) return h->fail(CID_ERR_INVALID, "cid_sr_forward: CID_SR_RAW needs an fp32 output");
     for (const int pad : {pad_left, pad_top, pad_right, pad_bottom})
-        if (pad < 0 || pad > 4096) return sfail(h, CID_ERR_INVALID, "cid_sr_forward: pads must lie in [0, 4096]");
+        if (pad < 0 || pad > 4096) return h->fail(CID_ERR_INVALID, "cid_sr_forward: pads must lie in [0, 4096]");
     if (N < 1 || H < 1 || W < 1 || H > 0x7fffffff - 8192 || W > 0x7fffffff - 8192)
-        return sfail(h, CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (N, H, W >= 1)");
+        return h->fail(CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (N, H, W >= 1)");
     const int Hp = H + pad_top + pad_bottom, Wp = W + pad_left + pad_right;
     SrPlan p;
     if (sr_plan(N, Hp, Wp, h->scale, p) != CID_OK)
-        return sfail(h, CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (scale^2 * Hp * Wp < 2^31)");
+        return h->fail(CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (scale^2 * Hp * Wp < 2^31)");
     if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return sfail(h, CID_ERR_WORKSPACE, "cid_sr_forward: workspace smaller than cid_sr_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return sfail(h, CID_ERR_STATE, "cid_sr_forward: weights not uploaded");
+        return h->fail(CID_ERR_WORKSPACE, "cid_sr_forward: workspace smaller than cid_sr_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_sr_forward: weights not uploaded");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return sfail(h, CID_ERR_HIP, std::string("cid_sr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_sr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
     char* ws = static_cast<char*>(workspace);
     float *x0 = reinterpret_cast<float*>(ws + p.x0), *mid = reinterpret_cast<float*>(ws + p.mid), *cur = reinterpret_cast<float*>(ws + p.cur);
     const float* blob = h->dev_blob;
@@ -3451,29 +3304,20 @@ const int kCgBn[4] = {0, 3, 6, 9};        // model.<i> of the four BatchNorms
 const int kCgUp[3] = {2, 5, 8};           // model.<i> of the three transposed convolutions
 const int kCgCin[3] = {128, 128, 64}, kCgCout[3] = {128, 64, 32};
 
-std::vector<EsrKey> cg_keys(int n_classes) {
-    std::vector<EsrKey> k;
-    const auto v = [&](const std::string& n, int c) { k.push_back({n, ESR_VEC, {c, 0, 0, 0}, 1, (size_t)c}); };
-    const auto bn = [&](int i, int c) {
-        const std::string b = "model." + std::to_string(i) + ".";
-        v(b + "weight", c);
-        v(b + "bias", c);
-        v(b + "running_mean", c);
-        v(b + "running_var", c);
-        k.push_back({b + "num_batches_tracked", ESR_COUNT, {0, 0, 0, 0}, 0, 1});
-    };
-    k.push_back({"label_emb.weight", ESR_W, {n_classes, CG_LATENT, 0, 0}, 2, (size_t)n_classes * CG_LATENT});
-    k.push_back({"l1.weight", ESR_W, {CG_FEAT, 2 * CG_LATENT, 0, 0}, 2, (size_t)CG_FEAT * 2 * CG_LATENT});
-    v("l1.bias", CG_FEAT);
-    bn(0, 128);
+std::string cg_layer(int i) { return "model." + std::to_string(i) + "."; }
+
+KeyTable cg_keys(int n_classes) {
+    KeyTable k;
+    k.tensor("label_emb.weight", {n_classes, CG_LATENT});
+    k.tensor("l1.weight", {CG_FEAT, 2 * CG_LATENT});
+    k.tensor("l1.bias", {CG_FEAT});
+    k.batchnorm(cg_layer(kCgBn[0]), 128);
     for (int u = 0; u < 3; ++u) {
-        const std::string c = "model." + std::to_string(kCgUp[u]) + ".";
-        k.push_back({c + "weight", ESR_W, {kCgCin[u], kCgCout[u], 4, 4}, 4, (size_t)kCgCin[u] * kCgCout[u] * 16});
-        v(c + "bias", kCgCout[u]);
-        bn(kCgBn[u + 1], kCgCout[u]);
+        k.tensor(cg_layer(kCgUp[u]) + "weight", {kCgCin[u], kCgCout[u], 4, 4});
+        k.tensor(cg_layer(kCgUp[u]) + "bias", {kCgCout[u]});
+        k.batchnorm(cg_layer(kCgBn[u + 1]), kCgCout[u]);
     }
-    k.push_back({"model.11.weight", ESR_W, {3, 32, 3, 3}, 4, 3 * 32 * 9});
-    v("model.11.bias", 3);
+    k.conv("model.11.", 3, 32, 3);
     return k;
 }
 
@@ -3498,15 +3342,9 @@ int cg_plan(int N, CgPlan& p) {
 
 }  // namespace
 
-struct cid_cg_s {
+struct cid_cg_s : WeightStore {
     int n_classes = 10;
-    std::vector<EsrKey> keys;
-    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
-    std::vector<char> have;
     double eps[4];
-    std::vector<float> staging;
-    const float* dev_blob = nullptr;
-    std::string err;
     // the linear, the three stages (weights, bias, s, t), the tail, the embedding table
     size_t up_off(int u) const {
         size_t at = cg_align64(CG_LIN_SEG);
@@ -3516,35 +3354,14 @@ struct cid_cg_s {
     size_t tail_off() const { return up_off(3); }
     size_t emb_off() const { return tail_off() + CG_TAIL_SEG; }
     size_t blob_floats() const { return emb_off() + cg_align64((size_t)n_classes * CG_LATENT); }
-    int find(const std::string& k) const {
-        for (size_t i = 0; i < keys.size(); ++i)
-            if (keys[i].name == k) return (int)i;
-        return -1;
-    }
 };
 
 namespace {
-int cgfail(cid_cg_t h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
-// The blob from the staged tensors: the kernels' weight layouts, each BatchNorm folded to y = s*v + t in fp64 as sr_pack does.
-void cg_pack(cid_cg_t h) {
-    h->staging.assign(h->blob_floats(), 0.f);
-    float* b = h->staging.data();
-    const auto get = [&](const std::string& k) -> const float* { return h->raw[h->find(k)].data(); };
-    const auto fold = [&](int which, int C, float* s_out, float* t_out) {
-        const std::string bn = "model." + std::to_string(kCgBn[which]) + ".";
-        const float *gamma = get(bn + "weight"), *beta = get(bn + "bias"), *mean = get(bn + "running_mean"), *var = get(bn + "running_var");
-        for (int ch = 0; ch < C; ++ch) {
-            const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + h->eps[which]);
-            s_out[ch] = (float)s;
-            t_out[ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
-        }
-    };
+// The blob from the staged tensors: the kernels' weight layouts, each BatchNorm folded (pack_bn_fold).
+void cg_pack(const cid_cg_s* h, float* b) {
+    const auto fold = [&](int which, int C, float* s_out, float* t_out) { pack_bn_fold(*h, cg_layer(kCgBn[which]), h->eps[which], C, s_out, t_out); };
     {   // linear: [tile][lane][52]: lane (l16, kq) holds row l16's weights of k = 4 s + kq
-        const float *w = get("l1.weight"), *bias = get("l1.bias");
+        const float *w = h->get("l1.weight"), *bias = h->get("l1.bias");
         for (int tile = 0; tile < CG_LIN_TILES; ++tile)
             for (int row = 0; row < 16; ++row) {
                 const int j = cg_lin_feature(tile, row);
@@ -3558,25 +3375,24 @@ void cg_pack(cid_cg_t h) {
     for (int u = 0; u < 3; ++u) {
         float* seg = b + h->up_off(u);
         const int CI = kCgCin[u], CO = kCgCout[u];
-        const std::string c = "model." + std::to_string(kCgUp[u]) + ".";
-        const float* w = get(c + "weight");
+        const float* w = h->get(cg_layer(kCgUp[u]) + "weight");
         for (int ci = 0; ci < CI; ++ci)
             for (int co = 0; co < CO; ++co)
                 for (int ky = 0; ky < 4; ++ky)
                     for (int kx = 0; kx < 4; ++kx) seg[cg_up_windex(CO, ci, co, ky, kx)] = w[(((size_t)ci * CO + co) * 4 + ky) * 4 + kx];
         float* tail = seg + (size_t)16 * CI * CO;
-        std::memcpy(tail, get(c + "bias"), CO * sizeof(float));
+        std::memcpy(tail, h->get(cg_layer(kCgUp[u]) + "bias"), CO * sizeof(float));
         fold(u + 1, CO, tail + CO, tail + 2 * CO);
     }
     {   // tail: [ci][tap][co], then the biases
         float* seg = b + h->tail_off();
-        const float* w = get("model.11.weight");
+        const float* w = h->get("model.11.weight");
         for (int co = 0; co < 3; ++co)
             for (int ci = 0; ci < 32; ++ci)
                 for (int tap = 0; tap < 9; ++tap) seg[(ci * 9 + tap) * 3 + co] = w[((size_t)co * 32 + ci) * 9 + tap];
-        std::memcpy(seg + CG_TAIL_W, get("model.11.bias"), 3 * sizeof(float));
+        std::memcpy(seg + CG_TAIL_W, h->get("model.11.bias"), 3 * sizeof(float));
     }
-    std::memcpy(b + h->emb_off(), get("label_emb.weight"), (size_t)h->n_classes * CG_LATENT * sizeof(float));
+    std::memcpy(b + h->emb_off(), h->get("label_emb.weight"), (size_t)h->n_classes * CG_LATENT * sizeof(float));
 }
 }  // namespace
 
@@ -3588,10 +3404,8 @@ int cid_cg_create(cid_cg_t* out, int n_classes) {
     if (n_classes < 1 || n_classes > kCgMaxClasses) return CID_ERR_INVALID;
     cid_cg_s* h = new (std::nothrow) cid_cg_s();
     if (!h) return CID_ERR_INVALID;
+    h->init("cid_cg", cg_keys(n_classes));
     h->n_classes = n_classes;
-    h->keys = cg_keys(n_classes);
-    h->raw.resize(h->keys.size());
-    h->have.assign(h->keys.size(), 0);
     std::fill(h->eps, h->eps + 4, 1e-5);
     *out = h;
     return CID_OK;
@@ -3601,60 +3415,26 @@ void cid_cg_destroy(cid_cg_t h) { delete h; }
 
 const char* cid_cg_last_error(cid_cg_t h) { return h ? h->err.c_str() : "null handle"; }
 
-const char* cid_cg_param_key(cid_cg_t h, int i) {
-    if (!h || i < 0 || (size_t)i >= h->keys.size()) return nullptr;
-    return h->keys[i].name.c_str();
-}
+const char* cid_cg_param_key(cid_cg_t h, int i) { return h ? h->key(i) : nullptr; }
 
 int cid_cg_set_weight(cid_cg_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    if (!h) return CID_ERR_INVALID;
-    if (!key || !data || (!shape && ndim > 0)) return cgfail(h, CID_ERR_INVALID, "cid_cg_set_weight: null argument");
-    const int i = h->find(key);
-    if (i < 0) return cgfail(h, CID_ERR_KEY, std::string("cid_cg_set_weight: unexpected key '") + key + "'");
-    const EsrKey& k = h->keys[i];
-    if (k.kind == ESR_COUNT) {   // num_batches_tracked: part of the state_dict, unused in eval mode
-        if (ndim != 0) return cgfail(h, CID_ERR_SHAPE, "cid_cg_set_weight: size mismatch for " + k.name);
-        h->have[i] = 1;
-        return CID_OK;
-    }
-    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return cgfail(h, CID_ERR_SHAPE, "cid_cg_set_weight: size mismatch for " + k.name);
-    const float* f = static_cast<const float*>(data);
-    h->raw[i].assign(f, f + k.count);
-    h->have[i] = 1;
-    return CID_OK;
+    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
 }
 
 int cid_cg_set_bn_eps(cid_cg_t h, int which, double eps) {
-    if (!h) return CID_ERR_INVALID;
-    if (which < 0 || which > 3) return cgfail(h, CID_ERR_INVALID, "cid_cg_set_bn_eps: no such BatchNorm");
-    if (!std::isfinite(eps) || eps < 0.0) return cgfail(h, CID_ERR_INVALID, "cid_cg_set_bn_eps: eps must be finite and >= 0");
-    h->eps[which] = eps;
-    return CID_OK;
+    return h ? h->set_bn_eps(which >= 0 && which <= 3 ? &h->eps[which] : nullptr, eps) : CID_ERR_INVALID;
 }
 
 int cid_cg_missing_weights(cid_cg_t h, int* count) {
     if (!h || !count) return CID_ERR_INVALID;
-    int m = 0;
-    for (size_t i = 0; i < h->keys.size(); ++i) m += h->keys[i].kind != ESR_COUNT && !h->have[i];
-    *count = m;
+    *count = h->missing();
     return CID_OK;
 }
 
 size_t cid_cg_packed_weights_bytes(cid_cg_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
 
 int cid_cg_upload_weights(cid_cg_t h, void* device_blob, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return cgfail(h, CID_ERR_INVALID, "cid_cg_upload_weights: null device pointer");
-    if ((uintptr_t)device_blob & 255) return cgfail(h, CID_ERR_WORKSPACE, "cid_cg_upload_weights: blob must be 256-byte aligned");
-    for (size_t i = 0; i < h->keys.size(); ++i)
-        if (h->keys[i].kind != ESR_COUNT && !h->have[i]) return cgfail(h, CID_ERR_STATE, "cid_cg_upload_weights: " + h->keys[i].name + " not set");
-    cg_pack(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return cgfail(h, CID_ERR_HIP, std::string("cid_cg_upload_weights: ") + hipGetErrorString(e));
-    h->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
+    return h ? h->upload(device_blob, stream, h->blob_floats(), [h](float* b) { cg_pack(h, b); }) : CID_ERR_INVALID;
 }
 
 int cid_cg_workspace_bytes(int N, size_t* bytes) {
@@ -3695,19 +3475,19 @@ int cid_cg_latent(uint64_t seed, uint64_t first_index, int N, float* z_out, void
 int cid_cg_forward(cid_cg_t h, const float* z, const int64_t* labels, void* out, int out_fmt, int N, unsigned flags, void* workspace,
                    size_t workspace_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!z || !labels || !out || !workspace) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: null pointer");
-    if (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: unknown format");
+    if (!z || !labels || !out || !workspace) return h->fail(CID_ERR_INVALID, "cid_cg_forward: null pointer");
+    if (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC) return h->fail(CID_ERR_INVALID, "cid_cg_forward: unknown format");
     if (((uintptr_t)z & 3) || ((uintptr_t)labels & 7) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
-        return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: misaligned operand");
-    if (flags & ~(unsigned)CID_CG_RAW) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: unknown flags");
-    if ((flags & CID_CG_RAW) && out_fmt != CID_FMT_F32_NCHW) return cgfail(h, CID_ERR_INVALID, "cid_cg_forward: CID_CG_RAW needs an fp32 output");
+        return h->fail(CID_ERR_INVALID, "cid_cg_forward: misaligned operand");
+    if (flags & ~(unsigned)CID_CG_RAW) return h->fail(CID_ERR_INVALID, "cid_cg_forward: unknown flags");
+    if ((flags & CID_CG_RAW) && out_fmt != CID_FMT_F32_NCHW) return h->fail(CID_ERR_INVALID, "cid_cg_forward: CID_CG_RAW needs an fp32 output");
     CgPlan p;
-    if (cg_plan(N, p) != CID_OK) return cgfail(h, CID_ERR_SHAPE, "cid_cg_forward: batch size not accepted (1 <= N <= 2^18)");
+    if (cg_plan(N, p) != CID_OK) return h->fail(CID_ERR_SHAPE, "cid_cg_forward: batch size not accepted (1 <= N <= 2^18)");
     if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return cgfail(h, CID_ERR_WORKSPACE, "cid_cg_forward: workspace smaller than cid_cg_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return cgfail(h, CID_ERR_STATE, "cid_cg_forward: weights not uploaded");
+        return h->fail(CID_ERR_WORKSPACE, "cid_cg_forward: workspace smaller than cid_cg_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_cg_forward: weights not uploaded");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return cgfail(h, CID_ERR_HIP, std::string("cid_cg_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_cg_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
     char* ws = static_cast<char*>(workspace);
     const float* blob = h->dev_blob;
     float* l1 = reinterpret_cast<float*>(ws + p.l1);
@@ -3754,24 +3534,23 @@ constexpr int kLpMinSide = 31;
 const int kLpSlice[5] = {0, 3, 6, 8, 10};            // net.slice<k+1>.<i>
 const int kLpCin[5] = {3, 64, 192, 384, 256}, kLpKs[5] = {11, 5, 3, 3, 3};
 
-std::vector<EsrKey> lp_keys() {
-    std::vector<EsrKey> k;
-    k.push_back({"scaling_layer.shift", ESR_W, {1, 3, 1, 1}, 4, 3});
-    k.push_back({"scaling_layer.scale", ESR_W, {1, 3, 1, 1}, 4, 3});
-    for (int l = 0; l < LP_TAPS; ++l) {
-        const std::string c = "net.slice" + std::to_string(l + 1) + "." + std::to_string(kLpSlice[l]) + ".";
-        const int co = lp_channels(l), ci = kLpCin[l], ks = kLpKs[l];
-        k.push_back({c + "weight", ESR_W, {co, ci, ks, ks}, 4, (size_t)co * ci * ks * ks});
-        k.push_back({c + "bias", ESR_VEC, {co, 0, 0, 0}, 1, (size_t)co});
-    }
-    for (int l = 0; l < LP_TAPS; ++l)
-        k.push_back({"lin" + std::to_string(l) + ".model.1.weight", ESR_W, {1, lp_channels(l), 1, 1}, 4, (size_t)lp_channels(l)});
-    return k;
+// scaling_layer.* ahead of a tower's convolutions, lin<k>.* behind them: the layout LPIPS and the VGG tower share
+void keys_scaling(KeyTable& k) {
+    k.tensor("scaling_layer.shift", {1, 3, 1, 1});
+    k.tensor("scaling_layer.scale", {1, 3, 1, 1});
 }
+std::string lp_lin_name(int l) { return "lin" + std::to_string(l) + ".model.1.weight"; }
+std::string lp_conv_name(int l) { return "net.slice" + std::to_string(l + 1) + "." + std::to_string(kLpSlice[l]) + "."; }
 
-const std::vector<EsrKey>& lp_key_table() {
-    static const std::vector<EsrKey> k = lp_keys();
-    return k;
+const KeyTable& lp_key_table() {
+    static const KeyTable table = [] {
+        KeyTable k;
+        keys_scaling(k);
+        for (int l = 0; l < LP_TAPS; ++l) k.conv(lp_conv_name(l), lp_channels(l), kLpCin[l], kLpKs[l]);
+        for (int l = 0; l < LP_TAPS; ++l) k.tensor(lp_lin_name(l), {1, lp_channels(l), 1, 1});
+        return k;
+    }();
+    return table;
 }
 
 // blob segments (floats, 64-float aligned): the head, relu2 ... relu5 (packed weights then biases), the five lin vectors
@@ -3806,52 +3585,31 @@ int lp_plan(int N, int H, int W, LpPlan& p) {
 
 }  // namespace
 
-struct cid_lpips_s {
-    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
-    std::vector<char> have;
-    std::vector<float> staging;
-    const float* dev_blob = nullptr;
-    std::string err;
-};
+struct cid_lpips_s : WeightStore {};
 
 namespace {
-int lpfail(cid_lpips_t h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
+// A tower's head segment: [k][64], bias, and (scaled) the scaling layer's shift and scale
+void lp_pack_head(const WeightStore& w, float* b, const std::string& conv, int K, int bias_at, int ss_at, bool scaled) {
+    pack_k64(b, w.get(conv + "weight"), K);
+    std::memcpy(b + bias_at, w.get(conv + "bias"), 64 * sizeof(float));
+    if (!scaled) return;
+    std::memcpy(b + ss_at, w.get("scaling_layer.shift"), 3 * sizeof(float));
+    std::memcpy(b + ss_at + 4, w.get("scaling_layer.scale"), 3 * sizeof(float));
 }
 
-int lp_find(const std::string& k) {
-    const auto& keys = lp_key_table();
-    for (size_t i = 0; i < keys.size(); ++i)
-        if (keys[i].name == k) return (int)i;
-    return -1;
-}
-
-void lp_pack(cid_lpips_t h) {
-    h->staging.assign(lp_blob_floats(), 0.f);
-    float* b = h->staging.data();
-    const auto get = [&](const std::string& k) -> const float* { return h->raw[lp_find(k)].data(); };
-    {   // head: [k][64], bias, shift, scale
-        const float *w = get("net.slice1.0.weight");
-        for (int co = 0; co < 64; ++co)
-            for (int k = 0; k < LP_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * LP_HEAD_K + k];
-        std::memcpy(b + LP_HEAD_B, get("net.slice1.0.bias"), 64 * sizeof(float));
-        std::memcpy(b + LP_HEAD_SS, get("scaling_layer.shift"), 3 * sizeof(float));
-        std::memcpy(b + LP_HEAD_SS + 4, get("scaling_layer.scale"), 3 * sizeof(float));
-    }
+void lp_pack(const cid_lpips_s* h, float* b) {
+    lp_pack_head(*h, b, lp_conv_name(0), LP_HEAD_K, LP_HEAD_B, LP_HEAD_SS, true);
     for (int l = 1; l < LP_TAPS; ++l) {
         float* seg = b + lp_conv_off(l);
         const int CO = lp_channels(l), CI = kLpCin[l], KS = kLpKs[l];
-        const std::string c = "net.slice" + std::to_string(l + 1) + "." + std::to_string(kLpSlice[l]) + ".";
-        const float* w = get(c + "weight");
+        const float* w = h->get(lp_conv_name(l) + "weight");
         for (int co = 0; co < CO; ++co)
             for (int ci = 0; ci < CI; ++ci)
                 for (int kh = 0; kh < KS; ++kh)
                     for (int kw = 0; kw < KS; ++kw) seg[lp_conv_windex(CI, KS, co, ci, kh, kw)] = w[(((size_t)co * CI + ci) * KS + kh) * KS + kw];
-        std::memcpy(seg + (size_t)CO * CI * KS * KS, get(c + "bias"), CO * sizeof(float));
+        std::memcpy(seg + (size_t)CO * CI * KS * KS, h->get(lp_conv_name(l) + "bias"), CO * sizeof(float));
     }
-    for (int l = 0; l < LP_TAPS; ++l)
-        std::memcpy(b + lp_conv_off(5) + lp_lin_off(l), get("lin" + std::to_string(l) + ".model.1.weight"), lp_channels(l) * sizeof(float));
+    for (int l = 0; l < LP_TAPS; ++l) std::memcpy(b + lp_conv_off(5) + lp_lin_off(l), h->get(lp_lin_name(l)), lp_channels(l) * sizeof(float));
 }
 
 template <int CIN, int COUT, int KS, bool POOL>
@@ -3869,8 +3627,7 @@ int cid_lpips_create(cid_lpips_t* out) {
     *out = nullptr;
     cid_lpips_s* h = new (std::nothrow) cid_lpips_s();
     if (!h) return CID_ERR_INVALID;
-    h->raw.resize(lp_key_table().size());
-    h->have.assign(lp_key_table().size(), 0);
+    h->init("cid_lpips", lp_key_table());
     *out = h;
     return CID_OK;
 }
@@ -3879,47 +3636,22 @@ void cid_lpips_destroy(cid_lpips_t h) { delete h; }
 
 const char* cid_lpips_last_error(cid_lpips_t h) { return h ? h->err.c_str() : "null handle"; }
 
-const char* cid_lpips_param_key(cid_lpips_t h, int i) {
-    if (!h || i < 0 || (size_t)i >= lp_key_table().size()) return nullptr;
-    return lp_key_table()[i].name.c_str();
-}
+const char* cid_lpips_param_key(cid_lpips_t h, int i) { return h ? h->key(i) : nullptr; }
 
 int cid_lpips_set_weight(cid_lpips_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    if (!h) return CID_ERR_INVALID;
-    if (!key || !data || (!shape && ndim > 0)) return lpfail(h, CID_ERR_INVALID, "cid_lpips_set_weight: null argument");
-    const int i = lp_find(key);
-    if (i < 0) return lpfail(h, CID_ERR_KEY, std::string("cid_lpips_set_weight: unexpected key '") + key + "'");
-    const EsrKey& k = lp_key_table()[i];
-    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return lpfail(h, CID_ERR_SHAPE, "cid_lpips_set_weight: size mismatch for " + k.name);
-    const float* f = static_cast<const float*>(data);
-    h->raw[i].assign(f, f + k.count);
-    h->have[i] = 1;
-    return CID_OK;
+    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
 }
 
 int cid_lpips_missing_weights(cid_lpips_t h, int* count) {
     if (!h || !count) return CID_ERR_INVALID;
-    int m = 0;
-    for (size_t i = 0; i < h->have.size(); ++i) m += !h->have[i];
-    *count = m;
+    *count = h->missing();
     return CID_OK;
 }
 
 size_t cid_lpips_packed_weights_bytes(cid_lpips_t h) { return h ? lp_blob_floats() * sizeof(float) : 0; }
 
 int cid_lpips_upload_weights(cid_lpips_t h, void* device_blob, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return lpfail(h, CID_ERR_INVALID, "cid_lpips_upload_weights: null device pointer");
-    if ((uintptr_t)device_blob & 255) return lpfail(h, CID_ERR_WORKSPACE, "cid_lpips_upload_weights: blob must be 256-byte aligned");
-    for (size_t i = 0; i < h->have.size(); ++i)
-        if (!h->have[i]) return lpfail(h, CID_ERR_STATE, "cid_lpips_upload_weights: " + lp_key_table()[i].name + " not set");
-    lp_pack(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return lpfail(h, CID_ERR_HIP, std::string("cid_lpips_upload_weights: ") + hipGetErrorString(e));
-    h->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
+    return h ? h->upload(device_blob, stream, lp_blob_floats(), [h](float* b) { lp_pack(h, b); }) : CID_ERR_INVALID;
 }
 
 int cid_lpips_workspace_bytes(int N, int H, int W, size_t* bytes) {
@@ -3949,21 +3681,21 @@ int cid_lpips_stage_view(const char* stage, int N, int H, int W, size_t* offset_
 int cid_lpips(cid_lpips_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
               double* layers, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!a || !b || !out || !workspace) return lpfail(h, CID_ERR_INVALID, "cid_lpips: null pointer");
+    if (!a || !b || !out || !workspace) return h->fail(CID_ERR_INVALID, "cid_lpips: null pointer");
     if ((fmt_a != CID_FMT_F32_NCHW && fmt_a != CID_FMT_U8_NHWC) || (fmt_b != CID_FMT_F32_NCHW && fmt_b != CID_FMT_U8_NHWC))
-        return lpfail(h, CID_ERR_INVALID, "cid_lpips: unknown format");
+        return h->fail(CID_ERR_INVALID, "cid_lpips: unknown format");
     if ((fmt_a == CID_FMT_F32_NCHW && ((uintptr_t)a & 3)) || (fmt_b == CID_FMT_F32_NCHW && ((uintptr_t)b & 3)) || ((uintptr_t)out & 7) ||
         ((uintptr_t)layers & 7))
-        return lpfail(h, CID_ERR_INVALID, "cid_lpips: misaligned operand");
-    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return lpfail(h, CID_ERR_INVALID, "cid_lpips: unknown flags");
+        return h->fail(CID_ERR_INVALID, "cid_lpips: misaligned operand");
+    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return h->fail(CID_ERR_INVALID, "cid_lpips: unknown flags");
     LpPlan p;
     if (lp_plan(N, H, W, p) != CID_OK)
-        return lpfail(h, CID_ERR_SHAPE, "cid_lpips: shape not accepted (1 <= N <= 2^20, H and W >= 31 and within the kernels' tile limit)");
+        return h->fail(CID_ERR_SHAPE, "cid_lpips: shape not accepted (1 <= N <= 2^20, H and W >= 31 and within the kernels' tile limit)");
     if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return lpfail(h, CID_ERR_WORKSPACE, "cid_lpips: workspace smaller than cid_lpips_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return lpfail(h, CID_ERR_STATE, "cid_lpips: weights not uploaded");
+        return h->fail(CID_ERR_WORKSPACE, "cid_lpips: workspace smaller than cid_lpips_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_lpips: weights not uploaded");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return lpfail(h, CID_ERR_HIP, std::string("cid_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
     char* ws = static_cast<char*>(workspace);
     const float* blob = h->dev_blob;
     float* t[LP_TAPS];
@@ -4015,22 +3747,15 @@ constexpr int kVgContentConvs = 7;                   // slice1 ... slice3
 
 std::string vg_conv_name(int l) { return "net.slice" + std::to_string(kVgSlice[l]) + "." + std::to_string(kVgIdx[l]) + "."; }
 
-std::vector<EsrKey> vg_keys() {
-    std::vector<EsrKey> k;
-    k.push_back({"scaling_layer.shift", ESR_W, {1, 3, 1, 1}, 4, 3});
-    k.push_back({"scaling_layer.scale", ESR_W, {1, 3, 1, 1}, 4, 3});
-    for (int l = 0; l < VG_CONVS; ++l) {
-        k.push_back({vg_conv_name(l) + "weight", ESR_W, {kVgCout[l], kVgCin[l], 3, 3}, 4, (size_t)kVgCout[l] * kVgCin[l] * 9});
-        k.push_back({vg_conv_name(l) + "bias", ESR_VEC, {kVgCout[l], 0, 0, 0}, 1, (size_t)kVgCout[l]});
-    }
-    for (int l = 0; l < LP_TAPS; ++l)
-        k.push_back({"lin" + std::to_string(l) + ".model.1.weight", ESR_W, {1, VgTaps::channels(l), 1, 1}, 4, (size_t)VgTaps::channels(l)});
-    return k;
-}
-
-const std::vector<EsrKey>& vg_key_table() {
-    static const std::vector<EsrKey> k = vg_keys();
-    return k;
+const KeyTable& vg_key_table() {
+    static const KeyTable table = [] {
+        KeyTable k;
+        keys_scaling(k);
+        for (int l = 0; l < VG_CONVS; ++l) k.conv(vg_conv_name(l), kVgCout[l], kVgCin[l], 3);
+        for (int l = 0; l < LP_TAPS; ++l) k.tensor(lp_lin_name(l), {1, VgTaps::channels(l), 1, 1});
+        return k;
+    }();
+    return table;
 }
 
 // blob segments (floats, 64-float aligned): the head, convolutions 1 ... 12 (packed weights then biases), the five lin vectors
@@ -4072,55 +3797,25 @@ int vg_plan(int what, int N, int H, int W, VgPlan& p) {
 
 }  // namespace
 
-struct cid_vgg_s {
-    std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
-    std::vector<char> have;
-    std::vector<float> staging;
-    const float* dev_blob = nullptr;
-    bool full = false;                     // the uploaded blob holds all 33 tensors (else slice1 ... slice3 only)
-    std::string err;
+struct cid_vgg_s : WeightStore {
+    bool full = false;   // the uploaded blob holds all 33 tensors (else slice1 ... slice3 only)
 };
 
 namespace {
-int vgfail(cid_vgg_t h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
-int vg_find(const std::string& k) {
-    const auto& keys = vg_key_table();
-    for (size_t i = 0; i < keys.size(); ++i)
-        if (keys[i].name == k) return (int)i;
-    return -1;
-}
-
-void vg_pack(cid_vgg_t h, bool full) {
-    h->staging.assign(vg_blob_floats(), 0.f);
-    float* b = h->staging.data();
-    const auto get = [&](const std::string& k) -> const float* { return h->raw[vg_find(k)].data(); };
-    {   // head: [k][64], bias, shift, scale
-        const float* w = get(vg_conv_name(0) + "weight");
-        for (int co = 0; co < 64; ++co)
-            for (int k = 0; k < VG_HEAD_K; ++k) b[(size_t)k * 64 + co] = w[(size_t)co * VG_HEAD_K + k];
-        std::memcpy(b + VG_HEAD_B, get(vg_conv_name(0) + "bias"), 64 * sizeof(float));
-        if (full) {
-            std::memcpy(b + VG_HEAD_SS, get("scaling_layer.shift"), 3 * sizeof(float));
-            std::memcpy(b + VG_HEAD_SS + 4, get("scaling_layer.scale"), 3 * sizeof(float));
-        }
-    }
+void vg_pack(const cid_vgg_s* h, float* b, bool full) {
+    lp_pack_head(*h, b, vg_conv_name(0), VG_HEAD_K, VG_HEAD_B, VG_HEAD_SS, full);
     for (int l = 1; l < (full ? VG_CONVS : kVgContentConvs); ++l) {
         float* seg = b + vg_conv_off(l);
         const int CO = kVgCout[l], CI = kVgCin[l];
-        const float* w = get(vg_conv_name(l) + "weight");
+        const float* w = h->get(vg_conv_name(l) + "weight");
         for (int co = 0; co < CO; ++co)
             for (int ci = 0; ci < CI; ++ci)
                 for (int t = 0; t < 9; ++t) seg[lp_conv_windex(CI, 3, co, ci, t / 3, t % 3)] = w[((size_t)co * CI + ci) * 9 + t];
-        std::memcpy(seg + (size_t)CO * CI * 9, get(vg_conv_name(l) + "bias"), CO * sizeof(float));
+        std::memcpy(seg + (size_t)CO * CI * 9, h->get(vg_conv_name(l) + "bias"), CO * sizeof(float));
     }
     if (full)
         for (int l = 0; l < LP_TAPS; ++l)
-            std::memcpy(b + vg_conv_off(VG_CONVS) + VgTaps::lin_off(l), get("lin" + std::to_string(l) + ".model.1.weight"),
-                        VgTaps::channels(l) * sizeof(float));
+            std::memcpy(b + vg_conv_off(VG_CONVS) + VgTaps::lin_off(l), h->get(lp_lin_name(l)), VgTaps::channels(l) * sizeof(float));
 }
 
 // One trunk convolution from an Hs x Ws tensor; the plane size follows the output map's width.  Only the launch that can meet a
@@ -4141,20 +3836,20 @@ void vg_conv_launch(const float* in, float* out, const float* w, int N, int Hs, 
 int vg_check(cid_vgg_t h, const char* fn, int what, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags,
              const void* out, const void* layers, const void* workspace, size_t workspace_bytes, VgPlan& p) {
     const std::string f(fn);
-    if (!a || !b || !out || !workspace) return vgfail(h, CID_ERR_INVALID, f + ": null pointer");
+    if (!a || !b || !out || !workspace) return h->fail(CID_ERR_INVALID, f + ": null pointer");
     if ((fmt_a != CID_FMT_F32_NCHW && fmt_a != CID_FMT_U8_NHWC) || (fmt_b != CID_FMT_F32_NCHW && fmt_b != CID_FMT_U8_NHWC))
-        return vgfail(h, CID_ERR_INVALID, f + ": unknown format");
+        return h->fail(CID_ERR_INVALID, f + ": unknown format");
     if ((fmt_a == CID_FMT_F32_NCHW && ((uintptr_t)a & 3)) || (fmt_b == CID_FMT_F32_NCHW && ((uintptr_t)b & 3)) || ((uintptr_t)out & 7) ||
         ((uintptr_t)layers & 7))
-        return vgfail(h, CID_ERR_INVALID, f + ": misaligned operand");
-    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return vgfail(h, CID_ERR_INVALID, f + ": unknown flags");
+        return h->fail(CID_ERR_INVALID, f + ": misaligned operand");
+    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return h->fail(CID_ERR_INVALID, f + ": unknown flags");
     if (vg_plan(what, N, H, W, p) != CID_OK)
-        return vgfail(h, CID_ERR_SHAPE, f + ": shape not accepted (1 <= N <= 2^20, " + std::to_string(kVgMinSide[what]) + " <= H, W <= " +
+        return h->fail(CID_ERR_SHAPE, f + ": shape not accepted (1 <= N <= 2^20, " + std::to_string(kVgMinSide[what]) + " <= H, W <= " +
                                             std::to_string(VG_MAX_SIDE) + ", 2 N H W < 2^37)");
     if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return vgfail(h, CID_ERR_WORKSPACE, f + ": workspace smaller than cid_vgg_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return vgfail(h, CID_ERR_STATE, f + ": weights not uploaded");
-    if (what == CID_VGG_LPIPS && !h->full) return vgfail(h, CID_ERR_STATE, f + ": the handle holds slice1 ... slice3 only (content loss)");
+        return h->fail(CID_ERR_WORKSPACE, f + ": workspace smaller than cid_vgg_workspace_bytes() or not 256-byte aligned");
+    if (!h->dev_blob) return h->fail(CID_ERR_STATE, f + ": weights not uploaded");
+    if (what == CID_VGG_LPIPS && !h->full) return h->fail(CID_ERR_STATE, f + ": the handle holds slice1 ... slice3 only (content loss)");
     return CID_OK;
 }
 
@@ -4206,8 +3901,7 @@ int cid_vgg_create(cid_vgg_t* out) {
     *out = nullptr;
     cid_vgg_s* h = new (std::nothrow) cid_vgg_s();
     if (!h) return CID_ERR_INVALID;
-    h->raw.resize(vg_key_table().size());
-    h->have.assign(vg_key_table().size(), 0);
+    h->init("cid_vgg", vg_key_table());
     *out = h;
     return CID_OK;
 }
@@ -4216,29 +3910,15 @@ void cid_vgg_destroy(cid_vgg_t h) { delete h; }
 
 const char* cid_vgg_last_error(cid_vgg_t h) { return h ? h->err.c_str() : "null handle"; }
 
-const char* cid_vgg_param_key(cid_vgg_t h, int i) {
-    if (!h || i < 0 || (size_t)i >= vg_key_table().size()) return nullptr;
-    return vg_key_table()[i].name.c_str();
-}
+const char* cid_vgg_param_key(cid_vgg_t h, int i) { return h ? h->key(i) : nullptr; }
 
 int cid_vgg_set_weight(cid_vgg_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    if (!h) return CID_ERR_INVALID;
-    if (!key || !data || (!shape && ndim > 0)) return vgfail(h, CID_ERR_INVALID, "cid_vgg_set_weight: null argument");
-    const int i = vg_find(key);
-    if (i < 0) return vgfail(h, CID_ERR_KEY, std::string("cid_vgg_set_weight: unexpected key '") + key + "'");
-    const EsrKey& k = vg_key_table()[i];
-    if (ndim != k.ndim || !std::equal(shape, shape + ndim, k.shape)) return vgfail(h, CID_ERR_SHAPE, "cid_vgg_set_weight: size mismatch for " + k.name);
-    const float* f = static_cast<const float*>(data);
-    h->raw[i].assign(f, f + k.count);
-    h->have[i] = 1;
-    return CID_OK;
+    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
 }
 
 int cid_vgg_missing_weights(cid_vgg_t h, int* count) {
     if (!h || !count) return CID_ERR_INVALID;
-    int m = 0;
-    for (size_t i = 0; i < h->have.size(); ++i) m += !h->have[i];
-    *count = m;
+    *count = h->missing();
     return CID_OK;
 }
 
@@ -4246,30 +3926,22 @@ size_t cid_vgg_packed_weights_bytes(cid_vgg_t h) { return h ? vg_blob_floats() *
 
 int cid_vgg_upload_weights(cid_vgg_t h, void* device_blob, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return vgfail(h, CID_ERR_INVALID, "cid_vgg_upload_weights: null device pointer");
-    // all 33 tensors, or exactly the 14 of slice1 ... slice3 (key table entries 2 ... 15)
+    if (!device_blob) return h->fail(CID_ERR_INVALID, "cid_vgg_upload_weights: null device pointer");
+    // all 33 tensors, or exactly the 14 of slice1 ... slice3 (key table entries 2 ... 15); this state check comes ahead of the
+    // blob's alignment check, which the shared upload makes
     int set = 0, content = 0;
     for (size_t i = 0; i < h->have.size(); ++i) {
         set += h->have[i] != 0;
         content += h->have[i] && i >= 2 && i < 2 + 2 * (size_t)kVgContentConvs;
     }
     const bool full = set == CID_VGG_NUM_WEIGHTS;
-    if (!full && !(set == 2 * kVgContentConvs && content == set)) {
-        std::string first;
-        for (size_t i = 0; i < h->have.size() && first.empty(); ++i)
-            if (!h->have[i]) first = vg_key_table()[i].name;
-        return vgfail(h, CID_ERR_STATE, "cid_vgg_upload_weights: needs all " + std::to_string(CID_VGG_NUM_WEIGHTS) +
-                                            " tensors or exactly the 14 of slice1 ... slice3; " + std::to_string(set) + " set, first missing " + first);
-    }
-    if ((uintptr_t)device_blob & 255) return vgfail(h, CID_ERR_WORKSPACE, "cid_vgg_upload_weights: blob must be 256-byte aligned");
-    vg_pack(h, full);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), h->staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return vgfail(h, CID_ERR_HIP, std::string("cid_vgg_upload_weights: ") + hipGetErrorString(e));
-    h->dev_blob = static_cast<const float*>(device_blob);
-    h->full = full;
-    return CID_OK;
+    if (!full && !(set == 2 * kVgContentConvs && content == set))
+        return h->fail(CID_ERR_STATE, "cid_vgg_upload_weights: needs all " + std::to_string(CID_VGG_NUM_WEIGHTS) +
+                                          " tensors or exactly the 14 of slice1 ... slice3; " + std::to_string(set) + " set, first missing " +
+                                          h->keys[h->first_missing()].name);
+    const int rc = h->upload(device_blob, stream, vg_blob_floats(), [h, full](float* b) { vg_pack(h, b, full); }, false);
+    if (rc == CID_OK) h->full = full;
+    return rc;
 }
 
 int cid_vgg_workspace_bytes(int what, int N, int H, int W, size_t* bytes) {
@@ -4303,7 +3975,7 @@ int cid_vgg_lpips(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_
     const int rc = vg_check(h, "cid_vgg_lpips", CID_VGG_LPIPS, a, fmt_a, b, fmt_b, N, H, W, flags, out, layers, workspace, workspace_bytes, p);
     if (rc != CID_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return vgfail(h, CID_ERR_HIP, std::string("cid_vgg_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_vgg_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
     char* ws = static_cast<char*>(workspace);
     if (const char* failed = vg_features(h, p, a, fmt_a, b, fmt_b, N, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0, true, 4, ws, s)) return herr(failed);
     LpDistArgs da;
@@ -4327,7 +3999,7 @@ int cid_vgg_content_loss(cid_vgg_t h, const void* a, int fmt_a, const void* b, i
     const int rc = vg_check(h, "cid_vgg_content_loss", CID_VGG_CONTENT, a, fmt_a, b, fmt_b, N, H, W, flags, out, nullptr, workspace, workspace_bytes, p);
     if (rc != CID_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return vgfail(h, CID_ERR_HIP, std::string("cid_vgg_content_loss: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
+    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_vgg_content_loss: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
     char* ws = static_cast<char*>(workspace);
     if (const char* failed = vg_features(h, p, a, fmt_a, b, fmt_b, N, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0, false, 2, ws, s)) return herr(failed);
     const VgContentArgs ca{reinterpret_cast<const float*>(ws + p.tap[2]), out, (long long)256 * p.Hs[2] * p.Ws[2], N};

@@ -15,14 +15,12 @@ shifts the image by pad//2 pixels whenever a size is not a multiple of 4.  That 
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Mapping, Optional, Union
 
-import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _packed
 
 MAX_RESIDUALS = 16
 
@@ -41,7 +39,7 @@ class ResidualBlock(nn.Module):
         )
 
 
-class ESRGANGenerator(nn.Module):
+class ESRGANGenerator(_packed.PackedModule):
     """The reference's ESRGAN generator.  `initial`, `residuals` and `final` are stock layers used as parameter containers, so
     state_dict keys, .to(), load_state_dict(), .train() and .eval() behave as in the reference.  forward(x):
       fp32 [N,3,H,W] in [0,1]  ->  the raw fp32 [N,3,H,W]
@@ -49,6 +47,8 @@ class ESRGANGenerator(nn.Module):
     (`out_dtype` picks the other output format for either input),
     asynchronous on the current stream, without autograd history.  Weight changes are found by the tensors' version counters and
     repacked at the next call (after writes through `.data` call pack_weights(force=True))."""
+
+    _abi = "esr"
 
     def __init__(self, num_residuals: int = 8):
         super().__init__()
@@ -58,124 +58,35 @@ class ESRGANGenerator(nn.Module):
         self.initial = nn.Sequential(nn.Conv2d(3, 64, 9, 1, 4), nn.PReLU())
         self.residuals = nn.Sequential(*[ResidualBlock(64) for _ in range(self.num_residuals)])
         self.final = nn.Conv2d(64, 3, 9, 1, 4)
-        self._cid = ctypes.c_void_p()
-        _lib.check_esr(None, _lib.lib().cid_esr_create(ctypes.byref(self._cid), self.num_residuals))
-        self._blob = None          # packed weights on the device (uint8 tensor, owns the memory)
-        self._packed_sig = None
-        self._ws = None            # workspace (uint8 tensor, grow-only)
+        self._create(self.num_residuals)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_cid", None):
-                _lib.lib().cid_esr_destroy(self._cid)
-                self._cid = None
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------------ weights
-    def _device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    def _tensors(self):
-        return list(self.state_dict(keep_vars=True).items())
-
-    def _signature(self):
-        eps = tuple(float(b.block[i].eps) for b in self.residuals for i in (1, 4))
-        return tuple((k, t.data_ptr(), t._version, str(t.device)) for k, t in self._tensors()) + eps
-
-    def pack_weights(self, force: bool = False) -> torch.Tensor:
-        """Pack the state_dict into the kernels' layout on the module's GPU, BatchNorm folded (if anything changed since the last
-        call)."""
-        sig = self._signature()
-        if not force and self._blob is not None and sig == self._packed_sig:
-            return self._blob
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("ESRGANGenerator runs only on an AMD GPU (HIP kernels behind libcid.so); move it with .to('cuda') "
-                               "first. There is no CPU fallback.")
-        L = _lib.lib()
-        for i, blk in enumerate(self.residuals):
-            for which, idx in enumerate((1, 4)):
-                bn = blk.block[idx]
-                if not (bn.affine and bn.track_running_stats):
-                    raise NotImplementedError(f"residuals.{i}.block.{idx}: only BatchNorm2d(affine=True, track_running_stats=True)")
-                _lib.check_esr(self._cid, L.cid_esr_set_bn_eps(self._cid, i, which, float(bn.eps)))
-        for key, t in self._tensors():
-            if key.endswith("num_batches_tracked"):
-                a = t.detach().cpu().numpy()   # 0-d int64: accepted and ignored by the library
-            else:
-                a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-            _lib.check_esr(self._cid, L.cid_esr_set_weight(self._cid, key.encode(), a.ctypes.data, shape, a.ndim))
-        blob = torch.empty(L.cid_esr_packed_weights_bytes(self._cid), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_esr(self._cid, L.cid_esr_upload_weights(self._cid, blob.data_ptr(), stream))
-        self._blob, self._packed_sig = blob, sig
-        return blob
-
-    # ------------------------------------------------------------------ forward
-    def _ensure_workspace(self, n: int, h: int, w: int, device: torch.device) -> None:
-        need = ctypes.c_size_t()
-        _lib.check_esr(self._cid, _lib.lib().cid_esr_workspace_bytes(n, h, w, ctypes.byref(need)))
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
-            if self._ws is not None:
-                torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+    def _batchnorms(self):
+        return [(f"residuals.{i}.block.{idx}", blk.block[idx], (i, which))
+                for i, blk in enumerate(self.residuals) for which, idx in enumerate((1, 4))]
 
     def forward(self, x: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         if self.training:
             raise RuntimeError("ESRGANGenerator is in train mode: train-mode BatchNorm (batch statistics) is not implemented; call "
                                ".eval() first, as the server does (app.py:240)")
-        if not isinstance(x, torch.Tensor):
-            raise TypeError("ESRGANGenerator expects a torch.Tensor")
-        if x.dtype == torch.uint8:
-            if x.dim() != 4 or x.shape[3] != 3:
-                raise RuntimeError(f"expected a uint8 input of shape [N,H,W,3], got {list(x.shape)}")
-            fmt, (n, h, w) = _lib.CID_FMT_U8_NHWC, (x.shape[0], x.shape[1], x.shape[2])
-        elif x.dtype == torch.float32:
-            if x.dim() != 4 or x.shape[1] != 3:
-                raise RuntimeError(f"expected a float32 input of shape [N,3,H,W], got {list(x.shape)}")
-            fmt, (n, h, w) = _lib.CID_FMT_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
-        else:
-            raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3] input, got {x.dtype}")
-        if x.device.type != "cuda":
-            raise RuntimeError("ESRGANGenerator.forward got a CPU tensor: this implementation is GPU-only (hand-written HIP kernels); "
-                               "there is no CPU fallback. Move the input with .to('cuda').")
-        dev = self._device()
-        if x.device != dev:
-            raise RuntimeError(f"input on {x.device} but module parameters on {dev}")
+        fmt, (n, h, w) = self._image_input(x)
+        dev = self._input_device(x)
         if n < 1 or h < 1 or w < 1:
             raise RuntimeError(f"empty input {list(x.shape)}")
         self.pack_weights()
-        self._ensure_workspace(n, h, w, dev)
+        self._ensure_workspace(dev, n, h, w)
         x = x.contiguous()
         out_dtype = x.dtype if out_dtype is None else out_dtype
-        if out_dtype == torch.uint8:
-            out_fmt, out = _lib.CID_FMT_U8_NHWC, torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-        elif out_dtype == torch.float32:
-            out_fmt, out = _lib.CID_FMT_F32_NCHW, torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
-        else:
-            raise RuntimeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
+        out_fmt, out = _packed.image_output(out_dtype, n, h, w, dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_esr(self._cid, _lib.lib().cid_esr_forward(self._cid, x.data_ptr(), fmt, out.data_ptr(), out_fmt, n, h, w,
-                                                                 self._ws.data_ptr(), self._ws.numel(), stream))
+            self._check(self._fn("forward")(self._cid, x.data_ptr(), fmt, out.data_ptr(), out_fmt, n, h, w, self._ws.data_ptr(),
+                                             self._ws.numel(), stream))
         return out
 
     def stage(self, name: str, n: int, h: int, w: int) -> torch.Tensor:
         """What the last forward of an [n,3,h,w] input left in the workspace as fp32 [n,64,h,w] (a copy): "x1", or "tail_in", the
         tensor the last launch read (cid_esr_stage_view)."""
-        off, c, hs, ws, cb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        rc = _lib.lib().cid_esr_stage_view(name.encode(), n, h, w, ctypes.byref(off), ctypes.byref(c), ctypes.byref(hs), ctypes.byref(ws),
-                                           ctypes.byref(cb))
-        if rc != _lib.CID_OK:
-            raise KeyError(f"no stored stage {name!r} for input [{n},3,{h},{w}] (cid_esr_stage_view -> {rc})")
-        count = n * c.value * hs.value * ws.value
-        t = self._ws[off.value:off.value + 4 * count].view(torch.float32)
-        t = t.view(n, c.value // cb.value, hs.value, ws.value, cb.value).permute(0, 1, 4, 2, 3)
-        return t.reshape(n, c.value, hs.value, ws.value).clone()
+        return self._stage(n, name, f"input [{n},3,{h},{w}]", n, h, w)
 
 
 def load_esrgan(source: Union[str, Mapping, None] = None, num_residuals: int = 8,
@@ -184,21 +95,8 @@ def load_esrgan(source: Union[str, Mapping, None] = None, num_residuals: int = 8
     checkpoint dict or a state_dict: the state_dict is looked up under "generator", "state_dict" and "G" (the server's own loader
     reads checkpoint['G'], app.py:236-241) and "module." prefixes are stripped, as load_state_safely does.  `source=None` keeps the
     default initialisation.  Returns the module in eval mode."""
-    from .api import _read_checkpoint_file, extract_state_dict
-
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    if device is None or torch.device(device).type != "cuda":
-        raise RuntimeError("celebrity_image_denoiser_amd.load_esrgan: an AMD GPU is required (no CPU fallback)")
-    model = ESRGANGenerator(num_residuals)
-    if isinstance(source, str):
-        model.load_state_dict(_read_checkpoint_file(source), strict=strict)
-    elif source is not None:
-        sd = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(v)) for k, v in extract_state_dict(source).items()}
-        model.load_state_dict(sd, strict=strict)
-    model.to(device).eval()
-    model.pack_weights()
-    return model
+    device = _packed.cuda_device(device, "load_esrgan")
+    return _packed.load_into(ESRGANGenerator(num_residuals), source, device, strict)
 
 
 def enhance(model: ESRGANGenerator, x: torch.Tensor) -> torch.Tensor:

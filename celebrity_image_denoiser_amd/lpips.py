@@ -16,14 +16,13 @@ ones, and INTEGRATION.md says how to obtain and pass the real ones.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Mapping, Optional, Union
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _packed
 
 CHANNELS = (64, 192, 384, 256, 256)
 MIN_SIDE = 31
@@ -56,19 +55,13 @@ def operand(x, what: str = "lpips"):
     """(CID format, (N, H, W)) of an fp32 [N,3,H,W] or uint8 [N,H,W,3] tensor."""
     if not isinstance(x, torch.Tensor) or x.dim() != 4:
         raise RuntimeError(f"{what}() expects 4-d torch tensors: float32 [N,3,H,W] or uint8 [N,H,W,3]")
-    if x.dtype == torch.float32 and x.shape[1] == 3:
-        return _lib.CID_FMT_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
-    if x.dtype == torch.uint8 and x.shape[3] == 3:
-        return _lib.CID_FMT_U8_NHWC, (x.shape[0], x.shape[1], x.shape[2])
-    raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3], got {x.dtype} {list(x.shape)}")
+    got = _packed.image_operand(x)
+    if got is None:
+        raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3], got {x.dtype} {list(x.shape)}")
+    return got
 
 
-def _shape_error(rc: int, what: str, n: int, h: int, w: int, why: str) -> None:
-    if rc == 2:   # CID_ERR_SHAPE
-        raise ValueError(f"image size {h}x{w} (N={n}) not accepted: {what} needs {why}")
-
-
-class LPIPS(nn.Module):
+class LPIPS(_packed.PackedModule):
     """lpips.LPIPS(net='alex' or 'vgg') as a parameter container plus the HIP forward.  `scaling_layer`, `net`, `lin0` ... `lin4` and `lins`
     are stock layers, so state_dict keys, .to() and load_state_dict() behave as in the package.  Eval mode only (dropout is inert).
     Asynchronous on the current stream, without autograd history.  Weight changes are found by the tensors' version counters and
@@ -80,6 +73,7 @@ class LPIPS(nn.Module):
             raise ValueError(f"unknown net {net!r}: 'alex' or 'vgg'")
         self.pnet_type = net
         convs, self.chns, self._abi = _NETS[net]
+        self._form = (_lib.CID_VGG_LPIPS,) if self._abi == "vgg" else ()
         self.scaling_layer = _ScalingLayer()
         self.net = nn.Module()
         for k in range(1, 6):
@@ -92,75 +86,10 @@ class LPIPS(nn.Module):
         for p in self.parameters():
             p.requires_grad_(False)
         self.eval()
-        self._cid = ctypes.c_void_p()
-        self._check(self._fn("create")(ctypes.byref(self._cid)), handle=False)
-        self._blob = None          # packed weights on the device (uint8 tensor, owns the memory)
-        self._packed_sig = None
-        self._ws = None            # workspace (uint8 tensor, grow-only)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_cid", None):
-                self._fn("destroy")(self._cid)
-                self._cid = None
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------------ the C ABI family of this net: cid_lpips_* or cid_vgg_*
-    def _fn(self, name: str):
-        return getattr(_lib.lib(), f"cid_{self._abi}_{name}")
-
-    def _check(self, rc: int, handle: bool = True) -> None:
-        (_lib.check_vgg if self._abi == "vgg" else _lib.check_lpips)(self._cid if handle else None, rc)
-
-    def _form(self) -> tuple:
-        """The leading `what` argument of cid_vgg_workspace_bytes / cid_vgg_stage_view; cid_lpips_* has none."""
-        return (_lib.CID_VGG_LPIPS,) if self._abi == "vgg" else ()
-
-    # ------------------------------------------------------------------ weights
-    def _device(self) -> torch.device:
-        return next(self.parameters()).device
+        self._create()
 
     def _tensors(self):
         return [(k, t) for k, t in self.state_dict(keep_vars=True).items() if not k.startswith("lins.")]
-
-    def _signature(self):
-        return tuple((k, t.data_ptr(), t._version, str(t.device)) for k, t in self._tensors())
-
-    def pack_weights(self, force: bool = False) -> torch.Tensor:
-        """Pack the state_dict into the kernels' layout on the module's GPU (if anything changed since the last call)."""
-        sig = self._signature()
-        if not force and self._blob is not None and sig == self._packed_sig:
-            return self._blob
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("LPIPS runs only on an AMD GPU (HIP kernels behind libcid.so); move it with .to('cuda') first. "
-                               "There is no CPU fallback.")
-        for key, t in self._tensors():
-            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-            self._check(self._fn("set_weight")(self._cid, key.encode(), a.ctypes.data, shape, a.ndim))
-        blob = torch.empty(self._fn("packed_weights_bytes")(self._cid), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self._check(self._fn("upload_weights")(self._cid, blob.data_ptr(), stream))
-        self._blob, self._packed_sig = blob, sig
-        return blob
-
-    # ------------------------------------------------------------------ forward
-    def _ensure_workspace(self, n: int, h: int, w: int, device: torch.device) -> None:
-        need = ctypes.c_size_t()
-        rc = self._fn("workspace_bytes")(*self._form(), n, h, w, ctypes.byref(need))
-        if self._abi == "vgg":
-            _shape_error(rc, "LPIPS(net='vgg')", n, h, w, f"{VGG_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE} (four 2x2 pools down to 1x1)")
-        else:
-            _shape_error(rc, "LPIPS", n, h, w, f"H, W >= {MIN_SIDE} (AlexNet's maps 7 -> 3 -> 1) and sides of at most 1024")
-        self._check(rc)
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
-            if self._ws is not None:
-                torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=device)
 
     def distances(self, a: torch.Tensor, b: torch.Tensor, unit_view: bool = False, per_layer: bool = False):
         """cid_lpips on the current stream: float64 [N] on the device, with per_layer also float64 [N,5] = d_0 ... d_4.  Each operand
@@ -169,7 +98,11 @@ class LPIPS(nn.Module):
             raise RuntimeError("LPIPS is in train mode: the metric is defined in eval mode (dropout inert); call .eval()")
         dev = self._device()
         (fa, fb), (n, h, w) = _check_pair(a, b, dev, "LPIPS")
-        self._ensure_workspace(n, h, w, dev)
+        if self._abi == "vgg":
+            needs = f"LPIPS(net='vgg') needs {VGG_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE} (four 2x2 pools down to 1x1)"
+        else:
+            needs = f"LPIPS needs H, W >= {MIN_SIDE} (AlexNet's maps 7 -> 3 -> 1) and sides of at most 1024"
+        self._ensure_workspace(dev, n, h, w, needs=needs)
         self.pack_weights()
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty((n,), dtype=torch.float64, device=dev)
@@ -197,19 +130,7 @@ class LPIPS(nn.Module):
     def stage(self, name: str, n: int, h: int, w: int) -> torch.Tensor:
         """What the last call over n pairs of h x w images left in the workspace, as fp32 [2 n,C,Hs,Ws] (a copy): "relu1" ... "relu5";
         operand a's n images, then operand b's (cid_lpips_stage_view)."""
-        off, c, hs, ws, cb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        rc = self._fn("stage_view")(*self._form(), name.encode(), n, h, w, ctypes.byref(off), ctypes.byref(c), ctypes.byref(hs),
-                                    ctypes.byref(ws), ctypes.byref(cb))
-        if rc != _lib.CID_OK:
-            raise KeyError(f"no stored stage {name!r} for {n} pairs of {h}x{w} (cid_{self._abi}_stage_view -> {rc})")
-        return _stage_tensor(self._ws, off.value, n, c.value, hs.value, ws.value, cb.value)
-
-
-def _stage_tensor(ws: torch.Tensor, off: int, n: int, c: int, hs: int, wsz: int, cb: int) -> torch.Tensor:
-    count = 2 * n * c * hs * wsz
-    t = ws[off:off + 4 * count].view(torch.float32)
-    t = t.view(2 * n, c // cb, hs, wsz, cb).permute(0, 1, 4, 2, 3)
-    return t.reshape(2 * n, c, hs, wsz).clone()
+        return self._stage(2 * n, name, f"{n} pairs of {h}x{w}", n, h, w)
 
 
 def _check_pair(a, b, dev, what: str):
@@ -228,13 +149,17 @@ def _check_pair(a, b, dev, what: str):
 
 
 _VGG_LOSS_IDX = (0, 2, 5, 7, 10, 12, 14)
+_VGG_SLICE_OF = {idx: k for k, idx, *_ in _VGG_CONVS}
 
 
-class VGGPerceptualLoss(nn.Module):
+class VGGPerceptualLoss(_packed.PackedModule):
     """The reference trainers' VGGPerceptualLoss (sr_ganTrainGNew.py:83-94, training.py:101-111): MSELoss of vgg16.features[:16] on
     the two operands as they are, with the reference's parameter names slice.{0,2,5,7,10,12,14}.weight / .bias, frozen, eval mode.
     The forward runs in HIP kernels (cid_vgg_content_loss) on the current stream and has NO autograd history: the backward through
     VGG is not implemented, so the value can be logged or compared but not trained through."""
+
+    _abi = "vgg"
+    _form = (_lib.CID_VGG_CONTENT,)
 
     def __init__(self):
         super().__init__()
@@ -244,66 +169,24 @@ class VGGPerceptualLoss(nn.Module):
         for p in self.parameters():
             p.requires_grad_(False)
         self.eval()
-        self._cid = ctypes.c_void_p()
-        _lib.check_vgg(None, _lib.lib().cid_vgg_create(ctypes.byref(self._cid)))
-        self._blob = None
-        self._packed_sig = None
-        self._ws = None
+        self._create()
 
-    def __del__(self):
-        try:
-            if getattr(self, "_cid", None):
-                _lib.lib().cid_vgg_destroy(self._cid)
-                self._cid = None
-        except Exception:
-            pass
-
-    def _signature(self):
-        return tuple((k, t.data_ptr(), t._version, str(t.device)) for k, t in self.state_dict(keep_vars=True).items())
-
-    def pack_weights(self, force: bool = False) -> torch.Tensor:
-        """Pack the state_dict into the kernels' layout on the module's GPU (if anything changed since the last call)."""
-        sig = self._signature()
-        if not force and self._blob is not None and sig == self._packed_sig:
-            return self._blob
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("VGGPerceptualLoss runs only on an AMD GPU (HIP kernels behind libcid.so); move it with .to('cuda') "
-                               "first. There is no CPU fallback.")
-        L = _lib.lib()
-        slice_of = {idx: k for k, idx, *_ in _VGG_CONVS}
-        for key, t in self.state_dict(keep_vars=True).items():
-            _, idx, leaf = key.split(".")
-            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-            name = f"net.slice{slice_of[int(idx)]}.{idx}.{leaf}"
-            _lib.check_vgg(self._cid, L.cid_vgg_set_weight(self._cid, name.encode(), a.ctypes.data, shape, a.ndim))
-        blob = torch.empty(L.cid_vgg_packed_weights_bytes(self._cid), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check_vgg(self._cid, L.cid_vgg_upload_weights(self._cid, blob.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-        self._blob, self._packed_sig = blob, sig
-        return blob
+    def _key(self, key: str) -> str:
+        _, idx, leaf = key.split(".")
+        return f"net.slice{_VGG_SLICE_OF[int(idx)]}.{idx}.{leaf}"
 
     def per_image(self, x: torch.Tensor, y: torch.Tensor, unit_view: bool = False) -> torch.Tensor:
         """cid_vgg_content_loss on the current stream: float64 [N] on the device, the mean squared difference of relu3_3 per pair."""
         if self.training:
             raise RuntimeError("VGGPerceptualLoss is in train mode: the reference keeps it in eval mode; call .eval()")
-        dev = next(self.parameters()).device
+        dev = self._device()
         (fx, fy), (n, h, w) = _check_pair(x, y, dev, "VGGPerceptualLoss")
-        need = ctypes.c_size_t()
-        rc = _lib.lib().cid_vgg_workspace_bytes(_lib.CID_VGG_CONTENT, n, h, w, ctypes.byref(need))
-        _shape_error(rc, "VGGPerceptualLoss", n, h, w, f"{VGG_LOSS_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE}")
-        _lib.check_vgg(self._cid, rc)
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != dev:
-            if self._ws is not None:
-                torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        self._ensure_workspace(dev, n, h, w, needs=f"VGGPerceptualLoss needs {VGG_LOSS_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE}")
         self.pack_weights()
         x, y = x.detach().contiguous(), y.detach().contiguous()
         out = torch.empty((n,), dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
-            _lib.check_vgg(self._cid, _lib.lib().cid_vgg_content_loss(
+            self._check(_lib.lib().cid_vgg_content_loss(
                 self._cid, x.data_ptr(), fx, y.data_ptr(), fy, n, h, w, _lib.CID_LPIPS_UNIT_VIEW if unit_view else 0, out.data_ptr(),
                 self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
         return out
@@ -314,12 +197,7 @@ class VGGPerceptualLoss(nn.Module):
 
     def stage(self, name: str, n: int, h: int, w: int) -> torch.Tensor:
         """ "relu1" ... "relu3" (relu1_2, relu2_2, relu3_3) of the last call, fp32 [2 n,C,Hs,Ws] (a copy): x's n images, then y's."""
-        off, c, hs, ws, cb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        rc = _lib.lib().cid_vgg_stage_view(_lib.CID_VGG_CONTENT, name.encode(), n, h, w, ctypes.byref(off), ctypes.byref(c),
-                                           ctypes.byref(hs), ctypes.byref(ws), ctypes.byref(cb))
-        if rc != _lib.CID_OK:
-            raise KeyError(f"no stored stage {name!r} for {n} pairs of {h}x{w} (cid_vgg_stage_view -> {rc})")
-        return _stage_tensor(self._ws, off.value, n, c.value, hs.value, ws.value, cb.value)
+        return self._stage(2 * n, name, f"{n} pairs of {h}x{w}", n, h, w)
 
 
 def vgg_loss_state_dict(backbone_sd: Mapping) -> dict:
@@ -353,10 +231,7 @@ def build_vgg_loss(backbone, reader=None) -> VGGPerceptualLoss:
 def load_vgg_loss(backbone: Union[str, Mapping], device: Optional[Union[str, torch.device]] = None) -> VGGPerceptualLoss:
     """A VGGPerceptualLoss on `device` (default: current GPU) from a torchvision vgg16 state dict or a features-only one, a path or
     a mapping."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    if device is None or torch.device(device).type != "cuda":
-        raise RuntimeError("celebrity_image_denoiser_amd.load_vgg_loss: an AMD GPU is required (no CPU fallback)")
+    device = _packed.cuda_device(device, "load_vgg_loss")
     model = build_vgg_loss(backbone)
     model.to(device).eval()
     model.pack_weights()
@@ -402,10 +277,7 @@ def load_lpips(lin_ckpt: Union[str, Mapping], backbone: Union[str, Mapping, None
     unexpected key, as load_state_dict does."""
     from .api import _read_checkpoint_file
 
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    if device is None or torch.device(device).type != "cuda":
-        raise RuntimeError("celebrity_image_denoiser_amd.load_lpips: an AMD GPU is required (no CPU fallback)")
+    device = _packed.cuda_device(device, "load_lpips")
     model = build_lpips(lin_ckpt, backbone, strict, _read_checkpoint_file, net=net)
     model.to(device).eval()
     model.pack_weights()
