@@ -28,8 +28,9 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     LPIPS(net) / load_lpips(lin_ckpt, backbone, net=net)   lpips.LPIPS(net='alex'), the trainers' third metric, or net='vgg', the ESRGAN
                                   trainer's: metrics.lpips(a, b, model) -> float64 [N]; evaluate(denoised, clean, lpips=model) fills
                                   the third value
-    VGGPerceptualLoss() / load_vgg_loss(backbone)          the SRGAN and denoise trainers' content loss, MSE of vgg16.features[:16]
-                                  (forward value only, no autograd history)
+    VGGPerceptualLoss() / load_vgg_loss(backbone)          the SRGAN and denoise trainers' content loss, MSE of vgg16.features[:16];
+                                  with autograd=True differentiable with respect to its first operand (HIP backward), else the
+                                  value only, no autograd history
 
 Everything numeric runs in hand-written HIP kernels behind the C ABI in include/cid.h
 (csrc/ -> libcid.so).  There is no CPU fallback: if the library is missing the calls raise.

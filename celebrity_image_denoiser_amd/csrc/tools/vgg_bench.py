@@ -11,8 +11,13 @@ calls [min-max] after --warmup calls, the algorithmic TFLOP/s of the convolution
 in launch order, the mean and the minimum kernel time, the fp32-MFMA bound of the launch (its MACs over the peak) and the fraction of
 the peak it reaches; the slowest launch is named.
 
+--backward times the differentiable content loss instead: VGGPerceptualLoss(autograd=True)(x, y).backward() (cid_vgg_content_loss_saved
++ cid_vgg_content_backward, with torch's own mean / cast / accumulate around them) next to ATen fp32 autograd of the same slice with
+x alone requiring grad, at 16 pairs of 256 x 256 (the SRGAN trainer's hr_size and batch_size) and 4 pairs of 128 x 128.  With --trace
+the per-launch breakdown is that of the sixteen launches of one forward + backward.
+
     python celebrity_image_denoiser_amd/csrc/tools/vgg_bench.py [--iters 50] [--warmup 5] [--case N,SIDE ...] [--no-aten] [--trace]
-                                                                [--json out.json]
+                                                                [--backward] [--json out.json]
 """
 import argparse
 import csv
@@ -29,6 +34,7 @@ sys.path.insert(0, ROOT)
 
 MFMA_F32_PEAK = 157.3e12
 CASES = ((64, 128), (16, 256))
+BWD_CASES = ((16, 256), (4, 128))
 # (name, Cin, Cout, level): launch order of cid_vgg_lpips; the map of level k is (side >> k) squared
 LAUNCHES = (("relu1_1 (head, VALU)", 3, 64, 0), ("relu1_2", 64, 64, 0), ("relu2_1", 64, 128, 1), ("relu2_2", 128, 128, 1), ("relu3_1", 128, 256, 2),
             ("relu3_2", 256, 256, 2), ("relu3_3", 256, 256, 2), ("relu4_1", 256, 512, 3), ("relu4_2", 512, 512, 3), ("relu4_3", 512, 512, 3),
@@ -79,6 +85,25 @@ def aten_content(sd, a, b):
     t = aten_features(sd, torch.cat([a, b]), 3)[2]
     n = a.shape[0]
     return ((t[:n] - t[n:]) ** 2).mean(dim=(1, 2, 3))
+
+
+# launch order of the backward: (name, forward convolution whose data gradient it is, or None)
+BWD_LAUNCHES = (("grad3_3 (seed)", None), ("grad3_2", 6), ("grad3_1", 5), ("gradpool2", 4), ("grad2_1", 3), ("gradpool1", 2), ("grad1_1", 1),
+                ("grad_a (head, VALU)", 0))
+
+
+def train_flops(n, side):
+    """Forward of both towers and the data gradient of tower a through the seven convolutions."""
+    return 2.0 * 3 * n * sum(macs(l, side) for l in LAUNCHES[:7])
+
+
+def aten_content_train(sd, x, b):
+    """ATen fp32 autograd of the trainer's scalar with x alone requiring grad."""
+    import torch
+
+    with torch.no_grad():
+        fb = aten_features(sd, b, 3)[2]
+    return ((aten_features(sd, x, 3)[2] - fb) ** 2).mean()
 
 
 def timed_alternating(fns, warmup, iters):
@@ -155,6 +180,107 @@ def run_case(n, side, args):
     return row
 
 
+def setup_backward(n, side):
+    import torch
+
+    import celebrity_image_denoiser_amd as cid
+    from celebrity_image_denoiser_amd import synth
+
+    _, _, sd, a, b = setup(n, side)
+    np_sd = synth.make_lpips_state_dict("default", net="vgg")
+    loss = cid.load_vgg_loss({k: torch.from_numpy(v) for k, v in synth.vgg_loss_state_dict(np_sd).items()}, device="cuda:0", autograd=True)
+    return loss, sd, a.requires_grad_(True), b
+
+
+def run_backward_case(n, side, args):
+    import torch
+
+    loss, sd, a, b = setup_backward(n, side)
+    a2 = a.detach().clone().requires_grad_(True)
+
+    def hip():
+        a.grad = None
+        loss(a, b).backward()
+
+    def aten():
+        a2.grad = None
+        aten_content_train(sd, a2, b).backward()
+
+    fl = train_flops(n, side)
+    t = timed_alternating([hip] if args.no_aten else [hip, aten], args.warmup, args.iters)
+    row = {"N": n, "side": side, "content_loss_backward": {"gflop": fl / 1e9, "hip": summary(t[0], fl)}}
+    r = row["content_loss_backward"]
+    line = f"N={n:3d} pairs {side}x{side} loss + backward {fl / 1e9:.1f} GFLOP | " + fmt("hip", r["hip"])
+    if not args.no_aten:
+        hip(), aten()
+        # two fp32 runs decide some of the 1e8 ReLU units and pool windows differently, and each such unit moves a few pixels of the
+        # gradient by a visible amount: the maximum is theirs; the share of elements beyond 1e-5 of the scale says how few they are
+        # (the accuracy claim is tests/test_vgg_backward.py's, against float64 with each run's own decisions)
+        delta, scale = (a.grad - a2.grad).abs(), float(a2.grad.abs().max())
+        r["max_delta_vs_aten_over_max"] = float(delta.max()) / scale
+        r["share_beyond_1e-5_of_max"] = float((delta > 1e-5 * scale).double().mean())
+        r["aten"] = summary(t[1], fl)
+        line += " | " + fmt("aten", r["aten"]) + f" | hip/aten {r['hip']['ms_median'] / r['aten']['ms_median']:.2f}"
+        line += f" | max|delta| / max|grad| {r['max_delta_vs_aten_over_max']:.1e}, {100 * r['share_beyond_1e-5_of_max']:.4f}% of the elements beyond 1e-5"
+    print(line, flush=True)
+    return row
+
+
+def run_traced_backward(n, side, calls):
+    """The child of --backward --trace: a few forward + backward calls, nothing else."""
+    import torch
+
+    loss, _, a, b = setup_backward(n, side)
+    for _ in range(calls):
+        a.grad = None
+        loss(a, b).backward()
+    torch.cuda.synchronize()
+
+
+def trace_rows(n, side, args, extra, kernels):
+    with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR", "/tmp")) as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
+               "--traced-child", f"{n},{side}", "--trace-calls", str(args.trace_calls)] + extra
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode:
+            raise SystemExit(f"rocprofv3 failed ({r.returncode}):\n{r.stderr[-2000:]}")
+        rows = []
+        for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+            with open(f, newline="") as fh:
+                rows += list(csv.DictReader(fh))
+    if not rows:
+        raise SystemExit("rocprofv3 wrote no kernel trace")
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    return [r for r in rows if any(k in r["Kernel_Name"] for k in kernels)]
+
+
+def trace_backward(n, side, args):
+    """Per launch of one forward + backward, in launch order: mean and min ms, the launch's fp32-MFMA bound and its fraction of peak."""
+    ours = trace_rows(n, side, args, ["--backward"], ("k_vgg_head", "k_lpips_conv", "k_vgg_content", "k_vgg_seed", "k_vgg_dgrad"))
+    names = [(l[0], 2 * macs(l, side)) for l in LAUNCHES[:7]] + [("loss (float64, VALU)", 0)]
+    names += [(name, macs(LAUNCHES[conv], side) if conv is not None else 0) for name, conv in BWD_LAUNCHES]
+    per_call = len(names)
+    if len(ours) != per_call * args.trace_calls:
+        raise SystemExit(f"expected {per_call * args.trace_calls} launches in the trace, found {len(ours)}")
+    print(f"per launch of loss + backward at N={n} pairs {side}x{side} (one rocprofv3 --kernel-trace run of {args.trace_calls} calls, the first "
+          "dropped; mean / min ms)")
+    out, total = {}, 0.0
+    for i, (name, m) in enumerate(names):
+        t = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in ours[per_call + i::per_call]]
+        mean, mn = statistics.mean(t), min(t)
+        kernel = ours[i]["Kernel_Name"].split("(")[0].replace("void ", "").replace("cid::", "")
+        line = f"{name:26s} {kernel:48s} {mean:8.4f} / {mn:8.4f}"
+        if m:
+            bnd = 2.0 * n * m / MFMA_F32_PEAK * 1e3
+            line += f"   fp32-MFMA bound {bnd:7.4f} ms, fraction of peak {bnd / mean:.3f}"
+        print(line)
+        out[name] = {"kernel": kernel, "ms_mean": mean, "ms_min": mn}
+        total += mean
+    fwd = sum(v["ms_mean"] for v in list(out.values())[:8])
+    print(f"sum of one call's launches {total:.4f} ms: forward {fwd:.4f}, backward {total - fwd:.4f}")
+    return out
+
+
 def run_traced(n, side, calls):
     """The child of --trace: a few plain cid_vgg_lpips calls, nothing else."""
     import torch
@@ -219,26 +345,27 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--trace", action="store_true", help="per-launch times of each case from one rocprofv3 --kernel-trace run")
     ap.add_argument("--trace-calls", type=int, default=4)
+    ap.add_argument("--backward", action="store_true", help="time VGGPerceptualLoss(autograd=True) forward + backward against ATen autograd")
     ap.add_argument("--traced-child", type=parse_case, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.traced_child:
-        run_traced(*args.traced_child, args.trace_calls)
+        (run_traced_backward if args.backward else run_traced)(*args.traced_child, args.trace_calls)
         return
     if args.child:
-        rows = [run_case(n, side, args) for n, side in args.case]
+        rows = [(run_backward_case if args.backward else run_case)(n, side, args) for n, side in args.case]
     else:
         rows = []
-        for n, side in (args.case or CASES):
+        for n, side in (args.case or (BWD_CASES if args.backward else CASES)):
             # each case in a process of its own: allocator state and clocks of one do not reach the next
             with tempfile.NamedTemporaryFile(suffix=".json") as tf:
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case", f"{n},{side}", "--iters", str(args.iters),
                        "--warmup", str(args.warmup), "--json", tf.name]
-                cmd += ["--no-aten"] * args.no_aten
+                cmd += ["--no-aten"] * args.no_aten + ["--backward"] * args.backward
                 subprocess.run(cmd, check=True)
                 rows += json.load(open(tf.name))
             if args.trace:
-                rows.append({"trace": [n, side], "per_launch": trace(n, side, args)})
+                rows.append({"trace": [n, side], "per_launch": (trace_backward if args.backward else trace)(n, side, args)})
     if args.json:
         with open(args.json, "w") as f:
             json.dump(rows, f, indent=1)

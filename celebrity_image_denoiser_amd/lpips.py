@@ -6,9 +6,10 @@ perceptual metric (esrgan_train.py:65,133; net='vgg') — and the trainers' VGGP
     load_lpips(lin_ckpt, backbone=None, net="alex")   -> LPIPS from a full LPIPS state dict, or from the package's lin*-only weight
                                           file together with a torchvision AlexNet / vgg16 state dict
     metrics.lpips(a, b, model)            float64 [N] on the device (metrics.py)
-    VGGPerceptualLoss()                   the trainers' content loss: MSE of vgg16.features[:16]; forward(x, y) -> fp32 scalar,
-                                          per_image(x, y) -> float64 [N]; no autograd history
-    load_vgg_loss(backbone)               -> VGGPerceptualLoss from a torchvision vgg16 (or features-only) state dict
+    VGGPerceptualLoss(autograd=False)     the trainers' content loss: MSE of vgg16.features[:16]; forward(x, y) -> fp32 scalar,
+                                          per_image(x, y) -> float64 [N]; with autograd=True differentiable with respect to x
+                                          (cid_vgg_content_loss_saved / cid_vgg_content_backward), else no autograd history
+    load_vgg_loss(backbone, autograd=False)   -> VGGPerceptualLoss from a torchvision vgg16 (or features-only) state dict
 
 The definitions are stated once, in the header comments of include/cid.h (cid_lpips, cid_vgg_lpips, cid_vgg_content_loss).
 Everything numeric runs in HIP kernels behind cid_lpips_* and cid_vgg_*; there is no CPU fallback.  No weights ship with this package: synth.make_lpips_state_dict draws portable synthetic
@@ -16,6 +17,7 @@ ones, and INTEGRATION.md says how to obtain and pass the real ones.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Mapping, Optional, Union
 
 import numpy as np
@@ -152,17 +154,71 @@ _VGG_LOSS_IDX = (0, 2, 5, 7, 10, 12, 14)
 _VGG_SLICE_OF = {idx: k for k, idx, *_ in _VGG_CONVS}
 
 
+class _VGGLossFunction(torch.autograd.Function):
+    """forward = cid_vgg_content_loss_saved into an arena owned by this call's context, backward = cid_vgg_content_backward."""
+
+    @staticmethod
+    def forward(ctx, module, fy, shape, unit_view, x, y):
+        n, h, w = shape
+        dev = x.device
+        L = _lib.lib()
+        need = ctypes.c_size_t()
+        module._check(L.cid_vgg_saved_bytes(n, h, w, ctypes.byref(need)))
+        saved = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        out = torch.empty((n,), dtype=torch.float64, device=dev)
+        flags = _lib.CID_LPIPS_UNIT_VIEW if unit_view else 0
+        xc, yc = x.detach().contiguous(), y.detach().contiguous()
+        with torch.cuda.device(dev):
+            module._check(L.cid_vgg_content_loss_saved(
+                module._cid, xc.data_ptr(), _lib.CID_FMT_F32_NCHW, yc.data_ptr(), fy, n, h, w, flags, out.data_ptr(), saved.data_ptr(),
+                saved.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        ctx.module, ctx.shape, ctx.flags, ctx.saved = module, shape, flags, saved
+        ctx.save_for_backward(torch.empty(0, device=dev))   # freed with the graph: a second backward() raises torch's own error
+        ctx.names = [k for k, _ in module.named_parameters()]
+        ctx.versions = [p._version for p in module.parameters()]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        module = ctx.module
+        ctx.saved_tensors   # raises torch's "backward through the graph a second time" once the graph was freed
+        if ctx.saved is None:   # retain_graph=True
+            raise RuntimeError("VGGPerceptualLoss: this call's saved activations were released by its first backward")
+        for name, p, v in zip(ctx.names, module.parameters(), ctx.versions):
+            if p._version != v:
+                raise RuntimeError(f"VGGPerceptualLoss: parameter {name} was modified in place between a forward and its backward "
+                                   f"(version {p._version}, expected {v}); the gradient would be taken at the wrong weights")
+        n, h, w = ctx.shape
+        dev = ctx.saved.device
+        grad_x = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+        go = grad_out.to(torch.float64).contiguous()
+        with torch.cuda.device(dev):
+            module._pack_backward_weights()
+            module._check(_lib.lib().cid_vgg_content_backward(
+                module._cid, go.data_ptr(), grad_x.data_ptr(), n, h, w, ctx.flags, ctx.saved.data_ptr(), ctx.saved.numel(),
+                torch.cuda.current_stream(dev).cuda_stream))
+        ctx.saved = None
+        return None, None, None, None, grad_x, None
+
+
 class VGGPerceptualLoss(_packed.PackedModule):
     """The reference trainers' VGGPerceptualLoss (sr_ganTrainGNew.py:83-94, training.py:101-111): MSELoss of vgg16.features[:16] on
     the two operands as they are, with the reference's parameter names slice.{0,2,5,7,10,12,14}.weight / .bias, frozen, eval mode.
-    The forward runs in HIP kernels (cid_vgg_content_loss) on the current stream and has NO autograd history: the backward through
-    VGG is not implemented, so the value can be logged or compared but not trained through."""
+    The forward runs in HIP kernels (cid_vgg_content_loss) on the current stream.
+
+    autograd=False (default): no autograd history.  autograd=True: when grad mode is on and `x` requires grad, per_image records a
+    torch.autograd.Function whose backward is cid_vgg_content_backward (HIP kernels, d loss / d x through the seven frozen
+    convolutions), so the trainer's `g_loss = vgg(fake, hr) + ...; g_loss.backward()` reaches the generator; the activations live in a
+    per-call arena that is released after the backward.  `y` gets no gradient (y.requires_grad raises NotImplementedError); a uint8 `x`
+    has none and takes the plain path.  The weights stay frozen."""
 
     _abi = "vgg"
     _form = (_lib.CID_VGG_CONTENT,)
 
-    def __init__(self):
+    def __init__(self, autograd: bool = False):
         super().__init__()
+        self.autograd = bool(autograd)
         self.slice = nn.Sequential()
         for k, idx, cin, cout, ks, stride, pad in _VGG_CONVS[:7]:
             self.slice.add_module(str(idx), nn.Conv2d(cin, cout, ks, stride=stride, padding=pad))
@@ -170,18 +226,43 @@ class VGGPerceptualLoss(_packed.PackedModule):
             p.requires_grad_(False)
         self.eval()
         self._create()
+        self._bwd_blob = None      # the data-gradient weights on the device, packed at the first differentiable call
+        self._bwd_of = None        # the forward blob they were packed with
 
     def _key(self, key: str) -> str:
         _, idx, leaf = key.split(".")
         return f"net.slice{_VGG_SLICE_OF[int(idx)]}.{idx}.{leaf}"
 
+    def _pack_backward_weights(self) -> torch.Tensor:
+        """The backward blob (cid_vgg_upload_backward_weights) of the packed forward weights; rebuilt when pack_weights rebuilt those."""
+        blob = self.pack_weights()
+        if self._bwd_blob is None or self._bwd_of is not blob:
+            dev = blob.device
+            bwd = torch.empty(_lib.lib().cid_vgg_backward_weights_bytes(self._cid), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                self._check(_lib.lib().cid_vgg_upload_backward_weights(self._cid, bwd.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            self._bwd_blob, self._bwd_of = bwd, blob
+        return self._bwd_blob
+
     def per_image(self, x: torch.Tensor, y: torch.Tensor, unit_view: bool = False) -> torch.Tensor:
-        """cid_vgg_content_loss on the current stream: float64 [N] on the device, the mean squared difference of relu3_3 per pair."""
+        """cid_vgg_content_loss on the current stream: float64 [N] on the device, the mean squared difference of relu3_3 per pair.
+        With autograd=True, grad mode on and x requiring grad, the result carries the history of x."""
         if self.training:
             raise RuntimeError("VGGPerceptualLoss is in train mode: the reference keeps it in eval mode; call .eval()")
         dev = self._device()
         (fx, fy), (n, h, w) = _check_pair(x, y, dev, "VGGPerceptualLoss")
-        self._ensure_workspace(dev, n, h, w, needs=f"VGGPerceptualLoss needs {VGG_LOSS_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE}")
+        needs = f"VGGPerceptualLoss needs {VGG_LOSS_MIN_SIDE} <= H, W <= {VGG_MAX_SIDE}"
+        if self.autograd and torch.is_grad_enabled():
+            if y.requires_grad:
+                raise NotImplementedError("VGGPerceptualLoss(autograd=True): no gradient for the second operand (the reference's "
+                                          "hr_img never requires one); detach it")
+            if x.requires_grad and fx == _lib.CID_FMT_F32_NCHW:
+                need = ctypes.c_size_t()
+                if _lib.lib().cid_vgg_saved_bytes(n, h, w, ctypes.byref(need)) == 2:   # CID_ERR_SHAPE
+                    raise ValueError(f"image size {h}x{w} (N={n}) not accepted: {needs}")
+                self._pack_backward_weights()
+                return _VGGLossFunction.apply(self, fy, (n, h, w), bool(unit_view), x, y)
+        self._ensure_workspace(dev, n, h, w, needs=needs)
         self.pack_weights()
         x, y = x.detach().contiguous(), y.detach().contiguous()
         out = torch.empty((n,), dtype=torch.float64, device=dev)
@@ -192,7 +273,8 @@ class VGGPerceptualLoss(_packed.PackedModule):
         return out
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """The reference's call: the fp32 scalar MSELoss()(slice(x), slice(y)), the mean of per_image.  No autograd history."""
+        """The reference's call: the fp32 scalar MSELoss()(slice(x), slice(y)), the mean of per_image (torch's own differentiable
+        ops over the float64 [N], so with autograd=True the scalar trains through)."""
         return self.per_image(x, y).mean().to(torch.float32)
 
     def stage(self, name: str, n: int, h: int, w: int) -> torch.Tensor:
@@ -219,20 +301,21 @@ def vgg_loss_state_dict(backbone_sd: Mapping) -> dict:
     return out
 
 
-def build_vgg_loss(backbone, reader=None) -> VGGPerceptualLoss:
+def build_vgg_loss(backbone, reader=None, autograd: bool = False) -> VGGPerceptualLoss:
     """load_vgg_loss without the move to the GPU."""
     if reader is None:
         from .api import _read_checkpoint_file as reader
-    model = VGGPerceptualLoss()
+    model = VGGPerceptualLoss(autograd=autograd)
     model.load_state_dict(vgg_loss_state_dict(reader(backbone) if isinstance(backbone, str) else backbone), strict=True)
     return model
 
 
-def load_vgg_loss(backbone: Union[str, Mapping], device: Optional[Union[str, torch.device]] = None) -> VGGPerceptualLoss:
+def load_vgg_loss(backbone: Union[str, Mapping], device: Optional[Union[str, torch.device]] = None,
+                  autograd: bool = False) -> VGGPerceptualLoss:
     """A VGGPerceptualLoss on `device` (default: current GPU) from a torchvision vgg16 state dict or a features-only one, a path or
-    a mapping."""
+    a mapping.  `autograd=True` makes it differentiable with respect to its first operand (VGGPerceptualLoss)."""
     device = _packed.cuda_device(device, "load_vgg_loss")
-    model = build_vgg_loss(backbone)
+    model = build_vgg_loss(backbone, autograd=autograd)
     model.to(device).eval()
     model.pack_weights()
     return model

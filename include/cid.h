@@ -842,7 +842,8 @@ int cid_lpips(cid_lpips_t h, const void* a, int fmt_a, const void* b, int fmt_b,
 /*
  * VGG16 features — what the reference's trainers build on torchvision's vgg16: lpips.LPIPS(net='vgg') of lpips 0.1.4, the ESRGAN
  * trainer's perceptual metric (esrgan_code/esrgan_train.py:65,133), and VGGPerceptualLoss, the content loss of the SRGAN and denoise
- * trainers (srgan_code/sr_ganTrainGNew.py:83-94,217,405; denoise_gan_code/training.py:101-111).  Forward only, eval mode, fp32.
+ * trainers (srgan_code/sr_ganTrainGNew.py:83-94,217,405; denoise_gan_code/training.py:101-111).  Eval mode, fp32; the content loss
+ * also has its input gradient (cid_vgg_content_backward, below).
  * THE DEFINITION (kept here and nowhere else):
  *
  *   1. The backbone is torchvision vgg16 `features`, every convolution Conv2d(Cin,Cout,3,pad 1) + ReLU, every pool MaxPool2d(2,2)
@@ -908,6 +909,63 @@ int cid_vgg_lpips(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_
                   double* layers, void* workspace, size_t workspace_bytes, void* stream);
 int cid_vgg_content_loss(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The input gradient of the content loss — what the SRGAN trainer's generator step takes from VGGPerceptualLoss
+ * (srgan_code/sr_ganTrainGNew.py:403-409: content_loss = vgg_loss(fake_hr, hr_img); g_loss.backward()).  The weights are frozen, so
+ * there is no weight gradient; operand b (the trainer's hr_img) never requires one, so there is none for b either.
+ *
+ * cid_vgg_content_loss_saved is cid_vgg_content_loss — the same definition, the same kernels, the same `out` bits — with a
+ * caller-owned PER-CALL arena of cid_vgg_saved_bytes(N, H, W) bytes, 256-byte aligned, in place of the workspace.  It leaves the seven
+ * activations of both towers there, each in its own tensor (the plain call overwrites four of them in its two scratch tensors).
+ * Operand a must be fp32 [N,3,H,W]: a uint8 image has no gradient, and fmt_a = CID_FMT_U8_NHWC is CID_ERR_INVALID.  b may be either
+ * format.  Shape limits are cid_vgg_content_loss's: 4 <= H, W <= 512.
+ *
+ * cid_vgg_content_backward(h, grad_out, grad_a, N, H, W, flags, saved, saved_bytes, stream): N, H, W, flags and `saved` are those of
+ * the cid_vgg_content_loss_saved call to differentiate, on the same weights.  grad_out is device double [N] = dL/d out[n], read on
+ * the device; grad_a is device fp32 [N,3,H,W]:
+ *     grad_a[n] = grad_out[n] * d out[n] / d a[n],
+ * with the factor 0.5 of v*0.5f+0.5f included under CID_LPIPS_UNIT_VIEW.  1 + 6 + 1 launches on `stream`, no host synchronisation:
+ * the seed, six data gradients on the exact-fp32 MFMA (each a 3x3 convolution of the gradient with the flipped, transposed weights,
+ * summed as the forward sums: chains cut every 4 chunks of 4 channels, partial sums added in order) with both max-pool backwards
+ * taken while the operand is staged (first maximum of the 2x2 window in row-major order, v > max || isnan(v): ATen's rule; no
+ * unpooled tensor exists), and the first convolution's backward on the VALU.  A ReLU's mask is `saved activation > 0`.  No atomics:
+ * grad_a[n] depends on pair n and grad_out[n] alone, bit-identical in any batch, at any position in it and across runs.
+ *
+ * The data-gradient weights are a second blob of cid_vgg_backward_weights_bytes(h) bytes (about 7 MB), which only handles that run
+ * a backward pay for: cid_vgg_upload_backward_weights(h, device_blob, stream) packs it from the 14 tensors of net.slice1 ...
+ * net.slice3 (any missing: CID_ERR_STATE; blob not 256-byte aligned: CID_ERR_WORKSPACE).  cid_vgg_upload_weights drops it: upload
+ * it again after the forward blob.
+ *
+ * The arena holds, after the 7 activations ("relu1_1", "relu1_2", "relu2_1", "relu2_2", "relu3_1", "relu3_2", "relu3_3"; 2 N images
+ * each, operand a's N first), the 7 gradient tensors the backward stores, each written exactly once, N images, fp32.  With L the
+ * scalar sum_n grad_out[n] * out[n], z the value of a convolution before its ReLU and p a max-pool's output:
+ *     "grad3_3"    dL/d z3_3 = grad_out[n] * 2 / (256 H3 W3) * (relu3_3(a) - relu3_3(b)) where relu3_3(a) > 0, else 0
+ *                  (formed in double, rounded once)                                                     [N,256,H3,W3]
+ *     "grad3_2"    dL/d z3_2: masked by relu3_2 > 0                                                     [N,256,H3,W3]
+ *     "grad3_1"    dL/d z3_1: masked by relu3_1 > 0                                                     [N,256,H3,W3]
+ *     "gradpool2"  dL/d p2, the gradient of the second pool's OUTPUT: no mask, no routing yet           [N,128,H3,W3]
+ *     "grad2_1"    dL/d z2_1: masked by relu2_1 > 0 (dL/d z2_2, gradpool2 routed through the pool and
+ *                  masked by relu2_2 > 0, exists only in the staging of this launch)                    [N,128,H2,W2]
+ *     "gradpool1"  dL/d p1, the gradient of the first pool's output                                     [N,64,H2,W2]
+ *     "grad1_1"    dL/d z1_1: masked by relu1_1 > 0 (dL/d z1_2 likewise exists only in staging)         [N,64,H,W]
+ * cid_vgg_saved_view (testing aid) gives a stage's byte offset in the arena, its image count (2 N or N), channels, size and
+ * channel block (the C8 layout cid_lpips_stage_view describes).  Unknown stage -> CID_ERR_KEY.
+ *
+ * Everything refused is refused on the host before any launch:
+ *   CID_ERR_INVALID    null pointer, unknown format or flags, fmt_a not fp32, misaligned fp32 operand / out / grad_out / grad_a
+ *   CID_ERR_SHAPE      as cid_vgg_content_loss
+ *   CID_ERR_WORKSPACE  arena smaller than cid_vgg_saved_bytes(N, H, W) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded; cid_vgg_content_backward: backward weights not uploaded
+ */
+int cid_vgg_saved_bytes(int N, int H, int W, size_t* bytes);
+int cid_vgg_saved_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* images, int* C, int* Hs, int* Ws, int* channel_block);
+int cid_vgg_content_loss_saved(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags,
+                               double* out, void* saved, size_t saved_bytes, void* stream);
+size_t cid_vgg_backward_weights_bytes(cid_vgg_t h);
+int cid_vgg_upload_backward_weights(cid_vgg_t h, void* device_blob, void* stream);
+int cid_vgg_content_backward(cid_vgg_t h, const double* grad_out, float* grad_a, int N, int H, int W, unsigned flags, void* saved,
+                             size_t saved_bytes, void* stream);
 
 /*
  * Testing aid (no reference counterpart): fills the LDS of every CU with NaN on `stream`.  LDS is not cleared between
