@@ -1,0 +1,369 @@
+// The discriminator's saved forward, backward pass, device pack, masks and losses (cid_disc_*); kernels in disc_bwd_kernels.h.  Host code.
+#pragma once
+#include "../disc_bwd_kernels.h"
+#include "disc_forward.h"
+
+namespace {
+
+// What cid_disc_forward_saved keeps for one call.
+struct DiscSavedPlan {
+    size_t a0, z2, z5, z8, st, mi, slab[3], total;
+};
+
+void disc_saved_plan(int N, int H, int W, int training, const DiscPlan& p, DiscSavedPlan& q) {
+    const size_t n = (size_t)N, f = sizeof(float);
+    size_t at = 0;
+    q.a0 = take(at, n * 64 * H * W * f);
+    q.z2 = take(at, n * 64 * p.H2 * p.W2 * f);
+    q.z5 = take(at, n * 128 * p.H2 * p.W2 * f);
+    q.z8 = take(at, n * 128 * p.H4 * p.W4 * f);
+    q.st = take(at, 3 * 256 * f);
+    q.mi = take(at, 3 * 256 * sizeof(double));
+    const int couts[3] = {64, 128, 128};
+    for (int l = 0; l < 3; ++l) q.slab[l] = training ? take(at, (size_t)couts[l] * 2 * n * p.tiles[l] * sizeof(double)) : at;
+    q.total = at;
+}
+
+DiscBufs disc_saved_bufs(void* saved, const DiscSavedPlan& q) {
+    char* sv = static_cast<char*>(saved);
+    DiscBufs b{};
+    b.a0 = reinterpret_cast<float*>(sv + q.a0);
+    b.z2 = reinterpret_cast<float*>(sv + q.z2);
+    b.z5 = reinterpret_cast<float*>(sv + q.z5);
+    b.z8 = reinterpret_cast<float*>(sv + q.z8);
+    for (int l = 0; l < 3; ++l) {
+        b.st[l] = reinterpret_cast<float*>(sv + q.st) + l * 256;
+        b.mi[l] = reinterpret_cast<double*>(sv + q.mi) + l * 256;
+        b.slab[l] = reinterpret_cast<double*>(sv + q.slab[l]);
+    }
+    return b;
+}
+
+// Workspace of one backward call.  X holds the gradient of a6 and later of a0, Y the gradient of a3 (the forward's two regions).
+struct DiscBwdPlan {
+    int strips[3];                  // BatchNorm strips per image
+    int wg_tiles_x[3], wg_tiles[3]; // wgrad items per image of layers 2, 5, 8
+    int wg_splits[3];
+    int dg_tiles_x[3], dg_tiles[3]; // dgrad tiles of the largest class
+    int w0_strips, w0_splits;
+    size_t dl, mean, coef, bnslab, X, Y, part, part_b, part0, total;
+};
+
+constexpr int kDiscWgCD[3] = {64, 128, 128}, kDiscWgCX[3] = {64, 64, 128}, kDiscWgS[3] = {2, 1, 2};
+constexpr int kDiscDgTileRows[3] = {DiscDgradGeom<64, 64, 2>::TH, DiscDgradGeom<128, 64, 1>::TH, DiscDgradGeom<128, 128, 2>::TH};
+
+void disc_bwd_plan(int N, int H, int W, const DiscPlan& p, DiscBwdPlan& q) {
+    const size_t n = (size_t)N, f = sizeof(float);
+    const int ho[3] = {p.H2, p.H2, p.H4}, wo[3] = {p.W2, p.W2, p.W4};
+    const int hin[3] = {H, p.H2, p.H2}, win[3] = {W, p.W2, p.W2};
+    size_t bnslab = 0, part = 0, part_b = 0;
+    for (int l = 0; l < 3; ++l) {
+        q.strips[l] = (int)(((long long)ho[l] * wo[l] + D_BN_STRIP - 1) / D_BN_STRIP);
+        bnslab = std::max(bnslab, (size_t)kDiscBnC[l] * 2 * n * q.strips[l] * sizeof(double));
+        q.wg_tiles_x[l] = (wo[l] + D_TW - 1) / D_TW;
+        q.wg_tiles[l] = ((ho[l] + D_WG_TH - 1) / D_WG_TH) * q.wg_tiles_x[l];
+        const long long items = (long long)N * q.wg_tiles[l];
+        q.wg_splits[l] = (int)std::min<long long>(items, 512 / (kDiscWgCX[l] / 16));
+        part = std::max(part, (size_t)q.wg_splits[l] * kDiscWgCX[l] * kDiscWgCD[l] * 9 * f);
+        part_b = std::max(part_b, (size_t)q.wg_splits[l] * kDiscWgCD[l] * sizeof(double));
+        const int hc = (hin[l] + kDiscWgS[l] - 1) / kDiscWgS[l], wc = (win[l] + kDiscWgS[l] - 1) / kDiscWgS[l];
+        q.dg_tiles_x[l] = (wc + D_TW - 1) / D_TW;
+        q.dg_tiles[l] = ((hc + kDiscDgTileRows[l] - 1) / kDiscDgTileRows[l]) * q.dg_tiles_x[l];
+    }
+    q.w0_strips = (int)(((long long)H * W + 63) / 64);
+    q.w0_splits = (int)std::min<long long>((long long)N * q.w0_strips, 1024);
+    size_t at = 0;
+    q.dl = take(at, n * f);
+    q.mean = take(at, n * 128 * sizeof(double));
+    q.coef = take(at, 3 * 128 * D_COEF * f);
+    q.bnslab = take(at, bnslab);
+    q.X = take(at, std::max(n * 128 * p.H2 * p.W2, n * 64 * H * W) * f);
+    q.Y = take(at, n * 64 * p.H2 * p.W2 * f);
+    q.part = take(at, part);
+    q.part_b = take(at, part_b);
+    q.part0 = take(at, (size_t)q.w0_splits * 64 * 28 * sizeof(double));
+    q.total = at;
+}
+
+template <int CD, int CX, int S, bool BN_IN, bool HEAD>
+hipError_t disc_wgrad_launch(const DiscWgradArgs& a, float* dw, float* db, hipStream_t s) {
+    hipLaunchKernelGGL((k_disc_wgrad<CD, CX, S, BN_IN, HEAD>), dim3((unsigned)a.splits, CX / 16), dim3(D_THREADS), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const DiscWgradReduceArgs r{a.part, a.part_b, dw, db, a.splits, CD, CX};
+    hipLaunchKernelGGL(k_disc_wgrad_reduce, dim3((CD * CX * 9 + CD + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
+    return hipGetLastError();
+}
+
+template <int CD, int CX, int S, bool HEAD>
+hipError_t disc_dgrad_launch(const DiscDgradArgs& base, int tiles, int N, hipStream_t s) {
+    (void)for_each_launch(N, [&](int n0, int n) {
+        DiscDgradArgs a = base;
+        a.n0 = n0;
+        const dim3 grid((unsigned)tiles, (unsigned)n, DiscDgradGeom<CD, CX, S>::CLASSES);
+        hipLaunchKernelGGL((k_disc_dgrad<CD, CX, S, HEAD>), grid, dim3(D_THREADS), 0, s, a);
+    });
+    return hipGetLastError();
+}
+
+template <int C, bool HEAD>
+hipError_t disc_bn_part_launch(const DiscBnPartArgs& base, int N, hipStream_t s) {
+    (void)for_each_launch(N, [&](int n0, int n) {
+        DiscBnPartArgs a = base;
+        a.n0 = n0;
+        hipLaunchKernelGGL((k_disc_bn_bwd_part<C, HEAD>), dim3((unsigned)a.strips, (unsigned)n), dim3(D_THREADS), 0, s, a);
+    });
+    return hipGetLastError();
+}
+
+// Shape checks shared by the backward entry points.
+int disc_bwd_shape(const Call& cx, int N, int H, int W, int training, DiscPlan& p) {
+    if (training != 0 && training != 1) return cx.fail(CID_ERR_INVALID, "training must be 0 or 1");
+    if (disc_plan(N, H, W, training, p) != CID_OK)
+        return cx.fail(CID_ERR_SHAPE, "shape not accepted (N, H, W >= 1, H*W < 2^31, more than one value per channel in train mode)");
+    return CID_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cid_disc_saved_bytes(int N, int H, int W, int training, size_t* bytes) {
+    if (!bytes || (training != 0 && training != 1)) return CID_ERR_INVALID;
+    DiscPlan p;
+    DiscSavedPlan q;
+    const int rc = disc_plan(N, H, W, training, p);
+    if (rc == CID_OK) disc_saved_plan(N, H, W, training, p, q);
+    return plan_bytes(rc, q, bytes);
+}
+
+int cid_disc_forward_saved(cid_disc_t d, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn,
+                           int training, void* saved, size_t saved_bytes, void* stream) {
+    if (!d) return CID_ERR_INVALID;
+    const Call cx(d, "cid_disc_forward_saved", stream);
+    DiscPlan p;
+    if (const int rc = disc_check_forward(cx, in, in_fmt, out, N, H, W, bn, training, saved, p)) return rc;
+    DiscSavedPlan q;
+    disc_saved_plan(N, H, W, training, p, q);
+    if (const int rc = cx.room(saved, saved_bytes, q.total, "cid_disc_saved_bytes", "saved buffer")) return rc;
+    if (const int rc = cx.uploaded()) return rc;
+    return disc_forward_run(cx, in, in_fmt, out, N, H, W, bn, training, p, disc_saved_bufs(saved, q));
+}
+
+int cid_disc_backward_workspace_bytes(int N, int H, int W, int training, size_t* bytes) {
+    if (!bytes || (training != 0 && training != 1)) return CID_ERR_INVALID;
+    DiscPlan p;
+    DiscBwdPlan q;
+    const int rc = disc_plan(N, H, W, training, p);
+    if (rc == CID_OK) disc_bwd_plan(N, H, W, p, q);
+    return plan_bytes(rc, q, bytes);
+}
+
+int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* grad_prob, int N, int H, int W, const cid_disc_bn* bn,
+                      int training, const void* saved, size_t saved_bytes, const cid_disc_grads* g, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (!d) return CID_ERR_INVALID;
+    const Call cx(d, "cid_disc_backward", stream);
+    if (!in || !grad_prob || !bn || !saved || !g || !workspace) return cx.fail(CID_ERR_INVALID, "null pointer");
+    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return cx.fail(CID_ERR_INVALID, "unknown input format");
+    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)grad_prob & 3))
+        return cx.fail(CID_ERR_INVALID, "misaligned fp32 operand");
+    for (int l = 0; l < 3; ++l)
+        if (!bn[l].gamma) return cx.fail(CID_ERR_INVALID, "null BatchNorm weight pointer");
+    bool misaligned = ((uintptr_t)g->input & 3) != 0;
+    for (int i = 0; i < 5; ++i) misaligned = misaligned || ((uintptr_t)g->w[i] & 3) || ((uintptr_t)g->b[i] & 3);
+    for (int l = 0; l < 3; ++l) misaligned = misaligned || ((uintptr_t)g->gamma[l] & 3) || ((uintptr_t)g->beta[l] & 3);
+    if (misaligned) return cx.fail(CID_ERR_INVALID, "misaligned gradient pointer");
+    if (g->input && in_fmt != CID_FMT_F32_NCHW)
+        return cx.fail(CID_ERR_INVALID, "a uint8 input has no gradient (grads.input must be null)");
+    DiscPlan p;
+    if (const int rc = disc_bwd_shape(cx, N, H, W, training, p)) return rc;
+    DiscSavedPlan sp;
+    disc_saved_plan(N, H, W, training, p, sp);
+    if (const int rc = cx.room(saved, saved_bytes, sp.total, "cid_disc_saved_bytes", "saved buffer")) return rc;
+    DiscBwdPlan q;
+    disc_bwd_plan(N, H, W, p, q);
+    if (const int rc = cx.room(workspace, workspace_bytes, q.total, "cid_disc_backward_workspace_bytes")) return rc;
+    if (const int rc = cx.uploaded()) return rc;
+
+    const hipStream_t s = cx.s;
+    const DiscBufs sv = disc_saved_bufs(const_cast<void*>(saved), sp);
+    char* ws = static_cast<char*>(workspace);
+    float* dl = reinterpret_cast<float*>(ws + q.dl);
+    double* mean = reinterpret_cast<double*>(ws + q.mean);
+    float* coef[3];
+    for (int l = 0; l < 3; ++l) coef[l] = reinterpret_cast<float*>(ws + q.coef) + l * 128 * D_COEF;
+    double* bnslab = reinterpret_cast<double*>(ws + q.bnslab);
+    float* X = reinterpret_cast<float*>(ws + q.X);
+    float* Y = reinterpret_cast<float*>(ws + q.Y);
+    float* part = reinterpret_cast<float*>(ws + q.part);
+    double* part_b = reinterpret_cast<double*>(ws + q.part_b);
+    double* part0 = reinterpret_cast<double*>(ws + q.part0);
+    const float* blob = d->dev_blob;
+
+    // what is asked for at or below each stage: head(8) > bn9(7) > conv8(6) > bn6(5) > conv5(4) > bn3(3) > conv2(2) > conv0(1) > input(0)
+    const bool want[9] = {g->input != nullptr, g->w[0] || g->b[0], g->w[1] || g->b[1], g->gamma[0] || g->beta[0], g->w[2] || g->b[2],
+                          g->gamma[1] || g->beta[1], g->w[3] || g->b[3], g->gamma[2] || g->beta[2], g->w[4] || g->b[4]};
+    bool below[10];   // below[k]: something at a stage < k is asked for
+    below[0] = false;
+    for (int k = 0; k < 9; ++k) below[k + 1] = below[k] || want[k];
+    if (!below[9]) return CID_OK;
+    const long long P4 = (long long)p.H4 * p.W4, P2 = (long long)p.H2 * p.W2;
+
+    // head
+    if (const int rc = cx.launches(N, "head", [&](int n0, int n) {
+        DiscHeadBwdArgs a{sv.z8, sv.st[2], blob + kDiscBlob.off[4], grad_prob, mean, dl, P4, n0};
+        hipLaunchKernelGGL(k_disc_head_bwd, dim3((unsigned)n), dim3(D_HEAD_THREADS), 0, s, a);
+    })) return rc;
+    {
+        DiscHeadReduceArgs a{mean, dl, blob + kDiscBlob.off[4], g->w[4], g->b[4], coef[2], (double)P4, N};
+        hipLaunchKernelGGL(k_disc_head_reduce, dim3(1), dim3(128), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("head reduce");
+    }
+    if (!below[8]) return CID_OK;
+
+    const auto bn_reduce = [&](int l, long long pix) {
+        DiscBnRedArgs a{bnslab, (long long)N * q.strips[l], (double)N * (double)pix, bn[l].gamma, sv.st[l], sv.mi[l], training,
+                        coef[l], g->gamma[l], g->beta[l]};
+        hipLaunchKernelGGL(k_disc_bn_bwd_reduce, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
+        return hipPeekAtLastError();
+    };
+    const auto bn_part = [&](int l, const float* z, const float* up, long long pix) {
+        DiscBnPartArgs a{z, up, dl, coef[l], sv.st[l], sv.mi[l], bnslab, (long long)N * q.strips[l], pix, q.strips[l], 0};
+        return a;
+    };
+    const auto wg_args = [&](int l, const DiscDzSrc& dz, const float* ain, const float* st_in, int Hin, int Win, int Ho, int Wo) {
+        DiscWgradArgs a{};
+        a.dz = dz;
+        a.ain = ain;
+        a.st_in = st_in;
+        a.part = part;
+        a.part_b = part_b;
+        a.items = (long long)N * q.wg_tiles[l];
+        a.splits = q.wg_splits[l];
+        a.Hin = Hin;
+        a.Win = Win;
+        a.Ho = Ho;
+        a.Wo = Wo;
+        a.tiles_x = q.wg_tiles_x[l];
+        a.tiles = q.wg_tiles[l];
+        return a;
+    };
+    const auto dg_args = [&](int l, int ci, const DiscDzSrc& dz, float* out, int Hin, int Win, int Ho, int Wo) {
+        DiscDgradArgs a{};
+        a.dz = dz;
+        a.w = blob + kDiscBlob.off[ci];
+        a.out = out;
+        a.Hin = Hin;
+        a.Win = Win;
+        a.Ho = Ho;
+        a.Wo = Wo;
+        a.tiles_x = q.dg_tiles_x[l];
+        return a;
+    };
+
+    // BN9 (upstream: the head's dl[n] * w12[c] / P4), layer 8
+    if (disc_bn_part_launch<128, true>(bn_part(2, sv.z8, nullptr, P4), N, s) != hipSuccess) return cx.hip("bn9 sums");
+    if (bn_reduce(2, P4) != hipSuccess) return cx.hip("bn9 reduce");
+    const DiscDzSrc dz8{sv.z8, nullptr, dl, coef[2]};
+    if (want[6] && disc_wgrad_launch<128, 128, 2, true, true>(wg_args(2, dz8, sv.z5, sv.st[1], p.H2, p.W2, p.H4, p.W4), g->w[3], g->b[3], s) != hipSuccess)
+        return cx.hip("wgrad8");
+    if (!below[6]) return CID_OK;
+    if (disc_dgrad_launch<128, 128, 2, true>(dg_args(2, 3, dz8, X, p.H2, p.W2, p.H4, p.W4), q.dg_tiles[2], N, s) != hipSuccess) return cx.hip("dgrad8");
+    // BN6, layer 5
+    if (disc_bn_part_launch<128, false>(bn_part(1, sv.z5, X, P2), N, s) != hipSuccess) return cx.hip("bn6 sums");
+    if (bn_reduce(1, P2) != hipSuccess) return cx.hip("bn6 reduce");
+    const DiscDzSrc dz5{sv.z5, X, nullptr, coef[1]};
+    if (want[4] && disc_wgrad_launch<128, 64, 1, true, false>(wg_args(1, dz5, sv.z2, sv.st[0], p.H2, p.W2, p.H2, p.W2), g->w[2], g->b[2], s) != hipSuccess)
+        return cx.hip("wgrad5");
+    if (!below[4]) return CID_OK;
+    if (disc_dgrad_launch<128, 64, 1, false>(dg_args(1, 2, dz5, Y, p.H2, p.W2, p.H2, p.W2), q.dg_tiles[1], N, s) != hipSuccess) return cx.hip("dgrad5");
+    // BN3, layer 2
+    if (disc_bn_part_launch<64, false>(bn_part(0, sv.z2, Y, P2), N, s) != hipSuccess) return cx.hip("bn3 sums");
+    if (bn_reduce(0, P2) != hipSuccess) return cx.hip("bn3 reduce");
+    const DiscDzSrc dz2{sv.z2, Y, nullptr, coef[0]};
+    if (want[2] && disc_wgrad_launch<64, 64, 2, false, false>(wg_args(0, dz2, sv.a0, nullptr, H, W, p.H2, p.W2), g->w[1], g->b[1], s) != hipSuccess)
+        return cx.hip("wgrad2");
+    if (!below[2]) return CID_OK;
+    if (disc_dgrad_launch<64, 64, 2, false>(dg_args(0, 1, dz2, X, H, W, p.H2, p.W2), q.dg_tiles[0], N, s) != hipSuccess) return cx.hip("dgrad2");
+    // layer 0
+    if (want[1]) {
+        DiscWgrad0Args a{in, sv.a0, X, part0, (long long)N * q.w0_strips, q.w0_splits, q.w0_strips, H, W};
+        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_wgrad0<true>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_disc_wgrad0<false>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("wgrad0");
+        DiscWgrad0ReduceArgs r{part0, g->w[0], g->b[0], q.w0_splits};
+        hipLaunchKernelGGL(k_disc_wgrad0_reduce, dim3((64 * 28 + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("wgrad0 reduce");
+    }
+    if (want[0]) {
+        if (const int rc = cx.launches(N, "dgrad0", [&](int n0, int n) {
+            DiscDgrad0Args a{sv.a0, X, blob + kDiscBlob.off[0], g->input, H, W, n0};
+            const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)n);
+            hipLaunchKernelGGL(k_disc_dgrad0, grid, dim3(D_THREADS), 0, s, a);
+        })) return rc;
+    }
+    return CID_OK;
+}
+
+int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, void* device_blob, void* stream) {
+    if (!d) return CID_ERR_INVALID;
+    if (!dev_params || !device_blob) return d->fail(CID_ERR_INVALID, "cid_disc_pack_weights_device: null pointer");
+    for (int i = 0; i < CID_DISC_NUM_WEIGHTS; ++i)
+        if (!dev_params[i] || ((uintptr_t)dev_params[i] & 3))
+            return d->fail(CID_ERR_INVALID, "cid_disc_pack_weights_device: null or misaligned parameter pointer");
+    if ((uintptr_t)device_blob & 255) return d->fail(CID_ERR_WORKSPACE, "cid_disc_pack_weights_device: blob must be 256-byte aligned");
+    DiscPackArgs a{};
+    for (int i = 0; i < kDiscConvs; ++i) {
+        a.w[i] = dev_params[2 * i];
+        a.b[i] = dev_params[2 * i + 1];
+        a.off[i] = (int)kDiscBlob.off[i];
+        a.cin[i] = kDiscConv[i].cin;
+        a.cout[i] = kDiscConv[i].cout;
+        a.kk[i] = kDiscConv[i].k * kDiscConv[i].k;
+    }
+    a.blob = static_cast<float*>(device_blob);
+    a.total = (int)kDiscBlob.total;
+    hipLaunchKernelGGL(k_disc_pack, dim3((a.total + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    if (hipGetLastError() != hipSuccess) return d->fail(CID_ERR_HIP, "cid_disc_pack_weights_device: launch failed");
+    d->dev_blob = static_cast<const float*>(device_blob);
+    return CID_OK;
+}
+
+int cid_disc_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int W, int training, unsigned char* const* masks, void* stream) {
+    if (!saved || !masks || (training != 0 && training != 1)) return CID_ERR_INVALID;
+    for (int i = 0; i < 4; ++i)
+        if (!masks[i]) return CID_ERR_INVALID;
+    DiscPlan p;
+    const int rc = disc_plan(N, H, W, training, p);
+    if (rc != CID_OK) return rc;
+    DiscSavedPlan sp;
+    disc_saved_plan(N, H, W, training, p, sp);
+    if (saved_bytes < sp.total || ((uintptr_t)saved & 255)) return CID_ERR_WORKSPACE;
+    const DiscBufs sv = disc_saved_bufs(const_cast<void*>(saved), sp);
+    const float* z[4] = {sv.a0, sv.z2, sv.z5, sv.z8};
+    const float* st[4] = {nullptr, sv.st[0], sv.st[1], sv.st[2]};
+    const int C[4] = {64, 64, 128, 128};
+    const long long P[4] = {(long long)H * W, (long long)p.H2 * p.W2, (long long)p.H2 * p.W2, (long long)p.H4 * p.W4};
+    for (int i = 0; i < 4; ++i) {
+        DiscMaskArgs a{z[i], st[i], masks[i], (long long)N * C[i] * P[i], P[i], C[i]};
+        const long long blocks = (a.total + D_THREADS - 1) / D_THREADS;
+        if (blocks > 0x7fffffffLL) return CID_ERR_SHAPE;
+        hipLaunchKernelGGL(k_disc_masks, dim3((unsigned)blocks), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
+        if (hipGetLastError() != hipSuccess) return CID_ERR_HIP;
+    }
+    return CID_OK;
+}
+
+int cid_disc_losses(const float* p_real, const float* p_fake, const void* den, int d_fmt, const void* clean, int c_fmt,
+                    int N, int H, int W, double* out, void* stream) {
+    if (!p_real || !p_fake || !den || !clean || !out) return CID_ERR_INVALID;
+    if (!fmt_ok(den, d_fmt) || !fmt_ok(clean, c_fmt) || ((uintptr_t)p_real & 3) || ((uintptr_t)p_fake & 3) || ((uintptr_t)out & 7))
+        return CID_ERR_INVALID;
+    if (N < 1 || H < 1 || W < 1) return CID_ERR_SHAPE;
+    DiscLossArgs a{p_real, p_fake, den, clean, d_fmt, c_fmt, N, (long long)H * W, out};
+    hipLaunchKernelGGL(k_disc_losses, dim3(1), dim3(D_LOSS_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
-// cid_api.hip — the C ABI of include/cid.h: weight repacking, workspace planning and the launch
-// sequence of one forward.  Host code; the device kernels are in conv_kernels.h.
-//
+// cid_api.hip — the C ABI of include/cid.h, one translation unit.  This file holds the denoising generator (cid_*: weight repacking,
+// workspace planning, the launch sequence of one forward, the weight broadcast, the backward pass) and includes every other family's
+// host file from api/; the device kernels are in the *_kernels.h headers, shared host plumbing in api_common.h and weight_store.h.
 // Layer table = the reference module's declaration order, backend/app.py:42-78.
 #include "../../include/cid.h"
 #include "conv_kernels.h"
@@ -256,11 +256,9 @@ Plan make_plan(const Dims& d) {
 
 }  // namespace
 
-struct cid_handle_s {
+struct cid_handle_s : HandleBase {
     std::vector<float> staging;        // packed host blob
     bool have[NL][2];
-    const float* dev_blob = nullptr;
-    std::string err;
     int dtype = CID_DTYPE_F32;         // storage type of activations/weights between the first and last kernel
     int tail_algo = CID_TAIL_FUSED;    // last layer: see cid_set_tail_algo
     int algo = CID_ALGO_WINOGRAD42;    // 3x3 GEMM layers: Winograd F(4x2,3x3) (default), Winograd F(2x2,3x3) or CID_ALGO_DIRECT (9-tap implicit GEMM)
@@ -359,11 +357,6 @@ struct KernelNames {
 };
 const KernelNames kKernelNames;
 
-int fail(cid_handle_t h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
 bool find_key(const char* key, int& layer, int& is_bias) {
     if (!key) return false;
     const std::string k(key);
@@ -374,8 +367,6 @@ bool find_key(const char* key, int& layer, int& is_bias) {
     }
     return false;
 }
-
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // The tile grid of a launch over N images of Hc x Wc computed pixels in tw x th tiles: the fields the kernels' tile decode
 // reads.  The head and tail kernels then walk groups of tiles (tile_groups); the others deal tiles to the eight XCD groups.
@@ -665,20 +656,20 @@ int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_f
                 hipStream_t s, hipEvent_t* ev = nullptr, const Window* src_win = nullptr, const Window* crop_win = nullptr,
                 const Config* cfg = nullptr) {
     if (!h) return CID_ERR_INVALID;
-    if (!in || !out || !ws) return fail(h, CID_ERR_INVALID, "cid_forward: null pointer");
-    if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_forward: no device weights attached (call cid_upload_weights or cid_attach_weights)");
+    if (!in || !out || !ws) return h->fail(CID_ERR_INVALID, "cid_forward: null pointer");
+    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_forward: no device weights attached (call cid_upload_weights or cid_attach_weights)");
     Dims d;
     if (const char* why = shape_error(N, H, W, d)) {
         char m[256];
         std::snprintf(m, sizeof m, "cid_forward: input [%d,3,%d,%d] not accepted: %s", N, H, W, why);
-        return fail(h, CID_ERR_SHAPE, m);
+        return h->fail(CID_ERR_SHAPE, m);
     }
     const Plan p = make_plan(d);
-    if (ws_bytes < p.total_bytes) return fail(h, CID_ERR_WORKSPACE, "cid_forward: workspace smaller than cid_workspace_bytes()");
+    if (ws_bytes < p.total_bytes) return h->fail(CID_ERR_WORKSPACE, "cid_forward: workspace smaller than cid_workspace_bytes()");
     if ((in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) || (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC))
-        return fail(h, CID_ERR_INVALID, "cid_forward: unknown tensor format");
+        return h->fail(CID_ERR_INVALID, "cid_forward: unknown tensor format");
     if (((uintptr_t)ws & 255) || ((uintptr_t)h->dev_blob & 255) || (in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)))
-        return fail(h, CID_ERR_WORKSPACE, "cid_forward: workspace/weights must be 256-byte aligned, fp32 input 4-byte aligned");
+        return h->fail(CID_ERR_WORKSPACE, "cid_forward: workspace/weights must be 256-byte aligned, fp32 input 4-byte aligned");
     const bool armed = !ev && !cfg && h->tev_used < h->tev_forwards;
     if (armed) ev = h->tev.data() + (size_t)h->tev_used * (NL + 1);
     float* base = static_cast<float*>(ws);
@@ -692,7 +683,7 @@ int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_f
         if (ev && hipEventRecord(ev[li], s) != hipSuccess) e = hipErrorUnknown;            \
         if (e == hipSuccess) e = (call);                                                   \
         if (e != hipSuccess) {                                                             \
-            return fail(h, CID_ERR_HIP, std::string("launch '") + kLayers[li].name + "' failed: " + hipGetErrorString(e)); \
+            return h->fail(CID_ERR_HIP, std::string("launch '") + kLayers[li].name + "' failed: " + hipGetErrorString(e)); \
         }                                                                                  \
         ++li;                                                                              \
     } while (0)
@@ -730,7 +721,7 @@ int run_forward(cid_handle_t h, const void* in, int in_fmt, void* out, int out_f
     // upconv1[2] + tanh, NHWC t4 -> NCHW out                                             app.py:77,103
     STEP(launch_tail(x, B[T4], out, out_fmt == CID_FMT_U8_NHWC, crop_win ? *crop_win : Window{0, 0, d.Hu1, d.Wu1}, d.Hu1, d.Wu1));
 #undef STEP
-    if (ev && hipEventRecord(ev[NL], s) != hipSuccess) return fail(h, CID_ERR_HIP, "hipEventRecord failed");
+    if (ev && hipEventRecord(ev[NL], s) != hipSuccess) return h->fail(CID_ERR_HIP, "hipEventRecord failed");
     if (armed) ++h->tev_used;
     return CID_OK;
 }
@@ -763,9 +754,9 @@ const char* cid_param_key(int i) {
 
 int cid_set_weight(cid_handle_t h, const char* key, const float* data, const int64_t* shape, int ndim) {
     if (!h) return CID_ERR_INVALID;
-    if (!key || !data || !shape) return fail(h, CID_ERR_INVALID, "cid_set_weight: null argument");
+    if (!key || !data || !shape) return h->fail(CID_ERR_INVALID, "cid_set_weight: null argument");
     int l, is_bias;
-    if (!find_key(key, l, is_bias)) return fail(h, CID_ERR_KEY, std::string("unexpected key '") + key + "' in state_dict");
+    if (!find_key(key, l, is_bias)) return h->fail(CID_ERR_KEY, std::string("unexpected key '") + key + "' in state_dict");
     const LayerDef& L = kLayers[l];
     int64_t want[4]; int wn;
     if (is_bias) { want[0] = L.cout; wn = 1; }
@@ -778,7 +769,7 @@ int cid_set_weight(cid_handle_t h, const char* key, const float* data, const int
         for (int i = 0; i < wn; ++i) m += (i ? "," : "") + std::to_string(want[i]);
         m += "], got [";
         for (int i = 0; i < ndim; ++i) m += (i ? "," : "") + std::to_string(shape[i]);
-        return fail(h, CID_ERR_SHAPE, m + "]");
+        return h->fail(CID_ERR_SHAPE, m + "]");
     }
     stage_segments(h->staging.data(), 2 * l + is_bias, data);   // every layout of this tensor, the reference-layout copy included
     h->have[l][is_bias] = true;
@@ -787,12 +778,12 @@ int cid_set_weight(cid_handle_t h, const char* key, const float* data, const int
 
 int cid_get_weight(cid_handle_t h, const char* key, float* out, size_t count) {
     if (!h) return CID_ERR_INVALID;
-    if (!key || !out) return fail(h, CID_ERR_INVALID, "cid_get_weight: null argument");
+    if (!key || !out) return h->fail(CID_ERR_INVALID, "cid_get_weight: null argument");
     int l, is_bias;
-    if (!find_key(key, l, is_bias)) return fail(h, CID_ERR_KEY, std::string("unknown key '") + key + "'");
+    if (!find_key(key, l, is_bias)) return h->fail(CID_ERR_KEY, std::string("unknown key '") + key + "'");
     const LayerDef& L = kLayers[l];
     const size_t need = is_bias ? (size_t)L.cout : ref_weight_count(L);
-    if (count != need) return fail(h, CID_ERR_SHAPE, std::string("cid_get_weight: wrong element count for ") + key);
+    if (count != need) return h->fail(CID_ERR_SHAPE, std::string("cid_get_weight: wrong element count for ") + key);
     // the blob carries a reference-layout copy of every tensor (the Winograd U is not invertible bit-for-bit)
     std::memcpy(out, h->staging.data() + (is_bias ? kBlob.raw_b_off[l] : kBlob.raw_w_off[l]), sizeof(float) * need);
     return CID_OK;
@@ -810,26 +801,26 @@ size_t cid_packed_weights_bytes(void) { return kBlob.total * sizeof(float); }
 
 int cid_upload_weights(cid_handle_t h, void* device_blob, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return fail(h, CID_ERR_INVALID, "cid_upload_weights: null device pointer");
-    if ((uintptr_t)device_blob & 255) return fail(h, CID_ERR_WORKSPACE, "cid_upload_weights: blob must be 256-byte aligned");
+    if (!device_blob) return h->fail(CID_ERR_INVALID, "cid_upload_weights: null device pointer");
+    if ((uintptr_t)device_blob & 255) return h->fail(CID_ERR_WORKSPACE, "cid_upload_weights: blob must be 256-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), kBlob.total * sizeof(float), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return fail(h, CID_ERR_HIP, std::string("cid_upload_weights: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return h->fail(CID_ERR_HIP, std::string("cid_upload_weights: ") + hipGetErrorString(e));
     h->dev_blob = static_cast<const float*>(device_blob);
     return CID_OK;
 }
 
 int cid_pack_weights_device(cid_handle_t h, const float* const* dev_params, void* device_blob, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!dev_params || !device_blob) return fail(h, CID_ERR_INVALID, "cid_pack_weights_device: null pointer");
+    if (!dev_params || !device_blob) return h->fail(CID_ERR_INVALID, "cid_pack_weights_device: null pointer");
     for (int i = 0; i < CID_NUM_PARAMS; ++i)
         if (!dev_params[i] || ((uintptr_t)dev_params[i] & 3))
-            return fail(h, CID_ERR_INVALID, "cid_pack_weights_device: null or misaligned parameter pointer");
-    if ((uintptr_t)device_blob & 255) return fail(h, CID_ERR_WORKSPACE, "cid_pack_weights_device: blob must be 256-byte aligned");
+            return h->fail(CID_ERR_INVALID, "cid_pack_weights_device: null or misaligned parameter pointer");
+    if ((uintptr_t)device_blob & 255) return h->fail(CID_ERR_WORKSPACE, "cid_pack_weights_device: blob must be 256-byte aligned");
     const GenPackArgs a = gen_pack_args(dev_params, device_blob);
     hipLaunchKernelGGL(k_gen_pack, dim3((a.nitems + GP_THREADS / 64 - 1) / (GP_THREADS / 64)), dim3(GP_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    if (hipGetLastError() != hipSuccess) return fail(h, CID_ERR_HIP, "cid_pack_weights_device: launch failed");
+    if (hipGetLastError() != hipSuccess) return h->fail(CID_ERR_HIP, "cid_pack_weights_device: launch failed");
     h->dev_blob = static_cast<const float*>(device_blob);
     return CID_OK;
 }
@@ -846,16 +837,16 @@ int cid_packed_segment(int index, const char** name, size_t* offset_bytes, size_
 
 int cid_export_packed(cid_handle_t h, void* host_out, size_t bytes) {
     if (!h) return CID_ERR_INVALID;
-    if (!host_out) return fail(h, CID_ERR_INVALID, "cid_export_packed: null pointer");
-    if (bytes != kBlob.total * sizeof(float)) return fail(h, CID_ERR_SHAPE, "cid_export_packed: size != cid_packed_weights_bytes()");
+    if (!host_out) return h->fail(CID_ERR_INVALID, "cid_export_packed: null pointer");
+    if (bytes != kBlob.total * sizeof(float)) return h->fail(CID_ERR_SHAPE, "cid_export_packed: size != cid_packed_weights_bytes()");
     std::memcpy(host_out, h->staging.data(), bytes);
     return CID_OK;
 }
 
 int cid_import_packed(cid_handle_t h, const void* host_in, size_t bytes) {
     if (!h) return CID_ERR_INVALID;
-    if (!host_in) return fail(h, CID_ERR_INVALID, "cid_import_packed: null pointer");
-    if (bytes != kBlob.total * sizeof(float)) return fail(h, CID_ERR_SHAPE, "cid_import_packed: size != cid_packed_weights_bytes()");
+    if (!host_in) return h->fail(CID_ERR_INVALID, "cid_import_packed: null pointer");
+    if (bytes != kBlob.total * sizeof(float)) return h->fail(CID_ERR_SHAPE, "cid_import_packed: size != cid_packed_weights_bytes()");
     std::memcpy(h->staging.data(), host_in, bytes);
     std::memset(h->have, 1, sizeof(h->have));
     return CID_OK;
@@ -863,8 +854,8 @@ int cid_import_packed(cid_handle_t h, const void* host_in, size_t bytes) {
 
 int cid_attach_weights(cid_handle_t h, const void* device_blob) {
     if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return fail(h, CID_ERR_INVALID, "cid_attach_weights: null device pointer");
-    if ((uintptr_t)device_blob & 255) return fail(h, CID_ERR_WORKSPACE, "cid_attach_weights: blob must be 256-byte aligned");
+    if (!device_blob) return h->fail(CID_ERR_INVALID, "cid_attach_weights: null device pointer");
+    if ((uintptr_t)device_blob & 255) return h->fail(CID_ERR_WORKSPACE, "cid_attach_weights: blob must be 256-byte aligned");
     h->dev_blob = static_cast<const float*>(device_blob);
     return CID_OK;
 }
@@ -898,17 +889,17 @@ int cid_forward_padded(cid_handle_t h, const void* in, int in_fmt, void* out, in
                        int pad_left, int pad_top, int pad_right, int pad_bottom, void* ws, size_t ws_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
     if (pad_left < 0 || pad_top < 0 || pad_right < 0 || pad_bottom < 0 || H < 1 || W < 1 || pad_left > 4096 || pad_top > 4096 || pad_right > 4096 || pad_bottom > 4096)
-        return fail(h, CID_ERR_INVALID, "cid_forward_padded: paddings must lie in [0, 4096] and the image must not be empty");
+        return h->fail(CID_ERR_INVALID, "cid_forward_padded: paddings must lie in [0, 4096] and the image must not be empty");
     const long long Hp = (long long)H + pad_top + pad_bottom, Wp = (long long)W + pad_left + pad_right;
-    if (Hp > 0x7fffffff || Wp > 0x7fffffff) return fail(h, CID_ERR_SHAPE, "cid_forward_padded: padded size overflows");
+    if (Hp > 0x7fffffff || Wp > 0x7fffffff) return h->fail(CID_ERR_SHAPE, "cid_forward_padded: padded size overflows");
     int Ho = 0, Wo = 0;
-    if (cid_out_shape((int)Hp, (int)Wp, &Ho, &Wo) != CID_OK) return fail(h, CID_ERR_SHAPE, "cid_forward_padded: padded image smaller than 4x4 (output size is too small)");
+    if (cid_out_shape((int)Hp, (int)Wp, &Ho, &Wo) != CID_OK) return h->fail(CID_ERR_SHAPE, "cid_forward_padded: padded image smaller than 4x4 (output size is too small)");
     // the reference crops [top, top + H) x [left, left + W) out of the network's output (app.py:474-480): that window must exist
     if (pad_top + H > Ho || pad_left + W > Wo) {
         char m[256];
         std::snprintf(m, sizeof m, "cid_forward_padded: the crop window [%d+%d, %d+%d] does not fit the network output %dx%d of the padded image %lldx%lld "
                                    "(pad to a multiple of 4, app.py:276-281)", pad_top, H, pad_left, W, Ho, Wo, Hp, Wp);
-        return fail(h, CID_ERR_SHAPE, m);
+        return h->fail(CID_ERR_SHAPE, m);
     }
     const Window src{pad_top, pad_left, H, W}, crop{pad_top, pad_left, H, W};
     return run_forward(h, in, in_fmt, out, out_fmt, N, (int)Hp, (int)Wp, ws, ws_bytes, static_cast<hipStream_t>(stream), nullptr, &src, &crop);
@@ -941,14 +932,14 @@ int cid_debug_half_workgroups_per_cu(int k) {
 
 int cid_timing_begin(cid_handle_t h, int max_forwards) {
     if (!h) return CID_ERR_INVALID;
-    if (max_forwards < 1 || max_forwards > 4096) return fail(h, CID_ERR_INVALID, "cid_timing_begin: max_forwards out of range");
-    if (!h->tev.empty()) return fail(h, CID_ERR_STATE, "cid_timing_begin: timing already armed");
+    if (max_forwards < 1 || max_forwards > 4096) return h->fail(CID_ERR_INVALID, "cid_timing_begin: max_forwards out of range");
+    if (!h->tev.empty()) return h->fail(CID_ERR_STATE, "cid_timing_begin: timing already armed");
     h->tev.resize((size_t)max_forwards * (NL + 1));
     for (size_t i = 0; i < h->tev.size(); ++i)
         if (hipEventCreate(&h->tev[i]) != hipSuccess) {
             for (size_t j = 0; j < i; ++j) (void)hipEventDestroy(h->tev[j]);
             h->tev.clear();
-            return fail(h, CID_ERR_HIP, "cid_timing_begin: hipEventCreate failed");
+            return h->fail(CID_ERR_HIP, "cid_timing_begin: hipEventCreate failed");
         }
     h->tev_forwards = max_forwards;
     h->tev_used = 0;
@@ -957,16 +948,16 @@ int cid_timing_begin(cid_handle_t h, int max_forwards) {
 
 int cid_timing_end(cid_handle_t h, void* stream, float* launch_ms_sum, int* forwards) {
     if (!h) return CID_ERR_INVALID;
-    if (!launch_ms_sum || !forwards) return fail(h, CID_ERR_INVALID, "cid_timing_end: null pointer");
-    if (h->tev.empty()) return fail(h, CID_ERR_STATE, "cid_timing_end: timing not armed");
+    if (!launch_ms_sum || !forwards) return h->fail(CID_ERR_INVALID, "cid_timing_end: null pointer");
+    if (h->tev.empty()) return h->fail(CID_ERR_STATE, "cid_timing_end: timing not armed");
     int rc = CID_OK;
-    if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) rc = fail(h, CID_ERR_HIP, "cid_timing_end: stream sync failed");
+    if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) rc = h->fail(CID_ERR_HIP, "cid_timing_end: stream sync failed");
     for (int l = 0; l < NL; ++l) launch_ms_sum[l] = 0.f;
     for (int f = 0; rc == CID_OK && f < h->tev_used; ++f)
         for (int l = 0; l < NL; ++l) {
             float ms = 0.f;
             const hipEvent_t* e = h->tev.data() + (size_t)f * (NL + 1);
-            if (hipEventElapsedTime(&ms, e[l], e[l + 1]) != hipSuccess) { rc = fail(h, CID_ERR_HIP, "cid_timing_end: hipEventElapsedTime failed"); break; }
+            if (hipEventElapsedTime(&ms, e[l], e[l + 1]) != hipSuccess) { rc = h->fail(CID_ERR_HIP, "cid_timing_end: hipEventElapsedTime failed"); break; }
             launch_ms_sum[l] += ms;
         }
     *forwards = h->tev_used;
@@ -979,18 +970,18 @@ int cid_timing_end(cid_handle_t h, void* stream, float* launch_ms_sum, int* forw
 int cid_forward_timed(cid_handle_t h, const float* in, float* out, int N, int H, int W, void* ws, size_t ws_bytes,
                       void* stream, float* launch_ms) {
     if (!h) return CID_ERR_INVALID;
-    if (!launch_ms) return fail(h, CID_ERR_INVALID, "cid_forward_timed: null launch_ms");
+    if (!launch_ms) return h->fail(CID_ERR_INVALID, "cid_forward_timed: null launch_ms");
     hipEvent_t ev[NL + 1];
     int made = 0;
     for (; made <= NL; ++made)
         if (hipEventCreate(&ev[made]) != hipSuccess) break;
-    int rc = made == NL + 1 ? CID_OK : fail(h, CID_ERR_HIP, "hipEventCreate failed");
+    int rc = made == NL + 1 ? CID_OK : h->fail(CID_ERR_HIP, "hipEventCreate failed");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (rc == CID_OK) rc = run_forward(h, in, CID_FMT_F32_NCHW, out, CID_FMT_F32_NCHW, N, H, W, ws, ws_bytes, s, ev);
-    if (rc == CID_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(h, CID_ERR_HIP, "cid_forward_timed: stream sync failed");
+    if (rc == CID_OK && hipStreamSynchronize(s) != hipSuccess) rc = h->fail(CID_ERR_HIP, "cid_forward_timed: stream sync failed");
     if (rc == CID_OK)
         for (int l = 0; l < NL; ++l)
-            if (hipEventElapsedTime(&launch_ms[l], ev[l], ev[l + 1]) != hipSuccess) rc = fail(h, CID_ERR_HIP, "hipEventElapsedTime failed");
+            if (hipEventElapsedTime(&launch_ms[l], ev[l], ev[l + 1]) != hipSuccess) rc = h->fail(CID_ERR_HIP, "hipEventElapsedTime failed");
     for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
     return rc;
 }
@@ -1004,13 +995,13 @@ const char* cid_launch_kernel(cid_handle_t h, int i) {
 
 int cid_set_conv_algo(cid_handle_t h, int algo) {
     if (!h) return CID_ERR_INVALID;
-    if (algo != CID_ALGO_DIRECT && algo != CID_ALGO_WINOGRAD64 && algo != CID_ALGO_WINOGRAD42 && algo != CID_ALGO_SPLIT16) return fail(h, CID_ERR_INVALID, "cid_set_conv_algo: unknown algorithm");
+    if (algo != CID_ALGO_DIRECT && algo != CID_ALGO_WINOGRAD64 && algo != CID_ALGO_WINOGRAD42 && algo != CID_ALGO_SPLIT16) return h->fail(CID_ERR_INVALID, "cid_set_conv_algo: unknown algorithm");
     h->algo = algo;
     return CID_OK;
 }
 int cid_set_tail_algo(cid_handle_t h, int algo) {
     if (!h) return CID_ERR_INVALID;
-    if (algo != CID_TAIL_FUSED && algo != CID_TAIL_BANDS && algo != CID_TAIL_TILES) return fail(h, CID_ERR_INVALID, "cid_set_tail_algo: unknown algorithm");
+    if (algo != CID_TAIL_FUSED && algo != CID_TAIL_BANDS && algo != CID_TAIL_TILES) return h->fail(CID_ERR_INVALID, "cid_set_tail_algo: unknown algorithm");
     h->tail_algo = algo;
     return CID_OK;
 }
@@ -1021,7 +1012,7 @@ int cid_get_tail_algo(cid_handle_t h, int* algo) {
 }
 int cid_set_compute_dtype(cid_handle_t h, int dtype) {
     if (!h) return CID_ERR_INVALID;
-    if (dtype != CID_DTYPE_F32 && dtype != CID_DTYPE_F16) return fail(h, CID_ERR_INVALID, "cid_set_compute_dtype: unknown dtype");
+    if (dtype != CID_DTYPE_F32 && dtype != CID_DTYPE_F16) return h->fail(CID_ERR_INVALID, "cid_set_compute_dtype: unknown dtype");
     h->dtype = dtype;
     return CID_OK;
 }
@@ -1123,7 +1114,7 @@ const Rccl& rccl() {
     return r;
 }
 int rccl_fail(cid_handle_t h, const char* what, int rc) {
-    return fail(h, CID_ERR_HIP, std::string(what) + ": " + (rccl().error_string ? rccl().error_string(rc) : "RCCL error"));
+    return h->fail(CID_ERR_HIP, std::string(what) + ": " + (rccl().error_string ? rccl().error_string(rc) : "RCCL error"));
 }
 }  // namespace
 extern "C" {
@@ -1154,9 +1145,9 @@ int cid_comm_count(void* comm, int* nranks) {
 
 int cid_broadcast_weights(cid_handle_t h, void* comm, int root, int rank, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!comm || root < 0 || rank < 0) return fail(h, CID_ERR_INVALID, "cid_broadcast_weights: null communicator or negative rank");
-    if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_broadcast_weights: no device blob attached (root: cid_upload_weights; receivers: cid_attach_weights on an allocated buffer)");
-    if (!rccl().ok) return fail(h, CID_ERR_STATE, "cid_broadcast_weights: " + rccl().why);
+    if (!comm || root < 0 || rank < 0) return h->fail(CID_ERR_INVALID, "cid_broadcast_weights: null communicator or negative rank");
+    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_broadcast_weights: no device blob attached (root: cid_upload_weights; receivers: cid_attach_weights on an allocated buffer)");
+    if (!rccl().ok) return h->fail(CID_ERR_STATE, "cid_broadcast_weights: " + rccl().why);
     hipStream_t s = static_cast<hipStream_t>(stream);
     void* blob = const_cast<float*>(h->dev_blob);
     const size_t bytes = kBlob.total * sizeof(float);
@@ -1165,7 +1156,7 @@ int cid_broadcast_weights(cid_handle_t h, void* comm, int root, int rank, void* 
     if (rank != root) {   // receivers: refresh the host staging copy, so cid_get_weight / state_dict() return what the kernels use
         hipError_t e = hipMemcpyAsync(h->staging.data(), blob, bytes, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(h, CID_ERR_HIP, std::string("cid_broadcast_weights: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return h->fail(CID_ERR_HIP, std::string("cid_broadcast_weights: ") + hipGetErrorString(e));
         std::memset(h->have, 1, sizeof(h->have));
     }
     return CID_OK;
@@ -1220,1272 +1211,13 @@ int cid_launch_work_ex(cid_handle_t h, int i, int N, int H, int W, double* flops
 
 }  // extern "C"
 
-// ---- image-quality metrics (cid_quality): workspace plan and launch sequence; kernels in quality_kernels.h ----
-namespace {
-
-constexpr int kQualityMetrics = CID_METRIC_PSNR | CID_METRIC_SSIM | CID_METRIC_MS_SSIM;
-constexpr int kQualityChunk = 65535;   // images per launch (grid y of the tile kernel)
-
-struct QualityPlan {
-    int levels;                                  // 1, or 5 with MS-SSIM
-    int H[Q_LEVELS], W[Q_LEVELS], tiles_x[Q_LEVELS], tiles[Q_LEVELS], off[Q_LEVELS];
-    long long slab_stride;                       // slab rows per image
-    size_t pyr_a[Q_LEVELS], pyr_b[Q_LEVELS];     // byte offsets of the pooled planes of levels 1..4
-    size_t total;
-};
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Argument checks shared by cid_quality_workspace_bytes and cid_quality (metrics bits, then shape).
-int quality_plan(int N, int H, int W, int metrics, QualityPlan& q) {
-    if (metrics == 0 || (metrics & ~kQualityMetrics)) return CID_ERR_INVALID;
-    if (N < 1 || H < 1 || W < 1) return CID_ERR_SHAPE;
-    if ((metrics & CID_METRIC_SSIM) && (H < 7 || W < 7)) return CID_ERR_SHAPE;
-    if ((metrics & CID_METRIC_MS_SSIM) && (H <= 160 || W <= 160)) return CID_ERR_SHAPE;   // pytorch_msssim: min side > (11-1)*2^4
-    if ((long long)H * W > 0x7fffffffLL) return CID_ERR_SHAPE;                            // one plane < 2^31 pixels
-    q.levels = (metrics & CID_METRIC_MS_SSIM) ? Q_LEVELS : 1;
-    long long rows = 0;
-    int h = H, w = W;
-    for (int l = 0; l < q.levels; ++l) {
-        q.H[l] = h;
-        q.W[l] = w;
-        q.tiles_x[l] = (w + Q_TX - 1) / Q_TX;
-        q.tiles[l] = ((h + Q_TY - 1) / Q_TY) * q.tiles_x[l];
-        q.off[l] = (int)rows;
-        rows += q.tiles[l];
-        h = (h + 1) / 2;
-        w = (w + 1) / 2;
-    }
-    q.slab_stride = rows;
-    size_t at = align256((size_t)N * rows * QSLOTS * sizeof(double));
-    for (int side = 0; side < 2; ++side)
-        for (int l = 1; l < q.levels; ++l) {
-            (side ? q.pyr_b : q.pyr_a)[l] = at;
-            at += align256((size_t)N * 3 * q.H[l] * q.W[l] * sizeof(float));
-        }
-    q.total = at;
-    return CID_OK;
-}
-
-// pytorch_msssim _fspecial_gauss_1d(11, 1.5) in float32: exp(-(k-5)^2 / (2*1.5^2)), normalised by its sum.
-void gauss_window(float* g) {
-    float sum = 0.f;
-    for (int k = 0; k < 11; ++k) {
-        const float d = (float)(k - 5);
-        g[k] = std::exp(-(d * d) / 4.5f);
-        sum += g[k];
-    }
-    for (int k = 0; k < 11; ++k) g[k] /= sum;
-}
-
-}  // namespace
-
-extern "C" {
-
-int cid_quality_workspace_bytes(int N, int H, int W, int metrics, size_t* bytes) {
-    if (!bytes) return CID_ERR_INVALID;
-    QualityPlan q;
-    const int rc = quality_plan(N, H, W, metrics, q);
-    if (rc == CID_OK) *bytes = q.total;
-    return rc;
-}
-
-int cid_quality(const void* a, int a_fmt, const void* b, int b_fmt, int N, int H, int W, int metrics, double* out,
-                void* workspace, size_t workspace_bytes, void* stream) {
-    if (!a || !b || !out || !workspace) return CID_ERR_INVALID;
-    const auto fmt_ok = [](const void* p, int f) {
-        return (f == CID_FMT_U8_NHWC) || (f == CID_FMT_F32_NCHW && ((uintptr_t)p & 3) == 0);
-    };
-    if (!fmt_ok(a, a_fmt) || !fmt_ok(b, b_fmt) || ((uintptr_t)out & 7)) return CID_ERR_INVALID;
-    QualityPlan q;
-    const int rc = quality_plan(N, H, W, metrics, q);
-    if (rc != CID_OK) return rc;
-    if (workspace_bytes < q.total || ((uintptr_t)workspace & 255)) return CID_ERR_WORKSPACE;
-
-    static float g[11];
-    static const bool g_ready = (gauss_window(g), true);
-    (void)g_ready;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double* part = reinterpret_cast<double*>(ws);
-    const bool box = metrics & CID_METRIC_SSIM, gauss = metrics & CID_METRIC_MS_SSIM;
-
-    for (int n0 = 0; n0 < N; n0 += kQualityChunk) {
-        const int nc = std::min(kQualityChunk, N - n0);
-        for (int l = 0; l < q.levels; ++l) {
-            QualityLevelArgs p{};
-            p.a = l == 0 ? a : ws + q.pyr_a[l];
-            p.b = l == 0 ? b : ws + q.pyr_b[l];
-            p.fa = l == 0 ? a_fmt : CID_FMT_F32_NCHW;
-            p.fb = l == 0 ? b_fmt : CID_FMT_F32_NCHW;
-            p.H = q.H[l];
-            p.W = q.W[l];
-            p.tiles_x = q.tiles_x[l];
-            p.n0 = n0;
-            const bool pool = gauss && l + 1 < q.levels;
-            p.pa = pool ? reinterpret_cast<float*>(ws + q.pyr_a[l + 1]) : nullptr;
-            p.pb = pool ? reinterpret_cast<float*>(ws + q.pyr_b[l + 1]) : nullptr;
-            p.part = part + (size_t)q.off[l] * QSLOTS;
-            p.slab_stride = q.slab_stride;
-            std::memcpy(p.g, g, sizeof g);
-            const dim3 grid((unsigned)q.tiles[l], (unsigned)nc), block(Q_THREADS);
-            if (l > 0) {
-                if (pool) hipLaunchKernelGGL((k_quality_tile<false, false, true, true>), grid, block, 0, s, p);
-                else hipLaunchKernelGGL((k_quality_tile<false, false, true, false>), grid, block, 0, s, p);
-            } else if (box && gauss) {
-                hipLaunchKernelGGL((k_quality_tile<true, true, true, true>), grid, block, 0, s, p);
-            } else if (gauss) {
-                hipLaunchKernelGGL((k_quality_tile<true, false, true, true>), grid, block, 0, s, p);
-            } else if (box) {
-                hipLaunchKernelGGL((k_quality_tile<true, true, false, false>), grid, block, 0, s, p);
-            } else {
-                hipLaunchKernelGGL((k_quality_tile<true, false, false, false>), grid, block, 0, s, p);
-            }
-            if (hipGetLastError() != hipSuccess) return CID_ERR_HIP;
-        }
-        QualityFinishArgs f{};
-        f.part = part;
-        f.slab_stride = q.slab_stride;
-        f.H = H;
-        f.W = W;
-        for (int l = 0; l < q.levels; ++l) {
-            f.level_tiles[l] = q.tiles[l];
-            f.level_off[l] = q.off[l];
-        }
-        f.levels = q.levels;
-        f.metrics = metrics;
-        f.n0 = n0;
-        f.out = out;
-        hipLaunchKernelGGL(k_quality_finish, dim3((unsigned)nc), dim3(64), 0, s, f);
-        if (hipGetLastError() != hipSuccess) return CID_ERR_HIP;
-    }
-    return CID_OK;
-}
-
-}  // extern "C"
-
-// ---- noise synthesis (cid_add_noise): argument checks and launches; kernels in noise_kernels.h ----
-namespace {
-
-// exp(-lambda) for lambda = 0..255 from the host libm (std::exp), the value synth.add_poisson_noise takes from math.exp
-const double* poisson_exp_table() {
-    static double t[256];
-    static const bool ready = [] {
-        for (int l = 0; l < 256; ++l) t[l] = std::exp(-(double)l);
-        return true;
-    }();
-    (void)ready;
-    return t;
-}
-
-static_assert(CID_NOISE_GAUSSIAN == NK_GAUSSIAN && CID_NOISE_SALT_PEPPER == NK_SALT_PEPPER && CID_NOISE_SPECKLE == NK_SPECKLE &&
-                  CID_NOISE_POISSON == NK_POISSON && CID_NOISE_UNIFORM == NK_UNIFORM, "noise kind enums out of sync");
-
-}  // namespace
-
-extern "C" {
-
-int cid_add_noise(const void* clean_u8_nhwc, void* out_u8_nhwc, int N, int H, int W, int kind, const double* params, int nparams,
-                  uint64_t seed, uint64_t first_index, void* stream) {
-    if (!clean_u8_nhwc || !out_u8_nhwc) return CID_ERR_INVALID;
-    if (kind < CID_NOISE_GAUSSIAN || kind > CID_NOISE_UNIFORM) return CID_ERR_INVALID;
-    const int want = kind == CID_NOISE_POISSON ? 0 : 2;
-    if (nparams != want || (want && !params)) return CID_ERR_INVALID;
-    for (int i = 0; i < want; ++i)
-        if (!std::isfinite(params[i])) return CID_ERR_INVALID;
-    if ((kind == CID_NOISE_GAUSSIAN || kind == CID_NOISE_SPECKLE) && params[1] < 0.0) return CID_ERR_INVALID;
-    if (kind == CID_NOISE_SALT_PEPPER && (params[0] < 0.0 || params[0] > 1.0 || params[1] < 0.0 || params[1] > 1.0))
-        return CID_ERR_INVALID;
-    if (kind == CID_NOISE_UNIFORM && params[0] > params[1]) return CID_ERR_INVALID;
-    if (N < 1 || H < 1 || W < 1) return CID_ERR_SHAPE;
-    if (kind == CID_NOISE_SALT_PEPPER && (H < 2 || W < 2)) return CID_ERR_SHAPE;
-    if ((long long)H * W * 3 >= 0x80000000LL) return CID_ERR_SHAPE;
-
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const int per = H * W * 3;
-    const uint64_t seed0 = seed + first_index;
-    const unsigned gy = (unsigned)std::min(N, NOISE_MAX_GRID_Y);
-
-    if (kind == CID_NOISE_SALT_PEPPER) {
-        if (out_u8_nhwc != clean_u8_nhwc &&
-            hipMemcpyAsync(out_u8_nhwc, clean_u8_nhwc, (size_t)N * per, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return CID_ERR_HIP;
-        for (int pass = 0; pass < 2; ++pass) {   // salt, then pepper: stream order makes pepper win a collision
-            NoiseScatterArgs a{};
-            a.out = static_cast<uint8_t*>(out_u8_nhwc);
-            a.N = N;
-            a.H = H;
-            a.W = W;
-            a.draws = (int)((double)per * params[pass]);   // int(float(H*W*3) * prob); <= per
-            a.seed0 = seed0;
-            a.stream_row = pass ? NS_PEPPER_ROW : NS_SALT_ROW;
-            a.stream_col = pass ? NS_PEPPER_COL : NS_SALT_COL;
-            a.value = pass ? 0 : 255;
-            if (a.draws == 0) continue;
-            const dim3 grid((unsigned)((a.draws + NOISE_THREADS - 1) / NOISE_THREADS), gy);
-            hipLaunchKernelGGL(k_noise_scatter, grid, dim3(NOISE_THREADS), 0, s, a);
-            if (hipGetLastError() != hipSuccess) return CID_ERR_HIP;
-        }
-        return CID_OK;
-    }
-
-    NoiseArgs a{};
-    a.in = static_cast<const uint8_t*>(clean_u8_nhwc);
-    a.out = static_cast<uint8_t*>(out_u8_nhwc);
-    a.N = N;
-    a.per = per;
-    a.seed0 = seed0;
-    if (want) {
-        a.p0 = params[0];
-        a.p1 = params[1];
-    }
-    const dim3 grid((unsigned)((per + NOISE_THREADS * NOISE_EPT - 1) / (NOISE_THREADS * NOISE_EPT)), gy), block(NOISE_THREADS);
-    switch (kind) {
-        case CID_NOISE_GAUSSIAN:
-            a.stream_a = NS_GAUSS_U1;
-            a.stream_b = NS_GAUSS_U2;
-            hipLaunchKernelGGL(k_noise_elem<NK_GAUSSIAN>, grid, block, 0, s, a);
-            break;
-        case CID_NOISE_SPECKLE:
-            a.stream_a = NS_SPECKLE_U1;
-            a.stream_b = NS_SPECKLE_U2;
-            hipLaunchKernelGGL(k_noise_elem<NK_SPECKLE>, grid, block, 0, s, a);
-            break;
-        case CID_NOISE_UNIFORM:
-            a.stream_a = NS_UNIFORM;
-            hipLaunchKernelGGL(k_noise_elem<NK_UNIFORM>, grid, block, 0, s, a);
-            break;
-        default:   // CID_NOISE_POISSON
-            a.stream_a = NS_POISSON;
-            std::memcpy(a.exp_neg, poisson_exp_table(), sizeof a.exp_neg);
-            hipLaunchKernelGGL(k_noise_elem<NK_POISSON>, grid, block, 0, s, a);
-            break;
-    }
-    return hipGetLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
-}
-
-}  // extern "C"
-
-// ---- bicubic resize (cid_resize_*): coefficient tables, tile choice and the launch; kernel in resize_kernels.h ----
-namespace {
-
-// Pillow's bicubic filter (a = -0.5), in its evaluation order
-double resize_cubic(double t) {
-#pragma clang fp contract(off)
-    const double a = -0.5;
-    if (t < 0.0) t = -t;
-    if (t < 1.0) return ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0;
-    if (t < 2.0) return (((t - 5.0) * t + 8.0) * t - 4.0) * a;
-    return 0.0;
-}
-
-// One axis' tables (include/cid.h states the arithmetic; synth.resize_tables_np restates it): bounds [outS][2] = (min, n), coeffs
-// [outS][ksize] 22-bit fixed point, zero past n.
-void resize_tables(int inS, int outS, int& ksize, std::vector<int>& bounds, std::vector<int>& coeffs) {
-#pragma clang fp contract(off)
-    const double scale = (double)inS / (double)outS;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * fs;
-    ksize = (int)std::ceil(support) * 2 + 1;
-    const double ss = 1.0 / fs;
-    bounds.assign((size_t)outS * 2, 0);
-    coeffs.assign((size_t)outS * ksize, 0);
-    std::vector<double> w((size_t)ksize);
-    for (int xx = 0; xx < outS; ++xx) {
-        const double center = ((double)xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > inS) xmax = inS;
-        const int n = xmax - xmin;
-        double ww = 0.0;
-        for (int x = 0; x < n; ++x) {
-            w[x] = resize_cubic(((double)(x + xmin) - center + 0.5) * ss);
-            ww = ww + w[x];
-        }
-        int* k = &coeffs[(size_t)xx * ksize];
-        for (int x = 0; x < n; ++x) {
-            const double v = ww != 0.0 ? w[x] / ww : w[x];
-            k[x] = v < 0.0 ? (int)(-0.5 + v * 4194304.0) : (int)(0.5 + v * 4194304.0);
-        }
-        bounds[2 * (size_t)xx] = xmin;
-        bounds[2 * (size_t)xx + 1] = n;
-    }
-}
-
-constexpr int RESIZE_MAX_SIDE = 16384;
-constexpr int RESIZE_MAX_FACTOR = 64;
-
-int pow2_ceil(int v) {
-    int p = 1;
-    while (p < v) p *= 2;
-    return p;
-}
-
-// Over the tiles of `tile` outputs of one axis: the widest source span [first.min, last.min + last.n) and each tile's largest n.
-int resize_tile_spans(const std::vector<int>& bounds, int outS, int tile, std::vector<int>& tile_n) {
-    int widest = 0;
-    tile_n.clear();
-    for (int t0 = 0; t0 < outS; t0 += tile) {
-        const int t1 = std::min(outS, t0 + tile) - 1;
-        widest = std::max(widest, bounds[2 * (size_t)t1] + bounds[2 * (size_t)t1 + 1] - bounds[2 * (size_t)t0]);
-        int m = 0;
-        for (int i = t0; i <= t1; ++i) m = std::max(m, bounds[2 * (size_t)i + 1]);
-        tile_n.push_back(m);
-    }
-    return widest;
-}
-
-}  // namespace
-
-struct cid_resize_plan_s {
-    int Hs = 0, Ws = 0, Hd = 0, Wd = 0;
-    int mode = 0;                          // ResizeMode
-    int ksize[2] = {0, 0};                 // axis 0 vertical, 1 horizontal
-    std::vector<int> bounds[2], coeffs[2];
-    ResizeArgs args{};                     // src, dst, N, f32 are filled in per call
-    unsigned tiles = 0;
-    size_t lds_bytes = 0;
-    int* dev = nullptr;                    // the device copy of the tables; null on a machine without a GPU
-    int device = -1;
-};
-
-extern "C" {
-
-int cid_resize_plan_create(cid_resize_plan_t* out, int Hs, int Ws, int Hd, int Wd, int filter) {
-    if (!out) return CID_ERR_INVALID;
-    *out = nullptr;
-    if (filter != CID_RESAMPLE_BICUBIC) return CID_ERR_INVALID;
-    if (Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1) return CID_ERR_SHAPE;
-    if (Hs > RESIZE_MAX_SIDE || Ws > RESIZE_MAX_SIDE || Hd > RESIZE_MAX_SIDE || Wd > RESIZE_MAX_SIDE) return CID_ERR_SHAPE;
-    if ((long long)Hs * Ws * 3 >= 0x80000000LL || (long long)Hd * Wd * 3 >= 0x80000000LL) return CID_ERR_SHAPE;
-    if ((long long)Hs > (long long)RESIZE_MAX_FACTOR * Hd || (long long)Ws > (long long)RESIZE_MAX_FACTOR * Wd) return CID_ERR_SHAPE;
-
-    auto* p = new cid_resize_plan_s;
-    p->Hs = Hs; p->Ws = Ws; p->Hd = Hd; p->Wd = Wd;
-    resize_tables(Hs, Hd, p->ksize[0], p->bounds[0], p->coeffs[0]);
-    resize_tables(Ws, Wd, p->ksize[1], p->bounds[1], p->coeffs[1]);
-    // what the kernel relies on: spans that move monotonically (a tile's span is first.min .. last.min + last.n) and
-    // coefficients that fit the 24-bit multiply
-    for (int ax = 0; ax < 2; ++ax) {
-        const int outS = ax ? Wd : Hd;
-        const std::vector<int>& b = p->bounds[ax];
-        bool ok = true;
-        for (int i = 0; i < outS; ++i) {
-            if (b[2 * (size_t)i + 1] < 1) ok = false;
-            if (i && (b[2 * (size_t)i] < b[2 * (size_t)i - 2] || b[2 * (size_t)i] + b[2 * (size_t)i + 1] < b[2 * (size_t)i - 2] + b[2 * (size_t)i - 1])) ok = false;
-        }
-        for (int k : p->coeffs[ax])
-            if (k <= -(1 << 23) || k >= (1 << 23)) ok = false;
-        if (!ok) {
-            delete p;
-            return CID_ERR_SHAPE;
-        }
-    }
-    const bool hpass = Ws != Wd, vpass = Hs != Hd;
-    p->mode = hpass ? (vpass ? RM_BOTH : RM_HONLY) : (vpass ? RM_VONLY : RM_COPY);
-
-    // tile: about 4 pixels per lane, 64 columns wide where the image is; halved until band + stage fit the LDS budget
-    int TC = std::min(64, pow2_ceil(Wd)), TR = std::min(pow2_ceil(Hd), 1024 / TC);
-    std::vector<int> vtn, htn;
-    int band_pitch = 0, band_bytes = 0, stage_pitch = 0, nband = 0;
-    for (;;) {
-        nband = vpass ? resize_tile_spans(p->bounds[0], Hd, TR, vtn) : TR;
-        const int nsrc = hpass ? resize_tile_spans(p->bounds[1], Wd, TC, htn) : TC;
-        if (!vpass) vtn.assign((size_t)cdiv(Hd, TR), 0);
-        if (!hpass) htn.assign((size_t)cdiv(Wd, TC), 0);
-        band_pitch = p->mode == RM_BOTH ? TC * 3 : p->mode == RM_VONLY ? (15 + TC * 3 + 15) / 16 * 16 : 0;
-        band_bytes = (band_pitch * nband + 15) / 16 * 16;
-        stage_pitch = hpass ? (15 + nsrc * 3 + 15) / 16 * 16 : 0;
-        if (band_bytes + stage_pitch <= RESIZE_LDS_BUDGET) break;
-        if (TR > 1 && (band_bytes > RESIZE_LDS_BUDGET / 2 || TC == 1)) TR /= 2;
-        else if (TC > 1) TC /= 2;
-        else {   // a 1 x 1 tile needs at most 258 band rows of 32 bytes and one stage row of 3 * 258 + 30 bytes
-            delete p;
-            return CID_ERR_SHAPE;
-        }
-    }
-    ResizeArgs& a = p->args;
-    a.Hs = Hs; a.Ws = Ws; a.Hd = Hd; a.Wd = Wd;
-    a.TR = TR; a.TC = TC;
-    a.tiles_x = cdiv(Wd, TC);
-    a.band_pitch = band_pitch;
-    a.band_bytes = band_bytes;
-    a.stage_pitch = stage_pitch;
-    a.SR = hpass ? std::max(1, std::min(nband, (RESIZE_LDS_BUDGET - band_bytes) / stage_pitch)) : 0;
-    a.h.ksize = p->ksize[1];
-    a.v.ksize = p->ksize[0];
-    p->tiles = (unsigned)a.tiles_x * (unsigned)cdiv(Hd, TR);
-    p->lds_bytes = (size_t)band_bytes + (size_t)a.SR * stage_pitch;
-
-    // the device copy: vertical bounds, coefficients, tile maxima; horizontal bounds, TRANSPOSED coefficients, tile maxima.
-    // Without a GPU the plan keeps its host tables only (cid_resize_plan_table works; cid_resize returns CID_ERR_STATE).
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        *out = p;
-        return CID_OK;
-    }
-    std::vector<int> blob;
-    const auto put = [&blob](const std::vector<int>& v) {
-        const size_t at = blob.size();
-        blob.insert(blob.end(), v.begin(), v.end());
-        return at;
-    };
-    const size_t o_vb = put(p->bounds[0]), o_vc = put(p->coeffs[0]), o_vt = put(vtn), o_hb = put(p->bounds[1]);
-    std::vector<int> hT((size_t)p->ksize[1] * Wd);
-    for (int x = 0; x < Wd; ++x)
-        for (int k = 0; k < p->ksize[1]; ++k) hT[(size_t)k * Wd + x] = p->coeffs[1][(size_t)x * p->ksize[1] + k];
-    const size_t o_hc = put(hT), o_ht = put(htn);
-    if (hipGetDevice(&p->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&p->dev), blob.size() * sizeof(int)) != hipSuccess ||
-        hipMemcpy(p->dev, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-        if (p->dev) (void)hipFree(p->dev);
-        delete p;
-        return CID_ERR_HIP;
-    }
-    a.v.bounds = p->dev + o_vb; a.v.coeffs = p->dev + o_vc; a.v.tile_n = p->dev + o_vt;
-    a.h.bounds = p->dev + o_hb; a.h.coeffs = p->dev + o_hc; a.h.tile_n = p->dev + o_ht;
-    *out = p;
-    return CID_OK;
-}
-
-void cid_resize_plan_destroy(cid_resize_plan_t p) {
-    if (!p) return;
-    if (p->dev) (void)hipFree(p->dev);
-    delete p;
-}
-
-int cid_resize_plan_table(cid_resize_plan_t p, int axis, int* ksize, int* bounds, int* coeffs) {
-    if (!p || !ksize || (axis != 0 && axis != 1)) return CID_ERR_INVALID;
-    *ksize = p->ksize[axis];
-    if (bounds) std::memcpy(bounds, p->bounds[axis].data(), p->bounds[axis].size() * sizeof(int));
-    if (coeffs) std::memcpy(coeffs, p->coeffs[axis].data(), p->coeffs[axis].size() * sizeof(int));
-    return CID_OK;
-}
-
-int cid_resize(cid_resize_plan_t p, const void* src_u8_nhwc, void* dst, int dst_fmt, int N, void* stream) {
-    if (!p || !src_u8_nhwc || !dst) return CID_ERR_INVALID;
-    if (dst_fmt != CID_FMT_U8_NHWC && dst_fmt != CID_FMT_F32_NCHW) return CID_ERR_INVALID;
-    if (dst_fmt == CID_FMT_F32_NCHW && ((uintptr_t)dst & 3)) return CID_ERR_INVALID;
-    if (N < 1) return CID_ERR_INVALID;
-    if (!p->dev) return CID_ERR_STATE;   // created without a GPU
-    ResizeArgs a = p->args;
-    a.src = static_cast<const uint8_t*>(src_u8_nhwc);
-    a.dst = dst;
-    a.N = N;
-    a.f32 = dst_fmt == CID_FMT_F32_NCHW;
-    const dim3 grid(p->tiles, (unsigned)std::min(N, RESIZE_MAX_GRID_Y)), block(RESIZE_THREADS);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (p->mode) {
-        case RM_BOTH: hipLaunchKernelGGL(k_resize<RM_BOTH>, grid, block, p->lds_bytes, s, a); break;
-        case RM_HONLY: hipLaunchKernelGGL(k_resize<RM_HONLY>, grid, block, p->lds_bytes, s, a); break;
-        case RM_VONLY: hipLaunchKernelGGL(k_resize<RM_VONLY>, grid, block, p->lds_bytes, s, a); break;
-        default: hipLaunchKernelGGL(k_resize<RM_COPY>, grid, block, 0, s, a); break;
-    }
-    return hipGetLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
-}
-
-}  // extern "C"
-
-// ---- the trainer's discriminator (cid_disc_*): weight packing, workspace plan and launch sequence; kernels in disc_kernels.h ----
-namespace {
-
-struct DiscConvDef { const char* name; int cin, cout, k, stride; };
-constexpr int kDiscConvs = 5;
-constexpr DiscConvDef kDiscConv[kDiscConvs] = {
-    {"model.0", 3, 64, 3, 1}, {"model.2", 64, 64, 3, 2}, {"model.5", 64, 128, 3, 1}, {"model.8", 128, 128, 3, 2}, {"model.12", 128, 1, 1, 1},
-};
-constexpr int kDiscBnC[3] = {64, 128, 128};
-constexpr int kDiscChunk = 65535;   // images per launch (grid y of the conv kernels, grid x of the head)
-
-// Blob segments (floats, each 64-float aligned): weights then biases of each convolution.  Layer 0 and 12 keep the reference
-// layout; layers 2, 5, 8 are packed [CIN/8][9 taps][8][COUT] (DiscConvArgs::w) with the biases right behind.
-struct DiscBlob {
-    size_t off[kDiscConvs], total;
-    DiscBlob() : off{}, total(0) {
-        size_t at = 0;
-        for (int i = 0; i < kDiscConvs; ++i) {
-            off[i] = at;
-            const auto& L = kDiscConv[i];
-            at += (size_t)L.cout * L.cin * L.k * L.k + L.cout;
-            at = (at + 63) & ~(size_t)63;
-        }
-        total = at;
-    }
-};
-const DiscBlob kDiscBlob;
-
-struct DiscPlan {
-    int H2, W2, H4, W4;
-    int tiles_x[3], tiles[3];           // conv launches 2, 5, 8
-    size_t regA, regB, st, slab[3], total;
-};
-
-constexpr int kDiscTileRows[3] = {DiscGeom<64, 64, 2>::TH, DiscGeom<64, 128, 1>::TH, DiscGeom<128, 128, 2>::TH};
-
-int disc_plan(int N, int H, int W, int training, DiscPlan& p) {
-    if (N < 1 || H < 1 || W < 1) return CID_ERR_SHAPE;
-    if ((long long)H * W > 0x7fffffffLL) return CID_ERR_SHAPE;   // the layer-0 kernel indexes an image's pixels with int
-    p.H2 = (H - 1) / 2 + 1;
-    p.W2 = (W - 1) / 2 + 1;
-    p.H4 = (p.H2 - 1) / 2 + 1;
-    p.W4 = (p.W2 - 1) / 2 + 1;
-    if (training && (long long)N * p.H4 * p.W4 == 1) return CID_ERR_SHAPE;
-    const int ho[3] = {p.H2, p.H2, p.H4}, wo[3] = {p.W2, p.W2, p.W4};
-    for (int l = 0; l < 3; ++l) {
-        p.tiles_x[l] = (wo[l] + D_TW - 1) / D_TW;
-        p.tiles[l] = ((ho[l] + kDiscTileRows[l] - 1) / kDiscTileRows[l]) * p.tiles_x[l];
-    }
-    const size_t n = (size_t)N, f = sizeof(float);
-    // region A: a0 (64 x H x W), later z5 (128 x H2 x W2); region B: z2 (64 x H2 x W2), later z8 (128 x H4 x W4)
-    const size_t a = std::max(n * 64 * H * W, n * 128 * p.H2 * p.W2) * f;
-    const size_t b = std::max(n * 64 * p.H2 * p.W2, n * 128 * p.H4 * p.W4) * f;
-    size_t at = 0;
-    p.regA = at;
-    at += align256(a);
-    p.regB = at;
-    at += align256(b);
-    p.st = at;
-    at += align256(3 * 128 * 2 * f);
-    const int couts[3] = {64, 128, 128};
-    for (int l = 0; l < 3; ++l) {
-        p.slab[l] = at;
-        if (training) at += align256((size_t)couts[l] * 2 * n * p.tiles[l] * sizeof(double));
-    }
-    p.total = at;
-    return CID_OK;
-}
-
-template <int CIN, int COUT, int S, bool BN_IN>
-hipError_t disc_conv_launch(const DiscConvArgs& base, int layer, const DiscPlan& p, int N, bool training, hipStream_t s) {
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscConvArgs a = base;
-        a.n0 = n0;
-        a.tiles_x = p.tiles_x[layer];
-        a.tiles = p.tiles[layer];
-        const dim3 grid((unsigned)p.tiles[layer], (unsigned)std::min(kDiscChunk, N - n0)), block(D_THREADS);
-        if (training) hipLaunchKernelGGL((k_disc_conv<CIN, COUT, S, BN_IN, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_disc_conv<CIN, COUT, S, BN_IN, false>), grid, block, 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-bool disc_finite_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
-
-}  // namespace
-
-struct cid_disc_s {
-    std::vector<float> staging = std::vector<float>(kDiscBlob.total, 0.f);
-    bool have[kDiscConvs][2] = {};
-    const float* dev_blob = nullptr;
-    std::string err;
-};
-
-namespace {
-int dfail(cid_disc_t d, int code, const std::string& msg) {
-    if (d) d->err = msg;
-    return code;
-}
-
-// Where one forward keeps its tensors: two overlapping workspace regions (cid_disc_forward) or a per-call buffer (cid_disc_forward_saved).
-struct DiscBufs {
-    float *a0, *z2, *z5, *z8;
-    float* st[3];      // (scale, shift) pairs of the three BatchNorms
-    double* mi[3];     // (mean, invstd) pairs, or null
-    double* slab[3];   // train mode: per-tile partial sums
-};
-
-// The argument checks every forward entry point shares, in the order cid.h documents; `buf` is its workspace or saved buffer.
-int disc_check_forward(cid_disc_t d, const char* fn, const void* in, int in_fmt, const float* out, int N, int H, int W,
-                       const cid_disc_bn* bn, int training, const void* buf, DiscPlan& p) {
-    const std::string f = std::string(fn) + ": ";
-    if (!in || !out || !bn || !buf) return dfail(d, CID_ERR_INVALID, f + "null pointer");
-    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return dfail(d, CID_ERR_INVALID, f + "unknown input format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)out & 3))
-        return dfail(d, CID_ERR_INVALID, f + "misaligned fp32 operand");
-    if (training != 0 && training != 1) return dfail(d, CID_ERR_INVALID, f + "training must be 0 or 1");
-    for (int l = 0; l < 3; ++l) {
-        const cid_disc_bn& b = bn[l];
-        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || (training && !b.num_batches_tracked))
-            return dfail(d, CID_ERR_INVALID, f + "null BatchNorm pointer");
-        if (!disc_finite_nonneg(b.eps)) return dfail(d, CID_ERR_INVALID, f + "eps must be finite and >= 0");
-        if (training && !(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
-            return dfail(d, CID_ERR_INVALID, f + "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
-    }
-    if (disc_plan(N, H, W, training, p) != CID_OK)
-        return dfail(d, CID_ERR_SHAPE, training && N >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL
-                                           ? "Expected more than 1 value per channel when training"
-                                           : f + "input shape not accepted (N, H, W >= 1, H*W < 2^31)");
-    return CID_OK;
-}
-
-// The forward's launch sequence on checked arguments.
-int disc_forward_run(cid_disc_t d, const char* fn, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn,
-                     int training, const DiscPlan& p, const DiscBufs& b, hipStream_t s) {
-    const float* blob = d->dev_blob;
-    const auto herr = [&](const char* what) { return dfail(d, CID_ERR_HIP, std::string(fn) + ": " + what + ": " + hipGetErrorString(hipGetLastError())); };
-
-    if (!training) {
-        DiscBnEvalArgs e{};
-        for (int l = 0; l < 3; ++l) {
-            e.gamma[l] = bn[l].gamma;
-            e.beta[l] = bn[l].beta;
-            e.running_mean[l] = bn[l].running_mean;
-            e.running_var[l] = bn[l].running_var;
-            e.eps[l] = bn[l].eps;
-            e.st[l] = b.st[l];
-            e.C[l] = kDiscBnC[l];
-            e.mi[l] = b.mi[l];
-        }
-        hipLaunchKernelGGL(k_disc_bn_eval, dim3(3), dim3(128), 0, s, e);
-        if (hipPeekAtLastError() != hipSuccess) return herr("bn_eval");
-    }
-    // layer 0
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscConv0Args a{in, b.a0, blob + kDiscBlob.off[0], H, W, n0};
-        const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_conv0<true>, grid, dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_disc_conv0<false>, grid, dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("conv0");
-    }
-    const auto stats = [&](int l, long long pix) {
-        DiscStatsArgs a{};
-        a.slab = b.slab[l];
-        a.rows = (long long)N * p.tiles[l];
-        a.count = (double)N * (double)pix;
-        a.gamma = bn[l].gamma;
-        a.beta = bn[l].beta;
-        a.running_mean = bn[l].running_mean;
-        a.running_var = bn[l].running_var;
-        a.num_batches_tracked = reinterpret_cast<const long long*>(bn[l].num_batches_tracked);
-        a.eps = bn[l].eps;
-        a.momentum = bn[l].momentum == CID_DISC_MOMENTUM_NONE ? -1.0 : bn[l].momentum;
-        a.st = b.st[l];
-        a.mi = b.mi[l];
-        hipLaunchKernelGGL(k_disc_bn_stats, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
-        return hipPeekAtLastError();
-    };
-    const auto conv_args = [&](const float* src, float* dst, int ci, const float* st_in, int l, int Hin, int Win, int Ho, int Wo) {
-        DiscConvArgs a{};
-        a.in = src;
-        a.out = dst;
-        a.w = blob + kDiscBlob.off[ci];
-        a.st_in = st_in;
-        a.slab = training ? b.slab[l] : nullptr;
-        a.rows = (long long)N * p.tiles[l];
-        a.Hin = Hin;
-        a.Win = Win;
-        a.Ho = Ho;
-        a.Wo = Wo;
-        return a;
-    };
-    // layer 2 (reads a0, writes z2), BN3
-    if (disc_conv_launch<64, 64, 2, false>(conv_args(b.a0, b.z2, 1, nullptr, 0, H, W, p.H2, p.W2), 0, p, N, training, s) != hipSuccess)
-        return herr("conv2");
-    if (training && stats(0, (long long)p.H2 * p.W2) != hipSuccess) return herr("bn3 stats");
-    // layer 5 (reads z2 through BN3 + LeakyReLU, writes z5), BN6
-    if (disc_conv_launch<64, 128, 1, true>(conv_args(b.z2, b.z5, 2, b.st[0], 1, p.H2, p.W2, p.H2, p.W2), 1, p, N, training, s) != hipSuccess)
-        return herr("conv5");
-    if (training && stats(1, (long long)p.H2 * p.W2) != hipSuccess) return herr("bn6 stats");
-    // layer 8 (reads z5 through BN6 + LeakyReLU, writes z8), BN9
-    if (disc_conv_launch<128, 128, 2, true>(conv_args(b.z5, b.z8, 3, b.st[1], 2, p.H2, p.W2, p.H4, p.W4), 2, p, N, training, s) != hipSuccess)
-        return herr("conv8");
-    if (training && stats(2, (long long)p.H4 * p.W4) != hipSuccess) return herr("bn9 stats");
-    // head: BN9 + LeakyReLU, average pool, 1x1 conv, sigmoid
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscHeadArgs a{b.z8, b.st[2], blob + kDiscBlob.off[4], out, (long long)p.H4 * p.W4, n0};
-        hipLaunchKernelGGL(k_disc_head, dim3((unsigned)std::min(kDiscChunk, N - n0)), dim3(D_HEAD_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("head");
-    }
-    if (training) {
-        hipLaunchKernelGGL(k_disc_bn_count, dim3(1), dim3(64), 0, s, reinterpret_cast<long long*>(bn[0].num_batches_tracked),
-                           reinterpret_cast<long long*>(bn[1].num_batches_tracked), reinterpret_cast<long long*>(bn[2].num_batches_tracked));
-        if (hipPeekAtLastError() != hipSuccess) return herr("bn count");
-    }
-    return CID_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int cid_disc_create(cid_disc_t* out) {
-    if (!out) return CID_ERR_INVALID;
-    *out = new (std::nothrow) cid_disc_s();
-    return *out ? CID_OK : CID_ERR_INVALID;
-}
-
-void cid_disc_destroy(cid_disc_t d) { delete d; }
-
-const char* cid_disc_last_error(cid_disc_t d) { return d ? d->err.c_str() : "null handle"; }
-
-int cid_disc_set_weight(cid_disc_t d, const char* key, const float* data, const int64_t* shape, int ndim) {
-    if (!d) return CID_ERR_INVALID;
-    if (!key || !data || (!shape && ndim > 0)) return dfail(d, CID_ERR_INVALID, "cid_disc_set_weight: null argument");
-    const std::string k(key);
-    int li = -1, is_bias = 0;
-    for (int i = 0; i < kDiscConvs; ++i) {
-        if (k == std::string(kDiscConv[i].name) + ".weight") { li = i; is_bias = 0; }
-        if (k == std::string(kDiscConv[i].name) + ".bias") { li = i; is_bias = 1; }
-    }
-    if (li < 0)
-        return dfail(d, CID_ERR_KEY, "cid_disc_set_weight: unknown key '" + k +
-                                         "' (BatchNorm tensors model.3/6/9 are passed to cid_disc_forward, not staged)");
-    const auto& L = kDiscConv[li];
-    const int64_t want_w[4] = {L.cout, L.cin, L.k, L.k};
-    const bool ok = is_bias ? (ndim == 1 && shape[0] == L.cout)
-                            : (ndim == 4 && std::equal(shape, shape + 4, want_w));
-    if (!ok) return dfail(d, CID_ERR_SHAPE, "cid_disc_set_weight: size mismatch for " + k);
-    float* seg = d->staging.data() + kDiscBlob.off[li];
-    const size_t nw = (size_t)L.cout * L.cin * L.k * L.k;
-    const bool packed = li >= 1 && li <= 3;
-    if (is_bias) {
-        std::memcpy(seg + nw, data, (size_t)L.cout * sizeof(float));
-    } else if (!packed) {
-        std::memcpy(seg, data, nw * sizeof(float));
-    } else {
-        for (int co = 0; co < L.cout; ++co)
-            for (int ci = 0; ci < L.cin; ++ci)
-                for (int tap = 0; tap < 9; ++tap)
-                    seg[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * L.cout + co] = data[((size_t)co * L.cin + ci) * 9 + tap];
-    }
-    d->have[li][is_bias] = true;
-    return CID_OK;
-}
-
-size_t cid_disc_packed_weights_bytes(void) { return kDiscBlob.total * sizeof(float); }
-
-int cid_disc_upload_weights(cid_disc_t d, void* device_blob, void* stream) {
-    if (!d) return CID_ERR_INVALID;
-    if (!device_blob) return dfail(d, CID_ERR_INVALID, "cid_disc_upload_weights: null device pointer");
-    if ((uintptr_t)device_blob & 255) return dfail(d, CID_ERR_WORKSPACE, "cid_disc_upload_weights: blob must be 256-byte aligned");
-    for (int i = 0; i < kDiscConvs; ++i)
-        if (!d->have[i][0] || !d->have[i][1])
-            return dfail(d, CID_ERR_STATE, std::string("cid_disc_upload_weights: ") + kDiscConv[i].name + " not set");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, d->staging.data(), kDiscBlob.total * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return dfail(d, CID_ERR_HIP, std::string("cid_disc_upload_weights: ") + hipGetErrorString(e));
-    d->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
-}
-
-int cid_disc_workspace_bytes(int N, int H, int W, int training, size_t* bytes) {
-    if (!bytes || (training != 0 && training != 1)) return CID_ERR_INVALID;
-    DiscPlan p;
-    const int rc = disc_plan(N, H, W, training, p);
-    if (rc == CID_OK) *bytes = p.total;
-    return rc;
-}
-
-int cid_disc_forward(cid_disc_t d, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn,
-                     int training, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!d) return CID_ERR_INVALID;
-    DiscPlan p;
-    const int rc = disc_check_forward(d, "cid_disc_forward", in, in_fmt, out, N, H, W, bn, training, workspace, p);
-    if (rc != CID_OK) return rc;
-    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return dfail(d, CID_ERR_WORKSPACE, "cid_disc_forward: workspace smaller than cid_disc_workspace_bytes() or not 256-byte aligned");
-    if (!d->dev_blob) return dfail(d, CID_ERR_STATE, "cid_disc_forward: weights not uploaded");
-    char* ws = static_cast<char*>(workspace);
-    DiscBufs b{};
-    b.a0 = b.z5 = reinterpret_cast<float*>(ws + p.regA);
-    b.z2 = b.z8 = reinterpret_cast<float*>(ws + p.regB);
-    for (int l = 0; l < 3; ++l) {
-        b.st[l] = reinterpret_cast<float*>(ws + p.st) + l * 256;
-        b.slab[l] = reinterpret_cast<double*>(ws + p.slab[l]);
-    }
-    return disc_forward_run(d, "cid_disc_forward", in, in_fmt, out, N, H, W, bn, training, p, b, static_cast<hipStream_t>(stream));
-}
-
-// ---- backward pass: the per-call saved buffer, the workspace plan and the launch sequence; kernels in disc_bwd_kernels.h ----
-}  // extern "C"
-
-namespace {
-
-// What cid_disc_forward_saved keeps for one call.
-struct DiscSavedPlan {
-    size_t a0, z2, z5, z8, st, mi, slab[3], total;
-};
-
-void disc_saved_plan(int N, int H, int W, int training, const DiscPlan& p, DiscSavedPlan& q) {
-    const size_t n = (size_t)N, f = sizeof(float);
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align256(bytes);
-        return o;
-    };
-    q.a0 = take(n * 64 * H * W * f);
-    q.z2 = take(n * 64 * p.H2 * p.W2 * f);
-    q.z5 = take(n * 128 * p.H2 * p.W2 * f);
-    q.z8 = take(n * 128 * p.H4 * p.W4 * f);
-    q.st = take(3 * 256 * f);
-    q.mi = take(3 * 256 * sizeof(double));
-    const int couts[3] = {64, 128, 128};
-    for (int l = 0; l < 3; ++l) q.slab[l] = training ? take((size_t)couts[l] * 2 * n * p.tiles[l] * sizeof(double)) : at;
-    q.total = at;
-}
-
-DiscBufs disc_saved_bufs(void* saved, const DiscSavedPlan& q) {
-    char* sv = static_cast<char*>(saved);
-    DiscBufs b{};
-    b.a0 = reinterpret_cast<float*>(sv + q.a0);
-    b.z2 = reinterpret_cast<float*>(sv + q.z2);
-    b.z5 = reinterpret_cast<float*>(sv + q.z5);
-    b.z8 = reinterpret_cast<float*>(sv + q.z8);
-    for (int l = 0; l < 3; ++l) {
-        b.st[l] = reinterpret_cast<float*>(sv + q.st) + l * 256;
-        b.mi[l] = reinterpret_cast<double*>(sv + q.mi) + l * 256;
-        b.slab[l] = reinterpret_cast<double*>(sv + q.slab[l]);
-    }
-    return b;
-}
-
-// Workspace of one backward call.  X holds the gradient of a6 and later of a0, Y the gradient of a3 (the forward's two regions).
-struct DiscBwdPlan {
-    int strips[3];                  // BatchNorm strips per image
-    int wg_tiles_x[3], wg_tiles[3]; // wgrad items per image of layers 2, 5, 8
-    int wg_splits[3];
-    int dg_tiles_x[3], dg_tiles[3]; // dgrad tiles of the largest class
-    int w0_strips, w0_splits;
-    size_t dl, mean, coef, bnslab, X, Y, part, part_b, part0, total;
-};
-
-constexpr int kDiscWgCD[3] = {64, 128, 128}, kDiscWgCX[3] = {64, 64, 128}, kDiscWgS[3] = {2, 1, 2};
-constexpr int kDiscDgTileRows[3] = {DiscDgradGeom<64, 64, 2>::TH, DiscDgradGeom<128, 64, 1>::TH, DiscDgradGeom<128, 128, 2>::TH};
-
-void disc_bwd_plan(int N, int H, int W, const DiscPlan& p, DiscBwdPlan& q) {
-    const size_t n = (size_t)N, f = sizeof(float);
-    const int ho[3] = {p.H2, p.H2, p.H4}, wo[3] = {p.W2, p.W2, p.W4};
-    const int hin[3] = {H, p.H2, p.H2}, win[3] = {W, p.W2, p.W2};
-    size_t bnslab = 0, part = 0, part_b = 0;
-    for (int l = 0; l < 3; ++l) {
-        q.strips[l] = (int)(((long long)ho[l] * wo[l] + D_BN_STRIP - 1) / D_BN_STRIP);
-        bnslab = std::max(bnslab, (size_t)kDiscBnC[l] * 2 * n * q.strips[l] * sizeof(double));
-        q.wg_tiles_x[l] = (wo[l] + D_TW - 1) / D_TW;
-        q.wg_tiles[l] = ((ho[l] + D_WG_TH - 1) / D_WG_TH) * q.wg_tiles_x[l];
-        const long long items = (long long)N * q.wg_tiles[l];
-        q.wg_splits[l] = (int)std::min<long long>(items, 512 / (kDiscWgCX[l] / 16));
-        part = std::max(part, (size_t)q.wg_splits[l] * kDiscWgCX[l] * kDiscWgCD[l] * 9 * f);
-        part_b = std::max(part_b, (size_t)q.wg_splits[l] * kDiscWgCD[l] * sizeof(double));
-        const int hc = (hin[l] + kDiscWgS[l] - 1) / kDiscWgS[l], wc = (win[l] + kDiscWgS[l] - 1) / kDiscWgS[l];
-        q.dg_tiles_x[l] = (wc + D_TW - 1) / D_TW;
-        q.dg_tiles[l] = ((hc + kDiscDgTileRows[l] - 1) / kDiscDgTileRows[l]) * q.dg_tiles_x[l];
-    }
-    q.w0_strips = (int)(((long long)H * W + 63) / 64);
-    q.w0_splits = (int)std::min<long long>((long long)N * q.w0_strips, 1024);
-    size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align256(bytes);
-        return o;
-    };
-    q.dl = take(n * f);
-    q.mean = take(n * 128 * sizeof(double));
-    q.coef = take(3 * 128 * D_COEF * f);
-    q.bnslab = take(bnslab);
-    q.X = take(std::max(n * 128 * p.H2 * p.W2, n * 64 * H * W) * f);
-    q.Y = take(n * 64 * p.H2 * p.W2 * f);
-    q.part = take(part);
-    q.part_b = take(part_b);
-    q.part0 = take((size_t)q.w0_splits * 64 * 28 * sizeof(double));
-    q.total = at;
-}
-
-template <int CD, int CX, int S, bool BN_IN, bool HEAD>
-hipError_t disc_wgrad_launch(const DiscWgradArgs& a, float* dw, float* db, hipStream_t s) {
-    hipLaunchKernelGGL((k_disc_wgrad<CD, CX, S, BN_IN, HEAD>), dim3((unsigned)a.splits, CX / 16), dim3(D_THREADS), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const DiscWgradReduceArgs r{a.part, a.part_b, dw, db, a.splits, CD, CX};
-    hipLaunchKernelGGL(k_disc_wgrad_reduce, dim3((CD * CX * 9 + CD + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
-    return hipGetLastError();
-}
-
-template <int CD, int CX, int S, bool HEAD>
-hipError_t disc_dgrad_launch(const DiscDgradArgs& base, int tiles, int N, hipStream_t s) {
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscDgradArgs a = base;
-        a.n0 = n0;
-        const dim3 grid((unsigned)tiles, (unsigned)std::min(kDiscChunk, N - n0), DiscDgradGeom<CD, CX, S>::CLASSES);
-        hipLaunchKernelGGL((k_disc_dgrad<CD, CX, S, HEAD>), grid, dim3(D_THREADS), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-template <int C, bool HEAD>
-hipError_t disc_bn_part_launch(const DiscBnPartArgs& base, int N, hipStream_t s) {
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscBnPartArgs a = base;
-        a.n0 = n0;
-        hipLaunchKernelGGL((k_disc_bn_bwd_part<C, HEAD>), dim3((unsigned)a.strips, (unsigned)std::min(kDiscChunk, N - n0)), dim3(D_THREADS), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// Shape checks shared by the backward entry points.
-int disc_bwd_shape(cid_disc_t d, const char* fn, int N, int H, int W, int training, DiscPlan& p) {
-    if (training != 0 && training != 1) return dfail(d, CID_ERR_INVALID, std::string(fn) + ": training must be 0 or 1");
-    if (disc_plan(N, H, W, training, p) != CID_OK)
-        return dfail(d, CID_ERR_SHAPE, std::string(fn) + ": shape not accepted (N, H, W >= 1, H*W < 2^31, more than one value per channel in train mode)");
-    return CID_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int cid_disc_saved_bytes(int N, int H, int W, int training, size_t* bytes) {
-    if (!bytes || (training != 0 && training != 1)) return CID_ERR_INVALID;
-    DiscPlan p;
-    const int rc = disc_plan(N, H, W, training, p);
-    if (rc != CID_OK) return rc;
-    DiscSavedPlan q;
-    disc_saved_plan(N, H, W, training, p, q);
-    *bytes = q.total;
-    return CID_OK;
-}
-
-int cid_disc_forward_saved(cid_disc_t d, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn,
-                           int training, void* saved, size_t saved_bytes, void* stream) {
-    if (!d) return CID_ERR_INVALID;
-    DiscPlan p;
-    const int rc = disc_check_forward(d, "cid_disc_forward_saved", in, in_fmt, out, N, H, W, bn, training, saved, p);
-    if (rc != CID_OK) return rc;
-    DiscSavedPlan q;
-    disc_saved_plan(N, H, W, training, p, q);
-    if (saved_bytes < q.total || ((uintptr_t)saved & 255))
-        return dfail(d, CID_ERR_WORKSPACE, "cid_disc_forward_saved: saved buffer smaller than cid_disc_saved_bytes() or not 256-byte aligned");
-    if (!d->dev_blob) return dfail(d, CID_ERR_STATE, "cid_disc_forward_saved: weights not uploaded");
-    return disc_forward_run(d, "cid_disc_forward_saved", in, in_fmt, out, N, H, W, bn, training, p, disc_saved_bufs(saved, q),
-                            static_cast<hipStream_t>(stream));
-}
-
-int cid_disc_backward_workspace_bytes(int N, int H, int W, int training, size_t* bytes) {
-    if (!bytes || (training != 0 && training != 1)) return CID_ERR_INVALID;
-    DiscPlan p;
-    const int rc = disc_plan(N, H, W, training, p);
-    if (rc != CID_OK) return rc;
-    DiscBwdPlan q;
-    disc_bwd_plan(N, H, W, p, q);
-    *bytes = q.total;
-    return CID_OK;
-}
-
-int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* grad_prob, int N, int H, int W, const cid_disc_bn* bn,
-                      int training, const void* saved, size_t saved_bytes, const cid_disc_grads* g, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-    if (!d) return CID_ERR_INVALID;
-    const char* fn = "cid_disc_backward";
-    if (!in || !grad_prob || !bn || !saved || !g || !workspace) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: null pointer");
-    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: unknown input format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)grad_prob & 3))
-        return dfail(d, CID_ERR_INVALID, "cid_disc_backward: misaligned fp32 operand");
-    for (int l = 0; l < 3; ++l)
-        if (!bn[l].gamma) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: null BatchNorm weight pointer");
-    bool misaligned = ((uintptr_t)g->input & 3) != 0;
-    for (int i = 0; i < 5; ++i) misaligned = misaligned || ((uintptr_t)g->w[i] & 3) || ((uintptr_t)g->b[i] & 3);
-    for (int l = 0; l < 3; ++l) misaligned = misaligned || ((uintptr_t)g->gamma[l] & 3) || ((uintptr_t)g->beta[l] & 3);
-    if (misaligned) return dfail(d, CID_ERR_INVALID, "cid_disc_backward: misaligned gradient pointer");
-    if (g->input && in_fmt != CID_FMT_F32_NCHW)
-        return dfail(d, CID_ERR_INVALID, "cid_disc_backward: a uint8 input has no gradient (grads.input must be null)");
-    DiscPlan p;
-    const int rc = disc_bwd_shape(d, fn, N, H, W, training, p);
-    if (rc != CID_OK) return rc;
-    DiscSavedPlan sp;
-    disc_saved_plan(N, H, W, training, p, sp);
-    if (saved_bytes < sp.total || ((uintptr_t)saved & 255))
-        return dfail(d, CID_ERR_WORKSPACE, "cid_disc_backward: saved buffer smaller than cid_disc_saved_bytes() or not 256-byte aligned");
-    DiscBwdPlan q;
-    disc_bwd_plan(N, H, W, p, q);
-    if (workspace_bytes < q.total || ((uintptr_t)workspace & 255))
-        return dfail(d, CID_ERR_WORKSPACE, "cid_disc_backward: workspace smaller than cid_disc_backward_workspace_bytes() or not 256-byte aligned");
-    if (!d->dev_blob) return dfail(d, CID_ERR_STATE, "cid_disc_backward: weights not uploaded");
-
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const DiscBufs sv = disc_saved_bufs(const_cast<void*>(saved), sp);
-    char* ws = static_cast<char*>(workspace);
-    float* dl = reinterpret_cast<float*>(ws + q.dl);
-    double* mean = reinterpret_cast<double*>(ws + q.mean);
-    float* coef[3];
-    for (int l = 0; l < 3; ++l) coef[l] = reinterpret_cast<float*>(ws + q.coef) + l * 128 * D_COEF;
-    double* bnslab = reinterpret_cast<double*>(ws + q.bnslab);
-    float* X = reinterpret_cast<float*>(ws + q.X);
-    float* Y = reinterpret_cast<float*>(ws + q.Y);
-    float* part = reinterpret_cast<float*>(ws + q.part);
-    double* part_b = reinterpret_cast<double*>(ws + q.part_b);
-    double* part0 = reinterpret_cast<double*>(ws + q.part0);
-    const float* blob = d->dev_blob;
-    const auto herr = [&](const char* what) { return dfail(d, CID_ERR_HIP, std::string(fn) + ": " + what + ": " + hipGetErrorString(hipGetLastError())); };
-
-    // what is asked for at or below each stage: head(8) > bn9(7) > conv8(6) > bn6(5) > conv5(4) > bn3(3) > conv2(2) > conv0(1) > input(0)
-    const bool want[9] = {g->input != nullptr, g->w[0] || g->b[0], g->w[1] || g->b[1], g->gamma[0] || g->beta[0], g->w[2] || g->b[2],
-                          g->gamma[1] || g->beta[1], g->w[3] || g->b[3], g->gamma[2] || g->beta[2], g->w[4] || g->b[4]};
-    bool below[10];   // below[k]: something at a stage < k is asked for
-    below[0] = false;
-    for (int k = 0; k < 9; ++k) below[k + 1] = below[k] || want[k];
-    if (!below[9]) return CID_OK;
-    const long long P4 = (long long)p.H4 * p.W4, P2 = (long long)p.H2 * p.W2;
-
-    // head
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        DiscHeadBwdArgs a{sv.z8, sv.st[2], blob + kDiscBlob.off[4], grad_prob, mean, dl, P4, n0};
-        hipLaunchKernelGGL(k_disc_head_bwd, dim3((unsigned)std::min(kDiscChunk, N - n0)), dim3(D_HEAD_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("head");
-    }
-    {
-        DiscHeadReduceArgs a{mean, dl, blob + kDiscBlob.off[4], g->w[4], g->b[4], coef[2], (double)P4, N};
-        hipLaunchKernelGGL(k_disc_head_reduce, dim3(1), dim3(128), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("head reduce");
-    }
-    if (!below[8]) return CID_OK;
-
-    const auto bn_reduce = [&](int l, long long pix) {
-        DiscBnRedArgs a{bnslab, (long long)N * q.strips[l], (double)N * (double)pix, bn[l].gamma, sv.st[l], sv.mi[l], training,
-                        coef[l], g->gamma[l], g->beta[l]};
-        hipLaunchKernelGGL(k_disc_bn_bwd_reduce, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
-        return hipPeekAtLastError();
-    };
-    const auto bn_part = [&](int l, const float* z, const float* up, long long pix) {
-        DiscBnPartArgs a{z, up, dl, coef[l], sv.st[l], sv.mi[l], bnslab, (long long)N * q.strips[l], pix, q.strips[l], 0};
-        return a;
-    };
-    const auto wg_args = [&](int l, const DiscDzSrc& dz, const float* ain, const float* st_in, int Hin, int Win, int Ho, int Wo) {
-        DiscWgradArgs a{};
-        a.dz = dz;
-        a.ain = ain;
-        a.st_in = st_in;
-        a.part = part;
-        a.part_b = part_b;
-        a.items = (long long)N * q.wg_tiles[l];
-        a.splits = q.wg_splits[l];
-        a.Hin = Hin;
-        a.Win = Win;
-        a.Ho = Ho;
-        a.Wo = Wo;
-        a.tiles_x = q.wg_tiles_x[l];
-        a.tiles = q.wg_tiles[l];
-        return a;
-    };
-    const auto dg_args = [&](int l, int ci, const DiscDzSrc& dz, float* out, int Hin, int Win, int Ho, int Wo) {
-        DiscDgradArgs a{};
-        a.dz = dz;
-        a.w = blob + kDiscBlob.off[ci];
-        a.out = out;
-        a.Hin = Hin;
-        a.Win = Win;
-        a.Ho = Ho;
-        a.Wo = Wo;
-        a.tiles_x = q.dg_tiles_x[l];
-        return a;
-    };
-
-    // BN9 (upstream: the head's dl[n] * w12[c] / P4), layer 8
-    if (disc_bn_part_launch<128, true>(bn_part(2, sv.z8, nullptr, P4), N, s) != hipSuccess) return herr("bn9 sums");
-    if (bn_reduce(2, P4) != hipSuccess) return herr("bn9 reduce");
-    const DiscDzSrc dz8{sv.z8, nullptr, dl, coef[2]};
-    if (want[6] && disc_wgrad_launch<128, 128, 2, true, true>(wg_args(2, dz8, sv.z5, sv.st[1], p.H2, p.W2, p.H4, p.W4), g->w[3], g->b[3], s) != hipSuccess)
-        return herr("wgrad8");
-    if (!below[6]) return CID_OK;
-    if (disc_dgrad_launch<128, 128, 2, true>(dg_args(2, 3, dz8, X, p.H2, p.W2, p.H4, p.W4), q.dg_tiles[2], N, s) != hipSuccess) return herr("dgrad8");
-    // BN6, layer 5
-    if (disc_bn_part_launch<128, false>(bn_part(1, sv.z5, X, P2), N, s) != hipSuccess) return herr("bn6 sums");
-    if (bn_reduce(1, P2) != hipSuccess) return herr("bn6 reduce");
-    const DiscDzSrc dz5{sv.z5, X, nullptr, coef[1]};
-    if (want[4] && disc_wgrad_launch<128, 64, 1, true, false>(wg_args(1, dz5, sv.z2, sv.st[0], p.H2, p.W2, p.H2, p.W2), g->w[2], g->b[2], s) != hipSuccess)
-        return herr("wgrad5");
-    if (!below[4]) return CID_OK;
-    if (disc_dgrad_launch<128, 64, 1, false>(dg_args(1, 2, dz5, Y, p.H2, p.W2, p.H2, p.W2), q.dg_tiles[1], N, s) != hipSuccess) return herr("dgrad5");
-    // BN3, layer 2
-    if (disc_bn_part_launch<64, false>(bn_part(0, sv.z2, Y, P2), N, s) != hipSuccess) return herr("bn3 sums");
-    if (bn_reduce(0, P2) != hipSuccess) return herr("bn3 reduce");
-    const DiscDzSrc dz2{sv.z2, Y, nullptr, coef[0]};
-    if (want[2] && disc_wgrad_launch<64, 64, 2, false, false>(wg_args(0, dz2, sv.a0, nullptr, H, W, p.H2, p.W2), g->w[1], g->b[1], s) != hipSuccess)
-        return herr("wgrad2");
-    if (!below[2]) return CID_OK;
-    if (disc_dgrad_launch<64, 64, 2, false>(dg_args(0, 1, dz2, X, H, W, p.H2, p.W2), q.dg_tiles[0], N, s) != hipSuccess) return herr("dgrad2");
-    // layer 0
-    if (want[1]) {
-        DiscWgrad0Args a{in, sv.a0, X, part0, (long long)N * q.w0_strips, q.w0_splits, q.w0_strips, H, W};
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_wgrad0<true>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_disc_wgrad0<false>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("wgrad0");
-        DiscWgrad0ReduceArgs r{part0, g->w[0], g->b[0], q.w0_splits};
-        hipLaunchKernelGGL(k_disc_wgrad0_reduce, dim3((64 * 28 + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
-        if (hipPeekAtLastError() != hipSuccess) return herr("wgrad0 reduce");
-    }
-    if (want[0]) {
-        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-            DiscDgrad0Args a{sv.a0, X, blob + kDiscBlob.off[0], g->input, H, W, n0};
-            const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
-            hipLaunchKernelGGL(k_disc_dgrad0, grid, dim3(D_THREADS), 0, s, a);
-            if (hipPeekAtLastError() != hipSuccess) return herr("dgrad0");
-        }
-    }
-    return CID_OK;
-}
-
-int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, void* device_blob, void* stream) {
-    if (!d) return CID_ERR_INVALID;
-    if (!dev_params || !device_blob) return dfail(d, CID_ERR_INVALID, "cid_disc_pack_weights_device: null pointer");
-    for (int i = 0; i < CID_DISC_NUM_WEIGHTS; ++i)
-        if (!dev_params[i] || ((uintptr_t)dev_params[i] & 3))
-            return dfail(d, CID_ERR_INVALID, "cid_disc_pack_weights_device: null or misaligned parameter pointer");
-    if ((uintptr_t)device_blob & 255) return dfail(d, CID_ERR_WORKSPACE, "cid_disc_pack_weights_device: blob must be 256-byte aligned");
-    DiscPackArgs a{};
-    for (int i = 0; i < kDiscConvs; ++i) {
-        a.w[i] = dev_params[2 * i];
-        a.b[i] = dev_params[2 * i + 1];
-        a.off[i] = (int)kDiscBlob.off[i];
-        a.cin[i] = kDiscConv[i].cin;
-        a.cout[i] = kDiscConv[i].cout;
-        a.kk[i] = kDiscConv[i].k * kDiscConv[i].k;
-    }
-    a.blob = static_cast<float*>(device_blob);
-    a.total = (int)kDiscBlob.total;
-    hipLaunchKernelGGL(k_disc_pack, dim3((a.total + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    if (hipGetLastError() != hipSuccess) return dfail(d, CID_ERR_HIP, "cid_disc_pack_weights_device: launch failed");
-    d->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
-}
-
-int cid_disc_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int W, int training, unsigned char* const* masks, void* stream) {
-    if (!saved || !masks || (training != 0 && training != 1)) return CID_ERR_INVALID;
-    for (int i = 0; i < 4; ++i)
-        if (!masks[i]) return CID_ERR_INVALID;
-    DiscPlan p;
-    const int rc = disc_plan(N, H, W, training, p);
-    if (rc != CID_OK) return rc;
-    DiscSavedPlan sp;
-    disc_saved_plan(N, H, W, training, p, sp);
-    if (saved_bytes < sp.total || ((uintptr_t)saved & 255)) return CID_ERR_WORKSPACE;
-    const DiscBufs sv = disc_saved_bufs(const_cast<void*>(saved), sp);
-    const float* z[4] = {sv.a0, sv.z2, sv.z5, sv.z8};
-    const float* st[4] = {nullptr, sv.st[0], sv.st[1], sv.st[2]};
-    const int C[4] = {64, 64, 128, 128};
-    const long long P[4] = {(long long)H * W, (long long)p.H2 * p.W2, (long long)p.H2 * p.W2, (long long)p.H4 * p.W4};
-    for (int i = 0; i < 4; ++i) {
-        DiscMaskArgs a{z[i], st[i], masks[i], (long long)N * C[i] * P[i], P[i], C[i]};
-        const long long blocks = (a.total + D_THREADS - 1) / D_THREADS;
-        if (blocks > 0x7fffffffLL) return CID_ERR_SHAPE;
-        hipLaunchKernelGGL(k_disc_masks, dim3((unsigned)blocks), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
-        if (hipGetLastError() != hipSuccess) return CID_ERR_HIP;
-    }
-    return CID_OK;
-}
-
-int cid_disc_losses(const float* p_real, const float* p_fake, const void* den, int d_fmt, const void* clean, int c_fmt,
-                    int N, int H, int W, double* out, void* stream) {
-    if (!p_real || !p_fake || !den || !clean || !out) return CID_ERR_INVALID;
-    const auto fmt_ok = [](const void* q, int f) {
-        return (f == CID_FMT_U8_NHWC) || (f == CID_FMT_F32_NCHW && ((uintptr_t)q & 3) == 0);
-    };
-    if (!fmt_ok(den, d_fmt) || !fmt_ok(clean, c_fmt) || ((uintptr_t)p_real & 3) || ((uintptr_t)p_fake & 3) || ((uintptr_t)out & 7))
-        return CID_ERR_INVALID;
-    if (N < 1 || H < 1 || W < 1) return CID_ERR_SHAPE;
-    DiscLossArgs a{p_real, p_fake, den, clean, d_fmt, c_fmt, N, (long long)H * W, out};
-    hipLaunchKernelGGL(k_disc_losses, dim3(1), dim3(D_LOSS_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
-}
-
-// ---- the optimizer step (optim_kernels.h) ----
-}  // extern "C"
-namespace {
-// cid_adam_step's argument checks and k_adam_step's arguments; a.nent == 0: nothing to launch.
-int adam_plan(const cid_adam_tensor* tensors, int ntensors, const cid_adam_hyper* hp, AdamArgs& a) {
-    static_assert(CID_ADAM_MAX_TENSORS == ADAM_MAX_TENSORS, "cid.h and optim_kernels.h disagree");
-    if (!tensors || !hp) return CID_ERR_INVALID;
-    if (ntensors < 1 || ntensors > CID_ADAM_MAX_TENSORS) return CID_ERR_INVALID;
-    for (int i = 0; i < ntensors; ++i) {
-        const cid_adam_tensor& t = tensors[i];
-        if (t.count <= 0) continue;
-        const void* q[4] = {t.param, t.grad, t.exp_avg, t.exp_avg_sq};
-        for (const void* x : q)
-            if (!x || ((uintptr_t)x & 3)) return CID_ERR_INVALID;
-    }
-    for (int i = 0; i < ntensors; ++i)
-        if (tensors[i].count < 0 || tensors[i].step < 1) return CID_ERR_INVALID;
-    const auto in_range = [](double x, double hi_excl) { return std::isfinite(x) && x >= 0.0 && x < hi_excl; };
-    const double inf = std::numeric_limits<double>::infinity();
-    if (!in_range(hp->lr, inf) || !in_range(hp->beta1, 1.0) || !in_range(hp->beta2, 1.0) || !in_range(hp->eps, inf) ||
-        !in_range(hp->weight_decay, inf))
-        return CID_ERR_INVALID;
-
-    // No written range may meet another written range or a gradient: sweep over the ranges in address order with the furthest end of
-    // the written and of the read ranges seen so far.
-    struct Range { uintptr_t lo, hi; bool written; };
-    Range r[4 * CID_ADAM_MAX_TENSORS];
-    int nr = 0;
-    a.nent = 0;
-    unsigned long long items = 0;
-    for (int i = 0; i < ntensors; ++i) {
-        const cid_adam_tensor& t = tensors[i];
-        if (t.count == 0) continue;
-        if (t.count > (int64_t)1 << 44) return CID_ERR_INVALID;   // beyond any device memory; keeps the byte ranges and the grid in range
-        const uintptr_t bytes = (uintptr_t)t.count * 4;
-        r[nr++] = {(uintptr_t)t.param, (uintptr_t)t.param + bytes, true};
-        r[nr++] = {(uintptr_t)t.exp_avg, (uintptr_t)t.exp_avg + bytes, true};
-        r[nr++] = {(uintptr_t)t.exp_avg_sq, (uintptr_t)t.exp_avg_sq + bytes, true};
-        r[nr++] = {(uintptr_t)t.grad, (uintptr_t)t.grad + bytes, false};
-        AdamEntry& e = a.ent[a.nent++];
-        e.param = t.param;
-        e.grad = t.grad;
-        e.exp_avg = t.exp_avg;
-        e.exp_avg_sq = t.exp_avg_sq;
-        e.count = t.count;
-        e.t0 = (unsigned)items;
-        const unsigned mis = (unsigned)((uintptr_t)t.param & 15);
-        const bool same = ((uintptr_t)t.grad & 15) == mis && ((uintptr_t)t.exp_avg & 15) == mis && ((uintptr_t)t.exp_avg_sq & 15) == mis;
-        e.off = same ? mis / 4 : ADAM_SCALAR;   // mis / 4 phantom elements in front put quad q at byte 16 q - mis of the tensor: 16-byte aligned
-        items += ((unsigned long long)t.count + (same ? mis / 4 : 0) + ADAM_ITEM_ELEMS - 1) / ADAM_ITEM_ELEMS;
-        if (items > 0x7fffffffULL) return CID_ERR_INVALID;
-        const double t_d = (double)t.step;
-        e.step_size = hp->lr / (1.0 - std::pow(hp->beta1, t_d));
-        e.bc2_sqrt = std::sqrt(1.0 - std::pow(hp->beta2, t_d));
-    }
-    std::sort(r, r + nr, [](const Range& x, const Range& y) { return x.lo < y.lo; });
-    uintptr_t wend = 0, rend = 0;
-    for (int i = 0; i < nr; ++i) {
-        if (r[i].lo < wend || (r[i].written && r[i].lo < rend)) return CID_ERR_INVALID;
-        uintptr_t& end = r[i].written ? wend : rend;
-        end = std::max(end, r[i].hi);
-    }
-    a.beta1 = hp->beta1;
-    a.one_minus_beta1 = 1.0 - hp->beta1;
-    a.beta2 = hp->beta2;
-    a.one_minus_beta2 = 1.0 - hp->beta2;
-    a.eps = hp->eps;
-    a.weight_decay = hp->weight_decay;
-    a.nitems = (unsigned)items;
-    return CID_OK;
-}
-}  // namespace
-extern "C" {
-
-int cid_adam_step(const cid_adam_tensor* tensors, int ntensors, const cid_adam_hyper* hp, void* stream) {
-    AdamArgs a;
-    const int rc = adam_plan(tensors, ntensors, hp, a);
-    if (rc != CID_OK || a.nent == 0) return rc;
-    hipLaunchKernelGGL(k_adam_step, dim3(a.nitems), dim3(ADAM_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
-}
-
-int cid_debug_adam_step_host(const cid_adam_tensor* tensors, int ntensors, const cid_adam_hyper* hp) {
-    AdamArgs a;
-    const int rc = adam_plan(tensors, ntensors, hp, a);
-    if (rc != CID_OK || a.nent == 0) return rc;
-    for (unsigned item = 0; item < a.nitems; ++item)
-        for (unsigned tid = 0; tid < (unsigned)ADAM_THREADS; ++tid) adam_item(a, item, tid);
-    return CID_OK;
-}
-
-}  // extern "C"
+// ---- the other families, one host file each; their place here fixes the order in which kernel templates are first instantiated ----
+#include "api/quality.h"          // cid_quality
+#include "api/noise.h"            // cid_add_noise
+#include "api/resize.h"           // cid_resize_*
+#include "api/disc_forward.h"     // cid_disc_*: weights, forward
+#include "api/disc_backward.h"    // cid_disc_*: saved forward, backward, device pack, masks, losses
+#include "api/adam.h"             // cid_adam_step
 
 // ---- the generator's backward pass (gen_bwd_kernels.h) ----
 namespace {
@@ -2526,25 +1258,20 @@ void gen_bwd_plan(const Dims& d, GenBwdPlan& q) {
     q.w27_strips = (int)(((long long)d.H * d.W + 63) / 64);
     q.w27_splits = (int)std::min<long long>((long long)d.N * q.w27_strips, 1024);
     size_t at = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align256(bytes);
-        return o;
-    };
-    q.dz16 = take(s0 * 3 * f);
-    q.G4 = take(s0 * 64 * f);
-    q.dcat1 = take(s0 * 128 * f);
-    q.gd2 = take(s1 * 128 * f);
-    q.gt3 = take(s1 * 128 * f);
-    q.dcat2 = take(s1 * 256 * f);
-    q.gbt = take(s2 * 256 * f);
-    q.gt2 = take(s2 * 256 * f);
-    q.dp2 = take(s2 * 128 * f);
-    q.dp1 = take(s1 * 64 * f);
-    q.part = take(part);
-    q.part_b = take(part_b);
-    q.part27 = take((size_t)q.w27_splits * 64 * 28 * sizeof(double));
-    q.part27_b = take((size_t)q.w27_splits * 3 * sizeof(double));
+    q.dz16 = take(at, s0 * 3 * f);
+    q.G4 = take(at, s0 * 64 * f);
+    q.dcat1 = take(at, s0 * 128 * f);
+    q.gd2 = take(at, s1 * 128 * f);
+    q.gt3 = take(at, s1 * 128 * f);
+    q.dcat2 = take(at, s1 * 256 * f);
+    q.gbt = take(at, s2 * 256 * f);
+    q.gt2 = take(at, s2 * 256 * f);
+    q.dp2 = take(at, s2 * 128 * f);
+    q.dp1 = take(at, s1 * 64 * f);
+    q.part = take(at, part);
+    q.part_b = take(at, part_b);
+    q.part27 = take(at, (size_t)q.w27_splits * 64 * 28 * sizeof(double));
+    q.part27_b = take(at, (size_t)q.w27_splits * 3 * sizeof(double));
     q.total = at;
 }
 
@@ -2564,14 +1291,12 @@ hipError_t gen_dgrad_launch(GenDgradArgs a, int N, hipStream_t s) {
     using G = GenDgradGeom<CXB, TAPS>;
     a.tiles_x = cdiv(a.W, G_TW);
     a.tiles = cdiv(a.H, G::TH) * a.tiles_x;
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+    (void)for_each_launch(N, [&](int n0, int n) {
         a.n0 = n0;
-        const dim3 grid((unsigned)(a.tiles * (a.CX / CXB)), (unsigned)std::min(kDiscChunk, N - n0));
+        const dim3 grid((unsigned)(a.tiles * (a.CX / CXB)), (unsigned)n);
         hipLaunchKernelGGL((k_gen_dgrad<CD, CXB, TAPS>), grid, dim3(G_THREADS), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
+    return hipGetLastError();
 }
 
 // The data gradient of GEMM-shaped layer l (1 ... 10).
@@ -2613,17 +1338,17 @@ int cid_saved_bytes(int N, int H, int W, size_t* bytes) { return cid_workspace_b
 
 int cid_forward_saved(cid_handle_t h, const float* in, float* out, int N, int H, int W, void* saved, size_t saved_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    if (!in || !out || !saved) return fail(h, CID_ERR_INVALID, "cid_forward_saved: null pointer");
-    if (h->dtype != CID_DTYPE_F32) return fail(h, CID_ERR_STATE, "cid_forward_saved: the differentiable forward needs compute dtype CID_DTYPE_F32");
+    const Call cx(h, "cid_forward_saved", stream);
+    if (!in || !out || !saved) return cx.fail(CID_ERR_INVALID, "null pointer");
+    if (h->dtype != CID_DTYPE_F32) return cx.fail(CID_ERR_STATE, "the differentiable forward needs compute dtype CID_DTYPE_F32");
     Dims d;
     if (const char* why = gen_bwd_shape_error(N, H, W, d)) {
         char m[384];
         std::snprintf(m, sizeof m, "cid_forward_saved: input [%d,3,%d,%d] not accepted: %s", N, H, W, why);
-        return fail(h, CID_ERR_SHAPE, m);
+        return h->fail(CID_ERR_SHAPE, m);
     }
-    if (saved_bytes < make_plan(d).total_bytes || ((uintptr_t)saved & 255))
-        return fail(h, CID_ERR_WORKSPACE, "cid_forward_saved: saved buffer smaller than cid_saved_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_forward_saved: no device weights attached (call cid_upload_weights or cid_attach_weights)");
+    if (const int rc = cx.room(saved, saved_bytes, make_plan(d).total_bytes, "cid_saved_bytes", "saved buffer")) return rc;
+    if (!h->dev_blob) return cx.fail(CID_ERR_STATE, "no device weights attached (call cid_upload_weights or cid_attach_weights)");
     // the last layer as a launch of its own: the fused form never stores upconv1.0, which the backward pass reads
     const Config cfg{CID_DTYPE_F32, h->algo, CID_TAIL_TILES};
     return run_forward(h, in, CID_FMT_F32_NCHW, out, CID_FMT_F32_NCHW, N, H, W, saved, saved_bytes, static_cast<hipStream_t>(stream), nullptr,
@@ -2643,28 +1368,26 @@ int cid_backward_workspace_bytes(int N, int H, int W, size_t* bytes) {
 int cid_backward(cid_handle_t h, const float* in, const float* out, const float* grad_out, int N, int H, int W, const void* saved,
                  size_t saved_bytes, const cid_grads* g, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
-    const char* fn = "cid_backward";
-    if (!in || !out || !grad_out || !saved || !g || !workspace) return fail(h, CID_ERR_INVALID, "cid_backward: null pointer");
-    if (h->dtype != CID_DTYPE_F32) return fail(h, CID_ERR_STATE, "cid_backward: the backward pass needs compute dtype CID_DTYPE_F32");
+    const Call cx(h, "cid_backward", stream);
+    if (!in || !out || !grad_out || !saved || !g || !workspace) return cx.fail(CID_ERR_INVALID, "null pointer");
+    if (h->dtype != CID_DTYPE_F32) return cx.fail(CID_ERR_STATE, "the backward pass needs compute dtype CID_DTYPE_F32");
     bool misaligned = ((uintptr_t)in & 3) || ((uintptr_t)out & 3) || ((uintptr_t)grad_out & 3) || ((uintptr_t)g->input & 3);
     for (int l = 0; l < NL; ++l) misaligned = misaligned || ((uintptr_t)g->w[l] & 3) || ((uintptr_t)g->b[l] & 3);
-    if (misaligned) return fail(h, CID_ERR_INVALID, "cid_backward: misaligned fp32 pointer");
+    if (misaligned) return cx.fail(CID_ERR_INVALID, "misaligned fp32 pointer");
     Dims d;
     if (const char* why = gen_bwd_shape_error(N, H, W, d)) {
         char m[384];
         std::snprintf(m, sizeof m, "cid_backward: input [%d,3,%d,%d] not accepted: %s", N, H, W, why);
-        return fail(h, CID_ERR_SHAPE, m);
+        return h->fail(CID_ERR_SHAPE, m);
     }
     const Plan p = make_plan(d);
-    if (saved_bytes < p.total_bytes || ((uintptr_t)saved & 255))
-        return fail(h, CID_ERR_WORKSPACE, "cid_backward: saved buffer smaller than cid_saved_bytes() or not 256-byte aligned");
+    if (const int rc = cx.room(saved, saved_bytes, p.total_bytes, "cid_saved_bytes", "saved buffer")) return rc;
     GenBwdPlan q;
     gen_bwd_plan(d, q);
-    if (workspace_bytes < q.total || ((uintptr_t)workspace & 255))
-        return fail(h, CID_ERR_WORKSPACE, "cid_backward: workspace smaller than cid_backward_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return fail(h, CID_ERR_STATE, "cid_backward: no device weights attached (call cid_upload_weights or cid_attach_weights)");
+    if (const int rc = cx.room(workspace, workspace_bytes, q.total, "cid_backward_workspace_bytes")) return rc;
+    if (!h->dev_blob) return cx.fail(CID_ERR_STATE, "no device weights attached (call cid_upload_weights or cid_attach_weights)");
 
-    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const hipStream_t s = cx.s;
     const float* sv = static_cast<const float*>(saved);
     const float* B[NBUF];
     for (int b = 0; b < NBUF; ++b) B[b] = sv + p.off[b];
@@ -2678,7 +1401,6 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
     double* part27 = reinterpret_cast<double*>(ws + q.part27);
     double* part27_b = reinterpret_cast<double*>(ws + q.part27_b);
     const float* blob = h->dev_blob;
-    const auto herr = [&](const char* what) { return fail(h, CID_ERR_HIP, std::string(fn) + ": " + what + ": " + hipGetErrorString(hipGetLastError())); };
 
     // below[l]: the input gradient or a parameter gradient of a layer before l is asked for, so layer l's data gradient is needed
     bool need[NL], below[NL + 1];
@@ -2711,22 +1433,22 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
     {
         const long long total = (long long)N * 3 * H * W;
         hipLaunchKernelGGL(k_gen_dz16, dim3((unsigned)((total + G_THREADS - 1) / G_THREADS)), dim3(G_THREADS), 0, s, grad_out, out, dz16, total);
-        if (hipPeekAtLastError() != hipSuccess) return herr("dz16");
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("dz16");
     }
     if (need[11]) {
         const GenWgrad27Args a{dz16, B[T4], 64, 0, part27, part27_b, (long long)N * q.w27_strips, q.w27_splits, q.w27_strips, H, W};
         hipLaunchKernelGGL(k_gen_wgrad27<true>, dim3((unsigned)q.w27_splits), dim3(G_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("upconv1.2 weight gradient");
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("upconv1.2 weight gradient");
         const GenWgrad27ReduceArgs r{part27, part27_b, g->w[11], g->b[11], q.w27_splits};
         hipLaunchKernelGGL(k_gen_wgrad27_reduce<true>, dim3((unsigned)cdiv(64 * 28 + 3, G_THREADS)), dim3(G_THREADS), 0, s, r);
-        if (hipPeekAtLastError() != hipSuccess) return herr("upconv1.2 weight gradient reduce");
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("upconv1.2 weight gradient reduce");
     }
     if (!below[11]) return CID_OK;
     {
         const long long pixels = (long long)N * H * W;
         const GenDgradTailArgs a{dz16, blob + kBlob.raw_w_off[11], B[T4], G4, pixels, H, W};
         hipLaunchKernelGGL(k_gen_dgrad_tail, dim3((unsigned)((pixels + 63) / 64)), dim3(G_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("upconv1.2 data gradient");
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("upconv1.2 data gradient");
     }
 
     for (int l = 10; l >= 1; --l) {
@@ -2743,7 +1465,7 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
             a.part = part; a.part_b = part_b;
             a.items = (long long)N * gen_wg_tiles(wg);
             a.splits = q.splits[l];
-            if (gen_wgrad(wg, a, g->w[l], g->b[l], s) != hipSuccess) return herr((std::string(kLayers[l].name) + " weight gradient").c_str());
+            if (gen_wgrad(wg, a, g->w[l], g->b[l], s) != hipSuccess) return cx.hip(std::string(kLayers[l].name) + " weight gradient");
         }
         if (!below[l]) return CID_OK;
         GenDgradArgs a{};
@@ -2752,7 +1474,7 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
         a.act = r.act; a.act_ps = r.act_ps; a.act_coff = 0;
         a.out = r.dout; a.out_ps = r.out_ps; a.out_coff = 0;
         a.H = r.Ho; a.W = r.Wo; a.CX = kLayers[l].cin;
-        if (gen_dgrad(l, a, N, s) != hipSuccess) return herr((std::string(kLayers[l].name) + " data gradient").c_str());
+        if (gen_dgrad(l, a, N, s) != hipSuccess) return cx.hip(std::string(kLayers[l].name) + " data gradient");
         if (l == 4 || l == 2) {   // the pooled tensor's gradient is complete: finish dz of the skip tensor under it
             GenPoolBwdArgs pa{};
             const int C = l == 4 ? 128 : 64;
@@ -2762,10 +1484,10 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
             pa.Hp = r.Ho; pa.Wp = r.Wo;
             pa.total = (long long)N * r.Ho * r.Wo * (C / 4);
             const long long blocks = (pa.total + G_THREADS - 1) / G_THREADS;
-            if (blocks > 0x7fffffffLL) return fail(h, CID_ERR_SHAPE, "cid_backward: batch too large for one call");
+            if (blocks > 0x7fffffffLL) return cx.fail(CID_ERR_SHAPE, "batch too large for one call");
             if (l == 4) hipLaunchKernelGGL(k_gen_pool_bwd<128>, dim3((unsigned)blocks), dim3(G_THREADS), 0, s, pa);
             else hipLaunchKernelGGL(k_gen_pool_bwd<64>, dim3((unsigned)blocks), dim3(G_THREADS), 0, s, pa);
-            if (hipPeekAtLastError() != hipSuccess) return herr("max-pool gradient");
+            if (hipPeekAtLastError() != hipSuccess) return cx.hip("max-pool gradient");
         }
     }
 
@@ -2773,1456 +1495,25 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
     if (need[0]) {
         const GenWgrad27Args a{in, gt0, 64, 0, part27, part27_b, (long long)N * q.w27_strips, q.w27_splits, q.w27_strips, H, W};
         hipLaunchKernelGGL(k_gen_wgrad27<false>, dim3((unsigned)q.w27_splits), dim3(G_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("down1.0 weight gradient");
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("down1.0 weight gradient");
         const GenWgrad27ReduceArgs r{part27, part27_b, g->w[0], g->b[0], q.w27_splits};
         hipLaunchKernelGGL(k_gen_wgrad27_reduce<false>, dim3((unsigned)cdiv(64 * 28, G_THREADS)), dim3(G_THREADS), 0, s, r);
-        if (hipPeekAtLastError() != hipSuccess) return herr("down1.0 weight gradient reduce");
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("down1.0 weight gradient reduce");
     }
     if (g->input) {
-        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
+        if (const int rc = cx.launches(N, "down1.0 data gradient", [&](int n0, int n) {
             const GenDgradHeadArgs a{gt0, blob + kBlob.raw_w_off[0], g->input, H, W, n0};
-            const dim3 grid((unsigned)(((long long)H * W + G_THREADS - 1) / G_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
+            const dim3 grid((unsigned)(((long long)H * W + G_THREADS - 1) / G_THREADS), (unsigned)n);
             hipLaunchKernelGGL(k_gen_dgrad_head, grid, dim3(G_THREADS), 0, s, a);
-            if (hipPeekAtLastError() != hipSuccess) return herr("down1.0 data gradient");
-        }
+        })) return rc;
     }
     return CID_OK;
 }
 
 }  // extern "C"
 
-// ---- the server's ESRGANGenerator (cid_esr_*): weight staging, BatchNorm folding, workspace plan and launch sequence; kernels in
-// esrgan_kernels.h ----
-namespace {
-
-constexpr int kEsrMaxBlocks = CID_ESR_MAX_RESIDUALS;
-constexpr size_t kEsrHeadSeg = (size_t)E_HEAD_K * 64 + 128;      // weights, bias[64], slope (padded to 64)
-constexpr size_t kEsrConvSeg = (size_t)E_CONV_W + 256;           // weights, bias[64], s[64], t[64], slope (padded to 64)
-constexpr size_t kEsrTailSeg = (size_t)E_TAIL_W + 64;            // weights, bias[3] (padded to 64)
-
-// The key tables and pack steps below stand on WeightStore (weight_store.h).  What SRGAN shares with ESRGAN is written once here.
-void keys_head9(KeyTable& k) {
-    k.conv("initial.0.", 64, 3, 9);
-    k.tensor("initial.1.weight", {1});
-}
-
-// <blk>0 conv, <blk>1 BatchNorm, <blk>2 PReLU, <blk>3 conv, <blk>4 BatchNorm
-void keys_res_block(KeyTable& k, const std::string& blk) {
-    for (int c = 0; c < 2; ++c) {
-        k.conv(blk + std::to_string(3 * c) + ".", 64, 64, 3);
-        k.batchnorm(blk + std::to_string(3 * c + 1) + ".", 64);
-        if (c == 0) k.tensor(blk + "2.weight", {1});
-    }
-}
-
-KeyTable esr_keys(int R) {
-    KeyTable k;
-    keys_head9(k);
-    for (int i = 0; i < R; ++i) keys_res_block(k, "residuals." + std::to_string(i) + ".block.");
-    k.conv("final.", 3, 64, 9);
-    return k;
-}
-
-// The BatchNorm under the key prefix `bn` folded to y = s*z + t with s = gamma / sqrt(running_var + eps), t = beta - running_mean * s,
-// derived in fp64 and rounded once to fp32.
-void pack_bn_fold(const WeightStore& w, const std::string& bn, double eps, int C, float* s_out, float* t_out) {
-    const float *gamma = w.get(bn + "weight"), *beta = w.get(bn + "bias"), *mean = w.get(bn + "running_mean"), *var = w.get(bn + "running_var");
-    for (int ch = 0; ch < C; ++ch) {
-        const double s = (double)gamma[ch] / std::sqrt((double)var[ch] + eps);
-        s_out[ch] = (float)s;
-        t_out[ch] = (float)((double)beta[ch] - (double)mean[ch] * s);
-    }
-}
-
-// A 64-channel convolution's [co][K] weights as the [k][64] rows a head kernel reads.
-void pack_k64(float* dst, const float* w, int K) {
-    for (int co = 0; co < 64; ++co)
-        for (int k = 0; k < K; ++k) dst[(size_t)k * 64 + co] = w[(size_t)co * K + k];
-}
-
-// initial.*, the 9x9 head: [ci][kh][kw][co], bias, the PReLU's slope
-void pack_head9(const WeightStore& w, float* seg) {
-    pack_k64(seg, w.get("initial.0.weight"), E_HEAD_K);
-    std::memcpy(seg + E_HEAD_K * 64, w.get("initial.0.bias"), 64 * sizeof(float));
-    seg[E_HEAD_K * 64 + 64] = w.get("initial.1.weight")[0];
-}
-
-// One 3x3 64 -> 64 convolution into k_esr_conv's segment layout.
-void pack_conv64(float* seg, const float* w, const float* bias) {
-    for (int co = 0; co < 64; ++co)
-        for (int ci = 0; ci < 64; ++ci)
-            for (int tap = 0; tap < 9; ++tap) seg[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 64 + co] = w[((size_t)co * 64 + ci) * 9 + tap];
-    std::memcpy(seg + E_CONV_BIAS, bias, 64 * sizeof(float));
-}
-
-// Convolution c (0, 1) of the residual block under `blk` with its BatchNorm folded; the first one carries the block's PReLU slope.
-void pack_res_conv(const WeightStore& w, float* seg, const std::string& blk, int c, double eps) {
-    const std::string conv = blk + std::to_string(3 * c) + ".", bn = blk + std::to_string(3 * c + 1) + ".";
-    pack_conv64(seg, w.get(conv + "weight"), w.get(conv + "bias"));
-    pack_bn_fold(w, bn, eps, 64, seg + E_CONV_S, seg + E_CONV_T);
-    seg[E_CONV_SLOPE] = c == 0 ? w.get(blk + "2.weight")[0] : 0.f;
-}
-
-// final.*, the 9x9 tail: [ci][kh][co * 9 + kw], bias
-void pack_tail9(const WeightStore& w, float* seg) {
-    const float* f = w.get("final.weight");
-    for (int co = 0; co < 3; ++co)
-        for (int ci = 0; ci < 64; ++ci)
-            for (int kh = 0; kh < 9; ++kh)
-                for (int kw = 0; kw < 9; ++kw)
-                    seg[((size_t)ci * 9 + kh) * E_TAIL_WROW + co * 9 + kw] = f[(((size_t)co * 64 + ci) * 9 + kh) * 9 + kw];
-    std::memcpy(seg + E_TAIL_W, w.get("final.bias"), 3 * sizeof(float));
-}
-
-// The argument checks cid_esr_forward and cid_sr_forward share.
-int check_image_io(WeightStore* h, const std::string& fn, const void* in, int in_fmt, const void* out, int out_fmt, const void* workspace) {
-    if (!in || !out || !workspace) return h->fail(CID_ERR_INVALID, fn + ": null pointer");
-    if ((in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) || (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC))
-        return h->fail(CID_ERR_INVALID, fn + ": unknown format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
-        return h->fail(CID_ERR_INVALID, fn + ": misaligned fp32 operand");
-    return CID_OK;
-}
-
-struct EsrPlan {
-    size_t x1, mid, cur, total;   // byte offsets of the three C8 tensors; `cur` ends as the tensor the tail reads
-    int ctiles_x, ctiles, ttiles_x, ttiles;
-};
-
-int esr_plan(int N, int H, int W, EsrPlan& p) {
-    if (N < 1 || H < 1 || W < 1) return CID_ERR_SHAPE;
-    if ((long long)H * W > 0x7fffffffLL) return CID_ERR_SHAPE;   // a pixel index inside one image is an int
-    const size_t t = align256((size_t)N * 64 * H * W * sizeof(float));
-    p.x1 = 0;
-    p.mid = t;
-    p.cur = 2 * t;
-    p.total = 3 * t;
-    p.ctiles_x = (W + D_TW - 1) / D_TW;
-    p.ctiles = ((H + DiscGeom<64, 64, 1>::TH - 1) / DiscGeom<64, 64, 1>::TH) * p.ctiles_x;
-    p.ttiles_x = (W + E_TAIL_TW - 1) / E_TAIL_TW;
-    p.ttiles = ((H + E_TAIL_TH - 1) / E_TAIL_TH) * p.ttiles_x;
-    return CID_OK;
-}
-
-}  // namespace
-
-struct cid_esr_s : WeightStore {
-    int R = 0;
-    double eps[2 * kEsrMaxBlocks];
-    size_t blob_floats() const { return kEsrHeadSeg + 2 * (size_t)R * kEsrConvSeg + kEsrTailSeg; }
-};
-
-namespace {
-// The blob from the staged tensors: the head, the 2 R block convolutions, the tail.
-void esr_pack(const cid_esr_s* h, float* b) {
-    pack_head9(*h, b);
-    for (int l = 0; l < 2 * h->R; ++l)
-        pack_res_conv(*h, b + kEsrHeadSeg + (size_t)l * kEsrConvSeg, "residuals." + std::to_string(l / 2) + ".block.", l % 2, h->eps[l]);
-    pack_tail9(*h, b + kEsrHeadSeg + 2 * (size_t)h->R * kEsrConvSeg);
-}
-}  // namespace
-
-extern "C" {
-
-int cid_esr_create(cid_esr_t* out, int num_residuals) {
-    if (!out) return CID_ERR_INVALID;
-    *out = nullptr;
-    if (num_residuals < 0 || num_residuals > kEsrMaxBlocks) return CID_ERR_INVALID;
-    cid_esr_s* h = new (std::nothrow) cid_esr_s();
-    if (!h) return CID_ERR_INVALID;
-    h->init("cid_esr", esr_keys(num_residuals));
-    h->R = num_residuals;
-    std::fill(h->eps, h->eps + 2 * kEsrMaxBlocks, 1e-5);
-    *out = h;
-    return CID_OK;
-}
-
-void cid_esr_destroy(cid_esr_t h) { delete h; }
-
-const char* cid_esr_last_error(cid_esr_t h) { return h ? h->err.c_str() : "null handle"; }
-
-const char* cid_esr_param_key(cid_esr_t h, int i) { return h ? h->key(i) : nullptr; }
-
-int cid_esr_set_weight(cid_esr_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
-}
-
-int cid_esr_set_bn_eps(cid_esr_t h, int block, int which, double eps) {
-    if (!h) return CID_ERR_INVALID;
-    return h->set_bn_eps(block >= 0 && block < h->R && (which == 0 || which == 1) ? &h->eps[2 * block + which] : nullptr, eps);
-}
-
-int cid_esr_missing_weights(cid_esr_t h, int* count) {
-    if (!h || !count) return CID_ERR_INVALID;
-    *count = h->missing();
-    return CID_OK;
-}
-
-size_t cid_esr_packed_weights_bytes(cid_esr_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
-
-int cid_esr_upload_weights(cid_esr_t h, void* device_blob, void* stream) {
-    return h ? h->upload(device_blob, stream, h->blob_floats(), [h](float* b) { esr_pack(h, b); }) : CID_ERR_INVALID;
-}
-
-int cid_esr_workspace_bytes(int N, int H, int W, size_t* bytes) {
-    if (!bytes) return CID_ERR_INVALID;
-    EsrPlan p;
-    const int rc = esr_plan(N, H, W, p);
-    if (rc == CID_OK) *bytes = p.total;
-    return rc;
-}
-
-int cid_esr_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
-    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
-    EsrPlan p;
-    const int rc = esr_plan(N, H, W, p);
-    if (rc != CID_OK) return rc;
-    const std::string s(stage);
-    if (s == "x1") *offset_bytes = p.x1;
-    else if (s == "tail_in") *offset_bytes = p.cur;
-    else return CID_ERR_KEY;
-    *C = 64;
-    *Hs = H;
-    *Ws = W;
-    *channel_block = 8;
-    return CID_OK;
-}
-
-int cid_esr_forward(cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (const int rc = check_image_io(h, "cid_esr_forward", in, in_fmt, out, out_fmt, workspace)) return rc;
-    EsrPlan p;
-    if (esr_plan(N, H, W, p) != CID_OK) return h->fail(CID_ERR_SHAPE, "cid_esr_forward: input shape not accepted (N, H, W >= 1, H*W < 2^31)");
-    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return h->fail(CID_ERR_WORKSPACE, "cid_esr_forward: workspace smaller than cid_esr_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_esr_forward: weights not uploaded");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_esr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
-    char* ws = static_cast<char*>(workspace);
-    float *x1 = reinterpret_cast<float*>(ws + p.x1), *mid = reinterpret_cast<float*>(ws + p.mid), *cur = reinterpret_cast<float*>(ws + p.cur);
-    const float* blob = h->dev_blob;
-    const int R = h->R;
-
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        const unsigned imgs = (unsigned)std::min(kDiscChunk, N - n0);
-        const EsrHeadArgs a{in, x1, R == 0 ? cur : nullptr, blob, H, W, n0};
-        const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), imgs);
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_esr_head<true>, grid, dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_esr_head<false>, grid, dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("head");
-    }
-    for (int i = 0; i < R; ++i)
-        for (int c = 0; c < 2; ++c)
-            for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-                EsrConvArgs a{};
-                a.w = blob + kEsrHeadSeg + (size_t)(2 * i + c) * kEsrConvSeg;
-                a.H = H;
-                a.W = W;
-                a.tiles_x = p.ctiles_x;
-                a.n0 = n0;
-                const dim3 grid((unsigned)p.ctiles, (unsigned)std::min(kDiscChunk, N - n0)), block(D_THREADS);
-                if (c == 0) {   // block.0-2: the block's input (x1 for the first block) -> mid
-                    a.in = i == 0 ? x1 : cur;
-                    a.out = mid;
-                    hipLaunchKernelGGL(k_esr_conv<EPI_PRELU>, grid, block, 0, s, a);
-                } else {        // block.3-4 and the residual sum -> cur (in place from the second block on)
-                    a.in = mid;
-                    a.out = cur;
-                    a.res = i == 0 ? x1 : cur;
-                    a.x1 = x1;
-                    if (i == R - 1) hipLaunchKernelGGL(k_esr_conv<EPI_SUM>, grid, block, 0, s, a);
-                    else hipLaunchKernelGGL(k_esr_conv<EPI_RES>, grid, block, 0, s, a);
-                }
-                if (hipPeekAtLastError() != hipSuccess) return herr("trunk");
-            }
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        const EsrTailArgs a{cur, out, blob + kEsrHeadSeg + 2 * (size_t)R * kEsrConvSeg, H, W, p.ttiles_x, n0};
-        const dim3 grid((unsigned)p.ttiles, (unsigned)std::min(kDiscChunk, N - n0));
-        if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_esr_tail<true>, grid, dim3(E_TAIL_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_esr_tail<false>, grid, dim3(E_TAIL_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("tail");
-    }
-    return CID_OK;
-}
-
-}  // extern "C"
-
-// ---- the server's SRGANGenerator (cid_sr_*): weight staging, BatchNorm folding, workspace plan and launch sequence; kernels in
-// srgan_kernels.h (head, upscale stage, tail) and esrgan_kernels.h (trunk) ----
-namespace {
-
-constexpr int kSrBlocks = 5;
-constexpr size_t kSrUpSeg = (size_t)S_UP_W + 256 + 64;           // weights, bias[256] in packed order, slope (padded to 64)
-
-KeyTable sr_keys(int stages) {
-    KeyTable k;
-    keys_head9(k);
-    for (int i = 0; i < kSrBlocks; ++i) keys_res_block(k, "res_blocks." + std::to_string(i) + ".");
-    k.conv("mid.", 64, 64, 3);
-    for (int u = 0; u < stages; ++u) {
-        k.conv("upscale." + std::to_string(3 * u) + ".", 256, 64, 3);
-        k.tensor("upscale." + std::to_string(3 * u + 2) + ".weight", {1});
-    }
-    k.conv("final.", 3, 64, 9);
-    return k;
-}
-
-int sr_stages(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }
-
-struct SrPlan {
-    int stages;
-    size_t x0, mid, cur, up[3], total;   // byte offsets of the C8 tensors; `mid` ends as the trunk's result, up[k] is stage k's output
-    int ctiles_x, ctiles;                // trunk tiles (16 x 16) of the padded image
-};
-
-int sr_plan(int N, int Hp, int Wp, int scale, SrPlan& p) {
-    p.stages = sr_stages(scale);
-    if (p.stages < 0) return CID_ERR_INVALID;
-    if (N < 1 || Hp < 1 || Wp < 1) return CID_ERR_SHAPE;
-    if ((long long)Hp * Wp > 0x7fffffffLL / ((long long)scale * scale)) return CID_ERR_SHAPE;   // a pixel index inside one image is an int
-    const size_t t = align256((size_t)N * 64 * Hp * Wp * sizeof(float));
-    p.x0 = 0;
-    p.mid = t;
-    p.cur = 2 * t;
-    size_t at = 3 * t;
-    for (int u = 0; u < p.stages; ++u) {
-        p.up[u] = at;
-        at += align256((size_t)N * 64 * ((size_t)Hp << (u + 1)) * ((size_t)Wp << (u + 1)) * sizeof(float));
-    }
-    p.total = at;
-    p.ctiles_x = (Wp + D_TW - 1) / D_TW;
-    p.ctiles = ((Hp + DiscGeom<64, 64, 1>::TH - 1) / DiscGeom<64, 64, 1>::TH) * p.ctiles_x;
-    return CID_OK;
-}
-
-}  // namespace
-
-struct cid_sr_s : WeightStore {
-    int scale = 1, stages = 0;
-    double eps[2 * kSrBlocks];
-    // head, ten block convolutions, mid, the upscale stages, tail
-    size_t up_off(int u) const { return kEsrHeadSeg + (2 * (size_t)kSrBlocks + 1) * kEsrConvSeg + (size_t)u * kSrUpSeg; }
-    size_t tail_off() const { return up_off(stages); }
-    size_t blob_floats() const { return tail_off() + kEsrTailSeg; }
-};
-
-namespace {
-// Upscale stage u: [half][chunk][tap][ci % 8][128 packed columns], the columns in the order of s_up_conv_channel; bias; slope.
-void sr_pack_up(const cid_sr_s* h, float* seg, int u) {
-    const float* w = h->get("upscale." + std::to_string(3 * u) + ".weight");
-    const float* bias = h->get("upscale." + std::to_string(3 * u) + ".bias");
-    for (int J = 0; J < 256; ++J) {
-        const int cc = s_up_conv_channel(J);
-        for (int ci = 0; ci < 64; ++ci)
-            for (int tap = 0; tap < 9; ++tap)
-                seg[(size_t)(J / 128) * (64 * 9 * 128) + ((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * 128 + J % 128] = w[((size_t)cc * 64 + ci) * 9 + tap];
-        seg[S_UP_BIAS + J] = bias[cc];
-    }
-    seg[S_UP_SLOPE] = h->get("upscale." + std::to_string(3 * u + 2) + ".weight")[0];
-}
-
-// The blob from the staged tensors: the head, the ten block convolutions, `mid` with the identity fold (s, t) = (1, 0), the upscale
-// stages, the tail.
-void sr_pack(const cid_sr_s* h, float* b) {
-    pack_head9(*h, b);
-    for (int l = 0; l < 2 * kSrBlocks; ++l)
-        pack_res_conv(*h, b + kEsrHeadSeg + (size_t)l * kEsrConvSeg, "res_blocks." + std::to_string(l / 2) + ".", l % 2, h->eps[l]);
-    float* mid = b + kEsrHeadSeg + 2 * (size_t)kSrBlocks * kEsrConvSeg;   // bias only; fmaf(1, z, 0) = z
-    pack_conv64(mid, h->get("mid.weight"), h->get("mid.bias"));
-    std::fill(mid + E_CONV_S, mid + E_CONV_S + 64, 1.f);
-    for (int u = 0; u < h->stages; ++u) sr_pack_up(h, b + h->up_off(u), u);
-    pack_tail9(*h, b + h->tail_off());
-}
-}  // namespace
-
-extern "C" {
-
-int cid_sr_create(cid_sr_t* out, int scale_factor) {
-    if (!out) return CID_ERR_INVALID;
-    *out = nullptr;
-    if (sr_stages(scale_factor) < 0) return CID_ERR_INVALID;
-    cid_sr_s* h = new (std::nothrow) cid_sr_s();
-    if (!h) return CID_ERR_INVALID;
-    h->scale = scale_factor;
-    h->stages = sr_stages(scale_factor);
-    h->init("cid_sr", sr_keys(h->stages));
-    std::fill(h->eps, h->eps + 2 * kSrBlocks, 1e-5);
-    *out = h;
-    return CID_OK;
-}
-
-void cid_sr_destroy(cid_sr_t h) { delete h; }
-
-const char* cid_sr_last_error(cid_sr_t h) { return h ? h->err.c_str() : "null handle"; }
-
-const char* cid_sr_param_key(cid_sr_t h, int i) { return h ? h->key(i) : nullptr; }
-
-int cid_sr_set_weight(cid_sr_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
-}
-
-int cid_sr_set_bn_eps(cid_sr_t h, int block, int which, double eps) {
-    if (!h) return CID_ERR_INVALID;
-    return h->set_bn_eps(block >= 0 && block < kSrBlocks && (which == 0 || which == 1) ? &h->eps[2 * block + which] : nullptr, eps);
-}
-
-int cid_sr_missing_weights(cid_sr_t h, int* count) {
-    if (!h || !count) return CID_ERR_INVALID;
-    *count = h->missing();
-    return CID_OK;
-}
-
-size_t cid_sr_packed_weights_bytes(cid_sr_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
-
-int cid_sr_upload_weights(cid_sr_t h, void* device_blob, void* stream) {
-    return h ? h->upload(device_blob, stream, h->blob_floats(), [h](float* b) { sr_pack(h, b); }) : CID_ERR_INVALID;
-}
-
-int cid_sr_workspace_bytes(int N, int Hp, int Wp, int scale_factor, size_t* bytes) {
-    if (!bytes) return CID_ERR_INVALID;
-    SrPlan p;
-    const int rc = sr_plan(N, Hp, Wp, scale_factor, p);
-    if (rc == CID_OK) *bytes = p.total;
-    return rc;
-}
-
-int cid_sr_stage_view(const char* stage, int N, int Hp, int Wp, int scale_factor, size_t* offset_bytes, int* C, int* Hs, int* Ws,
-                      int* channel_block) {
-    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
-    SrPlan p;
-    const int rc = sr_plan(N, Hp, Wp, scale_factor, p);
-    if (rc != CID_OK) return rc;
-    const std::string s(stage);
-    int shift = 0;
-    if (s == "x0") *offset_bytes = p.x0;
-    else if (s == "trunk") *offset_bytes = p.mid;
-    else if (s == "up1" && p.stages >= 2) *offset_bytes = p.up[0], shift = 1;
-    else if (s == "up2" && p.stages >= 3) *offset_bytes = p.up[1], shift = 2;
-    else if (s == "tail_in") *offset_bytes = p.stages ? p.up[p.stages - 1] : p.mid, shift = p.stages;
-    else return CID_ERR_KEY;
-    *C = 64;
-    *Hs = Hp << shift;
-    *Ws = Wp << shift;
-    *channel_block = 8;
-    return CID_OK;
-}
-
-int cid_sr_forward(cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, int pad_left, int pad_top,
-                   int pad_right, int pad_bottom, unsigned flags, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (const int rc = check_image_io(h, "cid_sr_forward", in, in_fmt, out, out_fmt, workspace)) return rc;
-    if (flags & ~(unsigned)CID_SR_RAW) return h->fail(CID_ERR_INVALID, "cid_sr_forward: unknown flags");
-    if ((flags & CID_SR_RAW) && out_fmt != CID_FMT_F32_NCHW) return h->fail(CID_ERR_INVALID, "cid_sr_forward: CID_SR_RAW needs an fp32 output");
-    for (const int pad : {pad_left, pad_top, pad_right, pad_bottom})
-        if (pad < 0 || pad > 4096) return h->fail(CID_ERR_INVALID, "cid_sr_forward: pads must lie in [0, 4096]");
-    if (N < 1 || H < 1 || W < 1 || H > 0x7fffffff - 8192 || W > 0x7fffffff - 8192)
-        return h->fail(CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (N, H, W >= 1)");
-    const int Hp = H + pad_top + pad_bottom, Wp = W + pad_left + pad_right;
-    SrPlan p;
-    if (sr_plan(N, Hp, Wp, h->scale, p) != CID_OK)
-        return h->fail(CID_ERR_SHAPE, "cid_sr_forward: input shape not accepted (scale^2 * Hp * Wp < 2^31)");
-    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return h->fail(CID_ERR_WORKSPACE, "cid_sr_forward: workspace smaller than cid_sr_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_sr_forward: weights not uploaded");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_sr_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
-    char* ws = static_cast<char*>(workspace);
-    float *x0 = reinterpret_cast<float*>(ws + p.x0), *mid = reinterpret_cast<float*>(ws + p.mid), *cur = reinterpret_cast<float*>(ws + p.cur);
-    const float* blob = h->dev_blob;
-
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        const SrHeadArgs a{in, x0, blob, H, W, Hp, Wp, pad_left, pad_top, n0};
-        const dim3 grid((unsigned)(((long long)Hp * Wp + D_THREADS - 1) / D_THREADS), (unsigned)std::min(kDiscChunk, N - n0));
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_sr_head<true>, grid, dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_sr_head<false>, grid, dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("head");
-    }
-    // launches 0 .. 9: the blocks' convolutions (x0 or cur -> mid -> cur); launch 10: mid(cur) + x0 -> mid
-    for (int l = 0; l <= 2 * kSrBlocks; ++l)
-        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-            EsrConvArgs a{};
-            a.w = blob + kEsrHeadSeg + (size_t)l * kEsrConvSeg;
-            a.H = Hp;
-            a.W = Wp;
-            a.tiles_x = p.ctiles_x;
-            a.n0 = n0;
-            const dim3 grid((unsigned)p.ctiles, (unsigned)std::min(kDiscChunk, N - n0)), block(D_THREADS);
-            if (l == 2 * kSrBlocks) {
-                a.in = cur;
-                a.out = mid;
-                a.res = x0;
-                hipLaunchKernelGGL(k_esr_conv<EPI_RES>, grid, block, 0, s, a);
-            } else if (l % 2 == 0) {
-                a.in = l == 0 ? x0 : cur;
-                a.out = mid;
-                hipLaunchKernelGGL(k_esr_conv<EPI_PRELU>, grid, block, 0, s, a);
-            } else {
-                a.in = mid;
-                a.out = cur;
-                hipLaunchKernelGGL(k_esr_conv<EPI_BN>, grid, block, 0, s, a);
-            }
-            if (hipPeekAtLastError() != hipSuccess) return herr("trunk");
-        }
-    const float* u = mid;
-    int Hu = Hp, Wu = Wp;
-    for (int k = 0; k < p.stages; ++k) {
-        float* dst = reinterpret_cast<float*>(ws + p.up[k]);
-        const int tiles_x = (Wu + D_TW - 1) / D_TW;
-        const int tiles = ((Hu + DiscGeom<64, 128, 1>::TH - 1) / DiscGeom<64, 128, 1>::TH) * tiles_x;
-        for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-            const SrUpArgs a{u, dst, blob + h->up_off(k), Hu, Wu, tiles_x, n0};
-            const dim3 grid((unsigned)tiles, (unsigned)std::min(kDiscChunk, N - n0), 2);
-            hipLaunchKernelGGL(k_sr_up, grid, dim3(D_THREADS), 0, s, a);
-            if (hipPeekAtLastError() != hipSuccess) return herr("upscale");
-        }
-        u = dst;
-        Hu *= 2;
-        Wu *= 2;
-    }
-    const int ttiles_x = (Wu + E_TAIL_TW - 1) / E_TAIL_TW;
-    const int ttiles = ((Hu + E_TAIL_TH - 1) / E_TAIL_TH) * ttiles_x;
-    for (int n0 = 0; n0 < N; n0 += kDiscChunk) {
-        const EsrTailArgs a{u, out, blob + h->tail_off(), Hu, Wu, ttiles_x, n0};
-        const dim3 grid((unsigned)ttiles, (unsigned)std::min(kDiscChunk, N - n0));
-        if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_sr_tail<SR_OUT_U8>, grid, dim3(E_TAIL_THREADS), 0, s, a);
-        else if (flags & CID_SR_RAW) hipLaunchKernelGGL(k_sr_tail<SR_OUT_RAW>, grid, dim3(E_TAIL_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_sr_tail<SR_OUT_F32>, grid, dim3(E_TAIL_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("tail");
-    }
-    return CID_OK;
-}
-
-}  // extern "C"
-
-// ---- the server's CGANGenerator (cid_cg_*): weight staging, BatchNorm folding, workspace plan and launch sequence; kernels in
-// cgan_kernels.h ----
-namespace {
-
-constexpr int kCgMaxClasses = 1 << 20;
-constexpr int kCgMaxN = 1 << 18;          // every grid and every int index of the kernels stays below 2^31
-const int kCgBn[4] = {0, 3, 6, 9};        // model.<i> of the four BatchNorms
-const int kCgUp[3] = {2, 5, 8};           // model.<i> of the three transposed convolutions
-const int kCgCin[3] = {128, 128, 64}, kCgCout[3] = {128, 64, 32};
-
-std::string cg_layer(int i) { return "model." + std::to_string(i) + "."; }
-
-KeyTable cg_keys(int n_classes) {
-    KeyTable k;
-    k.tensor("label_emb.weight", {n_classes, CG_LATENT});
-    k.tensor("l1.weight", {CG_FEAT, 2 * CG_LATENT});
-    k.tensor("l1.bias", {CG_FEAT});
-    k.batchnorm(cg_layer(kCgBn[0]), 128);
-    for (int u = 0; u < 3; ++u) {
-        k.tensor(cg_layer(kCgUp[u]) + "weight", {kCgCin[u], kCgCout[u], 4, 4});
-        k.tensor(cg_layer(kCgUp[u]) + "bias", {kCgCout[u]});
-        k.batchnorm(cg_layer(kCgBn[u + 1]), kCgCout[u]);
-    }
-    k.conv("model.11.", 3, 32, 3);
-    return k;
-}
-
-size_t cg_align64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-
-struct CgPlan {
-    size_t l1, t[3], total;   // byte offsets of the C8 tensors: l1's [N,128,8,8] and the three stages' outputs
-};
-
-int cg_plan(int N, CgPlan& p) {
-    if (N < 1 || N > kCgMaxN) return CID_ERR_SHAPE;
-    size_t at = 0;
-    p.l1 = at;
-    at += align256((size_t)N * CG_FEAT * sizeof(float));
-    for (int u = 0; u < 3; ++u) {
-        p.t[u] = at;
-        at += align256((size_t)N * kCgCout[u] * (256u << (2 * u)) * sizeof(float));
-    }
-    p.total = at;
-    return CID_OK;
-}
-
-}  // namespace
-
-struct cid_cg_s : WeightStore {
-    int n_classes = 10;
-    double eps[4];
-    // the linear, the three stages (weights, bias, s, t), the tail, the embedding table
-    size_t up_off(int u) const {
-        size_t at = cg_align64(CG_LIN_SEG);
-        for (int i = 0; i < u; ++i) at += cg_align64((size_t)16 * kCgCin[i] * kCgCout[i] + 3 * kCgCout[i]);
-        return at;
-    }
-    size_t tail_off() const { return up_off(3); }
-    size_t emb_off() const { return tail_off() + CG_TAIL_SEG; }
-    size_t blob_floats() const { return emb_off() + cg_align64((size_t)n_classes * CG_LATENT); }
-};
-
-namespace {
-// The blob from the staged tensors: the kernels' weight layouts, each BatchNorm folded (pack_bn_fold).
-void cg_pack(const cid_cg_s* h, float* b) {
-    const auto fold = [&](int which, int C, float* s_out, float* t_out) { pack_bn_fold(*h, cg_layer(kCgBn[which]), h->eps[which], C, s_out, t_out); };
-    {   // linear: [tile][lane][52]: lane (l16, kq) holds row l16's weights of k = 4 s + kq
-        const float *w = h->get("l1.weight"), *bias = h->get("l1.bias");
-        for (int tile = 0; tile < CG_LIN_TILES; ++tile)
-            for (int row = 0; row < 16; ++row) {
-                const int j = cg_lin_feature(tile, row);
-                for (int kq = 0; kq < 4; ++kq)
-                    for (int s = 0; s < CG_LIN_STEPS; ++s)
-                        b[((size_t)tile * 64 + kq * 16 + row) * CG_LIN_LSTR + s] = w[(size_t)j * (2 * CG_LATENT) + 4 * s + kq];
-                b[CG_LIN_BIAS + tile * 16 + row] = bias[j];
-            }
-        fold(0, 128, b + CG_LIN_S, b + CG_LIN_T);
-    }
-    for (int u = 0; u < 3; ++u) {
-        float* seg = b + h->up_off(u);
-        const int CI = kCgCin[u], CO = kCgCout[u];
-        const float* w = h->get(cg_layer(kCgUp[u]) + "weight");
-        for (int ci = 0; ci < CI; ++ci)
-            for (int co = 0; co < CO; ++co)
-                for (int ky = 0; ky < 4; ++ky)
-                    for (int kx = 0; kx < 4; ++kx) seg[cg_up_windex(CO, ci, co, ky, kx)] = w[(((size_t)ci * CO + co) * 4 + ky) * 4 + kx];
-        float* tail = seg + (size_t)16 * CI * CO;
-        std::memcpy(tail, h->get(cg_layer(kCgUp[u]) + "bias"), CO * sizeof(float));
-        fold(u + 1, CO, tail + CO, tail + 2 * CO);
-    }
-    {   // tail: [ci][tap][co], then the biases
-        float* seg = b + h->tail_off();
-        const float* w = h->get("model.11.weight");
-        for (int co = 0; co < 3; ++co)
-            for (int ci = 0; ci < 32; ++ci)
-                for (int tap = 0; tap < 9; ++tap) seg[(ci * 9 + tap) * 3 + co] = w[((size_t)co * 32 + ci) * 9 + tap];
-        std::memcpy(seg + CG_TAIL_W, h->get("model.11.bias"), 3 * sizeof(float));
-    }
-    std::memcpy(b + h->emb_off(), h->get("label_emb.weight"), (size_t)h->n_classes * CG_LATENT * sizeof(float));
-}
-}  // namespace
-
-extern "C" {
-
-int cid_cg_create(cid_cg_t* out, int n_classes) {
-    if (!out) return CID_ERR_INVALID;
-    *out = nullptr;
-    if (n_classes < 1 || n_classes > kCgMaxClasses) return CID_ERR_INVALID;
-    cid_cg_s* h = new (std::nothrow) cid_cg_s();
-    if (!h) return CID_ERR_INVALID;
-    h->init("cid_cg", cg_keys(n_classes));
-    h->n_classes = n_classes;
-    std::fill(h->eps, h->eps + 4, 1e-5);
-    *out = h;
-    return CID_OK;
-}
-
-void cid_cg_destroy(cid_cg_t h) { delete h; }
-
-const char* cid_cg_last_error(cid_cg_t h) { return h ? h->err.c_str() : "null handle"; }
-
-const char* cid_cg_param_key(cid_cg_t h, int i) { return h ? h->key(i) : nullptr; }
-
-int cid_cg_set_weight(cid_cg_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
-}
-
-int cid_cg_set_bn_eps(cid_cg_t h, int which, double eps) {
-    return h ? h->set_bn_eps(which >= 0 && which <= 3 ? &h->eps[which] : nullptr, eps) : CID_ERR_INVALID;
-}
-
-int cid_cg_missing_weights(cid_cg_t h, int* count) {
-    if (!h || !count) return CID_ERR_INVALID;
-    *count = h->missing();
-    return CID_OK;
-}
-
-size_t cid_cg_packed_weights_bytes(cid_cg_t h) { return h ? h->blob_floats() * sizeof(float) : 0; }
-
-int cid_cg_upload_weights(cid_cg_t h, void* device_blob, void* stream) {
-    return h ? h->upload(device_blob, stream, h->blob_floats(), [h](float* b) { cg_pack(h, b); }) : CID_ERR_INVALID;
-}
-
-int cid_cg_workspace_bytes(int N, size_t* bytes) {
-    if (!bytes) return CID_ERR_INVALID;
-    CgPlan p;
-    const int rc = cg_plan(N, p);
-    if (rc == CID_OK) *bytes = p.total;
-    return rc;
-}
-
-int cid_cg_stage_view(const char* stage, int N, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
-    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
-    CgPlan p;
-    const int rc = cg_plan(N, p);
-    if (rc != CID_OK) return rc;
-    const std::string s(stage);
-    int u = -1;
-    if (s == "l1") *offset_bytes = p.l1;
-    else if (s == "t1") u = 0;
-    else if (s == "t2") u = 1;
-    else if (s == "t3") u = 2;
-    else return CID_ERR_KEY;
-    if (u >= 0) *offset_bytes = p.t[u];
-    *C = u < 0 ? 128 : kCgCout[u];
-    *Hs = *Ws = u < 0 ? 8 : 16 << u;
-    *channel_block = 8;
-    return CID_OK;
-}
-
-int cid_cg_latent(uint64_t seed, uint64_t first_index, int N, float* z_out, void* stream) {
-    if (!z_out || ((uintptr_t)z_out & 3)) return CID_ERR_INVALID;
-    if (N < 1 || N > kCgMaxN) return CID_ERR_SHAPE;
-    const CgLatentArgs a{z_out, (long long)N * CG_LATENT, seed + first_index};
-    hipLaunchKernelGGL(k_cg_latent, dim3((unsigned)((a.count + D_THREADS - 1) / D_THREADS)), dim3(D_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    return hipPeekAtLastError() == hipSuccess ? CID_OK : CID_ERR_HIP;
-}
-
-int cid_cg_forward(cid_cg_t h, const float* z, const int64_t* labels, void* out, int out_fmt, int N, unsigned flags, void* workspace,
-                   size_t workspace_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (!z || !labels || !out || !workspace) return h->fail(CID_ERR_INVALID, "cid_cg_forward: null pointer");
-    if (out_fmt != CID_FMT_F32_NCHW && out_fmt != CID_FMT_U8_NHWC) return h->fail(CID_ERR_INVALID, "cid_cg_forward: unknown format");
-    if (((uintptr_t)z & 3) || ((uintptr_t)labels & 7) || (out_fmt == CID_FMT_F32_NCHW && ((uintptr_t)out & 3)))
-        return h->fail(CID_ERR_INVALID, "cid_cg_forward: misaligned operand");
-    if (flags & ~(unsigned)CID_CG_RAW) return h->fail(CID_ERR_INVALID, "cid_cg_forward: unknown flags");
-    if ((flags & CID_CG_RAW) && out_fmt != CID_FMT_F32_NCHW) return h->fail(CID_ERR_INVALID, "cid_cg_forward: CID_CG_RAW needs an fp32 output");
-    CgPlan p;
-    if (cg_plan(N, p) != CID_OK) return h->fail(CID_ERR_SHAPE, "cid_cg_forward: batch size not accepted (1 <= N <= 2^18)");
-    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return h->fail(CID_ERR_WORKSPACE, "cid_cg_forward: workspace smaller than cid_cg_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_cg_forward: weights not uploaded");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_cg_forward: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
-    char* ws = static_cast<char*>(workspace);
-    const float* blob = h->dev_blob;
-    float* l1 = reinterpret_cast<float*>(ws + p.l1);
-    float* t[3] = {reinterpret_cast<float*>(ws + p.t[0]), reinterpret_cast<float*>(ws + p.t[1]), reinterpret_cast<float*>(ws + p.t[2])};
-
-    {
-        const CgLinearArgs a{z, reinterpret_cast<const long long*>(labels), l1, blob, blob + h->emb_off(), N, h->n_classes};
-        hipLaunchKernelGGL(k_cg_linear, dim3(CG_LIN_TILES), dim3(64), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("linear");
-    }
-    {
-        const CgUpArgs a{l1, t[0], blob + h->up_off(0)};
-        hipLaunchKernelGGL((k_cg_up<128, 128, 8>), dim3((unsigned)N * CgUpGeom<128, 128, 8>::TILES), dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("up 1");
-    }
-    {
-        const CgUpArgs a{t[0], t[1], blob + h->up_off(1)};
-        hipLaunchKernelGGL((k_cg_up<128, 64, 16>), dim3((unsigned)N * CgUpGeom<128, 64, 16>::TILES), dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("up 2");
-    }
-    {
-        const CgUpArgs a{t[1], t[2], blob + h->up_off(2)};
-        hipLaunchKernelGGL((k_cg_up<64, 32, 32>), dim3((unsigned)N * CgUpGeom<64, 32, 32>::TILES), dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("up 3");
-    }
-    {
-        const CgTailArgs a{t[2], out, blob + h->tail_off(), (long long)N * 4096};
-        const dim3 grid((unsigned)(a.count / D_THREADS));
-        if (out_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_cg_tail<CG_OUT_U8>, grid, dim3(D_THREADS), 0, s, a);
-        else if (flags & CID_CG_RAW) hipLaunchKernelGGL(k_cg_tail<CG_OUT_RAW>, grid, dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_cg_tail<CG_OUT_F32>, grid, dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return herr("tail");
-    }
-    return CID_OK;
-}
-
-}  // extern "C"
-
-// ---- LPIPS(net='alex') (cid_lpips_*): weight staging, workspace plan and launch sequence; kernels in lpips_kernels.h ----
-namespace {
-
-constexpr int kLpMaxN = 1 << 20;
-constexpr int kLpMinSide = 31;
-const int kLpSlice[5] = {0, 3, 6, 8, 10};            // net.slice<k+1>.<i>
-const int kLpCin[5] = {3, 64, 192, 384, 256}, kLpKs[5] = {11, 5, 3, 3, 3};
-
-// scaling_layer.* ahead of a tower's convolutions, lin<k>.* behind them: the layout LPIPS and the VGG tower share
-void keys_scaling(KeyTable& k) {
-    k.tensor("scaling_layer.shift", {1, 3, 1, 1});
-    k.tensor("scaling_layer.scale", {1, 3, 1, 1});
-}
-std::string lp_lin_name(int l) { return "lin" + std::to_string(l) + ".model.1.weight"; }
-std::string lp_conv_name(int l) { return "net.slice" + std::to_string(l + 1) + "." + std::to_string(kLpSlice[l]) + "."; }
-
-const KeyTable& lp_key_table() {
-    static const KeyTable table = [] {
-        KeyTable k;
-        keys_scaling(k);
-        for (int l = 0; l < LP_TAPS; ++l) k.conv(lp_conv_name(l), lp_channels(l), kLpCin[l], kLpKs[l]);
-        for (int l = 0; l < LP_TAPS; ++l) k.tensor(lp_lin_name(l), {1, lp_channels(l), 1, 1});
-        return k;
-    }();
-    return table;
-}
-
-// blob segments (floats, 64-float aligned): the head, relu2 ... relu5 (packed weights then biases), the five lin vectors
-size_t lp_conv_off(int l) {   // l = 1 .. 4; l = 5: the lin segment
-    size_t at = LP_HEAD_SEG;
-    for (int i = 1; i < l; ++i) at += cg_align64((size_t)lp_channels(i) * kLpCin[i] * kLpKs[i] * kLpKs[i] + lp_channels(i));
-    return at;
-}
-size_t lp_blob_floats() { return lp_conv_off(5) + LP_LIN_SEG; }
-
-struct LpPlan {
-    int Hs[LP_TAPS], Ws[LP_TAPS];   // sizes of relu1 ... relu5
-    size_t tap[LP_TAPS], total;     // byte offsets of the C8 tensors (2 N images each)
-};
-
-int lp_plan(int N, int H, int W, LpPlan& p) {
-    if (N < 1 || N > kLpMaxN || H < kLpMinSide || W < kLpMinSide || (long long)H * W >= (1ll << 31)) return CID_ERR_SHAPE;
-    p.Hs[0] = (H - 7) / 4 + 1, p.Ws[0] = (W - 7) / 4 + 1;
-    p.Hs[1] = (p.Hs[0] - 3) / 2 + 1, p.Ws[1] = (p.Ws[0] - 3) / 2 + 1;
-    p.Hs[2] = (p.Hs[1] - 3) / 2 + 1, p.Ws[2] = (p.Ws[1] - 3) / 2 + 1;
-    p.Hs[3] = p.Hs[4] = p.Hs[2], p.Ws[3] = p.Ws[4] = p.Ws[2];
-    // what a workgroup of the GEMM kernel stages must fit its LDS planes
-    if (lp_stage_bound(p.Hs[1], p.Ws[1], 2) > LP_XPOS || lp_stage_bound(p.Hs[2], p.Ws[2], 1) > LP_XPOS) return CID_ERR_SHAPE;
-    size_t at = 0;
-    for (int k = 0; k < LP_TAPS; ++k) {
-        p.tap[k] = at;
-        at += align256((size_t)2 * N * lp_channels(k) * p.Hs[k] * p.Ws[k] * sizeof(float));
-    }
-    p.total = at;
-    return CID_OK;
-}
-
-}  // namespace
-
-struct cid_lpips_s : WeightStore {};
-
-namespace {
-// A tower's head segment: [k][64], bias, and (scaled) the scaling layer's shift and scale
-void lp_pack_head(const WeightStore& w, float* b, const std::string& conv, int K, int bias_at, int ss_at, bool scaled) {
-    pack_k64(b, w.get(conv + "weight"), K);
-    std::memcpy(b + bias_at, w.get(conv + "bias"), 64 * sizeof(float));
-    if (!scaled) return;
-    std::memcpy(b + ss_at, w.get("scaling_layer.shift"), 3 * sizeof(float));
-    std::memcpy(b + ss_at + 4, w.get("scaling_layer.scale"), 3 * sizeof(float));
-}
-
-void lp_pack(const cid_lpips_s* h, float* b) {
-    lp_pack_head(*h, b, lp_conv_name(0), LP_HEAD_K, LP_HEAD_B, LP_HEAD_SS, true);
-    for (int l = 1; l < LP_TAPS; ++l) {
-        float* seg = b + lp_conv_off(l);
-        const int CO = lp_channels(l), CI = kLpCin[l], KS = kLpKs[l];
-        const float* w = h->get(lp_conv_name(l) + "weight");
-        for (int co = 0; co < CO; ++co)
-            for (int ci = 0; ci < CI; ++ci)
-                for (int kh = 0; kh < KS; ++kh)
-                    for (int kw = 0; kw < KS; ++kw) seg[lp_conv_windex(CI, KS, co, ci, kh, kw)] = w[(((size_t)co * CI + ci) * KS + kh) * KS + kw];
-        std::memcpy(seg + (size_t)CO * CI * KS * KS, h->get(lp_conv_name(l) + "bias"), CO * sizeof(float));
-    }
-    for (int l = 0; l < LP_TAPS; ++l) std::memcpy(b + lp_conv_off(5) + lp_lin_off(l), h->get(lp_lin_name(l)), lp_channels(l) * sizeof(float));
-}
-
-template <int CIN, int COUT, int KS, bool POOL>
-void lp_conv_launch(const float* in, float* out, const float* w, int N, int Hs, int Ws, int Ho, int Wo, hipStream_t s) {
-    const LpConvArgs a{in, out, w, (long long)2 * N * Ho * Wo, Hs, Ws, Ho, Wo};
-    const dim3 grid((unsigned)((a.total + LP_NT - 1) / LP_NT), COUT / LP_MT);
-    hipLaunchKernelGGL((k_lpips_conv<CIN, COUT, KS, POOL>), grid, dim3(D_THREADS), 0, s, a);
-}
-}  // namespace
-
-extern "C" {
-
-int cid_lpips_create(cid_lpips_t* out) {
-    if (!out) return CID_ERR_INVALID;
-    *out = nullptr;
-    cid_lpips_s* h = new (std::nothrow) cid_lpips_s();
-    if (!h) return CID_ERR_INVALID;
-    h->init("cid_lpips", lp_key_table());
-    *out = h;
-    return CID_OK;
-}
-
-void cid_lpips_destroy(cid_lpips_t h) { delete h; }
-
-const char* cid_lpips_last_error(cid_lpips_t h) { return h ? h->err.c_str() : "null handle"; }
-
-const char* cid_lpips_param_key(cid_lpips_t h, int i) { return h ? h->key(i) : nullptr; }
-
-int cid_lpips_set_weight(cid_lpips_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
-}
-
-int cid_lpips_missing_weights(cid_lpips_t h, int* count) {
-    if (!h || !count) return CID_ERR_INVALID;
-    *count = h->missing();
-    return CID_OK;
-}
-
-size_t cid_lpips_packed_weights_bytes(cid_lpips_t h) { return h ? lp_blob_floats() * sizeof(float) : 0; }
-
-int cid_lpips_upload_weights(cid_lpips_t h, void* device_blob, void* stream) {
-    return h ? h->upload(device_blob, stream, lp_blob_floats(), [h](float* b) { lp_pack(h, b); }) : CID_ERR_INVALID;
-}
-
-int cid_lpips_workspace_bytes(int N, int H, int W, size_t* bytes) {
-    if (!bytes) return CID_ERR_INVALID;
-    LpPlan p;
-    const int rc = lp_plan(N, H, W, p);
-    if (rc == CID_OK) *bytes = p.total;
-    return rc;
-}
-
-int cid_lpips_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
-    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
-    LpPlan p;
-    const int rc = lp_plan(N, H, W, p);
-    if (rc != CID_OK) return rc;
-    const std::string s(stage);
-    if (s.size() != 5 || s.compare(0, 4, "relu") != 0 || s[4] < '1' || s[4] > '5') return CID_ERR_KEY;
-    const int k = s[4] - '1';
-    *offset_bytes = p.tap[k];
-    *C = lp_channels(k);
-    *Hs = p.Hs[k];
-    *Ws = p.Ws[k];
-    *channel_block = 8;
-    return CID_OK;
-}
-
-int cid_lpips(cid_lpips_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
-              double* layers, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (!a || !b || !out || !workspace) return h->fail(CID_ERR_INVALID, "cid_lpips: null pointer");
-    if ((fmt_a != CID_FMT_F32_NCHW && fmt_a != CID_FMT_U8_NHWC) || (fmt_b != CID_FMT_F32_NCHW && fmt_b != CID_FMT_U8_NHWC))
-        return h->fail(CID_ERR_INVALID, "cid_lpips: unknown format");
-    if ((fmt_a == CID_FMT_F32_NCHW && ((uintptr_t)a & 3)) || (fmt_b == CID_FMT_F32_NCHW && ((uintptr_t)b & 3)) || ((uintptr_t)out & 7) ||
-        ((uintptr_t)layers & 7))
-        return h->fail(CID_ERR_INVALID, "cid_lpips: misaligned operand");
-    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return h->fail(CID_ERR_INVALID, "cid_lpips: unknown flags");
-    LpPlan p;
-    if (lp_plan(N, H, W, p) != CID_OK)
-        return h->fail(CID_ERR_SHAPE, "cid_lpips: shape not accepted (1 <= N <= 2^20, H and W >= 31 and within the kernels' tile limit)");
-    if (workspace_bytes < p.total || ((uintptr_t)workspace & 255))
-        return h->fail(CID_ERR_WORKSPACE, "cid_lpips: workspace smaller than cid_lpips_workspace_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return h->fail(CID_ERR_STATE, "cid_lpips: weights not uploaded");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
-    char* ws = static_cast<char*>(workspace);
-    const float* blob = h->dev_blob;
-    float* t[LP_TAPS];
-    for (int k = 0; k < LP_TAPS; ++k) t[k] = reinterpret_cast<float*>(ws + p.tap[k]);
-
-    for (long long n0 = 0; n0 < 2ll * N; n0 += kDiscChunk) {
-        const LpHeadArgs ha{a, b, t[0], blob, H, W, p.Hs[0], p.Ws[0], N, (int)n0, fmt_a == CID_FMT_U8_NHWC, fmt_b == CID_FMT_U8_NHWC,
-                            (flags & CID_LPIPS_UNIT_VIEW) != 0};
-        const dim3 grid((unsigned)((p.Hs[0] * p.Ws[0] + LP_HEAD_PIX - 1) / LP_HEAD_PIX), (unsigned)std::min<long long>(kDiscChunk, 2ll * N - n0));
-        hipLaunchKernelGGL(k_lpips_head, grid, dim3(LP_HEAD_PIX), 0, s, ha);
-        if (hipPeekAtLastError() != hipSuccess) return herr("head");
-    }
-    lp_conv_launch<64, 192, 5, true>(t[0], t[1], blob + lp_conv_off(1), N, p.Hs[0], p.Ws[0], p.Hs[1], p.Ws[1], s);
-    if (hipPeekAtLastError() != hipSuccess) return herr("relu2");
-    lp_conv_launch<192, 384, 3, true>(t[1], t[2], blob + lp_conv_off(2), N, p.Hs[1], p.Ws[1], p.Hs[2], p.Ws[2], s);
-    if (hipPeekAtLastError() != hipSuccess) return herr("relu3");
-    lp_conv_launch<384, 256, 3, false>(t[2], t[3], blob + lp_conv_off(3), N, p.Hs[2], p.Ws[2], p.Hs[3], p.Ws[3], s);
-    if (hipPeekAtLastError() != hipSuccess) return herr("relu4");
-    lp_conv_launch<256, 256, 3, false>(t[3], t[4], blob + lp_conv_off(4), N, p.Hs[3], p.Ws[3], p.Hs[4], p.Ws[4], s);
-    if (hipPeekAtLastError() != hipSuccess) return herr("relu5");
-    {
-        LpDistArgs da;
-        for (int k = 0; k < LP_TAPS; ++k) {
-            da.tap[k] = t[k];
-            da.P[k] = p.Hs[k] * p.Ws[k];
-        }
-        da.lin = blob + lp_conv_off(5);
-        da.out = out;
-        da.layers = layers;
-        da.N = N;
-        hipLaunchKernelGGL(k_lpips_dist<LpAlexTaps>, dim3((unsigned)N), dim3(D_THREADS), 0, s, da);
-        if (hipPeekAtLastError() != hipSuccess) return herr("distance");
-    }
-    return CID_OK;
-}
-
-}  // extern "C"
-
-// ---- VGG16 features (cid_vgg_*): LPIPS(net='vgg') and the content loss; kernels in vgg_kernels.h and lpips_kernels.h ----
-namespace {
-
-static_assert(VG_MAX_SIDE == CID_VGG_MAX_SIDE, "vgg_kernels.h and cid.h agree on the largest side");
-constexpr int kVgMinSide[2] = {16, 4};               // by form: CID_VGG_LPIPS, CID_VGG_CONTENT
-const int kVgIdx[VG_CONVS] = {0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28};   // torchvision's features indices
-const int kVgSlice[VG_CONVS] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5};
-const int kVgCin[VG_CONVS] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
-const int kVgCout[VG_CONVS] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
-constexpr int kVgContentConvs = 7;                   // slice1 ... slice3
-
-std::string vg_conv_name(int l) { return "net.slice" + std::to_string(kVgSlice[l]) + "." + std::to_string(kVgIdx[l]) + "."; }
-
-const KeyTable& vg_key_table() {
-    static const KeyTable table = [] {
-        KeyTable k;
-        keys_scaling(k);
-        for (int l = 0; l < VG_CONVS; ++l) k.conv(vg_conv_name(l), kVgCout[l], kVgCin[l], 3);
-        for (int l = 0; l < LP_TAPS; ++l) k.tensor(lp_lin_name(l), {1, VgTaps::channels(l), 1, 1});
-        return k;
-    }();
-    return table;
-}
-
-// blob segments (floats, 64-float aligned): the head, convolutions 1 ... 12 (packed weights then biases), the five lin vectors
-size_t vg_conv_off(int l) {   // l = 1 .. 12; l = 13: the lin segment
-    size_t at = VG_HEAD_SEG;
-    for (int i = 1; i < l; ++i) at += cg_align64((size_t)kVgCout[i] * kVgCin[i] * 9 + kVgCout[i]);
-    return at;
-}
-size_t vg_blob_floats() { return vg_conv_off(VG_CONVS) + VG_LIN_SEG; }
-
-struct VgPlan {
-    int Hs[LP_TAPS], Ws[LP_TAPS];    // sizes of relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
-    size_t s0, s1;                   // byte offsets of the two scratch tensors (the convolutions between the taps)
-    size_t tap[LP_TAPS], total;      // byte offsets of the taps (C8, 2 N images each); the content form has the first three
-};
-
-int vg_plan(int what, int N, int H, int W, VgPlan& p) {
-    if (what != CID_VGG_LPIPS && what != CID_VGG_CONTENT) return CID_ERR_INVALID;
-    if (N < 1 || N > kLpMaxN || H < kVgMinSide[what] || W < kVgMinSide[what] || H > VG_MAX_SIDE || W > VG_MAX_SIDE) return CID_ERR_SHAPE;
-    // the head's grid.x runs over the whole batch's pixels
-    if (((long long)2 * N * H * W + VG_HEAD_PIX - 1) / VG_HEAD_PIX > 0x7fffffffll) return CID_ERR_SHAPE;
-    const int taps = what == CID_VGG_LPIPS ? LP_TAPS : 3;
-    p.Hs[0] = H, p.Ws[0] = W;
-    for (int k = 1; k < LP_TAPS; ++k) p.Hs[k] = p.Hs[k - 1] / 2, p.Ws[k] = p.Ws[k - 1] / 2;
-    for (int k = 0; k < taps; ++k)
-        if (vg_stage_bound(p.Hs[k], p.Ws[k]) > (k < 1 ? VG_XPOS_WIDE : LP_XPOS)) return CID_ERR_SHAPE;   // cannot happen up to VG_MAX_SIDE
-    size_t at = 0;
-    p.s0 = at;
-    at += align256((size_t)2 * N * 64 * H * W * sizeof(float));
-    p.s1 = at;
-    at += align256((size_t)2 * N * 256 * p.Hs[2] * p.Ws[2] * sizeof(float));
-    for (int k = 0; k < LP_TAPS; ++k) {
-        p.tap[k] = at;
-        if (k < taps) at += align256((size_t)2 * N * VgTaps::channels(k) * p.Hs[k] * p.Ws[k] * sizeof(float));
-    }
-    p.total = at;
-    return CID_OK;
-}
-
-// The per-call arena of cid_vgg_content_loss_saved / cid_vgg_content_backward: the seven activations of both towers (2 N images),
-// then the seven gradient tensors of tower a (N images), in backward order.
-constexpr int kVgSaved = 7;
-const char* const kVgActName[kVgSaved] = {"relu1_1", "relu1_2", "relu2_1", "relu2_2", "relu3_1", "relu3_2", "relu3_3"};
-const int kVgActLevel[kVgSaved] = {0, 0, 1, 1, 2, 2, 2};
-const char* const kVgGradName[kVgSaved] = {"grad3_3", "grad3_2", "grad3_1", "gradpool2", "grad2_1", "gradpool1", "grad1_1"};
-const int kVgGradLevel[kVgSaved] = {2, 2, 2, 2, 1, 1, 0};       // the map size: Hs[level] x Ws[level]
-const int kVgGradC[kVgSaved] = {256, 256, 256, 128, 128, 64, 64};
-
-struct VgSavedPlan {
-    int Hs[3], Ws[3];
-    size_t act[kVgSaved], grad[kVgSaved], total;
-};
-
-int vg_saved_plan(int N, int H, int W, VgSavedPlan& p) {
-    VgPlan f;
-    const int rc = vg_plan(CID_VGG_CONTENT, N, H, W, f);
-    if (rc != CID_OK) return rc;
-    for (int k = 0; k < 3; ++k) p.Hs[k] = f.Hs[k], p.Ws[k] = f.Ws[k];
-    size_t at = 0;
-    for (int i = 0; i < kVgSaved; ++i) {
-        const int k = kVgActLevel[i];
-        p.act[i] = at;
-        at += align256((size_t)2 * N * VgTaps::channels(k) * p.Hs[k] * p.Ws[k] * sizeof(float));
-    }
-    for (int i = 0; i < kVgSaved; ++i) {
-        const int k = kVgGradLevel[i];
-        p.grad[i] = at;
-        at += align256((size_t)N * kVgGradC[i] * p.Hs[k] * p.Ws[k] * sizeof(float));
-    }
-    p.total = at;
-    return CID_OK;
-}
-
-// the backward blob (floats): the head's segment, then the data-gradient weights of convolutions 1 ... 6
-size_t vg_bwd_off(int l) {   // l = 1 .. 6; l = 7: the end
-    size_t at = VG_HEADB_SEG;
-    for (int i = 1; i < l; ++i) at += (size_t)kVgCout[i] * kVgCin[i] * 9;
-    return at;
-}
-size_t vg_bwd_floats() { return vg_bwd_off(kVgContentConvs); }
-
-}  // namespace
-
-struct cid_vgg_s : WeightStore {
-    bool full = false;   // the uploaded blob holds all 33 tensors (else slice1 ... slice3 only)
-    std::vector<float> bwd_staging;      // the backward blob's staging copy
-    const float* dev_bwd = nullptr;      // the uploaded backward blob; dropped when the forward blob is uploaded again
-};
-
-namespace {
-void vg_pack(const cid_vgg_s* h, float* b, bool full) {
-    lp_pack_head(*h, b, vg_conv_name(0), VG_HEAD_K, VG_HEAD_B, VG_HEAD_SS, full);
-    for (int l = 1; l < (full ? VG_CONVS : kVgContentConvs); ++l) {
-        float* seg = b + vg_conv_off(l);
-        const int CO = kVgCout[l], CI = kVgCin[l];
-        const float* w = h->get(vg_conv_name(l) + "weight");
-        for (int co = 0; co < CO; ++co)
-            for (int ci = 0; ci < CI; ++ci)
-                for (int t = 0; t < 9; ++t) seg[lp_conv_windex(CI, 3, co, ci, t / 3, t % 3)] = w[((size_t)co * CI + ci) * 9 + t];
-        std::memcpy(seg + (size_t)CO * CI * 9, h->get(vg_conv_name(l) + "bias"), CO * sizeof(float));
-    }
-    if (full)
-        for (int l = 0; l < LP_TAPS; ++l)
-            std::memcpy(b + vg_conv_off(VG_CONVS) + VgTaps::lin_off(l), h->get(lp_lin_name(l)), VgTaps::channels(l) * sizeof(float));
-}
-
-// The data gradient of a 3x3, pad-1, stride-1 convolution is a 3x3 convolution with the channel axes swapped and the taps flipped:
-// w'[ci][co][kh][kw] = w[co][ci][2 - kh][2 - kw], packed with lp_conv_windex like a forward convolution of co -> ci channels.
-void vg_pack_backward(const cid_vgg_s* h, float* b) {
-    const float* w0 = h->get(vg_conv_name(0) + "weight");
-    for (int t = 0; t < 9; ++t)
-        for (int co = 0; co < 64; ++co)
-            for (int ci = 0; ci < 3; ++ci) b[(t * 64 + co) * 3 + ci] = w0[(co * 3 + ci) * 9 + (2 - t / 3) * 3 + (2 - t % 3)];
-    for (int l = 1; l < kVgContentConvs; ++l) {
-        float* seg = b + vg_bwd_off(l);
-        const int CG = kVgCout[l], CX = kVgCin[l];
-        const float* w = h->get(vg_conv_name(l) + "weight");
-        for (int cx = 0; cx < CX; ++cx)
-            for (int cg = 0; cg < CG; ++cg)
-                for (int t = 0; t < 9; ++t) seg[lp_conv_windex(CG, 3, cx, cg, t / 3, t % 3)] = w[((size_t)cg * CX + cx) * 9 + (8 - t)];
-    }
-}
-
-// One trunk convolution from an Hs x Ws tensor; the plane size follows the output map's width.  Only the launch that can meet a
-// map wider than 339 (relu1_2, at the image's own size) has a wide instantiation.
-template <int CIN, int COUT, bool POOL, bool CAN_BE_WIDE>
-void vg_conv_launch(const float* in, float* out, const float* w, int N, int Hs, int Ws, hipStream_t s) {
-    const int Ho = POOL ? Hs / 2 : Hs, Wo = POOL ? Ws / 2 : Ws;
-    const LpConvArgs a{in, out, w, (long long)2 * N * Ho * Wo, Hs, Ws, Ho, Wo};
-    const dim3 grid((unsigned)((a.total + LP_NT - 1) / LP_NT), COUT / LP_MT);
-    if (vg_stage_bound(Ho, Wo) <= LP_XPOS) {
-        hipLaunchKernelGGL((k_lpips_conv<CIN, COUT, 3, POOL, 2, LP_XPOS>), grid, dim3(D_THREADS), 0, s, a);
-    } else if constexpr (CAN_BE_WIDE) {
-        hipLaunchKernelGGL((k_lpips_conv<CIN, COUT, 3, POOL, 2, VG_XPOS_WIDE>), grid, dim3(D_THREADS), 0, s, a);
-    }
-}
-
-// the checks cid_vgg_lpips and cid_vgg_content_loss share
-int vg_check(cid_vgg_t h, const char* fn, int what, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags,
-             const void* out, const void* layers, const void* workspace, size_t workspace_bytes, VgPlan& p, bool saved = false) {
-    const std::string f(fn);
-    if (!a || !b || !out || !workspace) return h->fail(CID_ERR_INVALID, f + ": null pointer");
-    if ((fmt_a != CID_FMT_F32_NCHW && fmt_a != CID_FMT_U8_NHWC) || (fmt_b != CID_FMT_F32_NCHW && fmt_b != CID_FMT_U8_NHWC))
-        return h->fail(CID_ERR_INVALID, f + ": unknown format");
-    if (saved && fmt_a != CID_FMT_F32_NCHW) return h->fail(CID_ERR_INVALID, f + ": operand a must be fp32 (a uint8 image has no gradient)");
-    if ((fmt_a == CID_FMT_F32_NCHW && ((uintptr_t)a & 3)) || (fmt_b == CID_FMT_F32_NCHW && ((uintptr_t)b & 3)) || ((uintptr_t)out & 7) ||
-        ((uintptr_t)layers & 7))
-        return h->fail(CID_ERR_INVALID, f + ": misaligned operand");
-    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return h->fail(CID_ERR_INVALID, f + ": unknown flags");
-    if (vg_plan(what, N, H, W, p) != CID_OK)
-        return h->fail(CID_ERR_SHAPE, f + ": shape not accepted (1 <= N <= 2^20, " + std::to_string(kVgMinSide[what]) + " <= H, W <= " +
-                                            std::to_string(VG_MAX_SIDE) + ", 2 N H W < 2^37)");
-    VgSavedPlan sp;
-    if (saved) vg_saved_plan(N, H, W, sp);
-    if (workspace_bytes < (saved ? sp.total : p.total) || ((uintptr_t)workspace & 255))
-        return h->fail(CID_ERR_WORKSPACE, f + (saved ? ": saved arena smaller than cid_vgg_saved_bytes() or not 256-byte aligned"
-                                                     : ": workspace smaller than cid_vgg_workspace_bytes() or not 256-byte aligned"));
-    if (!h->dev_blob) return h->fail(CID_ERR_STATE, f + ": weights not uploaded");
-    if (what == CID_VGG_LPIPS && !h->full) return h->fail(CID_ERR_STATE, f + ": the handle holds slice1 ... slice3 only (content loss)");
-    return CID_OK;
-}
-
-// Head and trunk up to convolution `convs` (7: relu3_3, 13: relu5_3); convolution l writes t[l], every tensor C8 with 2 N images, and
-// Hs / Ws are the sizes by level (the image's, then one halving per pool).  The plain calls pass their two scratch tensors and the
-// taps, the saved call seven tensors of its arena: the same kernels on the same operands, so the same bits.  Returns the name of the
-// launch that failed, or null.
-const char* vg_features(cid_vgg_t h, float* const* t, const int* Hs, const int* Ws, const void* a, int fmt_a, const void* b, int fmt_b, int N,
-                        int H, int W, bool unit, bool scaled, int convs, hipStream_t s) {
-    const float* blob = h->dev_blob;
-    const auto bad = [] { return hipPeekAtLastError() != hipSuccess; };
-    {
-        const VgHeadArgs ha{a, b, t[0], blob, (long long)2 * N * H * W, H, W, N, fmt_a == CID_FMT_U8_NHWC, fmt_b == CID_FMT_U8_NHWC, unit, scaled};
-        hipLaunchKernelGGL(k_vgg_head, dim3((unsigned)((ha.total + VG_HEAD_PIX - 1) / VG_HEAD_PIX)), dim3(VG_HEAD_PIX), 0, s, ha);
-        if (bad()) return "relu1_1";
-    }
-    vg_conv_launch<64, 64, false, true>(t[0], t[1], blob + vg_conv_off(1), N, Hs[0], Ws[0], s);
-    if (bad()) return "relu1_2";
-    vg_conv_launch<64, 128, true, false>(t[1], t[2], blob + vg_conv_off(2), N, Hs[0], Ws[0], s);
-    if (bad()) return "relu2_1";
-    vg_conv_launch<128, 128, false, false>(t[2], t[3], blob + vg_conv_off(3), N, Hs[1], Ws[1], s);
-    if (bad()) return "relu2_2";
-    vg_conv_launch<128, 256, true, false>(t[3], t[4], blob + vg_conv_off(4), N, Hs[1], Ws[1], s);
-    if (bad()) return "relu3_1";
-    vg_conv_launch<256, 256, false, false>(t[4], t[5], blob + vg_conv_off(5), N, Hs[2], Ws[2], s);
-    if (bad()) return "relu3_2";
-    vg_conv_launch<256, 256, false, false>(t[5], t[6], blob + vg_conv_off(6), N, Hs[2], Ws[2], s);
-    if (bad()) return "relu3_3";
-    if (convs == kVgContentConvs) return nullptr;
-    vg_conv_launch<256, 512, true, false>(t[6], t[7], blob + vg_conv_off(7), N, Hs[2], Ws[2], s);
-    if (bad()) return "relu4_1";
-    vg_conv_launch<512, 512, false, false>(t[7], t[8], blob + vg_conv_off(8), N, Hs[3], Ws[3], s);
-    if (bad()) return "relu4_2";
-    vg_conv_launch<512, 512, false, false>(t[8], t[9], blob + vg_conv_off(9), N, Hs[3], Ws[3], s);
-    if (bad()) return "relu4_3";
-    vg_conv_launch<512, 512, true, false>(t[9], t[10], blob + vg_conv_off(10), N, Hs[3], Ws[3], s);
-    if (bad()) return "relu5_1";
-    vg_conv_launch<512, 512, false, false>(t[10], t[11], blob + vg_conv_off(11), N, Hs[4], Ws[4], s);
-    if (bad()) return "relu5_2";
-    vg_conv_launch<512, 512, false, false>(t[11], t[12], blob + vg_conv_off(12), N, Hs[4], Ws[4], s);
-    if (bad()) return "relu5_3";
-    return nullptr;
-}
-
-// the plain calls' tensors by convolution: the two scratch tensors between the taps
-void vg_plain_tensors(const VgPlan& p, char* ws, float** t) {
-    float *s0 = reinterpret_cast<float*>(ws + p.s0), *s1 = reinterpret_cast<float*>(ws + p.s1), *tap[LP_TAPS];
-    for (int k = 0; k < LP_TAPS; ++k) tap[k] = reinterpret_cast<float*>(ws + p.tap[k]);
-    float* const by_conv[VG_CONVS] = {s0, tap[0], s0, tap[1], s0, s1, tap[2], s0, s1, tap[3], s0, s1, tap[4]};
-    std::copy(by_conv, by_conv + VG_CONVS, t);
-}
-
-// One data-gradient launch over tower a's N images of an Ho x Wo map; the plane size follows the map's width, as in vg_conv_launch.
-template <int CG, int CX, bool UNPOOL, bool MASK, bool CAN_BE_WIDE>
-void vg_dgrad_launch(const float* g, const float* pool, const float* act, float* out, const float* w, int N, int Ho, int Wo, hipStream_t s) {
-    const VgDgradArgs a{g, pool, act, out, w, (long long)N * Ho * Wo, Ho, Wo};
-    const dim3 grid((unsigned)((a.total + LP_NT - 1) / LP_NT), CX / LP_MT);
-    if (vg_stage_bound(Ho, Wo) <= LP_XPOS) {
-        hipLaunchKernelGGL((k_vgg_dgrad<CG, CX, UNPOOL, MASK, LP_XPOS>), grid, dim3(D_THREADS), 0, s, a);
-    } else if constexpr (CAN_BE_WIDE) {
-        hipLaunchKernelGGL((k_vgg_dgrad<CG, CX, UNPOOL, MASK, VG_XPOS_WIDE>), grid, dim3(D_THREADS), 0, s, a);
-    }
-}
-}  // namespace
-
-extern "C" {
-
-int cid_vgg_create(cid_vgg_t* out) {
-    if (!out) return CID_ERR_INVALID;
-    *out = nullptr;
-    cid_vgg_s* h = new (std::nothrow) cid_vgg_s();
-    if (!h) return CID_ERR_INVALID;
-    h->init("cid_vgg", vg_key_table());
-    *out = h;
-    return CID_OK;
-}
-
-void cid_vgg_destroy(cid_vgg_t h) { delete h; }
-
-const char* cid_vgg_last_error(cid_vgg_t h) { return h ? h->err.c_str() : "null handle"; }
-
-const char* cid_vgg_param_key(cid_vgg_t h, int i) { return h ? h->key(i) : nullptr; }
-
-int cid_vgg_set_weight(cid_vgg_t h, const char* key, const void* data, const int64_t* shape, int ndim) {
-    return h ? h->set(key, data, shape, ndim) : CID_ERR_INVALID;
-}
-
-int cid_vgg_missing_weights(cid_vgg_t h, int* count) {
-    if (!h || !count) return CID_ERR_INVALID;
-    *count = h->missing();
-    return CID_OK;
-}
-
-size_t cid_vgg_packed_weights_bytes(cid_vgg_t h) { return h ? vg_blob_floats() * sizeof(float) : 0; }
-
-int cid_vgg_upload_weights(cid_vgg_t h, void* device_blob, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    if (!device_blob) return h->fail(CID_ERR_INVALID, "cid_vgg_upload_weights: null device pointer");
-    // all 33 tensors, or exactly the 14 of slice1 ... slice3 (key table entries 2 ... 15); this state check comes ahead of the
-    // blob's alignment check, which the shared upload makes
-    int set = 0, content = 0;
-    for (size_t i = 0; i < h->have.size(); ++i) {
-        set += h->have[i] != 0;
-        content += h->have[i] && i >= 2 && i < 2 + 2 * (size_t)kVgContentConvs;
-    }
-    const bool full = set == CID_VGG_NUM_WEIGHTS;
-    if (!full && !(set == 2 * kVgContentConvs && content == set))
-        return h->fail(CID_ERR_STATE, "cid_vgg_upload_weights: needs all " + std::to_string(CID_VGG_NUM_WEIGHTS) +
-                                          " tensors or exactly the 14 of slice1 ... slice3; " + std::to_string(set) + " set, first missing " +
-                                          h->keys[h->first_missing()].name);
-    const int rc = h->upload(device_blob, stream, vg_blob_floats(), [h, full](float* b) { vg_pack(h, b, full); }, false);
-    if (rc == CID_OK) {
-        h->full = full;
-        h->dev_bwd = nullptr;   // packed from the previous weights
-    }
-    return rc;
-}
-
-int cid_vgg_workspace_bytes(int what, int N, int H, int W, size_t* bytes) {
-    if (!bytes) return CID_ERR_INVALID;
-    VgPlan p;
-    const int rc = vg_plan(what, N, H, W, p);
-    if (rc == CID_OK) *bytes = p.total;
-    return rc;
-}
-
-int cid_vgg_stage_view(int what, const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block) {
-    if (!stage || !offset_bytes || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
-    VgPlan p;
-    const int rc = vg_plan(what, N, H, W, p);
-    if (rc != CID_OK) return rc;
-    const std::string s(stage);
-    if (s.size() != 5 || s.compare(0, 4, "relu") != 0 || s[4] < '1' || s[4] > (what == CID_VGG_LPIPS ? '5' : '3')) return CID_ERR_KEY;
-    const int k = s[4] - '1';
-    *offset_bytes = p.tap[k];
-    *C = VgTaps::channels(k);
-    *Hs = p.Hs[k];
-    *Ws = p.Ws[k];
-    *channel_block = 8;
-    return CID_OK;
-}
-
-int cid_vgg_lpips(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
-                  double* layers, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    VgPlan p;
-    const int rc = vg_check(h, "cid_vgg_lpips", CID_VGG_LPIPS, a, fmt_a, b, fmt_b, N, H, W, flags, out, layers, workspace, workspace_bytes, p);
-    if (rc != CID_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_vgg_lpips: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
-    char* ws = static_cast<char*>(workspace);
-    float* t[VG_CONVS];
-    vg_plain_tensors(p, ws, t);
-    if (const char* failed = vg_features(h, t, p.Hs, p.Ws, a, fmt_a, b, fmt_b, N, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0, true, VG_CONVS, s))
-        return herr(failed);
-    LpDistArgs da;
-    for (int k = 0; k < LP_TAPS; ++k) {
-        da.tap[k] = reinterpret_cast<const float*>(ws + p.tap[k]);
-        da.P[k] = p.Hs[k] * p.Ws[k];
-    }
-    da.lin = h->dev_blob + vg_conv_off(VG_CONVS);
-    da.out = out;
-    da.layers = layers;
-    da.N = N;
-    hipLaunchKernelGGL(k_lpips_dist<VgTaps>, dim3((unsigned)N), dim3(D_THREADS), 0, s, da);
-    if (hipPeekAtLastError() != hipSuccess) return herr("distance");
-    return CID_OK;
-}
-
-int cid_vgg_content_loss(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags, double* out,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    VgPlan p;
-    const int rc = vg_check(h, "cid_vgg_content_loss", CID_VGG_CONTENT, a, fmt_a, b, fmt_b, N, H, W, flags, out, nullptr, workspace, workspace_bytes, p);
-    if (rc != CID_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_vgg_content_loss: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
-    char* ws = static_cast<char*>(workspace);
-    float* t[VG_CONVS];
-    vg_plain_tensors(p, ws, t);
-    if (const char* failed = vg_features(h, t, p.Hs, p.Ws, a, fmt_a, b, fmt_b, N, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0, false, kVgContentConvs, s))
-        return herr(failed);
-    const VgContentArgs ca{reinterpret_cast<const float*>(ws + p.tap[2]), out, (long long)256 * p.Hs[2] * p.Ws[2], N};
-    hipLaunchKernelGGL(k_vgg_content, dim3((unsigned)N), dim3(D_THREADS), 0, s, ca);
-    if (hipPeekAtLastError() != hipSuccess) return herr("loss");
-    return CID_OK;
-}
-
-int cid_vgg_saved_bytes(int N, int H, int W, size_t* bytes) {
-    if (!bytes) return CID_ERR_INVALID;
-    VgSavedPlan p;
-    const int rc = vg_saved_plan(N, H, W, p);
-    if (rc == CID_OK) *bytes = p.total;
-    return rc;
-}
-
-int cid_vgg_saved_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* images, int* C, int* Hs, int* Ws, int* channel_block) {
-    if (!stage || !offset_bytes || !images || !C || !Hs || !Ws || !channel_block) return CID_ERR_INVALID;
-    VgSavedPlan p;
-    const int rc = vg_saved_plan(N, H, W, p);
-    if (rc != CID_OK) return rc;
-    const std::string s(stage);
-    for (int i = 0; i < kVgSaved; ++i) {
-        const bool act = s == kVgActName[i];
-        if (!act && s != kVgGradName[i]) continue;
-        const int k = act ? kVgActLevel[i] : kVgGradLevel[i];
-        *offset_bytes = act ? p.act[i] : p.grad[i];
-        *images = act ? 2 * N : N;
-        *C = act ? VgTaps::channels(k) : kVgGradC[i];
-        *Hs = p.Hs[k];
-        *Ws = p.Ws[k];
-        *channel_block = 8;
-        return CID_OK;
-    }
-    return CID_ERR_KEY;
-}
-
-int cid_vgg_content_loss_saved(cid_vgg_t h, const void* a, int fmt_a, const void* b, int fmt_b, int N, int H, int W, unsigned flags,
-                               double* out, void* saved, size_t saved_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    VgPlan fp;
-    const int rc = vg_check(h, "cid_vgg_content_loss_saved", CID_VGG_CONTENT, a, fmt_a, b, fmt_b, N, H, W, flags, out, nullptr, saved, saved_bytes, fp, true);
-    if (rc != CID_OK) return rc;
-    VgSavedPlan p;
-    vg_saved_plan(N, H, W, p);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, std::string("cid_vgg_content_loss_saved: ") + what + ": " + hipGetErrorString(hipGetLastError())); };
-    char* sv = static_cast<char*>(saved);
-    float* t[kVgSaved];
-    for (int i = 0; i < kVgSaved; ++i) t[i] = reinterpret_cast<float*>(sv + p.act[i]);
-    if (const char* failed = vg_features(h, t, p.Hs, p.Ws, a, fmt_a, b, fmt_b, N, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0, false, kVgContentConvs, s))
-        return herr(failed);
-    const VgContentArgs ca{t[6], out, (long long)256 * p.Hs[2] * p.Ws[2], N};
-    hipLaunchKernelGGL(k_vgg_content, dim3((unsigned)N), dim3(D_THREADS), 0, s, ca);
-    if (hipPeekAtLastError() != hipSuccess) return herr("loss");
-    return CID_OK;
-}
-
-size_t cid_vgg_backward_weights_bytes(cid_vgg_t h) { return h ? vg_bwd_floats() * sizeof(float) : 0; }
-
-int cid_vgg_upload_backward_weights(cid_vgg_t h, void* device_blob, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    const std::string fn = "cid_vgg_upload_backward_weights: ";
-    if (!device_blob) return h->fail(CID_ERR_INVALID, fn + "null device pointer");
-    for (int i = 2; i < 2 + 2 * kVgContentConvs; ++i)
-        if (!h->have[i]) return h->fail(CID_ERR_STATE, fn + h->keys[i].name + " not set");
-    if ((uintptr_t)device_blob & 255) return h->fail(CID_ERR_WORKSPACE, fn + "blob must be 256-byte aligned");
-    h->bwd_staging.assign(vg_bwd_floats(), 0.f);
-    vg_pack_backward(h, h->bwd_staging.data());
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->bwd_staging.data(), h->bwd_staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // the staging copy is pageable
-    if (e != hipSuccess) return h->fail(CID_ERR_HIP, fn + hipGetErrorString(e));
-    h->dev_bwd = static_cast<const float*>(device_blob);
-    return CID_OK;
-}
-
-int cid_vgg_content_backward(cid_vgg_t h, const double* grad_out, float* grad_a, int N, int H, int W, unsigned flags, void* saved,
-                             size_t saved_bytes, void* stream) {
-    if (!h) return CID_ERR_INVALID;
-    const std::string f = "cid_vgg_content_backward";
-    if (!grad_out || !grad_a || !saved) return h->fail(CID_ERR_INVALID, f + ": null pointer");
-    if (((uintptr_t)grad_out & 7) || ((uintptr_t)grad_a & 3)) return h->fail(CID_ERR_INVALID, f + ": misaligned operand");
-    if (flags & ~(unsigned)CID_LPIPS_UNIT_VIEW) return h->fail(CID_ERR_INVALID, f + ": unknown flags");
-    VgSavedPlan p;
-    if (vg_saved_plan(N, H, W, p) != CID_OK)
-        return h->fail(CID_ERR_SHAPE, f + ": shape not accepted (1 <= N <= 2^20, 4 <= H, W <= " + std::to_string(VG_MAX_SIDE) + ", 2 N H W < 2^37)");
-    if (saved_bytes < p.total || ((uintptr_t)saved & 255))
-        return h->fail(CID_ERR_WORKSPACE, f + ": saved arena smaller than cid_vgg_saved_bytes() or not 256-byte aligned");
-    if (!h->dev_blob) return h->fail(CID_ERR_STATE, f + ": weights not uploaded");
-    if (!h->dev_bwd) return h->fail(CID_ERR_STATE, f + ": backward weights not uploaded (cid_vgg_upload_backward_weights)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto herr = [&](const char* what) { return h->fail(CID_ERR_HIP, f + ": " + what + ": " + hipGetErrorString(hipGetLastError())); };
-    const auto bad = [] { return hipPeekAtLastError() != hipSuccess; };
-    char* sv = static_cast<char*>(saved);
-    const float* act[kVgSaved];
-    float* g[kVgSaved];
-    for (int i = 0; i < kVgSaved; ++i) {
-        act[i] = reinterpret_cast<const float*>(sv + p.act[i]);
-        g[i] = reinterpret_cast<float*>(sv + p.grad[i]);
-    }
-    const float* bw = h->dev_bwd;
-    const int H1 = p.Hs[0], W1 = p.Ws[0], H2 = p.Hs[1], W2 = p.Ws[1], H3 = p.Hs[2], W3 = p.Ws[2];
-    {
-        VgSeedArgs sa{act[6], grad_out, g[0], (long long)256 * H3 * W3, 0, N};
-        sa.total = sa.count * N;
-        hipLaunchKernelGGL(k_vgg_seed, dim3((unsigned)((sa.total / 4 + D_THREADS - 1) / D_THREADS)), dim3(D_THREADS), 0, s, sa);
-        if (bad()) return herr("grad3_3");
-    }
-    vg_dgrad_launch<256, 256, false, true, false>(g[0], nullptr, act[5], g[1], bw + vg_bwd_off(6), N, H3, W3, s);
-    if (bad()) return herr("grad3_2");
-    vg_dgrad_launch<256, 256, false, true, false>(g[1], nullptr, act[4], g[2], bw + vg_bwd_off(5), N, H3, W3, s);
-    if (bad()) return herr("grad3_1");
-    vg_dgrad_launch<256, 128, false, false, false>(g[2], nullptr, nullptr, g[3], bw + vg_bwd_off(4), N, H3, W3, s);
-    if (bad()) return herr("gradpool2");
-    vg_dgrad_launch<128, 128, true, true, false>(g[3], act[3], act[2], g[4], bw + vg_bwd_off(3), N, H2, W2, s);
-    if (bad()) return herr("grad2_1");
-    vg_dgrad_launch<128, 64, false, false, false>(g[4], nullptr, nullptr, g[5], bw + vg_bwd_off(2), N, H2, W2, s);
-    if (bad()) return herr("gradpool1");
-    vg_dgrad_launch<64, 64, true, true, true>(g[5], act[1], act[0], g[6], bw + vg_bwd_off(1), N, H1, W1, s);
-    if (bad()) return herr("grad1_1");
-    {
-        const VgHeadBwdArgs ha{g[6], grad_a, bw, (long long)N * H * W, H, W, (flags & CID_LPIPS_UNIT_VIEW) != 0};
-        hipLaunchKernelGGL(k_vgg_head_bwd, dim3((unsigned)((ha.total + VG_HEAD_PIX - 1) / VG_HEAD_PIX)), dim3(VG_HEAD_PIX), 0, s, ha);
-        if (bad()) return herr("grad_a");
-    }
-    return CID_OK;
-}
-
-}  // extern "C"
+#include "api/esrgan.h"           // cid_esr_*
+#include "api/srgan.h"            // cid_sr_*
+#include "api/cgan.h"             // cid_cg_*
+#include "api/lpips.h"            // cid_lpips_*
+#include "api/vgg.h"              // cid_vgg_*

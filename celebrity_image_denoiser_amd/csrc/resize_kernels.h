@@ -1,7 +1,7 @@
 // resize_kernels.h — gfx950 device kernel of the bicubic resize (cid_resize, include/cid.h): PIL's Image.resize(size, BICUBIC) on
 // uint8 NHWC batches, the first step of every reference entry point (noise_generation.py:61, denoisegan_eval.py,
 // denoise_eavl_iter.py:89, training.py:303-304), bit for bit.  The arithmetic is integer: 22-bit fixed-point coefficients built on
-// the host (resize_tables in cid_api.hip, restated as synth.resize_tables_np), a horizontal pass into a uint8 intermediate, a
+// the host (resize_tables in api/resize.h, restated as synth.resize_tables_np), a horizontal pass into a uint8 intermediate, a
 // vertical pass over that intermediate, each out = clamp((2^21 + sum in * k) >> 22, 0, 255) in int32.
 //
 // k_resize<MODE>: ONE launch per call; a workgroup of RESIZE_THREADS owns a tile of TR x TC output pixels of one image (the plan

@@ -1,17 +1,13 @@
-// weight_store.h — the host-side weight staging the model handles of cid_api.hip share (cid_esr_*, cid_sr_*, cid_cg_*, cid_lpips_*,
-// cid_vgg_*): the key table, the tensors as they were set, the packed blob's staging copy and the handle's last error.  Host code only.
+// weight_store.h — the host-side weight staging the model handles of api/*.h share (cid_esr_*, cid_sr_*, cid_cg_*, cid_lpips_*,
+// cid_vgg_*): the key table, the tensors as they were set and the packed blob's staging copy, over HandleBase.  Host code only.
 //
 // A handle struct derives from WeightStore and adds its few own fields; its extern "C" functions are a few lines over the store.  A
 // new model supplies a key table (KeyTable), a pack step (the staged tensors -> the kernels' layout) and its own fields and forward.
 #pragma once
 
-#include "../../include/cid.h"
+#include "api_common.h"
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
 #include <initializer_list>
 #include <string>
 #include <utility>
@@ -45,25 +41,18 @@ struct KeyTable : std::vector<WeightKey> {
     }
 };
 
-struct WeightStore {
+struct WeightStore : HandleBase {
     std::string prefix;                    // the family's name in every message: "cid_esr", ...
     std::vector<WeightKey> keys;
     std::vector<std::vector<float>> raw;   // the tensors as set, reference layout
     std::vector<char> have;
     std::vector<float> staging;            // the packed blob; pageable host memory owned by the handle
-    const float* dev_blob = nullptr;
-    std::string err;
 
     void init(const char* family, std::vector<WeightKey> table) {
         prefix = family;
         keys = std::move(table);
         raw.resize(keys.size());
         have.assign(keys.size(), 0);
-    }
-
-    int fail(int code, const std::string& msg) {
-        err = msg;
-        return code;
     }
 
     int find(const std::string& k) const {

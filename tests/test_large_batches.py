@@ -1,7 +1,7 @@
 """Batches past 65,535 images: a grid's y dimension holds at most 65,535 images, so cid_disc_forward(_saved), cid_disc_backward,
-cid_backward and cid_quality loop over launches of 65,535 images on the host (every kernel adds the launch's first image to its
-block index), and cid_add_noise and cid_resize loop over the rest inside the kernel.  Every case here runs N = 65,535 + 9 images
-of the smallest size its entry point accepts and makes two checks:
+cid_backward, cid_quality, cid_esr_forward and cid_sr_forward loop over launches of 65,535 images on the host (every kernel adds
+the launch's first image to its block index), and cid_add_noise and cid_resize loop over the rest inside the kernel.  Every case
+here runs N = 65,535 + 9 images of the smallest size its entry point accepts and makes two checks:
 
   (i)  every image's result in the one call is bit-equal to its result in two calls of at most 65,535 images, on [0, 32772) and
        [32772, N), compared on the device;
@@ -240,6 +240,53 @@ def test_discriminator_train_forward():
 @pytest.mark.gpu
 def test_discriminator_train_backward():
     TDB.gradient_parity("default", (N, 1, 1), True, "real1", x=_train_images(N, 1, 1)[1])
+
+
+# ------------------------------------------------------------------------------------------- the server's ESRGAN and SRGAN generators
+@pytest.mark.gpu
+def test_esrgan_forward():
+    """Two residual blocks on 1 x 1 images: the head's and the tail's launches and the trunk's three epilogues (PReLU, residual, the
+    closing sum) each take the split.  x is the true /255 view of the uint8 batch, so the uint8 input must give its bits."""
+    import test_esrgan as TE
+    from celebrity_image_denoiser_amd.esrgan import load_esrgan
+
+    r = 2
+    u8 = distinct_u8(N, 1, 1, 20)
+    x = np.ascontiguousarray((u8.astype(np.float32) / np.float32(255.0)).transpose(0, 3, 1, 2))
+    m = load_esrgan(synth.make_esrgan_state_dict("hot", r), num_residuals=r, device=DEV, strict=True)   # not TE's cache: freed below
+    xd = torch.from_numpy(x).to(DEV)
+    big = m(xd)
+    assert torch.equal(big.view(torch.int32), _in_parts(lambda lo, hi: m(xd[lo:hi])).view(torch.int32))
+    assert torch.equal(big.view(torch.int32), m(torch.from_numpy(u8).to(DEV), out_dtype=torch.float32).view(torch.int32))
+    idx = list(SEAM)
+    ref = TE.esrgan_oracle.forward(synth.make_esrgan_state_dict("hot", r), x[idx], r)
+    TE.check(f"esrgan hot r{r} {N}x1x1, out on SEAM", big.cpu().numpy()[idx], ref["out"])
+    del m, big, xd
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+def test_srgan_forward():
+    """scale_factor 2 on 1 x 1 images: the head, the eleven trunk launches, one upscale stage (grid z = 2) and the tail each take the
+    split.  As in test_srgan.py the output is held to the bound of the sums before tanh, which the raw call gives."""
+    import test_srgan as TS
+    from celebrity_image_denoiser_amd.srgan import load_srgan
+
+    scale = 2
+    u8 = distinct_u8(N, 1, 1, 21)
+    x = TS.srgan_oracle.normalise_u8(u8)
+    m = load_srgan(synth.make_srgan_state_dict("hot", scale), scale_factor=scale, device=DEV, strict=True)   # not TS's cache: freed below
+    xd = torch.from_numpy(x).to(DEV)
+    idx = list(SEAM)
+    ref = TS.srgan_oracle.forward(synth.make_srgan_state_dict("hot", scale), x[idx])
+    for raw, name in ((True, "pre"), (False, "out")):
+        big = m(xd, raw=raw)
+        assert big.shape == (N, 3, scale, scale)
+        assert torch.equal(big.view(torch.int32), _in_parts(lambda lo, hi: m(xd[lo:hi], raw=raw)).view(torch.int32)), name
+        assert torch.equal(big.view(torch.int32), m(torch.from_numpy(u8).to(DEV), out_dtype=torch.float32, raw=raw).view(torch.int32)), name
+        TS.check(f"srgan hot s{scale} {N}x1x1, {name} on SEAM", big.cpu().numpy()[idx], ref[name], bound=TS.srgan_oracle.bound(ref["pre"]))
+    del m, big, xd
+    torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------------------------------------------------------ the generator
