@@ -26,6 +26,7 @@ CID_LPIPS_UNIT_VIEW = 1
 CID_LPIPS_NUM_WEIGHTS = 17
 CID_VGG_LPIPS, CID_VGG_CONTENT = 0, 1
 CID_VGG_NUM_WEIGHTS = 33
+CID_SRD_NUM_WEIGHTS = 14
 CID_VGG_MAX_SIDE = 512
 
 
@@ -108,6 +109,16 @@ SYMBOLS = {
     "cid_disc_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
     "cid_disc_forward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                     _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_srd_create": (_c.c_int, [_c.POINTER(_c.c_void_p)]),
+    "cid_srd_destroy": (None, [_c.c_void_p]),
+    "cid_srd_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_srd_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_srd_packed_weights_bytes": (_c.c_size_t, []),
+    "cid_srd_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_srd_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_srd_forward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                   _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_srd_losses": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "cid_disc_saved_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
     "cid_disc_forward_saved": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                           _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
@@ -256,7 +267,7 @@ def check(handle, code: int):
 
 
 def check_abi(abi: str, handle, code: int):
-    """check() for the handle of the family cid_<abi>_*: "esr", "sr", "cg", "lpips", "vgg" or "disc"."""
+    """check() for the handle of the family cid_<abi>_*: "esr", "sr", "cg", "lpips", "vgg", "disc" or "srd"."""
     if code != CID_OK:
         msg = getattr(lib(), f"cid_{abi}_last_error")(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")
@@ -265,6 +276,11 @@ def check_abi(abi: str, handle, code: int):
 def check_disc(handle, code: int):
     """check() for a cid_disc_t handle."""
     check_abi("disc", handle, code)
+
+
+def check_srd(handle, code: int):
+    """check() for a cid_srd_t handle."""
+    check_abi("srd", handle, code)
 
 
 def check_lpips(handle, code: int):

@@ -1,5 +1,5 @@
 """What the modules over a cid_<abi>_* weight-store handle share (ESRGANGenerator, SRGANGenerator, CGANGenerator, LPIPS,
-VGGPerceptualLoss): the handle, the packed blob, the grow-only workspace and the decode of a stored stage.
+VGGPerceptualLoss, SRGANDiscriminator): the handle, the packed blob, the grow-only workspace and the decode of a stored stage.
 
 A subclass sets `_abi`, builds its layers, calls `_create(...)`, and keeps its forward and its shape errors.  Where it differs it
 overrides `_batchnorms()` (BatchNorm layers whose eps the library needs), `_key()` (state_dict key -> library key) and `_tensors()`
@@ -59,7 +59,7 @@ def load_into(model, source, device, strict: bool):
 
 
 class PackedModule(nn.Module):
-    _abi = ""     # the C ABI family: "esr", "sr", "cg", "lpips" or "vgg"
+    _abi = ""     # the C ABI family: "esr", "sr", "cg", "lpips", "vgg" or "srd"
     _form = ()    # the leading `what` argument of cid_vgg_workspace_bytes / cid_vgg_stage_view; the other families have none
 
     def _create(self, *args) -> None:
@@ -100,6 +100,10 @@ class PackedModule(nn.Module):
         """(name, BatchNorm2d, its leading arguments of cid_<abi>_set_bn_eps) of every BatchNorm the pack folds."""
         return ()
 
+    def _blob_bytes(self) -> int:
+        """Size of the packed blob (a family whose layout does not depend on the handle takes no argument and overrides this)."""
+        return self._fn("packed_weights_bytes")(self._cid)
+
     def _signature(self):
         eps = tuple(float(bn.eps) for _, bn, _ in self._batchnorms())
         return tuple((k, t.data_ptr(), t._version, str(t.device)) for k, t in self._tensors()) + eps
@@ -125,7 +129,7 @@ class PackedModule(nn.Module):
                 a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
             shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
             self._check(self._fn("set_weight")(self._cid, self._key(key).encode(), a.ctypes.data, shape, a.ndim))
-        blob = torch.empty(self._fn("packed_weights_bytes")(self._cid), dtype=torch.uint8, device=dev)
+        blob = torch.empty(self._blob_bytes(), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             self._check(self._fn("upload_weights")(self._cid, blob.data_ptr(), stream))

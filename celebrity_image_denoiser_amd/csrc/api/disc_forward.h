@@ -67,21 +67,70 @@ int disc_plan(int N, int H, int W, int training, DiscPlan& p) {
     return CID_OK;
 }
 
-template <int CIN, int COUT, int S, bool BN_IN>
-hipError_t disc_conv_launch(const DiscConvArgs& base, int layer, const DiscPlan& p, int N, bool training, hipStream_t s) {
+// One MFMA convolution layer over a plan's tiles (DiscPlan, or the SRGAN discriminator's plan).  COUT_TOTAL > COUT: the layer's
+// COUT-channel parts are the grid's z (k_disc_conv).
+template <int CIN, int COUT, int S, bool BN_IN, int COUT_TOTAL = COUT, class Plan>
+hipError_t disc_conv_launch(const DiscConvArgs& base, int layer, const Plan& p, int N, bool training, hipStream_t s) {
     (void)for_each_launch(N, [&](int n0, int n) {
         DiscConvArgs a = base;
         a.n0 = n0;
         a.tiles_x = p.tiles_x[layer];
         a.tiles = p.tiles[layer];
-        const dim3 grid((unsigned)p.tiles[layer], (unsigned)n), block(D_THREADS);
-        if (training) hipLaunchKernelGGL((k_disc_conv<CIN, COUT, S, BN_IN, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_disc_conv<CIN, COUT, S, BN_IN, false>), grid, block, 0, s, a);
+        const dim3 grid((unsigned)p.tiles[layer], (unsigned)n, COUT_TOTAL / COUT), block(D_THREADS);
+        if (training) hipLaunchKernelGGL((k_disc_conv<CIN, COUT, S, BN_IN, true, COUT_TOTAL>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_disc_conv<CIN, COUT, S, BN_IN, false, COUT_TOTAL>), grid, block, 0, s, a);
     });
     return hipGetLastError();
 }
 
 bool disc_finite_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
+
+// The tensors of one MFMA convolution launch: `w` its packed weights, `slab` null in eval mode, `rows` = N * tiles of the layer.
+DiscConvArgs disc_conv_args(const float* src, float* dst, const float* w, const float* st_in, double* slab, long long rows, int Hin,
+                            int Win, int Ho, int Wo) {
+    DiscConvArgs a{};
+    a.in = src;
+    a.out = dst;
+    a.w = w;
+    a.st_in = st_in;
+    a.slab = slab;
+    a.rows = rows;
+    a.Hin = Hin;
+    a.Win = Win;
+    a.Ho = Ho;
+    a.Wo = Wo;
+    return a;
+}
+
+// Train-mode statistics of one C-channel BatchNorm from its layer's slab: (scale, shift) into `st`, the running buffers updated.
+hipError_t disc_stats_launch(const cid_disc_bn& bn, int C, const double* slab, long long rows, double count, float* st, double* mi,
+                             hipStream_t s) {
+    DiscStatsArgs a{};
+    a.slab = slab;
+    a.rows = rows;
+    a.count = count;
+    a.gamma = bn.gamma;
+    a.beta = bn.beta;
+    a.running_mean = bn.running_mean;
+    a.running_var = bn.running_var;
+    a.num_batches_tracked = reinterpret_cast<const long long*>(bn.num_batches_tracked);
+    a.eps = bn.eps;
+    a.momentum = bn.momentum == CID_DISC_MOMENTUM_NONE ? -1.0 : bn.momentum;
+    a.st = st;
+    a.mi = mi;
+    hipLaunchKernelGGL(k_disc_bn_stats, dim3(C), dim3(D_THREADS), 0, s, a);
+    return hipPeekAtLastError();
+}
+
+// The layer-0 launches (model.0 + LeakyReLU -> a0), shared with the SRGAN discriminator.
+int disc_conv0_launches(const Call& cx, const void* in, int in_fmt, float* a0, const float* w, int N, int H, int W) {
+    return cx.launches(N, "conv0", [&](int n0, int n) {
+        DiscConv0Args a{in, a0, w, H, W, n0};
+        const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)n);
+        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_conv0<true>, grid, dim3(D_THREADS), 0, cx.s, a);
+        else hipLaunchKernelGGL(k_disc_conv0<false>, grid, dim3(D_THREADS), 0, cx.s, a);
+    });
+}
 
 }  // namespace
 
@@ -99,15 +148,17 @@ struct DiscBufs {
     double* slab[3];   // train mode: per-tile partial sums
 };
 
-// The argument checks every forward entry point shares, in the order cid.h documents; `buf` is its workspace or saved buffer.
-int disc_check_forward(const Call& cx, const void* in, int in_fmt, const float* out, int N, int H, int W, const cid_disc_bn* bn,
-                       int training, const void* buf, DiscPlan& p) {
+// The argument checks every forward entry point of the two discriminators shares, in the order cid.h documents; `buf` is its
+// workspace or saved buffer, bn[0 .. nbn-1] its BatchNorms and plan() its family's plan function on (N, H, W, training).
+template <class PlanFn>
+int disc_check_args(const Call& cx, const void* in, int in_fmt, const float* out, int N, int H, int W, const cid_disc_bn* bn, int nbn,
+                    int training, const void* buf, PlanFn&& plan) {
     if (!in || !out || !bn || !buf) return cx.fail(CID_ERR_INVALID, "null pointer");
     if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return cx.fail(CID_ERR_INVALID, "unknown input format");
     if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)out & 3))
         return cx.fail(CID_ERR_INVALID, "misaligned fp32 operand");
     if (training != 0 && training != 1) return cx.fail(CID_ERR_INVALID, "training must be 0 or 1");
-    for (int l = 0; l < 3; ++l) {
+    for (int l = 0; l < nbn; ++l) {
         const cid_disc_bn& b = bn[l];
         if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || (training && !b.num_batches_tracked))
             return cx.fail(CID_ERR_INVALID, "null BatchNorm pointer");
@@ -115,11 +166,16 @@ int disc_check_forward(const Call& cx, const void* in, int in_fmt, const float* 
         if (training && !(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
             return cx.fail(CID_ERR_INVALID, "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
     }
-    if (disc_plan(N, H, W, training, p) != CID_OK)
+    if (plan() != CID_OK)
         return training && N >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL
                    ? cx.h->fail(CID_ERR_SHAPE, "Expected more than 1 value per channel when training")
                    : cx.fail(CID_ERR_SHAPE, "input shape not accepted (N, H, W >= 1, H*W < 2^31)");
     return CID_OK;
+}
+
+int disc_check_forward(const Call& cx, const void* in, int in_fmt, const float* out, int N, int H, int W, const cid_disc_bn* bn,
+                       int training, const void* buf, DiscPlan& p) {
+    return disc_check_args(cx, in, in_fmt, out, N, H, W, bn, 3, training, buf, [&] { return disc_plan(N, H, W, training, p); });
 }
 
 // The forward's launch sequence on checked arguments.
@@ -144,42 +200,13 @@ int disc_forward_run(const Call& cx, const void* in, int in_fmt, float* out, int
         if (hipPeekAtLastError() != hipSuccess) return cx.hip("bn_eval");
     }
     // layer 0
-    if (const int rc = cx.launches(N, "conv0", [&](int n0, int n) {
-        DiscConv0Args a{in, b.a0, blob + kDiscBlob.off[0], H, W, n0};
-        const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)n);
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_conv0<true>, grid, dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_disc_conv0<false>, grid, dim3(D_THREADS), 0, s, a);
-    })) return rc;
+    if (const int rc = disc_conv0_launches(cx, in, in_fmt, b.a0, blob + kDiscBlob.off[0], N, H, W)) return rc;
     const auto stats = [&](int l, long long pix) {
-        DiscStatsArgs a{};
-        a.slab = b.slab[l];
-        a.rows = (long long)N * p.tiles[l];
-        a.count = (double)N * (double)pix;
-        a.gamma = bn[l].gamma;
-        a.beta = bn[l].beta;
-        a.running_mean = bn[l].running_mean;
-        a.running_var = bn[l].running_var;
-        a.num_batches_tracked = reinterpret_cast<const long long*>(bn[l].num_batches_tracked);
-        a.eps = bn[l].eps;
-        a.momentum = bn[l].momentum == CID_DISC_MOMENTUM_NONE ? -1.0 : bn[l].momentum;
-        a.st = b.st[l];
-        a.mi = b.mi[l];
-        hipLaunchKernelGGL(k_disc_bn_stats, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
-        return hipPeekAtLastError();
+        return disc_stats_launch(bn[l], kDiscBnC[l], b.slab[l], (long long)N * p.tiles[l], (double)N * (double)pix, b.st[l], b.mi[l], s);
     };
     const auto conv_args = [&](const float* src, float* dst, int ci, const float* st_in, int l, int Hin, int Win, int Ho, int Wo) {
-        DiscConvArgs a{};
-        a.in = src;
-        a.out = dst;
-        a.w = blob + kDiscBlob.off[ci];
-        a.st_in = st_in;
-        a.slab = training ? b.slab[l] : nullptr;
-        a.rows = (long long)N * p.tiles[l];
-        a.Hin = Hin;
-        a.Win = Win;
-        a.Ho = Ho;
-        a.Wo = Wo;
-        return a;
+        return disc_conv_args(src, dst, blob + kDiscBlob.off[ci], st_in, training ? b.slab[l] : nullptr, (long long)N * p.tiles[l], Hin,
+                              Win, Ho, Wo);
     };
     // layer 2 (reads a0, writes z2), BN3
     if (disc_conv_launch<64, 64, 2, false>(conv_args(b.a0, b.z2, 1, nullptr, 0, H, W, p.H2, p.W2), 0, p, N, training, s) != hipSuccess)

@@ -15,7 +15,9 @@
 //     y = s*z + t, y > 0 ? y : 0.2*y, is applied once per staged element there.  Halo positions outside the image are written as 0:
 //     the reference pads the activated tensor, so padding is zero AFTER BatchNorm and LeakyReLU.  The kernel stores the raw
 //     pre-BatchNorm z = conv + bias.  With STATS (train mode) every workgroup also writes its per-channel sums of z and z^2, in fp64,
-//     to its own row of a slab (no atomics).
+//     to its own row of a slab (no atomics).  A sixth template argument COUT_TOTAL > COUT runs a wider layer as COUT_TOTAL / COUT
+//     channel parts, one per grid z (the SRGAN discriminator's 128 -> 256 layer, srgan_disc_kernels.h); left at its default it is COUT
+//     and the kernel is the single-part one.
 //   * k_disc_bn_stats (train): one workgroup per channel reduces the slab in a fixed order in fp64, writes the channel's (scale,
 //     shift) for the next layer's staging and updates running_mean / running_var in the module's own buffers.
 //   * k_disc_bn_eval (eval): (scale, shift) of all three BatchNorms from the running buffers.
@@ -104,7 +106,8 @@ __global__ void __launch_bounds__(D_THREADS) k_disc_conv0(const DiscConv0Args a)
 struct DiscConvArgs {
     const float* in;      // C8, CIN channels, Hin x Win (a0, or the previous layer's raw z)
     float* out;           // C8, COUT channels, Ho x Wo: z = conv + bias (before BatchNorm)
-    const float* w;       // packed: [CIN/8][9 taps][8][COUT] (w[((chunk*9 + tap)*8 + ci%8)*COUT + co]), then the COUT biases
+    const float* w;       // packed: [CIN/8][9 taps][8][COUT] (w[((chunk*9 + tap)*8 + ci%8)*COUT + co]), then the COUT biases;
+                          // with COUT_TOTAL > COUT one such block (weights, then biases) per COUT-channel part, back to back
     const float* st_in;   // BN_IN: (scale, shift) of the previous BatchNorm, float pairs [CIN]
     double* slab;         // STATS: slab[(co*2 + k)*rows + row], k = 0: sum z, 1: sum z^2; row = image * tiles + tile
     long long rows;
@@ -132,8 +135,11 @@ struct DiscGeom {
     static_assert(CIN % 8 == 0, "8-channel chunks");
 };
 
-template <int CIN, int COUT, int S, bool BN_IN, bool STATS>
+// COUT_TOTAL > COUT: the tensor has COUT_TOTAL channels and the launch's grid z counts its COUT-channel parts; workgroup z computes
+// channels z*COUT ... z*COUT + COUT - 1 from part z of the weights (DiscConvArgs::w), staging the input halo itself.
+template <int CIN, int COUT, int S, bool BN_IN, bool STATS, int COUT_TOTAL = COUT>
 __global__ void __launch_bounds__(D_THREADS, 2) k_disc_conv(const DiscConvArgs a) {
+    static_assert(COUT_TOTAL % COUT == 0, "whole parts");
     using G = DiscGeom<CIN, COUT, S>;
     constexpr int WM = G::WM, TH = G::TH, HWD = G::HWD, NPIX = G::NPIX, XSTR = G::XSTR, WSTR = G::WSTR;
     __shared__ float lds_x[8 * XSTR];
@@ -148,6 +154,8 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_conv(const DiscConvArgs a
     const size_t n = (size_t)a.n0 + blockIdx.y;
     const int iy0 = ty * TH * S - 1, ix0 = tx * D_TW * S - 1;
     const size_t in_plane = (size_t)a.Hin * a.Win;
+    const int co0 = COUT_TOTAL == COUT ? 0 : (int)blockIdx.z * COUT;                                       // first channel of this part
+    const float* wpart = COUT_TOTAL == COUT ? a.w : a.w + (size_t)blockIdx.z * (CIN * 9 * COUT + COUT);   // its weights and biases
 
     if (BN_IN)
         for (int i = tid; i < 2 * CIN; i += D_THREADS) lds_st[i] = a.st_in[i];
@@ -186,7 +194,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_conv(const DiscConvArgs a
             }
         }
         // ---- this chunk's weights: 72 rows (tap, channel) of COUT
-        const float* wsrc = a.w + (size_t)chunk * 72 * COUT;
+        const float* wsrc = wpart + (size_t)chunk * 72 * COUT;
         for (int i = tid; i < 72 * COUT / 4; i += D_THREADS) {
             const int r = i / (COUT / 4), c4 = i - r * (COUT / 4);
             *reinterpret_cast<d_f32x4*>(&lds_w[r * WSTR + c4 * 4]) = *reinterpret_cast<const d_f32x4*>(wsrc + (size_t)r * COUT + c4 * 4);
@@ -212,7 +220,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_conv(const DiscConvArgs a
     }
 
     // ---- epilogue: + bias, store z (four consecutive channels of one pixel per lane), per-channel partial sums
-    const float* bias = a.w + (size_t)CIN * 9 * COUT;
+    const float* bias = wpart + (size_t)CIN * 9 * COUT;
     const int ox = tx * D_TW + l16;
     bool ok[4];
 #pragma unroll
@@ -227,7 +235,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_conv(const DiscConvArgs a
             const d_f32x4 z = acc[ct][pt] + b4;
             if (ok[pt]) {
                 const int oy = ty * TH + wm * 4 + pt;
-                *reinterpret_cast<d_f32x4*>(a.out + (((n * (COUT / 8) + co / 8) * a.Ho + oy) * (size_t)a.Wo + ox) * 8 + (co & 7)) = z;
+                *reinterpret_cast<d_f32x4*>(a.out + (((n * (COUT_TOTAL / 8) + (co0 + co) / 8) * a.Ho + oy) * (size_t)a.Wo + ox) * 8 + (co & 7)) = z;
                 if (STATS)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -262,8 +270,8 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_conv(const DiscConvArgs a
                 t2 += lds_red[(m * COUT + tid) * 2 + 1];
             }
             const long long row = (long long)n * a.tiles + t;
-            a.slab[(size_t)(tid * 2) * a.rows + row] = t1;
-            a.slab[(size_t)(tid * 2 + 1) * a.rows + row] = t2;
+            a.slab[(size_t)((co0 + tid) * 2) * a.rows + row] = t1;
+            a.slab[(size_t)((co0 + tid) * 2 + 1) * a.rows + row] = t2;
         }
     }
 }
@@ -335,16 +343,22 @@ struct DiscBnEvalArgs {
     double* mi[3];                // may be null: (running_mean, invstd) pairs [C] for the backward pass
 };
 
+// Channel c of one eval-mode BatchNorm: its (scale, shift) and, where `mi` is not null, its (running_mean, invstd).
+__device__ __forceinline__ void d_bn_eval_channel(const float* gamma, const float* beta, const float* running_mean,
+                                                  const float* running_var, double eps, float* st, double* mi, int c) {
+    const double sc = (double)gamma[c] / sqrt((double)running_var[c] + eps);
+    st[2 * c] = (float)sc;
+    st[2 * c + 1] = (float)((double)beta[c] - (double)running_mean[c] * sc);
+    if (mi) {
+        mi[2 * c] = (double)running_mean[c];
+        mi[2 * c + 1] = 1.0 / sqrt((double)running_var[c] + eps);
+    }
+}
+
 __global__ void __launch_bounds__(128) k_disc_bn_eval(const DiscBnEvalArgs a) {
     const int l = blockIdx.x, c = threadIdx.x;
     if (c >= a.C[l]) return;
-    const double sc = (double)a.gamma[l][c] / sqrt((double)a.running_var[l][c] + a.eps[l]);
-    a.st[l][2 * c] = (float)sc;
-    a.st[l][2 * c + 1] = (float)((double)a.beta[l][c] - (double)a.running_mean[l][c] * sc);
-    if (a.mi[l]) {
-        a.mi[l][2 * c] = (double)a.running_mean[l][c];
-        a.mi[l][2 * c + 1] = 1.0 / sqrt((double)a.running_var[l][c] + a.eps[l]);
-    }
+    d_bn_eval_channel(a.gamma[l], a.beta[l], a.running_mean[l], a.running_var[l], a.eps[l], a.st[l], a.mi[l], c);
 }
 
 __global__ void __launch_bounds__(64) k_disc_bn_count(long long* a, long long* b, long long* c) {
@@ -437,6 +451,14 @@ __device__ __forceinline__ double d_block_sum(double v, double* red) {
     return r;
 }
 
+// One image's three BCE terms, logs clamped at -100: -log(p_real) (target 1), -log(1 - p_fake) (target 0), -log(p_fake) (target 1),
+// each added to its running sum.  The one statement of the term: k_disc_losses and k_srd_losses (srgan_disc_kernels.h) call it.
+__device__ __forceinline__ void d_bce_terms(double pr, double pf, double& real1, double& fake0, double& fake1) {
+    real1 -= fmax(log(pr), -100.0);
+    fake0 -= fmax(log(1.0 - pf), -100.0);
+    fake1 -= fmax(log(pf), -100.0);
+}
+
 __global__ void __launch_bounds__(D_LOSS_THREADS) k_disc_losses(const DiscLossArgs a) {
     __shared__ double red[D_LOSS_THREADS];
     const int tid = threadIdx.x;
@@ -447,12 +469,7 @@ __global__ void __launch_bounds__(D_LOSS_THREADS) k_disc_losses(const DiscLossAr
         se += (double)d * (double)d;
     }
     double real1 = 0.0, fake0 = 0.0, fake1 = 0.0;
-    for (int i = tid; i < a.N; i += D_LOSS_THREADS) {
-        const double pr = a.p_real[i], pf = a.p_fake[i];
-        real1 -= fmax(log(pr), -100.0);
-        fake0 -= fmax(log(1.0 - pf), -100.0);
-        fake1 -= fmax(log(pf), -100.0);
-    }
+    for (int i = tid; i < a.N; i += D_LOSS_THREADS) d_bce_terms(a.p_real[i], a.p_fake[i], real1, fake0, fake1);
     se = d_block_sum(se, red);
     real1 = d_block_sum(real1, red);
     fake0 = d_block_sum(fake0, red);

@@ -576,6 +576,63 @@ def make_srgan_state_dict(kind: str = "default", scale_factor: int = 4, seed: in
     return sd
 
 
+SRGAN_DISC_CONVS = ((0, 3, 64, 3), (2, 64, 64, 3), (5, 64, 128, 3), (8, 128, 128, 3), (11, 128, 256, 3), (15, 256, 512, 1), (17, 512, 1, 1))
+SRGAN_DISC_BNS = ((3, 64), (6, 128), (9, 128), (12, 256))
+
+
+def srgan_disc_param_shapes() -> "OrderedDict[str, tuple]":
+    """state_dict key -> (shape, dtype name) of SRGANDiscriminator, in the module's own order, BatchNorm buffers and
+    num_batches_tracked included."""
+    layers = {i: ("conv", (cin, cout, k)) for i, cin, cout, k in SRGAN_DISC_CONVS}
+    layers.update({i: ("bn", c) for i, c in SRGAN_DISC_BNS})
+    out: "OrderedDict[str, tuple]" = OrderedDict()
+    f = "float32"
+    for i in sorted(layers):
+        what, d = layers[i]
+        if what == "conv":
+            out[f"model.{i}.weight"] = ((d[1], d[0], d[2], d[2]), f)
+            out[f"model.{i}.bias"] = ((d[1],), f)
+        else:
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                out[f"model.{i}.{k}"] = ((d,), f)
+            out[f"model.{i}.num_batches_tracked"] = ((), "int64")
+    return out
+
+
+def make_srgan_disc_state_dict(kind: str = "default", seed: int = WEIGHT_SEED) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights keyed like the reference's SRGANDiscriminator state_dict, from the hash streams "srgan_disc:<kind>:<key>":
+    convolution weights and biases U(+-1/sqrt(fan_in)), the scale of PyTorch's default Conv2d initialisation.
+    kind="default": fresh BatchNorms (gamma 1, beta 0, running_mean 0, running_var 1, num_batches_tracked 0).
+    kind="trained": BatchNorm values far from those, so that a swapped or unused pointer shows: gamma in [0.5, 1.5], beta in +-0.3,
+        running_mean in +-0.2, running_var in [0.2, 3.0], num_batches_tracked 7."""
+    if kind not in ("default", "trained"):
+        raise ValueError(f"unknown weight set {kind!r}")
+    shapes = srgan_disc_param_shapes()
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for key, (shape, dtype) in shapes.items():
+        if dtype == "int64":
+            sd[key] = np.array(7 if kind == "trained" else 0, dtype=np.int64)
+            continue
+        n = int(np.prod(shape))
+        u = hash_uniform(seed, _fnv1a64("srgan_disc:" + kind + ":" + key), n)
+        layer, leaf = key.rsplit(".", 1)
+        wshape = shapes[layer + ".weight"][0]
+        if len(wshape) == 4:
+            v = (2.0 * u - 1.0) / math.sqrt(wshape[1] * wshape[2] * wshape[3])
+        elif kind == "default":
+            v = np.full(n, 1.0 if leaf in ("weight", "running_var") else 0.0)
+        elif leaf == "weight":
+            v = 0.5 + u
+        elif leaf == "bias":
+            v = (2.0 * u - 1.0) * 0.3
+        elif leaf == "running_mean":
+            v = (2.0 * u - 1.0) * 0.2
+        else:                                                  # running_var
+            v = 0.2 + 2.8 * u
+        sd[key] = np.asarray(v).astype(np.float32).reshape(shape)
+    return sd
+
+
 def srgan_inputs_u8(n: int, h: int, w: int, first_index: int = 0) -> np.ndarray:
     """uint8 [n,h,w,3] inputs for the SRGAN tests: the noisy face-like fields of make_batch."""
     return add_gaussian_noise(clean_images_u8(n, h, w, first_index), 25.0, first_index)

@@ -483,6 +483,50 @@ int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* gra
 int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, void* device_blob, void* stream);
 
 /*
+ * The SRGAN trainer's discriminator — SRGANDiscriminator (backend/trainingcode/srgan_code/sr_ganTrainGNew.py:54-80), which that
+ * trainer calls three times per step (:395-404) for d_loss = BCE(D(hr), 1) + BCE(D(fake), 0) and adv_loss = BCE(D(fake), 1).
+ * Forward only: nothing is kept for a backward pass.  Its own handle and blob, as cid_disc_* has.
+ *
+ *   model.0 ... model.10 are DenoiseDiscriminator's layers 0 ... 10 (above); then
+ *  11 Conv2d(128,256,3,p=1)  12 BatchNorm2d(256)  13 LeakyReLU(0.2)  14 AdaptiveAvgPool2d(1)  15 Conv2d(256,512,1)  16 LeakyReLU(0.2)
+ *  17 Conv2d(512,1,1)  18 Sigmoid;   forward(x) = model(x).view(-1): one probability per image.  H2, H4 as above; any H, W >= 1.
+ *
+ * cid_srd_set_weight takes the fourteen convolution tensors by their state_dict keys "model.{0,2,5,8,11,15,17}.{weight,bias}" (fp32,
+ * reference layout); the BatchNorm tensors ("model.{3,6,9,12}.*") are not staged (CID_ERR_KEY) but passed at every forward as
+ * bn[0..3], a cid_disc_bn each, with the eval / train semantics of cid_disc_forward.  cid_srd_upload_weights needs all fourteen
+ * (CID_ERR_STATE otherwise) and waits for its copy.
+ *
+ * cid_srd_forward: arguments, formats, arithmetic, determinism and asynchrony as cid_disc_forward.  Layer 11 runs on the same exact-fp32
+ * MFMA kernel as layers 5 and 8, as two 128-channel halves; the head (average pool, both 1x1 layers, sigmoid) accumulates in fp64
+ * in a fixed order, one workgroup per image, so in eval mode an image's probability is bit-identical in any batch.  The argument
+ * checks, their order and their codes are cid_disc_forward's (with four BatchNorms), all before any launch; train mode with
+ * N*H4*W4 == 1 is CID_ERR_SHAPE ("Expected more than 1 value per channel when training").
+ *
+ * cid_srd_workspace_bytes(N, H, W, training), with a256(v) = v rounded up to a multiple of 256 and every tensor fp32:
+ *     a256(4 * N * max(64*H*W, 128*H2*W2, 256*H4*W4))      region A: a0, then z5, then z11
+ *   + a256(4 * N * max(64*H2*W2, 128*H4*W4))               region B: z2, then z8
+ *   + a256(4 * 4 * 256 * 2)                                (scale, shift) pairs of the four BatchNorms
+ *   + in train mode, for (Ho, Wo, TH, C) in (H2, W2, 16, 64), (H2, W2, 8, 128), (H4, W4, 8, 128), (H4, W4, 8, 256):
+ *       a256(8 * C * 2 * N * ceil(Ho / TH) * ceil(Wo / 16))  fp64 per-tile partial sums of z and z^2
+ *
+ * cid_srd_losses: p_real = D(hr_img) and p_fake = D(fake_hr) (device fp32 [N]) -> device double out[2] = d_loss = BCE(p_real, 1) +
+ * BCE(p_fake, 0), adv_loss = BCE(p_fake, 1), logs clamped at -100 as nn.BCELoss does (the BCE term of cid_disc_losses).  One workgroup,
+ * fp64, fixed order.  CID_ERR_INVALID for a null or misaligned pointer, CID_ERR_SHAPE for N < 1.
+ */
+typedef struct cid_srd_s* cid_srd_t;
+#define CID_SRD_NUM_WEIGHTS 14
+int cid_srd_create(cid_srd_t* out);
+void cid_srd_destroy(cid_srd_t d);
+const char* cid_srd_last_error(cid_srd_t d);
+int cid_srd_set_weight(cid_srd_t d, const char* key, const float* host_data, const int64_t* shape, int ndim);
+size_t cid_srd_packed_weights_bytes(void);
+int cid_srd_upload_weights(cid_srd_t d, void* device_blob, void* stream);
+int cid_srd_workspace_bytes(int N, int H, int W, int training, size_t* bytes);
+int cid_srd_forward(cid_srd_t d, const void* in, int in_fmt, float* out_prob, int N, int H, int W, const cid_disc_bn* bn,
+                    int training, void* workspace, size_t workspace_bytes, void* stream);
+int cid_srd_losses(const float* p_real, const float* p_fake, int N, double* out, void* stream);
+
+/*
  * The generator's backward pass — g_loss.backward() through DenoiseGenerator in the trainer's generator step
  * (backend/trainingcode/denoise_gan_code/training.py:420-426; the module itself :59-74).  fp32 NCHW in and out, CID_DTYPE_F32 only.
  *
