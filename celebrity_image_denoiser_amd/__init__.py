@@ -16,8 +16,9 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
                                   autograd=True its forward is differentiable (HIP backward pass): d_loss.backward() and the
                                   adversarial gradient on the denoised batch, for a stock torch.optim optimizer
     trainer_losses(D, denoised, clean)                  the trainer's d_loss / g_loss / content_loss / adv_loss of one batch
-    SRGANDiscriminator() / load_srgan_discriminator(ckpt)   the SRGAN trainer's discriminator, forward only (eval or train-mode
-                                  BatchNorm); srgan_trainer_losses(D, fake_hr, hr_img, vgg_loss) -> its d_loss / adv_loss / g_loss
+    SRGANDiscriminator() / load_srgan_discriminator(ckpt)   the SRGAN trainer's discriminator (eval or train-mode BatchNorm); with
+                                  autograd=True its forward is differentiable (HIP backward pass), as DenoiseDiscriminator's;
+                                  srgan_trainer_losses(D, fake_hr, hr_img, vgg_loss) -> its d_loss / adv_loss / g_loss
     Adam(params, lr, betas, eps, weight_decay)          the trainer's optimizer as one kernel per step (cid_adam_step); its state
                                   interchanges with torch.optim.Adam's
     ESRGANGenerator(num_residuals=8) / load_esrgan(ckpt)   the server's ESRGAN model (eval mode); enhance(model, x) -> the raw

@@ -39,81 +39,251 @@ DiscBufs disc_saved_bufs(void* saved, const DiscSavedPlan& q) {
     return b;
 }
 
-// Workspace of one backward call.  X holds the gradient of a6 and later of a0, Y the gradient of a3 (the forward's two regions).
-struct DiscBwdPlan {
+// How the launches of layers 2, 5, 8 and 0 tile one backward call, and what the scratch regions they share must hold.  Both
+// discriminators' backward passes plan with it (Plan: DiscPlan, or the SRGAN discriminator's SrdPlan).
+struct DiscBwdTiling {
     int strips[3];                  // BatchNorm strips per image
     int wg_tiles_x[3], wg_tiles[3]; // wgrad items per image of layers 2, 5, 8
     int wg_splits[3];
     int dg_tiles_x[3], dg_tiles[3]; // dgrad tiles of the largest class
     int w0_strips, w0_splits;
-    size_t dl, mean, coef, bnslab, X, Y, part, part_b, part0, total;
+    size_t max_bnslab, max_part, max_part_b;   // bytes, the largest of the three layers
 };
 
 constexpr int kDiscWgCD[3] = {64, 128, 128}, kDiscWgCX[3] = {64, 64, 128}, kDiscWgS[3] = {2, 1, 2};
 constexpr int kDiscDgTileRows[3] = {DiscDgradGeom<64, 64, 2>::TH, DiscDgradGeom<128, 64, 1>::TH, DiscDgradGeom<128, 128, 2>::TH};
 
-void disc_bwd_plan(int N, int H, int W, const DiscPlan& p, DiscBwdPlan& q) {
+template <class Plan>
+void disc_bwd_tiling(int N, int H, int W, const Plan& p, DiscBwdTiling& q) {
     const size_t n = (size_t)N, f = sizeof(float);
     const int ho[3] = {p.H2, p.H2, p.H4}, wo[3] = {p.W2, p.W2, p.W4};
     const int hin[3] = {H, p.H2, p.H2}, win[3] = {W, p.W2, p.W2};
-    size_t bnslab = 0, part = 0, part_b = 0;
+    q.max_bnslab = q.max_part = q.max_part_b = 0;
     for (int l = 0; l < 3; ++l) {
         q.strips[l] = (int)(((long long)ho[l] * wo[l] + D_BN_STRIP - 1) / D_BN_STRIP);
-        bnslab = std::max(bnslab, (size_t)kDiscBnC[l] * 2 * n * q.strips[l] * sizeof(double));
+        q.max_bnslab = std::max(q.max_bnslab, (size_t)kDiscBnC[l] * 2 * n * q.strips[l] * sizeof(double));
         q.wg_tiles_x[l] = (wo[l] + D_TW - 1) / D_TW;
         q.wg_tiles[l] = ((ho[l] + D_WG_TH - 1) / D_WG_TH) * q.wg_tiles_x[l];
         const long long items = (long long)N * q.wg_tiles[l];
         q.wg_splits[l] = (int)std::min<long long>(items, 512 / (kDiscWgCX[l] / 16));
-        part = std::max(part, (size_t)q.wg_splits[l] * kDiscWgCX[l] * kDiscWgCD[l] * 9 * f);
-        part_b = std::max(part_b, (size_t)q.wg_splits[l] * kDiscWgCD[l] * sizeof(double));
+        q.max_part = std::max(q.max_part, (size_t)q.wg_splits[l] * kDiscWgCX[l] * kDiscWgCD[l] * 9 * f);
+        q.max_part_b = std::max(q.max_part_b, (size_t)q.wg_splits[l] * kDiscWgCD[l] * sizeof(double));
         const int hc = (hin[l] + kDiscWgS[l] - 1) / kDiscWgS[l], wc = (win[l] + kDiscWgS[l] - 1) / kDiscWgS[l];
         q.dg_tiles_x[l] = (wc + D_TW - 1) / D_TW;
         q.dg_tiles[l] = ((hc + kDiscDgTileRows[l] - 1) / kDiscDgTileRows[l]) * q.dg_tiles_x[l];
     }
     q.w0_strips = (int)(((long long)H * W + 63) / 64);
     q.w0_splits = (int)std::min<long long>((long long)N * q.w0_strips, 1024);
+}
+
+// Workspace of one backward call.  X holds the gradient of a6 and later of a0, Y the gradient of a3 (the forward's two regions).
+struct DiscBwdPlan : DiscBwdTiling {
+    size_t dl, mean, coef, bnslab, X, Y, part, part_b, part0, total;
+};
+
+void disc_bwd_plan(int N, int H, int W, const DiscPlan& p, DiscBwdPlan& q) {
+    const size_t n = (size_t)N, f = sizeof(float);
+    disc_bwd_tiling(N, H, W, p, q);
     size_t at = 0;
     q.dl = take(at, n * f);
     q.mean = take(at, n * 128 * sizeof(double));
     q.coef = take(at, 3 * 128 * D_COEF * f);
-    q.bnslab = take(at, bnslab);
+    q.bnslab = take(at, q.max_bnslab);
     q.X = take(at, std::max(n * 128 * p.H2 * p.W2, n * 64 * H * W) * f);
     q.Y = take(at, n * 64 * p.H2 * p.W2 * f);
-    q.part = take(at, part);
-    q.part_b = take(at, part_b);
+    q.part = take(at, q.max_part);
+    q.part_b = take(at, q.max_part_b);
     q.part0 = take(at, (size_t)q.w0_splits * 64 * 28 * sizeof(double));
     q.total = at;
 }
 
-template <int CD, int CX, int S, bool BN_IN, bool HEAD>
+// The trailing template arguments are the kernels' (disc_bwd_kernels.h); at their defaults the launches are the denoise discriminator's.
+template <int CD, int CX, int S, bool BN_IN, bool HEAD, bool POOL = false, int CD_TOTAL = CD>
 hipError_t disc_wgrad_launch(const DiscWgradArgs& a, float* dw, float* db, hipStream_t s) {
-    hipLaunchKernelGGL((k_disc_wgrad<CD, CX, S, BN_IN, HEAD>), dim3((unsigned)a.splits, CX / 16), dim3(D_THREADS), 0, s, a);
+    hipLaunchKernelGGL((k_disc_wgrad<CD, CX, S, BN_IN, HEAD, POOL, CD_TOTAL>), dim3((unsigned)a.splits, CX / 16, CD_TOTAL / CD), dim3(D_THREADS),
+                       0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const DiscWgradReduceArgs r{a.part, a.part_b, dw, db, a.splits, CD, CX};
-    hipLaunchKernelGGL(k_disc_wgrad_reduce, dim3((CD * CX * 9 + CD + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
+    const DiscWgradReduceArgs r{a.part, a.part_b, dw, db, a.splits, CD_TOTAL, CX};
+    hipLaunchKernelGGL(k_disc_wgrad_reduce, dim3((CD_TOTAL * CX * 9 + CD_TOTAL + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
     return hipGetLastError();
 }
 
-template <int CD, int CX, int S, bool HEAD>
+template <int CD, int CX, int S, bool HEAD, bool POOL = false, int CD_PART = CD>
 hipError_t disc_dgrad_launch(const DiscDgradArgs& base, int tiles, int N, hipStream_t s) {
     (void)for_each_launch(N, [&](int n0, int n) {
         DiscDgradArgs a = base;
         a.n0 = n0;
         const dim3 grid((unsigned)tiles, (unsigned)n, DiscDgradGeom<CD, CX, S>::CLASSES);
-        hipLaunchKernelGGL((k_disc_dgrad<CD, CX, S, HEAD>), grid, dim3(D_THREADS), 0, s, a);
+        hipLaunchKernelGGL((k_disc_dgrad<CD, CX, S, HEAD, POOL, CD_PART>), grid, dim3(D_THREADS), 0, s, a);
     });
     return hipGetLastError();
 }
 
-template <int C, bool HEAD>
+template <int C, bool HEAD, bool POOL = false>
 hipError_t disc_bn_part_launch(const DiscBnPartArgs& base, int N, hipStream_t s) {
     (void)for_each_launch(N, [&](int n0, int n) {
         DiscBnPartArgs a = base;
         a.n0 = n0;
-        hipLaunchKernelGGL((k_disc_bn_bwd_part<C, HEAD>), dim3((unsigned)a.strips, (unsigned)n), dim3(D_THREADS), 0, s, a);
+        hipLaunchKernelGGL((k_disc_bn_bwd_part<C, HEAD, POOL>), dim3((unsigned)a.strips, (unsigned)n), dim3(D_THREADS), 0, s, a);
     });
     return hipGetLastError();
+}
+
+// The arguments of one launch, as both discriminators' backward passes build them.
+hipError_t disc_bn_reduce_launch(int C, const double* bnslab, long long rows, double count, const cid_disc_bn& bn, const float* st,
+                                 const double* mi, int training, float* coef, float* dgamma, float* dbeta, hipStream_t s) {
+    DiscBnRedArgs a{bnslab, rows, count, bn.gamma, st, mi, training, coef, dgamma, dbeta};
+    hipLaunchKernelGGL(k_disc_bn_bwd_reduce, dim3(C), dim3(D_THREADS), 0, s, a);
+    return hipPeekAtLastError();
+}
+
+DiscBnPartArgs disc_bn_part_args(const float* z, const float* up, const float* dl, const float* coef, const float* st, const double* mi,
+                                 double* bnslab, int N, int strips, long long pix) {
+    return DiscBnPartArgs{z, up, dl, coef, st, mi, bnslab, (long long)N * strips, pix, strips, 0};
+}
+
+DiscWgradArgs disc_wgrad_args(const DiscDzSrc& dz, const float* ain, const float* st_in, float* part, double* part_b, int N, int tiles_x,
+                              int tiles, int splits, int Hin, int Win, int Ho, int Wo) {
+    DiscWgradArgs a{};
+    a.dz = dz;
+    a.ain = ain;
+    a.st_in = st_in;
+    a.part = part;
+    a.part_b = part_b;
+    a.items = (long long)N * tiles;
+    a.splits = splits;
+    a.Hin = Hin;
+    a.Win = Win;
+    a.Ho = Ho;
+    a.Wo = Wo;
+    a.tiles_x = tiles_x;
+    a.tiles = tiles;
+    return a;
+}
+
+DiscDgradArgs disc_dgrad_args(const DiscDzSrc& dz, const float* w, float* out, int tiles_x, int Hin, int Win, int Ho, int Wo) {
+    DiscDgradArgs a{};
+    a.dz = dz;
+    a.w = w;
+    a.out = out;
+    a.Hin = Hin;
+    a.Win = Win;
+    a.Ho = Ho;
+    a.Wo = Wo;
+    a.tiles_x = tiles_x;
+    return a;
+}
+
+// The stages both discriminators share, BatchNorm 9 down to the input, on one call's tensors.
+struct DiscBwdLower {
+    const void* in;
+    int in_fmt, N, H, W, H2, W2, H4, W4, training;
+    const cid_disc_bn* bn;             // BatchNorms 3, 6, 9
+    const float *a0, *z2, *z5, *z8;    // saved by the forward
+    float* const* st;                  // [3]
+    double* const* mi;                 // [3]
+    const float* w[4];                 // model.0, 2, 5, 8 in the packed blob
+    float *gw[4], *gb[4], *ggamma[3], *gbeta[3], *ginput;   // what is asked for (null: not)
+    float* coef[3];                    // scratch, as DiscBwdPlan lays it out
+    double* bnslab;
+    float *X, *Y, *part;
+    double *part_b, *part0;
+};
+
+// BatchNorm 9's upstream gradient is the head's rank-one form (HEAD: dl[N] and coef[2]'s slot 7, the denoise discriminator) or the
+// tensor up9 (the SRGAN discriminator: the data gradient of its model.11, which may be Y).
+template <bool HEAD>
+int disc_bwd_lower(const Call& cx, const DiscBwdLower& c, const DiscBwdTiling& q, const float* up9, const float* dl) {
+    const hipStream_t s = cx.s;
+    const int N = c.N, H = c.H, W = c.W;
+    // what is asked for at each stage: bn9(7) > conv8(6) > bn6(5) > conv5(4) > bn3(3) > conv2(2) > conv0(1) > input(0)
+    const bool want[8] = {c.ginput != nullptr, c.gw[0] || c.gb[0], c.gw[1] || c.gb[1], c.ggamma[0] || c.gbeta[0], c.gw[2] || c.gb[2],
+                          c.ggamma[1] || c.gbeta[1], c.gw[3] || c.gb[3], c.ggamma[2] || c.gbeta[2]};
+    bool below[9];   // below[k]: something at a stage < k is asked for
+    below[0] = false;
+    for (int k = 0; k < 8; ++k) below[k + 1] = below[k] || want[k];
+    if (!below[8]) return CID_OK;
+    const long long P4 = (long long)c.H4 * c.W4, P2 = (long long)c.H2 * c.W2;
+
+    const auto bn_reduce = [&](int l, long long pix) {
+        return disc_bn_reduce_launch(kDiscBnC[l], c.bnslab, (long long)N * q.strips[l], (double)N * (double)pix, c.bn[l], c.st[l], c.mi[l],
+                                     c.training, c.coef[l], c.ggamma[l], c.gbeta[l], s);
+    };
+    const auto bn_part = [&](int l, const float* z, const float* up, long long pix) {
+        return disc_bn_part_args(z, up, dl, c.coef[l], c.st[l], c.mi[l], c.bnslab, N, q.strips[l], pix);
+    };
+    const auto wg_args = [&](int l, const DiscDzSrc& dz, const float* ain, const float* st_in, int Hin, int Win, int Ho, int Wo) {
+        return disc_wgrad_args(dz, ain, st_in, c.part, c.part_b, N, q.wg_tiles_x[l], q.wg_tiles[l], q.wg_splits[l], Hin, Win, Ho, Wo);
+    };
+    const auto dg_args = [&](int l, int ci, const DiscDzSrc& dz, float* out, int Hin, int Win, int Ho, int Wo) {
+        return disc_dgrad_args(dz, c.w[ci], out, q.dg_tiles_x[l], Hin, Win, Ho, Wo);
+    };
+    float* const X = c.X;
+    float* const Y = c.Y;
+
+    // BN9, layer 8
+    if (disc_bn_part_launch<128, HEAD>(bn_part(2, c.z8, up9, P4), N, s) != hipSuccess) return cx.hip("bn9 sums");
+    if (bn_reduce(2, P4) != hipSuccess) return cx.hip("bn9 reduce");
+    const DiscDzSrc dz8{c.z8, up9, dl, c.coef[2]};
+    if (want[6] && disc_wgrad_launch<128, 128, 2, true, HEAD>(wg_args(2, dz8, c.z5, c.st[1], c.H2, c.W2, c.H4, c.W4), c.gw[3], c.gb[3], s) != hipSuccess)
+        return cx.hip("wgrad8");
+    if (!below[6]) return CID_OK;
+    if (disc_dgrad_launch<128, 128, 2, HEAD>(dg_args(2, 3, dz8, X, c.H2, c.W2, c.H4, c.W4), q.dg_tiles[2], N, s) != hipSuccess) return cx.hip("dgrad8");
+    // BN6, layer 5
+    if (disc_bn_part_launch<128, false>(bn_part(1, c.z5, X, P2), N, s) != hipSuccess) return cx.hip("bn6 sums");
+    if (bn_reduce(1, P2) != hipSuccess) return cx.hip("bn6 reduce");
+    const DiscDzSrc dz5{c.z5, X, nullptr, c.coef[1]};
+    if (want[4] && disc_wgrad_launch<128, 64, 1, true, false>(wg_args(1, dz5, c.z2, c.st[0], c.H2, c.W2, c.H2, c.W2), c.gw[2], c.gb[2], s) != hipSuccess)
+        return cx.hip("wgrad5");
+    if (!below[4]) return CID_OK;
+    if (disc_dgrad_launch<128, 64, 1, false>(dg_args(1, 2, dz5, Y, c.H2, c.W2, c.H2, c.W2), q.dg_tiles[1], N, s) != hipSuccess) return cx.hip("dgrad5");
+    // BN3, layer 2
+    if (disc_bn_part_launch<64, false>(bn_part(0, c.z2, Y, P2), N, s) != hipSuccess) return cx.hip("bn3 sums");
+    if (bn_reduce(0, P2) != hipSuccess) return cx.hip("bn3 reduce");
+    const DiscDzSrc dz2{c.z2, Y, nullptr, c.coef[0]};
+    if (want[2] && disc_wgrad_launch<64, 64, 2, false, false>(wg_args(0, dz2, c.a0, nullptr, H, W, c.H2, c.W2), c.gw[1], c.gb[1], s) != hipSuccess)
+        return cx.hip("wgrad2");
+    if (!below[2]) return CID_OK;
+    if (disc_dgrad_launch<64, 64, 2, false>(dg_args(0, 1, dz2, X, H, W, c.H2, c.W2), q.dg_tiles[0], N, s) != hipSuccess) return cx.hip("dgrad2");
+    // layer 0
+    if (want[1]) {
+        DiscWgrad0Args a{c.in, c.a0, X, c.part0, (long long)N * q.w0_strips, q.w0_splits, q.w0_strips, H, W};
+        if (c.in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_wgrad0<true>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_disc_wgrad0<false>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("wgrad0");
+        DiscWgrad0ReduceArgs r{c.part0, c.gw[0], c.gb[0], q.w0_splits};
+        hipLaunchKernelGGL(k_disc_wgrad0_reduce, dim3((64 * 28 + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
+        if (hipPeekAtLastError() != hipSuccess) return cx.hip("wgrad0 reduce");
+    }
+    if (want[0]) {
+        if (const int rc = cx.launches(N, "dgrad0", [&](int n0, int n) {
+            DiscDgrad0Args a{c.a0, X, c.w[0], c.ginput, H, W, n0};
+            const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)n);
+            hipLaunchKernelGGL(k_disc_dgrad0, grid, dim3(D_THREADS), 0, s, a);
+        })) return rc;
+    }
+    return CID_OK;
+}
+
+// The argument checks of a backward entry point that come before its shape check, in the order cid.h documents: nconv convolutions'
+// and nbn BatchNorms' gradient pointers in g_w, g_b, g_gamma, g_beta.
+int disc_bwd_check_args(const Call& cx, const void* in, int in_fmt, const float* grad_prob, const cid_disc_bn* bn, int nbn, const void* saved,
+                        const void* grads, const void* workspace, float* const* g_w, float* const* g_b, int nconv, float* const* g_gamma,
+                        float* const* g_beta, const float* g_input) {
+    if (!in || !grad_prob || !bn || !saved || !grads || !workspace) return cx.fail(CID_ERR_INVALID, "null pointer");
+    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return cx.fail(CID_ERR_INVALID, "unknown input format");
+    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)grad_prob & 3))
+        return cx.fail(CID_ERR_INVALID, "misaligned fp32 operand");
+    for (int l = 0; l < nbn; ++l)
+        if (!bn[l].gamma) return cx.fail(CID_ERR_INVALID, "null BatchNorm weight pointer");
+    bool misaligned = ((uintptr_t)g_input & 3) != 0;
+    for (int i = 0; i < nconv; ++i) misaligned = misaligned || ((uintptr_t)g_w[i] & 3) || ((uintptr_t)g_b[i] & 3);
+    for (int l = 0; l < nbn; ++l) misaligned = misaligned || ((uintptr_t)g_gamma[l] & 3) || ((uintptr_t)g_beta[l] & 3);
+    if (misaligned) return cx.fail(CID_ERR_INVALID, "misaligned gradient pointer");
+    if (g_input && in_fmt != CID_FMT_F32_NCHW)
+        return cx.fail(CID_ERR_INVALID, "a uint8 input has no gradient (grads.input must be null)");
+    return CID_OK;
 }
 
 // Shape checks shared by the backward entry points.
@@ -164,18 +334,9 @@ int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* gra
                       size_t workspace_bytes, void* stream) {
     if (!d) return CID_ERR_INVALID;
     const Call cx(d, "cid_disc_backward", stream);
-    if (!in || !grad_prob || !bn || !saved || !g || !workspace) return cx.fail(CID_ERR_INVALID, "null pointer");
-    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return cx.fail(CID_ERR_INVALID, "unknown input format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)grad_prob & 3))
-        return cx.fail(CID_ERR_INVALID, "misaligned fp32 operand");
-    for (int l = 0; l < 3; ++l)
-        if (!bn[l].gamma) return cx.fail(CID_ERR_INVALID, "null BatchNorm weight pointer");
-    bool misaligned = ((uintptr_t)g->input & 3) != 0;
-    for (int i = 0; i < 5; ++i) misaligned = misaligned || ((uintptr_t)g->w[i] & 3) || ((uintptr_t)g->b[i] & 3);
-    for (int l = 0; l < 3; ++l) misaligned = misaligned || ((uintptr_t)g->gamma[l] & 3) || ((uintptr_t)g->beta[l] & 3);
-    if (misaligned) return cx.fail(CID_ERR_INVALID, "misaligned gradient pointer");
-    if (g->input && in_fmt != CID_FMT_F32_NCHW)
-        return cx.fail(CID_ERR_INVALID, "a uint8 input has no gradient (grads.input must be null)");
+    if (const int rc = disc_bwd_check_args(cx, in, in_fmt, grad_prob, bn, 3, saved, g, workspace, g ? g->w : nullptr, g ? g->b : nullptr, 5,
+                                           g ? g->gamma : nullptr, g ? g->beta : nullptr, g ? g->input : nullptr))
+        return rc;
     DiscPlan p;
     if (const int rc = disc_bwd_shape(cx, N, H, W, training, p)) return rc;
     DiscSavedPlan sp;
@@ -191,119 +352,51 @@ int cid_disc_backward(cid_disc_t d, const void* in, int in_fmt, const float* gra
     char* ws = static_cast<char*>(workspace);
     float* dl = reinterpret_cast<float*>(ws + q.dl);
     double* mean = reinterpret_cast<double*>(ws + q.mean);
-    float* coef[3];
-    for (int l = 0; l < 3; ++l) coef[l] = reinterpret_cast<float*>(ws + q.coef) + l * 128 * D_COEF;
-    double* bnslab = reinterpret_cast<double*>(ws + q.bnslab);
-    float* X = reinterpret_cast<float*>(ws + q.X);
-    float* Y = reinterpret_cast<float*>(ws + q.Y);
-    float* part = reinterpret_cast<float*>(ws + q.part);
-    double* part_b = reinterpret_cast<double*>(ws + q.part_b);
-    double* part0 = reinterpret_cast<double*>(ws + q.part0);
     const float* blob = d->dev_blob;
+    DiscBwdLower c{};
+    c.in = in;
+    c.in_fmt = in_fmt;
+    c.N = N, c.H = H, c.W = W, c.H2 = p.H2, c.W2 = p.W2, c.H4 = p.H4, c.W4 = p.W4;
+    c.training = training;
+    c.bn = bn;
+    c.a0 = sv.a0, c.z2 = sv.z2, c.z5 = sv.z5, c.z8 = sv.z8;
+    c.st = sv.st;
+    c.mi = sv.mi;
+    for (int i = 0; i < 4; ++i) {
+        c.w[i] = blob + kDiscBlob.off[i];
+        c.gw[i] = g->w[i];
+        c.gb[i] = g->b[i];
+    }
+    for (int l = 0; l < 3; ++l) {
+        c.ggamma[l] = g->gamma[l];
+        c.gbeta[l] = g->beta[l];
+        c.coef[l] = reinterpret_cast<float*>(ws + q.coef) + l * 128 * D_COEF;
+    }
+    c.ginput = g->input;
+    c.bnslab = reinterpret_cast<double*>(ws + q.bnslab);
+    c.X = reinterpret_cast<float*>(ws + q.X);
+    c.Y = reinterpret_cast<float*>(ws + q.Y);
+    c.part = reinterpret_cast<float*>(ws + q.part);
+    c.part_b = reinterpret_cast<double*>(ws + q.part_b);
+    c.part0 = reinterpret_cast<double*>(ws + q.part0);
 
-    // what is asked for at or below each stage: head(8) > bn9(7) > conv8(6) > bn6(5) > conv5(4) > bn3(3) > conv2(2) > conv0(1) > input(0)
-    const bool want[9] = {g->input != nullptr, g->w[0] || g->b[0], g->w[1] || g->b[1], g->gamma[0] || g->beta[0], g->w[2] || g->b[2],
-                          g->gamma[1] || g->beta[1], g->w[3] || g->b[3], g->gamma[2] || g->beta[2], g->w[4] || g->b[4]};
-    bool below[10];   // below[k]: something at a stage < k is asked for
-    below[0] = false;
-    for (int k = 0; k < 9; ++k) below[k + 1] = below[k] || want[k];
-    if (!below[9]) return CID_OK;
-    const long long P4 = (long long)p.H4 * p.W4, P2 = (long long)p.H2 * p.W2;
+    bool any = g->input || g->w[4] || g->b[4];
+    for (int i = 0; i < 4; ++i) any = any || g->w[i] || g->b[i];
+    for (int l = 0; l < 3; ++l) any = any || g->gamma[l] || g->beta[l];
+    if (!any) return CID_OK;
+    const long long P4 = (long long)p.H4 * p.W4;
 
-    // head
+    // head (stage 8); the rest is the shared chain, with BatchNorm 9's upstream dl[n] * w12[c] / P4
     if (const int rc = cx.launches(N, "head", [&](int n0, int n) {
         DiscHeadBwdArgs a{sv.z8, sv.st[2], blob + kDiscBlob.off[4], grad_prob, mean, dl, P4, n0};
         hipLaunchKernelGGL(k_disc_head_bwd, dim3((unsigned)n), dim3(D_HEAD_THREADS), 0, s, a);
     })) return rc;
     {
-        DiscHeadReduceArgs a{mean, dl, blob + kDiscBlob.off[4], g->w[4], g->b[4], coef[2], (double)P4, N};
+        DiscHeadReduceArgs a{mean, dl, blob + kDiscBlob.off[4], g->w[4], g->b[4], c.coef[2], (double)P4, N};
         hipLaunchKernelGGL(k_disc_head_reduce, dim3(1), dim3(128), 0, s, a);
         if (hipPeekAtLastError() != hipSuccess) return cx.hip("head reduce");
     }
-    if (!below[8]) return CID_OK;
-
-    const auto bn_reduce = [&](int l, long long pix) {
-        DiscBnRedArgs a{bnslab, (long long)N * q.strips[l], (double)N * (double)pix, bn[l].gamma, sv.st[l], sv.mi[l], training,
-                        coef[l], g->gamma[l], g->beta[l]};
-        hipLaunchKernelGGL(k_disc_bn_bwd_reduce, dim3(kDiscBnC[l]), dim3(D_THREADS), 0, s, a);
-        return hipPeekAtLastError();
-    };
-    const auto bn_part = [&](int l, const float* z, const float* up, long long pix) {
-        DiscBnPartArgs a{z, up, dl, coef[l], sv.st[l], sv.mi[l], bnslab, (long long)N * q.strips[l], pix, q.strips[l], 0};
-        return a;
-    };
-    const auto wg_args = [&](int l, const DiscDzSrc& dz, const float* ain, const float* st_in, int Hin, int Win, int Ho, int Wo) {
-        DiscWgradArgs a{};
-        a.dz = dz;
-        a.ain = ain;
-        a.st_in = st_in;
-        a.part = part;
-        a.part_b = part_b;
-        a.items = (long long)N * q.wg_tiles[l];
-        a.splits = q.wg_splits[l];
-        a.Hin = Hin;
-        a.Win = Win;
-        a.Ho = Ho;
-        a.Wo = Wo;
-        a.tiles_x = q.wg_tiles_x[l];
-        a.tiles = q.wg_tiles[l];
-        return a;
-    };
-    const auto dg_args = [&](int l, int ci, const DiscDzSrc& dz, float* out, int Hin, int Win, int Ho, int Wo) {
-        DiscDgradArgs a{};
-        a.dz = dz;
-        a.w = blob + kDiscBlob.off[ci];
-        a.out = out;
-        a.Hin = Hin;
-        a.Win = Win;
-        a.Ho = Ho;
-        a.Wo = Wo;
-        a.tiles_x = q.dg_tiles_x[l];
-        return a;
-    };
-
-    // BN9 (upstream: the head's dl[n] * w12[c] / P4), layer 8
-    if (disc_bn_part_launch<128, true>(bn_part(2, sv.z8, nullptr, P4), N, s) != hipSuccess) return cx.hip("bn9 sums");
-    if (bn_reduce(2, P4) != hipSuccess) return cx.hip("bn9 reduce");
-    const DiscDzSrc dz8{sv.z8, nullptr, dl, coef[2]};
-    if (want[6] && disc_wgrad_launch<128, 128, 2, true, true>(wg_args(2, dz8, sv.z5, sv.st[1], p.H2, p.W2, p.H4, p.W4), g->w[3], g->b[3], s) != hipSuccess)
-        return cx.hip("wgrad8");
-    if (!below[6]) return CID_OK;
-    if (disc_dgrad_launch<128, 128, 2, true>(dg_args(2, 3, dz8, X, p.H2, p.W2, p.H4, p.W4), q.dg_tiles[2], N, s) != hipSuccess) return cx.hip("dgrad8");
-    // BN6, layer 5
-    if (disc_bn_part_launch<128, false>(bn_part(1, sv.z5, X, P2), N, s) != hipSuccess) return cx.hip("bn6 sums");
-    if (bn_reduce(1, P2) != hipSuccess) return cx.hip("bn6 reduce");
-    const DiscDzSrc dz5{sv.z5, X, nullptr, coef[1]};
-    if (want[4] && disc_wgrad_launch<128, 64, 1, true, false>(wg_args(1, dz5, sv.z2, sv.st[0], p.H2, p.W2, p.H2, p.W2), g->w[2], g->b[2], s) != hipSuccess)
-        return cx.hip("wgrad5");
-    if (!below[4]) return CID_OK;
-    if (disc_dgrad_launch<128, 64, 1, false>(dg_args(1, 2, dz5, Y, p.H2, p.W2, p.H2, p.W2), q.dg_tiles[1], N, s) != hipSuccess) return cx.hip("dgrad5");
-    // BN3, layer 2
-    if (disc_bn_part_launch<64, false>(bn_part(0, sv.z2, Y, P2), N, s) != hipSuccess) return cx.hip("bn3 sums");
-    if (bn_reduce(0, P2) != hipSuccess) return cx.hip("bn3 reduce");
-    const DiscDzSrc dz2{sv.z2, Y, nullptr, coef[0]};
-    if (want[2] && disc_wgrad_launch<64, 64, 2, false, false>(wg_args(0, dz2, sv.a0, nullptr, H, W, p.H2, p.W2), g->w[1], g->b[1], s) != hipSuccess)
-        return cx.hip("wgrad2");
-    if (!below[2]) return CID_OK;
-    if (disc_dgrad_launch<64, 64, 2, false>(dg_args(0, 1, dz2, X, H, W, p.H2, p.W2), q.dg_tiles[0], N, s) != hipSuccess) return cx.hip("dgrad2");
-    // layer 0
-    if (want[1]) {
-        DiscWgrad0Args a{in, sv.a0, X, part0, (long long)N * q.w0_strips, q.w0_splits, q.w0_strips, H, W};
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_disc_wgrad0<true>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_disc_wgrad0<false>, dim3((unsigned)q.w0_splits), dim3(D_THREADS), 0, s, a);
-        if (hipPeekAtLastError() != hipSuccess) return cx.hip("wgrad0");
-        DiscWgrad0ReduceArgs r{part0, g->w[0], g->b[0], q.w0_splits};
-        hipLaunchKernelGGL(k_disc_wgrad0_reduce, dim3((64 * 28 + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, s, r);
-        if (hipPeekAtLastError() != hipSuccess) return cx.hip("wgrad0 reduce");
-    }
-    if (want[0]) {
-        if (const int rc = cx.launches(N, "dgrad0", [&](int n0, int n) {
-            DiscDgrad0Args a{sv.a0, X, blob + kDiscBlob.off[0], g->input, H, W, n0};
-            const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)n);
-            hipLaunchKernelGGL(k_disc_dgrad0, grid, dim3(D_THREADS), 0, s, a);
-        })) return rc;
-    }
-    return CID_OK;
+    return disc_bwd_lower<true>(cx, c, q, nullptr, dl);
 }
 
 int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, void* device_blob, void* stream) {

@@ -84,6 +84,8 @@ struct SrdBufs {
     float *a0, *z2, *z5, *z8, *z11;
     float* st[SRD_BNS];      // (scale, shift) pairs of the four BatchNorms
     double* slab[SRD_BNS];   // train mode: per-tile partial sums
+    double* mi[SRD_BNS];     // (mean, invstd) pairs, or null
+    double *pooled, *hidden; // the head's 256 pooled means and 512 hidden pre-activations per image, or null (both or neither)
 };
 
 // The forward's launch sequence on checked arguments.
@@ -103,13 +105,18 @@ int srd_forward_run(const Call& cx, const void* in, int in_fmt, float* out, int 
             e.st[l] = b.st[l];
             e.C[l] = kSrdBnC[l];
         }
-        hipLaunchKernelGGL(k_srd_bn_eval, dim3(SRD_BNS), dim3(SRD_BN_MAXC), 0, s, e);
+        if (b.mi[0]) {
+            SrdBnEvalSavedArgs es{e, {b.mi[0], b.mi[1], b.mi[2], b.mi[3]}};
+            hipLaunchKernelGGL(k_srd_bn_eval_saved, dim3(SRD_BNS), dim3(SRD_BN_MAXC), 0, s, es);
+        } else {
+            hipLaunchKernelGGL(k_srd_bn_eval, dim3(SRD_BNS), dim3(SRD_BN_MAXC), 0, s, e);
+        }
         if (hipPeekAtLastError() != hipSuccess) return cx.hip("bn_eval");
     }
     // layer 0
     if (const int rc = disc_conv0_launches(cx, in, in_fmt, b.a0, blob + kSrdBlob.off[0], N, H, W)) return rc;
     const auto stats = [&](int l, long long pix) {
-        return disc_stats_launch(bn[l], kSrdBnC[l], b.slab[l], (long long)N * p.tiles[l], (double)N * (double)pix, b.st[l], nullptr, s);
+        return disc_stats_launch(bn[l], kSrdBnC[l], b.slab[l], (long long)N * p.tiles[l], (double)N * (double)pix, b.st[l], b.mi[l], s);
     };
     const auto conv_args = [&](const float* src, float* dst, int ci, const float* st_in, int l, int Hin, int Win, int Ho, int Wo) {
         return disc_conv_args(src, dst, blob + kSrdBlob.off[ci], st_in, training ? b.slab[l] : nullptr, (long long)N * p.tiles[l], Hin,
@@ -135,7 +142,12 @@ int srd_forward_run(const Call& cx, const void* in, int in_fmt, float* out, int 
     // head: BN12 + LeakyReLU, average pool, the two 1x1 convolutions, sigmoid
     if (const int rc = cx.launches(N, "head", [&](int n0, int n) {
         SrdHeadArgs a{b.z11, b.st[3], blob + kSrdBlob.off[5], blob + kSrdBlob.off[6], out, (long long)p.H4 * p.W4, n0};
-        hipLaunchKernelGGL(k_srd_head, dim3((unsigned)n), dim3(SRD_HEAD_THREADS), 0, s, a);
+        if (b.pooled) {
+            SrdHeadSavedArgs as{a, b.pooled, b.hidden};
+            hipLaunchKernelGGL(k_srd_head_saved, dim3((unsigned)n), dim3(SRD_HEAD_THREADS), 0, s, as);
+        } else {
+            hipLaunchKernelGGL(k_srd_head, dim3((unsigned)n), dim3(SRD_HEAD_THREADS), 0, s, a);
+        }
     })) return rc;
     if (training) {
         SrdBnCountArgs c{};

@@ -1219,6 +1219,7 @@ int cid_launch_work_ex(cid_handle_t h, int i, int N, int H, int W, double* flops
 #include "api/disc_forward.h"     // cid_disc_*: weights, forward
 #include "api/disc_backward.h"    // cid_disc_*: saved forward, backward, device pack, masks, losses
 #include "api/srgan_disc.h"       // cid_srd_*: the SRGAN trainer's discriminator, forward and losses
+#include "api/srgan_disc_backward.h"   // cid_srd_*: saved forward, backward, device pack, masks
 #include "api/adam.h"             // cid_adam_step
 
 // ---- the generator's backward pass (gen_bwd_kernels.h) ----

@@ -27,12 +27,20 @@
 //   * k_disc_wgrad0 / k_disc_wgrad0_reduce / k_disc_dgrad0: layer 0 (K = 27) on the VALU; LeakyReLU's mask is a0 > 0.
 //   * k_disc_masks: testing aid, the four masks as the kernels above decide them.
 //   * k_disc_pack: the forward's packed blob from the ten parameter tensors, on the device.
+// The SRGAN trainer's discriminator (cid_srd_backward, srgan_disc_bwd_kernels.h) runs its layers 0-10 on these kernels as they are
+// and its 128 -> 256 layer on further instantiations, through trailing template arguments that default to the kernels above: POOL, the
+// upstream gradient in a third form (D_UP_POOL: one value per image and channel, what an average pool passes down); CD_PART, the
+// data gradient reading the packed weights in COUT-channel parts; CD_TOTAL, the weight gradient running one part per grid z.
 #pragma once
 #include "disc_kernels.h"
 
 namespace cid {
 
 constexpr int D_COEF = 8;
+
+// Where the gradient of a BatchNorm's activated output comes from: a tensor; the denoise head's rank-one dl[n] * coef[c][7]; or
+// one value per (image, channel), up[n][c] (the pooled head of the SRGAN discriminator: dm[n][c] / P).
+constexpr int D_UP_TENSOR = 0, D_UP_HEAD = 1, D_UP_POOL = 2;
 
 __device__ __forceinline__ float d_slope(float y) { return y > 0.0f ? 1.0f : 0.2f; }
 
@@ -120,7 +128,7 @@ constexpr int D_BN_STRIP = 512;
 struct DiscBnPartArgs {
     const float* z;       // raw z of this BatchNorm, C8
     const float* up;      // gradient of the activated tensor, C8 (unused with HEAD)
-    const float* dl;      // HEAD: [N]
+    const float* dl;      // HEAD: [N]; POOL: [N][C]
     const float* coef;    // HEAD: slot 7 of this layer's coef
     const float* st;      // (scale, shift) pairs
     const double* mi;     // (mean, invstd) pairs
@@ -129,8 +137,10 @@ struct DiscBnPartArgs {
     int strips, n0;
 };
 
-template <int C, bool HEAD>
+template <int C, bool HEAD, bool POOL = false>
 __global__ void __launch_bounds__(D_THREADS) k_disc_bn_bwd_part(const DiscBnPartArgs a) {
+    static_assert(!(HEAD && POOL), "one form of upstream gradient");
+    constexpr int UP = POOL ? D_UP_POOL : (HEAD ? D_UP_HEAD : D_UP_TENSOR);
     constexpr int PS = D_THREADS / (C / 4);   // pixel slots
     __shared__ double red[D_THREADS * 8];
     const int tid = threadIdx.x, half = tid & 1, ps = (tid >> 1) % PS, cb = tid / (2 * PS);
@@ -146,13 +156,13 @@ __global__ void __launch_bounds__(D_THREADS) k_disc_bn_bwd_part(const DiscBnPart
         t[j] = a.st[2 * c + 1];
         mean[j] = (float)a.mi[2 * c];
         inv[j] = (float)a.mi[2 * c + 1];
-        uh[j] = HEAD ? a.dl[n] * a.coef[c * D_COEF + 7] : 0.0f;
+        uh[j] = HEAD ? a.dl[n] * a.coef[c * D_COEF + 7] : (UP == D_UP_POOL ? a.dl[n * C + c] : 0.0f);
     }
     double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (long long p = p0 + ps; p < p1; p += PS) {
         const d_f32x4 z = *reinterpret_cast<const d_f32x4*>(a.z + base + (size_t)p * 8);
         d_f32x4 u = d_f32x4{uh[0], uh[1], uh[2], uh[3]};
-        if (!HEAD) u = *reinterpret_cast<const d_f32x4*>(a.up + base + (size_t)p * 8);
+        if (UP == D_UP_TENSOR) u = *reinterpret_cast<const d_f32x4*>(a.up + base + (size_t)p * 8);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float g = u[j] * d_slope(d_bn(s[j], z[j], t[j]));
@@ -232,19 +242,22 @@ __global__ void __launch_bounds__(D_THREADS) k_disc_bn_bwd_reduce(const DiscBnRe
 struct DiscDzSrc {
     const float* z;      // C8, CD channels, Ho x Wo: the saved raw z of this convolution
     const float* up;     // C8, same shape: gradient of the activated tensor (null with HEAD)
-    const float* dl;     // HEAD: [N]
+    const float* dl;     // HEAD: [N]; POOL: [N][all channels of the tensor]
     const float* coef;   // [CD][D_COEF]
 };
 
-// Four consecutive channels (first channel c, a multiple of 4) of dz at element offset `off` of image n.
-template <bool HEAD>
-__device__ __forceinline__ d_f32x4 d_load_dz(const DiscDzSrc& s, const float* lds_cf, size_t n, size_t off, int c) {
+// Four consecutive channels (first channel c of lds_cf, a multiple of 4) of dz at element offset `off` of image n.  POOL: `pool` is
+// the index of lds_cf's channel 0 of this image in dl.
+template <int UP>
+__device__ __forceinline__ d_f32x4 d_load_dz(const DiscDzSrc& s, const float* lds_cf, size_t n, size_t off, int c, size_t pool = 0) {
     const d_f32x4 z = *reinterpret_cast<const d_f32x4*>(s.z + off);
     d_f32x4 u;
-    if (HEAD) {
+    if (UP == D_UP_HEAD) {
         const float dl = s.dl[n];
 #pragma unroll
         for (int j = 0; j < 4; ++j) u[j] = dl * lds_cf[(c + j) * D_COEF + 7];
+    } else if (UP == D_UP_POOL) {
+        u = *reinterpret_cast<const d_f32x4*>(s.dl + pool + c);
     } else {
         u = *reinterpret_cast<const d_f32x4*>(s.up + off);
     }
@@ -261,7 +274,8 @@ __device__ __forceinline__ d_f32x4 d_load_dz(const DiscDzSrc& s, const float* ld
 // B operand is a stride-1 read of a dz halo whatever S is.
 struct DiscDgradArgs {
     DiscDzSrc dz;
-    const float* w;       // the forward's packed weights of this layer: [CX/8][9 taps][8][CD]
+    const float* w;       // the forward's packed weights of this layer: [CX/8][9 taps][8][CD] (CD_PART < CD: one such block of
+                          // CD_PART channels, then their biases, per part: DiscConvArgs::w)
     float* out;           // C8, CX channels, Hin x Win
     int Hin, Win, Ho, Wo;
     int tiles_x;          // tiles per tile row of class (0, 0), the largest class
@@ -286,8 +300,12 @@ struct DiscDgradGeom {
     static_assert(S == 1 || S == 2, "stride");
 };
 
-template <int CD, int CX, int S, bool HEAD>
+// POOL: the upstream gradient is D_UP_POOL (HEAD false).  CD_PART < CD: the packed weights come in CD_PART-channel parts.  Left at
+// their defaults the kernel is the denoise discriminator's.
+template <int CD, int CX, int S, bool HEAD, bool POOL = false, int CD_PART = CD>
 __global__ void __launch_bounds__(D_THREADS, 2) k_disc_dgrad(const DiscDgradArgs a) {
+    static_assert(CD % CD_PART == 0 && !(HEAD && POOL), "whole parts, one form of upstream gradient");
+    constexpr int UP = POOL ? D_UP_POOL : (HEAD ? D_UP_HEAD : D_UP_TENSOR);
     using G = DiscDgradGeom<CD, CX, S>;
     constexpr int WM = G::WM, TH = G::TH, HWD = G::HWD, NPIX = G::NPIX, XSTR = G::XSTR, WSTR = G::WSTR, HOFF = G::HOFF;
     __shared__ float lds_x[8 * XSTR];
@@ -330,7 +348,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_dgrad(const DiscDgradArgs
                 const int oy = i0 - HOFF + hy, ox = j0 - HOFF + hx;
                 d_f32x4 v = d_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
                 if (oy >= 0 && oy < a.Ho && ox >= 0 && ox < a.Wo)
-                    v = d_load_dz<HEAD>(a.dz, lds_cf, n, src + ((size_t)oy * a.Wo + ox) * 8 + h * 4, chunk * 8 + h * 4);
+                    v = d_load_dz<UP>(a.dz, lds_cf, n, src + ((size_t)oy * a.Wo + ox) * 8 + h * 4, chunk * 8 + h * 4, n * CD);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) lds_x[(h * 4 + j) * XSTR + p] = v[j];
             }
@@ -338,7 +356,15 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_dgrad(const DiscDgradArgs
         // ---- this chunk's weights, transposed: row (tap, dz channel) holds the CX input channels
         for (int i = tid; i < 18 * CX; i += D_THREADS) {
             const int ci = i % CX, r = i / CX, h = r & 1, tap = r >> 1;
-            const d_f32x4 v = *reinterpret_cast<const d_f32x4*>(a.w + ((size_t)((ci >> 3) * 9 + tap) * 8 + (ci & 7)) * CD + chunk * 8 + h * 4);
+            const size_t row = (size_t)((ci >> 3) * 9 + tap) * 8 + (ci & 7);
+            d_f32x4 v;
+            if constexpr (CD_PART == CD) {
+                v = *reinterpret_cast<const d_f32x4*>(a.w + row * CD + chunk * 8 + h * 4);
+            } else {   // the chunk's part of the weights, and its channels there
+                const int wpart = chunk * 8 / CD_PART;
+                const float* wp = a.w + (size_t)wpart * (CX * 9 * CD_PART + CD_PART);
+                v = *reinterpret_cast<const d_f32x4*>(wp + row * CD_PART + (chunk * 8 - wpart * CD_PART) + h * 4);
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) lds_w[(tap * 8 + h * 4 + j) * WSTR + ci] = v[j];
         }
@@ -387,7 +413,7 @@ struct DiscWgradArgs {
     DiscDzSrc dz;
     const float* ain;      // C8, CX channels, Hin x Win: a0, or the previous convolution's raw z (BN_IN)
     const float* st_in;    // BN_IN: (scale, shift) of the previous BatchNorm
-    float* part;           // out: part[(((split*(CX/16) + block)*CD + co)*9 + tap)*16 + ci%16]
+    float* part;           // out: part[(((split*(CX/16) + block)*CD + co)*9 + tap)*16 + ci%16]   (CD: all channels of the layer)
     double* part_b;        // out: part_b[split*CD + co] (written by channel block 0)
     long long items;       // N * tiles
     int splits;
@@ -410,8 +436,12 @@ struct DiscWgradGeom {
     static_assert(S == 1 ? (RS % 2 == 1) : (RS % 16 == 8), "row stride");
 };
 
-template <int CD, int CX, int S, bool BN_IN, bool HEAD>
+// POOL: the upstream gradient is D_UP_POOL (HEAD false).  CD_TOTAL > CD: the layer has CD_TOTAL dz channels and the grid's z counts
+// its CD-channel parts (as k_disc_conv's COUT_TOTAL): grid = (splits, CX / 16, CD_TOTAL / CD).
+template <int CD, int CX, int S, bool BN_IN, bool HEAD, bool POOL = false, int CD_TOTAL = CD>
 __global__ void __launch_bounds__(D_THREADS, 2) k_disc_wgrad(const DiscWgradArgs a) {
+    static_assert(CD_TOTAL % CD == 0 && !(HEAD && POOL), "whole parts, one form of upstream gradient");
+    constexpr int UP = POOL ? D_UP_POOL : (HEAD ? D_UP_HEAD : D_UP_TENSOR);
     using G = DiscWgradGeom<S>;
     constexpr int HH = G::HH, HWD = G::HWD, RS = G::RS, XSTR = G::XSTR, ZSTR = G::ZSTR;
     constexpr int RT = CD / 64;   // 16-channel row tiles per wave
@@ -425,8 +455,9 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_wgrad(const DiscWgradArgs
     const int split = blockIdx.x, blk = blockIdx.y;
     const long long it0 = a.items * split / a.splits, it1 = a.items * (split + 1) / a.splits;
     const size_t in_plane = (size_t)a.Hin * a.Win, out_plane = (size_t)a.Ho * a.Wo;
+    const int co0 = CD_TOTAL == CD ? 0 : (int)blockIdx.z * CD;   // first dz channel of this part
 
-    for (int i = tid; i < CD * D_COEF; i += D_THREADS) lds_cf[i] = a.dz.coef[i];
+    for (int i = tid; i < CD * D_COEF; i += D_THREADS) lds_cf[i] = a.dz.coef[co0 * D_COEF + i];
     if (BN_IN && tid < 32) lds_st[tid] = a.st_in[blk * 32 + tid];
 
     d_f32x4 acc[RT][9];
@@ -451,7 +482,8 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_wgrad(const DiscWgradArgs
             const int oy = oy0 + r, ox = ox0 + c;
             d_f32x4 v = d_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             if (oy < a.Ho && ox < a.Wo)
-                v = d_load_dz<HEAD>(a.dz, lds_cf, n, ((n * (CD / 8) + cb) * out_plane + (size_t)oy * a.Wo + ox) * 8 + h * 4, cb * 8 + h * 4);
+                v = d_load_dz<UP>(a.dz, lds_cf, n, ((n * (CD_TOTAL / 8) + co0 / 8 + cb) * out_plane + (size_t)oy * a.Wo + ox) * 8 + h * 4,
+                                  cb * 8 + h * 4, n * CD_TOTAL + co0);
 #pragma unroll
             for (int j = 0; j < 4; ++j) lds_z[(cb * 8 + h * 4 + j) * ZSTR + r * D_TW + c] = v[j];
         }
@@ -494,7 +526,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_wgrad(const DiscWgradArgs
     }
 
     // a lane holds dz channels 4*kq .. 4*kq+3 of its row tile for input channel l16
-    float* part = a.part + ((size_t)split * (CX / 16) + blk) * CD * 144;
+    float* part = a.part + (((size_t)split * (CX / 16) + blk) * CD_TOTAL + co0) * 144;
 #pragma unroll
     for (int r = 0; r < RT; ++r)
 #pragma unroll
@@ -504,7 +536,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_wgrad(const DiscWgradArgs
                 const int co = (wave * RT + r) * 16 + kq * 4 + e;
                 part[((size_t)co * 9 + tap) * 16 + l16] = acc[r][tap][e];
             }
-    if (blk == 0 && tid < CD) a.part_b[(size_t)split * CD + tid] = bsum;
+    if (blk == 0 && tid < CD) a.part_b[(size_t)split * CD_TOTAL + co0 + tid] = bsum;
 }
 
 struct DiscWgradReduceArgs {

@@ -10,6 +10,9 @@
 //   * k_srd_head: one 1024-thread workgroup per image: BN12 + LeakyReLU of z11, the global average, Conv2d(256, 512, 1) + LeakyReLU,
 //     Conv2d(512, 1, 1) and the sigmoid, every sum in fp64 in a fixed order.
 //   * k_srd_losses: the SRGAN trainer's two BCE reductions over one batch (fp64, fixed order).
+//   * k_srd_bn_eval_saved, k_srd_head_saved: what cid_srd_forward_saved runs in their place.  The first also writes each BatchNorm's
+//     (running_mean, invstd) in fp64, the second also keeps the 256 pooled means and the 512 hidden pre-activations of each image, in
+//     fp64, for the backward's head (srgan_disc_bwd_kernels.h).  They share the plain kernels' arithmetic statement for statement.
 #pragma once
 #include "disc_kernels.h"
 
@@ -32,6 +35,17 @@ __global__ void __launch_bounds__(SRD_BN_MAXC) k_srd_bn_eval(const SrdBnEvalArgs
     const int l = blockIdx.x, c = threadIdx.x;
     if (c >= a.C[l]) return;
     d_bn_eval_channel(a.gamma[l], a.beta[l], a.running_mean[l], a.running_var[l], a.eps[l], a.st[l], nullptr, c);
+}
+
+struct SrdBnEvalSavedArgs {
+    SrdBnEvalArgs e;
+    double* mi[SRD_BNS];   // out: (running_mean, invstd) pairs [C]
+};
+
+__global__ void __launch_bounds__(SRD_BN_MAXC) k_srd_bn_eval_saved(const SrdBnEvalSavedArgs a) {
+    const int l = blockIdx.x, c = threadIdx.x;
+    if (c >= a.e.C[l]) return;
+    d_bn_eval_channel(a.e.gamma[l], a.e.beta[l], a.e.running_mean[l], a.e.running_var[l], a.e.eps[l], a.e.st[l], a.mi[l], c);
 }
 
 struct SrdBnCountArgs {
@@ -72,7 +86,9 @@ __device__ __forceinline__ void d_srd_pool_add(double (&acc)[4], const d_f32x4 v
     for (int j = 0; j < 4; ++j) acc[j] += (double)d_lrelu(d_bn(s[j], v[j], t[j]));
 }
 
-__global__ void __launch_bounds__(SRD_HEAD_THREADS) k_srd_head(const SrdHeadArgs a) {
+// SAVE: the pooled means go to pooled_out[n][256] and the hidden pre-activations to hidden_out[n][512] as well.
+template <bool SAVE>
+__device__ __forceinline__ void d_srd_head(const SrdHeadArgs& a, double* pooled_out, double* hidden_out) {
     static_assert(SRD_HEAD_C / 8 == 2 * (SRD_HEAD_THREADS / 64), "two channel blocks per wave");
     __shared__ double red[SRD_HEAD_HID];
     __shared__ double pooled[SRD_HEAD_C];
@@ -103,7 +119,10 @@ __global__ void __launch_bounds__(SRD_HEAD_THREADS) k_srd_head(const SrdHeadArgs
             for (int j = 0; j < 4; ++j) {
 #pragma unroll
                 for (int off = 2; off < 64; off <<= 1) acc[j] += __shfl_xor(acc[j], off, 64);
-                if (pl == 0) pooled[c0 + j] = acc[j] / (double)a.P;
+                if (pl == 0) {
+                    pooled[c0 + j] = acc[j] / (double)a.P;
+                    if (SAVE) pooled_out[n * SRD_HEAD_C + c0 + j] = pooled[c0 + j];
+                }
             }
         }
     }
@@ -124,6 +143,7 @@ __global__ void __launch_bounds__(SRD_HEAD_THREADS) k_srd_head(const SrdHeadArgs
         if (lane == 0) {
             const double h = acc + (double)a.w1[SRD_HEAD_HID * SRD_HEAD_C + j];
             red[j] = (double)a.w2[j] * (h > 0.0 ? h : h * 0.2);
+            if (SAVE) hidden_out[n * SRD_HEAD_HID + j] = h;
         }
     }
     __syncthreads();
@@ -135,6 +155,18 @@ __global__ void __launch_bounds__(SRD_HEAD_THREADS) k_srd_head(const SrdHeadArgs
         const double logit = (double)a.w2[SRD_HEAD_HID] + red[0];
         a.out[n] = (float)(1.0 / (1.0 + exp(-logit)));
     }
+}
+
+__global__ void __launch_bounds__(SRD_HEAD_THREADS) k_srd_head(const SrdHeadArgs a) { d_srd_head<false>(a, nullptr, nullptr); }
+
+struct SrdHeadSavedArgs {
+    SrdHeadArgs head;
+    double* pooled;   // out [N][256]
+    double* hidden;   // out [N][512]
+};
+
+__global__ void __launch_bounds__(SRD_HEAD_THREADS) k_srd_head_saved(const SrdHeadSavedArgs a) {
+    d_srd_head<true>(a.head, a.pooled, a.hidden);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

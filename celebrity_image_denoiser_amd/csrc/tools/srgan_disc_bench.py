@@ -17,7 +17,12 @@ For model.11's launch (k_disc_conv<128, 128, 1, true, ., 256>, two channel halve
 the time next to that of k_disc_conv<64, 128, 1, ...> (model.5: half the contraction, four times the pixels, one staging): per
 MFMA the two would cost the same if staging the halo twice were free.
 
-    python celebrity_image_denoiser_amd/csrc/tools/srgan_disc_bench.py [--reps 5] [--iters 20] [--case N,H,W ...] [--no-aten] [--json out.json]
+--backward times one training call instead: forward_saved + backward (SRGANDiscriminator(autograd=True) in train mode, BCE against
+ones, all 22 parameter gradients and the input gradient) next to the stock nn.Sequential under torch autograd (ATen/MIOpen fp32), in
+the same process by the same method; FLOP are counted as three times the forward's.  --shares on a trace of such a run names the
+backward's launches too; the two model.11 launches (the 256-channel k_disc_wgrad and k_disc_dgrad) are the ones to look at.
+
+    python celebrity_image_denoiser_amd/csrc/tools/srgan_disc_bench.py [--reps 5] [--iters 20] [--case N,H,W ...] [--no-aten] [--backward] [--json out.json]
 """
 import argparse
 import csv
@@ -79,9 +84,17 @@ def fmt(name, r):
 
 
 # kernel name prefix -> the launch it is, for --shares
-LAUNCHES = (("k_disc_conv0", "conv0"), ("k_disc_conv<64, 64, 2", "conv2"), ("k_disc_conv<64, 128, 1", "conv5"),
-            ("k_disc_conv<128, 128, 2", "conv8"), ("k_disc_conv<128, 128, 1", "conv11"), ("k_srd_head", "head"),
-            ("k_disc_bn_stats", "bn stats"), ("k_srd_bn_eval", "bn eval"), ("k_srd_bn_count", "bn count"))
+LAUNCHES = (
+    # the backward (--backward) first: the first match names the launch, so model.11's instantiations and the longer names lead
+    ("k_disc_wgrad<128, 128, 1", "wgrad11"), ("k_disc_dgrad<256, 128, 1", "dgrad11"), ("k_disc_bn_bwd_part<256", "bn12 sums"),
+    ("k_disc_wgrad<128, 128, 2", "wgrad8"), ("k_disc_dgrad<128, 128, 2", "dgrad8"), ("k_disc_wgrad<128, 64, 1", "wgrad5"),
+    ("k_disc_dgrad<128, 64, 1", "dgrad5"), ("k_disc_wgrad<64, 64, 2", "wgrad2"), ("k_disc_dgrad<64, 64, 2", "dgrad2"),
+    ("k_disc_wgrad0_reduce", "wgrad0 red"), ("k_disc_wgrad0", "wgrad0"), ("k_disc_dgrad0", "dgrad0"),
+    ("k_disc_wgrad_reduce", "wgrad red"), ("k_disc_bn_bwd_part", "bn sums"), ("k_disc_bn_bwd_reduce", "bn reduce"),
+    ("k_srd_head_bwd", "head bwd"), ("k_srd_head_reduce", "head red"), ("k_srd_pack", "pack"),
+    ("k_disc_conv0", "conv0"), ("k_disc_conv<64, 64, 2", "conv2"), ("k_disc_conv<64, 128, 1", "conv5"),
+    ("k_disc_conv<128, 128, 2", "conv8"), ("k_disc_conv<128, 128, 1", "conv11"), ("k_srd_head", "head"),
+    ("k_disc_bn_stats", "bn stats"), ("k_srd_bn_eval", "bn eval"), ("k_srd_bn_count", "bn count"))
 
 
 def shares(path, case):
@@ -102,7 +115,7 @@ def shares(path, case):
     avg = {}
     for launch, name, calls, tot, mean, lo, hi in sorted(rows, key=lambda r: -r[3]):
         short = name.split("(")[0].replace("void ", "")
-        line = f"{launch:9s} {short:58s} calls {calls:4d}  avg {mean / 1e3:9.1f} us  min {lo / 1e3:9.1f}  max {hi / 1e3:9.1f}  share {100 * tot / total:5.1f}%"
+        line = f"{launch:10s} {short:66s} calls {calls:4d}  avg {mean / 1e3:9.1f} us  min {lo / 1e3:9.1f}  max {hi / 1e3:9.1f}  share {100 * tot / total:5.1f}%"
         if launch in flops and launch != "head":
             line += f"  MFMA share {flops[launch] / MFMA_F32_PEAK / (mean * 1e-9):.2f}" if launch != "conv0" else ""
         avg.setdefault(launch, []).append(mean)
@@ -114,12 +127,52 @@ def shares(path, case):
               f"{t5 / 1e3:.1f} us for {flops['conv5'] / 1e9:.1f} GFLOP: time per FLOP conv11 / conv5 = {per11 / per5:.2f}")
 
 
+def backward_cases(args, cases, disc, dev):
+    """forward_saved + backward of one BCE loss in train mode, HIP next to ATen autograd on the same weights."""
+    import copy
+
+    import torch
+    from celebrity_image_denoiser_amd import synth
+
+    bce = torch.nn.BCELoss()
+    rows = []
+    for n, h, w in cases:
+        u8 = synth.add_gaussian_noise(synth.clean_images_u8(min(n, 16), h, w), 25.0)
+        x = torch.from_numpy(synth.normalize_u8(u8)).to(dev).repeat((n + 15) // 16, 1, 1, 1)[:n].contiguous().requires_grad_(True)
+        ones = torch.ones(n, device=dev)
+        flops = 3.0 * srd_flops(n, h, w)
+        stock = copy.deepcopy(disc.model).train()   # its own parameters and BatchNorm buffers
+        disc.train()
+
+        def step(fwd, params):
+            for q in params:
+                q.grad = None
+            x.grad = None
+            bce(fwd(x), ones).backward()
+
+        hip_params, aten_params = list(disc.parameters()), list(stock.parameters())
+        row = {"N": n, "H": h, "W": w, "gflop": flops / 1e9,
+               "train": summary(timed(lambda: step(disc, hip_params), args.reps, args.iters), n, flops)}
+        if not args.no_aten:
+            row["train_aten"] = summary(timed(lambda: step(lambda t: stock(t).view(-1), aten_params), args.reps, args.iters), n, flops)
+        rows.append(row)
+        line = f"B={n:3d} {h}x{w} forward_saved + backward, train | " + fmt("hip", row["train"])
+        if "train_aten" in row:
+            line += " | " + fmt("aten", row["train_aten"]) + f" | hip/aten {row['train']['ms_median'] / row['train_aten']['ms_median']:.2f}"
+        print(line, flush=True)
+    disc.eval()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--case", action="append", default=None, help="N,H,W (repeatable); default: the two cases above")
     ap.add_argument("--no-aten", action="store_true", help="skip the ATen/MIOpen baseline")
+    ap.add_argument("--backward", action="store_true", help="time forward_saved + backward in train mode against ATen autograd")
     ap.add_argument("--shares", default=None, help="a rocprofv3 kernel_stats CSV of a traced run: print each launch's share and exit")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -136,8 +189,11 @@ def main():
         raise SystemExit("srgan_disc_bench needs a GPU")
     dev = "cuda:0"
     sd = {k: torch.from_numpy(v) for k, v in synth.make_srgan_disc_state_dict("trained").items()}
-    disc = cid.load_srgan_discriminator(sd, device=dev, strict=True)
+    disc = cid.load_srgan_discriminator(sd, device=dev, strict=True, autograd=args.backward)
     rows = []
+    if args.backward:
+        backward_cases(args, cases, disc, dev)
+        return
     for n, h, w in cases:
         u8 = synth.add_gaussian_noise(synth.clean_images_u8(min(n, 16), h, w), 25.0)
         x = torch.from_numpy(synth.normalize_u8(u8)).to(dev).repeat((n + 15) // 16, 1, 1, 1)[:n].contiguous()

@@ -1,15 +1,19 @@
 """The SRGAN trainer's discriminator (`SRGANDiscriminator`, reference backend/trainingcode/srgan_code/sr_ganTrainGNew.py:54-80) on the GPU.
 
-    SRGANDiscriminator()                       nn.Module with the reference's parameter names (model.0 ... model.17, BatchNorm
+    SRGANDiscriminator(autograd=False)         nn.Module with the reference's parameter names (model.0 ... model.17, BatchNorm
                                                buffers included); forward(x) -> fp32 [N] probabilities, eval or train mode
     load_srgan_discriminator(path_or_sd)       -> SRGANDiscriminator from the "discriminator" entry of an SRGAN trainer checkpoint
     srgan_trainer_losses(D, fake_hr, hr_img)   -> the trainer's d_loss / adv_loss (and, with a VGGPerceptualLoss, content_loss / g_loss)
 
-Everything numeric runs in HIP kernels behind cid_srd_* (include/cid.h).  The module is forward only: the output carries no autograd
-history, so the trainer's d_loss.backward() on it raises torch's own "does not require grad" error.  There is no CPU fallback.
+Everything numeric runs in HIP kernels behind cid_srd_* (include/cid.h).  By default the module is forward only: the output carries
+no autograd history, so the trainer's d_loss.backward() on it raises torch's own "does not require grad" error.  With autograd=True
+the forward records a torch.autograd.Function whose backward is cid_srd_backward: the trainer's discriminator step
+(sr_ganTrainGNew.py:393-400) and the adversarial half of its generator step (:403-409) then run on these kernels, with a stock
+torch.optim optimizer or cid.Adam doing the update.  No double backward.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Mapping, Optional, Union
 
 import torch
@@ -22,18 +26,28 @@ _CONVS = (0, 2, 5, 8, 11, 15, 17)
 _BNS = (3, 6, 9, 12)
 
 
+class _GradsArg(ctypes.Structure):
+    """cid_srd_grads (include/cid.h)."""
+    _fields_ = [("w", ctypes.c_void_p * 7), ("b", ctypes.c_void_p * 7), ("gamma", ctypes.c_void_p * 4),
+                ("beta", ctypes.c_void_p * 4), ("input", ctypes.c_void_p)]
+
+
 class SRGANDiscriminator(_packed.PackedModule):
     """The reference's SRGAN discriminator.  `self.model` is a Sequential of stock layers used as parameter containers, so state_dict
     keys, buffers, .to(), load_state_dict(), .train() and .eval() behave as in the reference.  forward dispatches on self.training:
       eval   BatchNorm with the running buffers;
       train  BatchNorm with batch statistics, and the running buffers and num_batches_tracked of model.3 / 6 / 9 / 12 are updated
              in place on the device, as nn.BatchNorm2d does (momentum and eps are read from the containers at every call).
-    The forward is asynchronous on the current stream.  It is forward only: the output carries no autograd history."""
+    The forward is asynchronous on the current stream.  With autograd=False (the default) it carries no autograd history.  With
+    autograd=True, grad mode on and a parameter or the input requiring grad, it is differentiable once: each call keeps its own
+    activations (cid_srd_saved_bytes per call) until its backward has run, and weight changes are repacked on the device."""
 
     _abi = "srd"
 
-    def __init__(self):
+    def __init__(self, autograd: bool = False):
         super().__init__()
+        self._autograd = bool(autograd)
+        self._bws = None           # backward workspace (uint8 tensor, grow-only)
         self.model = nn.Sequential(
             nn.Conv2d(3, 64, kernel_size=3, padding=1),
             nn.LeakyReLU(0.2),
@@ -66,10 +80,36 @@ class SRGANDiscriminator(_packed.PackedModule):
     def _blob_bytes(self) -> int:
         return _lib.lib().cid_srd_packed_weights_bytes()
 
+    def pack_weights(self, force: bool = False) -> torch.Tensor:
+        """Repack the fourteen convolution tensors into the kernels' layout on the module's GPU (if they changed since the last
+        call).  With autograd=True the pack runs on the device, into one blob that stays in place: a training loop changes the
+        weights at every step."""
+        if not self._autograd:
+            return super().pack_weights(force)
+        sig = self._signature()
+        if not force and self._blob is not None and sig == self._packed_sig:
+            return self._blob
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("SRGANDiscriminator runs only on an AMD GPU (HIP kernels behind libcid.so); move it with "
+                               ".to('cuda') first. There is no CPU fallback.")
+        ts = [t.detach() for _, t in self._tensors()]
+        if any(t.dtype != torch.float32 or t.device != dev for t in ts):
+            raise RuntimeError(f"SRGANDiscriminator: convolution parameters must be float32 on {dev}")
+        ts = [t.contiguous() for t in ts]
+        if self._blob is None or self._blob.device != dev:
+            self._blob = torch.empty(self._blob_bytes(), dtype=torch.uint8, device=dev)
+        ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self._check(self._fn("pack_weights_device")(self._cid, ptrs, self._blob.data_ptr(), stream))
+        self._packed_sig = sig
+        return self._blob
+
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """fp32 [N,3,H,W] in [-1,1] or uint8 [N,H,W,3] on the GPU -> fp32 [N] probabilities on the same GPU (reference forward,
-        sr_ganTrainGNew.py:79-80).  In train mode the BatchNorm running buffers are updated in place.  No autograd history."""
+        sr_ganTrainGNew.py:79-80).  In train mode the BatchNorm running buffers are updated in place."""
         fmt, (n, h, w) = self._image_input(x)
         dev = self._input_device(x)
         if n < 1 or h < 1 or w < 1:
@@ -81,6 +121,8 @@ class SRGANDiscriminator(_packed.PackedModule):
                              f"{torch.Size([n, first, 1, 1])}")
         bn = bn_args(self.model, _BNS, dev)
         self.pack_weights()
+        if self._autograd and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return _SrdFunction.apply(self, fmt, (n, h, w), training, x, *self.parameters())
         self._ensure_workspace(dev, n, h, w, int(training))
         x = x.detach().contiguous()
         out = torch.empty(n, dtype=torch.float32, device=dev)
@@ -91,15 +133,84 @@ class SRGANDiscriminator(_packed.PackedModule):
         return out
 
 
+class _SrdFunction(torch.autograd.Function):
+    """forward = cid_srd_forward_saved into a buffer owned by this call's context, backward = cid_srd_backward."""
+
+    @staticmethod
+    def forward(ctx, module, fmt, shape, training, x, *params):
+        n, h, w = shape
+        dev = x.device
+        L = _lib.lib()
+        need = ctypes.c_size_t()
+        module._check(L.cid_srd_saved_bytes(n, h, w, int(training), ctypes.byref(need)))
+        saved = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        xc = x.detach().contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        bn = bn_args(module.model, _BNS, dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            module._check(L.cid_srd_forward_saved(module._cid, xc.data_ptr(), fmt, out.data_ptr(), n, h, w, bn, int(training),
+                                                  saved.data_ptr(), saved.numel(), stream))
+        ctx.module, ctx.fmt, ctx.shape, ctx.training = module, fmt, shape, training
+        ctx.saved, ctx.x = saved, xc
+        ctx.names = [k for k, _ in module.named_parameters()]
+        ctx.versions = [p._version for p in params]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_prob):
+        module = ctx.module
+        params = list(module.parameters())
+        for name, p, v in zip(ctx.names, params, ctx.versions):
+            if p._version != v:
+                raise RuntimeError(f"SRGANDiscriminator: parameter {name} was modified in place between a forward and its backward "
+                                   f"(version {p._version}, expected {v}); the gradient would be taken at the wrong weights")
+        n, h, w = ctx.shape
+        dev = ctx.x.device
+        L = _lib.lib()
+        needs = ctx.needs_input_grad
+        g = _GradsArg()
+        grads = [None] * len(params)
+        for i, (name, p) in enumerate(zip(ctx.names, params)):
+            if not needs[5 + i]:
+                continue
+            grads[i] = torch.empty(p.shape, dtype=torch.float32, device=dev)
+            idx, kind = int(name.split(".")[1]), name.rsplit(".", 1)[1]
+            if idx in _CONVS:
+                (g.w if kind == "weight" else g.b)[_CONVS.index(idx)] = grads[i].data_ptr()
+            else:
+                (g.gamma if kind == "weight" else g.beta)[_BNS.index(idx)] = grads[i].data_ptr()
+        grad_x = None
+        if needs[4] and ctx.fmt == _lib.CID_FMT_F32_NCHW:
+            grad_x = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+            g.input = grad_x.data_ptr()
+        need = ctypes.c_size_t()
+        module._check(L.cid_srd_backward_workspace_bytes(n, h, w, int(ctx.training), ctypes.byref(need)))
+        if module._bws is None or module._bws.numel() < need.value or module._bws.device != dev:
+            module._bws = None
+            module._bws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        gp = grad_prob.to(torch.float32).contiguous()
+        bn = bn_args(module.model, _BNS, dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            module._check(L.cid_srd_backward(module._cid, ctx.x.data_ptr(), ctx.fmt, gp.data_ptr(), n, h, w, bn, int(ctx.training),
+                                             ctx.saved.data_ptr(), ctx.saved.numel(), ctypes.byref(g), module._bws.data_ptr(),
+                                             module._bws.numel(), stream))
+        ctx.saved = None
+        return (None, None, None, None, grad_x, *grads)
+
+
 def load_srgan_discriminator(source: Union[str, Mapping, None] = None, device: Optional[Union[str, torch.device]] = None,
-                             strict: bool = False) -> SRGANDiscriminator:
+                             strict: bool = False, autograd: bool = False) -> SRGANDiscriminator:
     """Build an SRGANDiscriminator on `device` (default: current GPU) from an SRGAN trainer checkpoint path (its "discriminator"
     entry, sr_ganTrainGNew.py:342-353, read with the torch-free reader), a checkpoint dict or a state_dict; "module." prefixes are
-    stripped as for the generators.  `source=None` keeps the default initialisation.  Returns the module in eval mode."""
+    stripped as for the generators.  `source=None` keeps the default initialisation.  `autograd=True` makes the forward differentiable
+    (SRGANDiscriminator).  Returns the module in eval mode."""
     from .api import _read_checkpoint_file, extract_state_dict
 
     device = _packed.cuda_device(device, "load_srgan_discriminator")
-    model = SRGANDiscriminator()
+    model = SRGANDiscriminator(autograd=autograd)
     if isinstance(source, str):
         model.load_state_dict(_read_checkpoint_file(source, key_candidates=("discriminator",)), strict=strict)
     elif source is not None:

@@ -485,7 +485,7 @@ int cid_disc_pack_weights_device(cid_disc_t d, const float* const* dev_params, v
 /*
  * The SRGAN trainer's discriminator — SRGANDiscriminator (backend/trainingcode/srgan_code/sr_ganTrainGNew.py:54-80), which that
  * trainer calls three times per step (:395-404) for d_loss = BCE(D(hr), 1) + BCE(D(fake), 0) and adv_loss = BCE(D(fake), 1).
- * Forward only: nothing is kept for a backward pass.  Its own handle and blob, as cid_disc_* has.
+ * cid_srd_forward keeps nothing for a backward pass (cid_srd_forward_saved below does).  Its own handle and blob, as cid_disc_* has.
  *
  *   model.0 ... model.10 are DenoiseDiscriminator's layers 0 ... 10 (above); then
  *  11 Conv2d(128,256,3,p=1)  12 BatchNorm2d(256)  13 LeakyReLU(0.2)  14 AdaptiveAvgPool2d(1)  15 Conv2d(256,512,1)  16 LeakyReLU(0.2)
@@ -525,6 +525,55 @@ int cid_srd_workspace_bytes(int N, int H, int W, int training, size_t* bytes);
 int cid_srd_forward(cid_srd_t d, const void* in, int in_fmt, float* out_prob, int N, int H, int W, const cid_disc_bn* bn,
                     int training, void* workspace, size_t workspace_bytes, void* stream);
 int cid_srd_losses(const float* p_real, const float* p_fake, int N, double* out, void* stream);
+
+/*
+ * The SRGAN discriminator's backward pass (that trainer's d_loss.backward(), sr_ganTrainGNew.py:399, and the adversarial half of
+ * g_loss.backward(), :408).  The family mirrors cid_disc_forward_saved / cid_disc_backward above: the same conventions for what is
+ * null, what is overwritten, determinism (the same call twice gives the same bits; in eval mode an image's input gradient does not
+ * depend on its batch), asynchrony, and the same argument checks in the same order with the same codes, with four BatchNorms and
+ * seven convolutions.  Gradients of model.0 ... model.17 in fp32; every reduction accumulates in fp64 in a fixed order, no atomics;
+ * the GEMMs of layers 2, 5, 8, 11 (data and weight gradient) run on the exact-fp32 MFMA.
+ *
+ * cid_srd_forward_saved is cid_srd_forward with a caller-owned PER-CALL buffer in place of the workspace.  It keeps, without overlap,
+ * the activated a0, the raw z2, z5, z8, z11, each BatchNorm's (scale, shift) and (mean, invstd), per image the 256 pooled means of a12
+ * and the 512 pre-activations of model.15 in fp64 (the backward's head never reads z11), and in train mode the statistics slabs.
+ * Probabilities and BatchNorm buffer updates are bit-identical to cid_srd_forward.  cid_srd_saved_bytes(N, H, W, training), with
+ * a256 as above:
+ *     a256(4*N*64*H*W) + a256(4*N*64*H2*W2) + a256(4*N*128*H2*W2) + a256(4*N*128*H4*W4) + a256(4*N*256*H4*W4)      a0, z2, z5, z8, z11
+ *   + a256(4 * 4*256*2) + a256(8 * 4*256*2)                 (scale, shift) in fp32 and (mean, invstd) in fp64 of the four BatchNorms
+ *   + a256(8 * N*256) + a256(8 * N*512)                     pooled means, hidden pre-activations
+ *   + in train mode the four slabs of cid_srd_workspace_bytes
+ *
+ * cid_srd_backward: arguments as cid_disc_backward; `g` holds w[i], b[i] for model.{0,2,5,8,11,15,17}, gamma[l], beta[l] for
+ * model.{3,6,9,12} and input [N,3,H,W].  Every pointer may be null: only what is asked for is written, the chain stops at the lowest
+ * stage asked for (head > BatchNorm 12 > model.11 > BatchNorm 9 > ... > model.0 > input), a uint8 input has no gradient.  The slope of
+ * model.16's LeakyReLU is decided on the saved fp64 pre-activation, as the forward decides it.  Error codes as cid_disc_backward.
+ *
+ * cid_srd_pack_weights_device builds the forward's blob from the fourteen parameter tensors in DEVICE memory (order model.0.weight,
+ * model.0.bias, model.2.weight, ... model.17.bias) with one kernel and attaches it: byte for byte what cid_srd_set_weight x 14 +
+ * cid_srd_upload_weights produce, model.11's two 128-channel halves and the zero padding between segments included.
+ *
+ * cid_srd_saved_masks is a testing aid as cid_disc_saved_masks: the six LeakyReLU decisions as the backward takes them, uint8 (1 where
+ * the slope is 1): masks[0] a0 [N,64,H,W], masks[1..4] the outputs of BatchNorm 3, 6, 9, 12 ([N,64,H2,W2], [N,128,H2,W2],
+ * [N,128,H4,W4], [N,256,H4,W4]), masks[5] the hidden layer [N,512].
+ */
+typedef struct {
+    float* w[7];         /* model.0, 2, 5, 8, 11, 15, 17 .weight */
+    float* b[7];         /* model.0, 2, 5, 8, 11, 15, 17 .bias   */
+    float* gamma[4];     /* model.3, 6, 9, 12 .weight            */
+    float* beta[4];      /* model.3, 6, 9, 12 .bias              */
+    float* input;        /* fp32 [N,3,H,W]                       */
+} cid_srd_grads;
+int cid_srd_saved_bytes(int N, int H, int W, int training, size_t* bytes);
+int cid_srd_forward_saved(cid_srd_t d, const void* in, int in_fmt, float* out_prob, int N, int H, int W, const cid_disc_bn* bn,
+                          int training, void* saved, size_t saved_bytes, void* stream);
+int cid_srd_backward_workspace_bytes(int N, int H, int W, int training, size_t* bytes);
+int cid_srd_backward(cid_srd_t d, const void* in, int in_fmt, const float* grad_prob, int N, int H, int W, const cid_disc_bn* bn,
+                     int training, const void* saved, size_t saved_bytes, const cid_srd_grads* g, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cid_srd_pack_weights_device(cid_srd_t d, const float* const* dev_params, void* device_blob, void* stream);
+int cid_srd_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int W, int training, unsigned char* const* masks,
+                        void* stream);
 
 /*
  * The generator's backward pass — g_loss.backward() through DenoiseGenerator in the trainer's generator step
