@@ -160,11 +160,11 @@ class PackedModule(nn.Module):
             raise RuntimeError(f"input on {x.device} but module parameters on {dev}")
         return dev
 
-    def _ensure_workspace(self, device: torch.device, *dims, needs: str = "") -> None:
-        """The workspace of cid_<abi>_workspace_bytes(*dims) on `device`, grow-only.  With `needs` (LPIPS and the VGG loss, dims =
+    def _ensure_workspace(self, device: torch.device, *dims, needs: str = "", sizer: str = "workspace_bytes") -> None:
+        """The workspace of cid_<abi>_<sizer>(*dims) on `device`, grow-only.  With `needs` (LPIPS and the VGG loss, dims =
         (n, h, w)) a shape the library does not accept raises the ValueError that says what the model needs."""
         need = ctypes.c_size_t()
-        rc = self._fn("workspace_bytes")(*self._form, *dims, ctypes.byref(need))
+        rc = self._fn(sizer)(*self._form, *dims, ctypes.byref(need))
         if rc == 2 and needs:   # CID_ERR_SHAPE
             raise ValueError(f"image size {dims[1]}x{dims[2]} (N={dims[0]}) not accepted: {needs}")
         self._check(rc)
@@ -175,13 +175,13 @@ class PackedModule(nn.Module):
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
 
-    def _stage(self, images: int, name: str, what: str, *dims) -> torch.Tensor:
-        """The C8 tensor cid_<abi>_stage_view(name, *dims) names, out of the workspace, as fp32 [images,C,Hs,Ws] (a copy)."""
+    def _stage(self, images: int, name: str, what: str, *dims, view: str = "stage_view") -> torch.Tensor:
+        """The C8 tensor cid_<abi>_<view>(name, *dims) names, out of the workspace, as fp32 [images,C,Hs,Ws] (a copy)."""
         off, c, hs, ws, cb = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        rc = self._fn("stage_view")(*self._form, name.encode(), *dims, ctypes.byref(off), ctypes.byref(c), ctypes.byref(hs),
-                                    ctypes.byref(ws), ctypes.byref(cb))
+        rc = self._fn(view)(*self._form, name.encode(), *dims, ctypes.byref(off), ctypes.byref(c), ctypes.byref(hs),
+                            ctypes.byref(ws), ctypes.byref(cb))
         if rc != _lib.CID_OK:
-            raise KeyError(f"no stored stage {name!r} for {what} (cid_{self._abi}_stage_view -> {rc})")
+            raise KeyError(f"no stored stage {name!r} for {what} (cid_{self._abi}_{view} -> {rc})")
         count = images * c.value * hs.value * ws.value
         t = self._ws[off.value:off.value + 4 * count].view(torch.float32)
         t = t.view(images, c.value // cb.value, hs.value, ws.value, cb.value).permute(0, 1, 4, 2, 3)

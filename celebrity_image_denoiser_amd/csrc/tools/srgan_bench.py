@@ -9,8 +9,12 @@ stages and the tail at 16 times the pixels) and its share of the 157.3 TFLOP/s f
 --trace starts ONE `rocprofv3 --kernel-trace` run (no counters in it) of a few forwards of the given case and prints per launch the
 count, the mean and the minimum time, and the fp32-MFMA bound of the trunk and upscale launches.
 
+--train times the TRAIN-mode forward (SRGANGenerator(batch_stats=True), cid_sr_forward_train) at the SRGAN trainer's shape, B=16
+64x64 -> 256x256 at scale 4, and at B=8, next to a stock copy of the network in train mode on ATen/MIOpen (under no_grad, as this
+forward has no autograd history either) and to this build's own eval forward: 3 warm-up calls, median of 5 windows of 20 calls.
+
     python celebrity_image_denoiser_amd/csrc/tools/srgan_bench.py [--reps 5] [--iters 10] [--case N,H,W ...] [--scale 4]
-                                                                  [--no-aten] [--no-u8] [--json out.json] [--trace N,H,W]
+                                                                  [--no-aten] [--no-u8] [--json out.json] [--trace N,H,W] [--train]
 """
 import argparse
 import csv
@@ -27,6 +31,7 @@ sys.path.insert(0, ROOT)
 
 MFMA_F32_PEAK = 157.3e12
 CASES = ((4, 256, 256), (64, 64, 64))
+TRAIN_CASES = ((16, 64, 64), (8, 64, 64))
 
 
 def sr_macs_per_pixel(scale):
@@ -47,10 +52,10 @@ def aten_forward(m, x):
     return torch.tanh(m.final(m.upscale(m.mid(m.res_blocks(x0)) + x0)))
 
 
-def timed(fn, reps, iters):
+def timed(fn, reps, iters, warmup=2):
     import torch
 
-    for _ in range(2):
+    for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
     out = []
@@ -106,6 +111,40 @@ def run_case(n, h, w, args):
         with torch.no_grad():
             row["aten"] = summary(timed(lambda: aten_forward(model, x), args.reps, args.iters), n, flops)
         line += " | " + fmt("aten", row["aten"]) + f" | hip/aten {row['hip']['ms_median'] / row['aten']['ms_median']:.2f}"
+    print(line, flush=True)
+    return row
+
+
+def run_train_case(n, h, w, args):
+    """One train forward: HIP, the stock layers in train mode on ATen/MIOpen, and this build's eval forward."""
+    import copy
+
+    import torch
+
+    import celebrity_image_denoiser_amd as cid
+    from celebrity_image_denoiser_amd import synth
+
+    _, _, x = setup(n, h, w, args.scale)
+    sd = synth.make_srgan_state_dict("default", args.scale)
+    model = cid.load_srgan(sd, scale_factor=args.scale, device="cuda:0", strict=True, batch_stats=True)
+    # the stock layers of the module, copied (their BatchNorm buffers move) and run as the reference's forward does
+    stock = copy.deepcopy(torch.nn.ModuleDict({k: getattr(model, k) for k in ("initial", "res_blocks", "mid", "upscale", "final")})).train()
+
+    def stock_forward():
+        x0 = stock["initial"](x)
+        return torch.tanh(stock["final"](stock["upscale"](stock["mid"](stock["res_blocks"](x0)) + x0)))
+
+    flops = sr_flops(n, h, w, args.scale)
+    row = {"N": n, "H": h, "W": w, "scale": args.scale, "gflop": flops / 1e9, "mode": "train"}
+    row["hip_eval"] = summary(timed(lambda: model(x), args.reps, args.iters, 3), n, flops)
+    model.train()
+    row["hip_train"] = summary(timed(lambda: model(x), args.reps, args.iters, 3), n, flops)
+    line = f"train B={n:3d} {h}x{w} x{args.scale} | " + fmt("hip train", row["hip_train"]) + " | " + fmt("hip eval", row["hip_eval"])
+    line += f" | train/eval {row['hip_train']['ms_median'] / row['hip_eval']['ms_median']:.2f}"
+    if not args.no_aten:
+        with torch.no_grad():
+            row["aten_train"] = summary(timed(stock_forward, args.reps, args.iters, 3), n, flops)
+        line += " | " + fmt("aten train", row["aten_train"]) + f" | hip/aten {row['hip_train']['ms_median'] / row['aten_train']['ms_median']:.2f}"
     print(line, flush=True)
     return row
 
@@ -196,6 +235,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--trace", default=None, help="N,H,W: per-launch times of this case from one rocprofv3 --kernel-trace run")
     ap.add_argument("--trace-calls", type=int, default=4)
+    ap.add_argument("--train", action="store_true", help="the train-mode forward at the trainer's shapes (B=16 and B=8, 64x64)")
     ap.add_argument("--traced-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -204,15 +244,17 @@ def main():
         run_traced(*shape(args.traced_child), args)
         return
     rows = []
+    if args.train and not args.child:
+        args.iters = 20 if args.iters == ap.get_default("iters") else args.iters
     if args.child:
-        rows = [run_case(*shape(c), args) for c in args.case]
+        rows = [(run_train_case if args.train else run_case)(*shape(c), args) for c in args.case]
     elif args.case or not args.trace:
-        for c in ([shape(c) for c in args.case] if args.case else CASES):
+        for c in ([shape(c) for c in args.case] if args.case else TRAIN_CASES if args.train else CASES):
             # each case in a process of its own: allocator state and clocks of one do not reach the next
             with tempfile.NamedTemporaryFile(suffix=".json") as tf:
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case", ",".join(map(str, c)), "--scale", str(args.scale),
                        "--reps", str(args.reps), "--iters", str(args.iters), "--json", tf.name]
-                cmd += ["--no-aten"] * args.no_aten + ["--no-u8"] * args.no_u8
+                cmd += ["--no-aten"] * args.no_aten + ["--no-u8"] * args.no_u8 + ["--train"] * args.train
                 subprocess.run(cmd, check=True)
                 rows += json.load(open(tf.name))
     if args.trace:

@@ -44,26 +44,30 @@ def _out_side(s: int) -> int:
 
 
 def bn_args(model: nn.Sequential, indices, dev: torch.device):
-    """The cid_disc_bn array of the BatchNorm2d containers model[i], i in `indices`, whose tensors live on `dev`: device pointers
-    of the affine parameters, the running buffers and the counter, with eps and momentum as the containers hold them now."""
-    arr = (_BnArg * len(indices))()
-    for i, idx in enumerate(indices):
-        bn = model[idx]
+    """The cid_disc_bn array of the BatchNorm2d containers model[i], i in `indices` (named_bn_args)."""
+    return named_bn_args([(f"model.{idx}", model[idx]) for idx in indices], dev)
+
+
+def named_bn_args(named, dev: torch.device):
+    """The cid_disc_bn array of the (name, BatchNorm2d) pairs `named`, whose tensors live on `dev`: device pointers of the affine
+    parameters, the running buffers and the counter, with eps and momentum as the containers hold them now."""
+    arr = (_BnArg * len(named))()
+    for i, (name, bn) in enumerate(named):
         if not (bn.affine and bn.track_running_stats):
-            raise NotImplementedError(f"model.{idx}: only BatchNorm2d(affine=True, track_running_stats=True) is supported")
+            raise NotImplementedError(f"{name}: only BatchNorm2d(affine=True, track_running_stats=True) is supported")
         ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
         if any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in ts):
-            raise RuntimeError(f"model.{idx}: BatchNorm tensors must be contiguous float32 on {dev}")
+            raise RuntimeError(f"{name}: BatchNorm tensors must be contiguous float32 on {dev}")
         nbt = bn.num_batches_tracked
         if nbt.device != dev or nbt.dtype != torch.int64:
-            raise RuntimeError(f"model.{idx}.num_batches_tracked must be int64 on {dev}")
+            raise RuntimeError(f"{name}.num_batches_tracked must be int64 on {dev}")
         mom = bn.momentum
         arr[i] = _BnArg(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                         nbt.data_ptr(), float(bn.eps), _lib.CID_DISC_MOMENTUM_NONE if mom is None else float(mom))
         if mom is not None and (not np.isfinite(mom) or mom < 0):
-            raise ValueError(f"model.{idx}.momentum must be finite and >= 0 or None, got {mom}")
+            raise ValueError(f"{name}.momentum must be finite and >= 0 or None, got {mom}")
         if not np.isfinite(bn.eps) or bn.eps < 0:
-            raise ValueError(f"model.{idx}.eps must be finite and >= 0, got {bn.eps}")
+            raise ValueError(f"{name}.eps must be finite and >= 0, got {bn.eps}")
     return arr
 
 

@@ -808,6 +808,47 @@ int cid_sr_stage_view(const char* stage, int N, int Hp, int Wp, int scale_factor
                       int* channel_block);
 
 /*
+ * The same generator in TRAIN mode: the first line of the SRGAN trainer's step, fake_hr = self.generator(lr_img)
+ * (sr_ganTrainGNew.py:393, after self.generator.train()).  Forward only; the output carries no gradient.
+ *
+ * cid_sr_forward_train is cid_sr_forward with the ten BatchNorms on the statistics of THIS batch.  bn[0..9] describe
+ * res_blocks.0.1, res_blocks.0.4, res_blocks.1.1, ... res_blocks.4.4, a cid_disc_bn each (device pointers, so that the updates land in
+ * the caller's own buffers; eps and momentum as the containers hold them, CID_DISC_MOMENTUM_NONE for momentum=None), with the
+ * train semantics documented for cid_disc_forward(training = 1): each BatchNorm normalises with the batch mean and the BIASED batch
+ * variance over N*H*W values per channel, then running = (1 - m) * running + m * batch_stat with the UNBIASED variance for
+ * running_var, and num_batches_tracked += 1; m = momentum, or 1 / num_batches_tracked after the increment.  All of it runs on the
+ * device; there is no host synchronisation.  Convolution weights, biases and PReLU slopes come from the blob cid_sr_upload_weights
+ * made; the (s, t) it folded from the running statistics are not read, and the blob is not changed: after a train forward the
+ * running statistics differ from the ones the blob was folded from, so upload again before the next cid_sr_forward.
+ * There are no pad arguments (the trainer does not pad): the network runs on H x W.  in, out, in_fmt, out_fmt and flags are
+ * cid_sr_forward's (head and tail are its launches).  Launches: head, 10 x (convolution, statistics), one counter launch, mid,
+ * log2(s) upscale stages, tail.  A convolution stores its raw result z and per-tile fp64 sums of z and z^2 (one slab row per tile);
+ * the statistics launch reduces them in a fixed order in fp64 to (scale, shift) = (gamma / sqrt(var + eps), beta - mean * scale),
+ * rounded once to fp32; the next convolution applies fmaf(scale, z, shift), and PReLU where the block has one, while it stages its
+ * input.  No atomics: the same call on the same buffers gives the same bits (an image's result depends on its batch, as the
+ * statistics do).  N*H*W == 1 is CID_ERR_SHAPE ("Expected more than 1 value per channel when training").  Checked on the host before
+ * any launch:
+ *   CID_ERR_INVALID    null pointer (any of bn[l]'s five included), unknown format, misaligned fp32 operand, unknown flags,
+ *                      CID_SR_RAW with a uint8 output, an eps or momentum that is not finite or negative (other than
+ *                      CID_DISC_MOMENTUM_NONE)
+ *   CID_ERR_SHAPE      N < 1, H < 1, W < 1, s^2 * H * W >= 2^31, N*H*W == 1
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_sr_train_workspace_bytes(N, H, W, scale_factor) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_sr_train_workspace_bytes: with a(v) = v rounded up to 256, t = N * 64 * H * W * 4 and tiles = ceil(H/16) * ceil(W/16),
+ *   4 a(t)                                 x0, the two raw z tensors the convolutions alternate between, mid's result
+ *   + sum_{k=1..stages} a(4^k t)           the upscale stages' outputs
+ *   + a(64 * 2 * N * tiles * 8)            the slab (reused by all ten convolutions)
+ *   + a(10 * 64 * 2 * 4)                   the ten (scale, shift) tables
+ * cid_sr_train_stage_view is cid_sr_stage_view for that workspace: "x0", "trunk", "up1", "up2", "tail_in".
+ */
+int cid_sr_train_workspace_bytes(int N, int H, int W, int scale_factor, size_t* bytes);
+int cid_sr_forward_train(cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, unsigned flags,
+                         const cid_disc_bn* bn, void* workspace, size_t workspace_bytes, void* stream);
+int cid_sr_train_stage_view(const char* stage, int N, int H, int W, int scale_factor, size_t* offset_bytes, int* C, int* Hs, int* Ws,
+                            int* channel_block);
+
+/*
  * The server's fourth model — CGANGenerator(n_classes = 10, latent_dim = 100) (backend/app.py:105-143), the "cgan" branch of /enhance,
  * label-conditioned branch (cond a 1-D integer tensor).  Eval mode, fp32; the output is always 64 x 64:
  *
