@@ -24,7 +24,9 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     ESRGANGenerator(num_residuals=8) / load_esrgan(ckpt)   the server's ESRGAN model (eval mode); enhance(model, x) -> the raw
                                   fp32 output, enhance_u8(model, u8) -> the server's uint8 view
     SRGANGenerator(scale_factor=4) / load_srgan(ckpt)      the server's SRGAN model (eval mode): super_resolve(model, x) -> fp32 at
-                                  scale times the size, super_resolve_u8(model, u8) -> the server's padded uint8 view
+                                  scale times the size, super_resolve_u8(model, u8) -> the server's padded uint8 view; with
+                                  batch_stats=True a train-mode forward (batch-statistics BatchNorm), with autograd=True as well a
+                                  differentiable one (HIP backward pass): g_loss.backward() of the SRGAN trainer
     CGANGenerator(n_classes=10) / load_cgan(ckpt)          the server's class-conditional cGAN model (eval mode): latent(n, seed) draws
                                   its input on the device, generate(model, labels, seed=s) -> fp32 [N,3,64,64], generate_u8 -> the
                                   server's uint8 view

@@ -219,7 +219,7 @@ int cid_sr_forward(cid_sr_t h, const void* in, int in_fmt, void* out, int out_fm
         const int tiles = ((Hu + DiscGeom<64, 128, 1>::TH - 1) / DiscGeom<64, 128, 1>::TH) * tiles_x;
         if (const int rc = cx.launches(N, "upscale", [&](int n0, int n) {
             const SrUpArgs a{u, dst, blob + h->up_off(k), Hu, Wu, tiles_x, n0};
-            hipLaunchKernelGGL(k_sr_up, dim3((unsigned)tiles, (unsigned)n, 2), dim3(D_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k_sr_up<>, dim3((unsigned)tiles, (unsigned)n, 2), dim3(D_THREADS), 0, s, a);
         })) return rc;
         u = dst;
         Hu *= 2;

@@ -1,6 +1,7 @@
 // The SRGAN generator in train mode (cid_sr_forward_train): workspace plan, argument checks and launch sequence.  Head, upscale stages
 // and tail are cid_sr_forward's launches (srgan.h); the trunk runs on srgan_train_kernels.h with the statistics kernel and the
-// cid_disc_bn contract of the discriminators (disc_forward.h).  Host code.
+// cid_disc_bn contract of the discriminators (disc_forward.h).  The checks and the run are shared with cid_sr_forward_saved
+// (srgan_backward.h), which points the same launches into its saved buffer.  Host code.
 #pragma once
 #include "../srgan_train_kernels.h"
 #include "disc_forward.h"
@@ -36,6 +37,61 @@ int sr_train_plan(int N, int H, int W, int scale, SrTrainPlan& p) {
     return CID_OK;
 }
 
+// Where one train-mode forward writes.  cid_sr_forward_train points everything into its workspace and the ten z alternate between
+// two tensors; cid_sr_forward_saved (srgan_backward.h) gives each z a tensor of its own in the saved buffer, asks for the
+// (mean, invstd) tables and for the pre-activations of the head and the upscale stages.
+struct SrTrainBufs {
+    float* x0;
+    float* z[S_TRAIN_BNS];
+    float* trunk;
+    float* up[3];
+    double* slab;
+    float* st;             // ten (scale, shift) tables
+    double* mi;            // ten (mean, invstd) tables, or null
+    float* pre0;           // the head's sums before PReLU, or null
+    float* pre_up[3];      // with pre0: stage k's shuffled sums before PReLU
+};
+
+SrTrainBufs sr_train_bufs(void* workspace, const SrTrainPlan& p) {
+    char* ws = static_cast<char*>(workspace);
+    SrTrainBufs b{};
+    b.x0 = reinterpret_cast<float*>(ws + p.x0);
+    for (int l = 0; l < S_TRAIN_BNS; ++l) b.z[l] = reinterpret_cast<float*>(ws + p.z[l % 2]);
+    b.trunk = reinterpret_cast<float*>(ws + p.trunk);
+    for (int u = 0; u < p.stages; ++u) b.up[u] = reinterpret_cast<float*>(ws + p.up[u]);
+    b.slab = reinterpret_cast<double*>(ws + p.slab);
+    b.st = reinterpret_cast<float*>(ws + p.st);
+    return b;
+}
+
+// The error of a shape sr_train_plan does not accept, in the words every train-mode entry point uses.
+int sr_train_shape_fail(const Call& cx, int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1) return cx.fail(CID_ERR_SHAPE, "input shape not accepted (N, H, W >= 1)");
+    return (long long)N * H * W == 1 ? cx.h->fail(CID_ERR_SHAPE, "Expected more than 1 value per channel when training")
+                                     : cx.fail(CID_ERR_SHAPE, "input shape not accepted (scale^2 * H * W < 2^31)");
+}
+
+// The argument checks cid_sr_forward_train and cid_sr_forward_saved share, up to the plan.
+int sr_train_check(const Call& cx, cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, unsigned flags,
+                   const cid_disc_bn* bn, const void* workspace, SrTrainPlan& p) {
+    if (const int rc = check_image_io(cx, in, in_fmt, out, out_fmt, workspace)) return rc;
+    if (!bn) return cx.fail(CID_ERR_INVALID, "null pointer");
+    if (flags & ~(unsigned)CID_SR_RAW) return cx.fail(CID_ERR_INVALID, "unknown flags");
+    if ((flags & CID_SR_RAW) && out_fmt != CID_FMT_F32_NCHW) return cx.fail(CID_ERR_INVALID, "CID_SR_RAW needs an fp32 output");
+    for (int l = 0; l < S_TRAIN_BNS; ++l) {
+        const cid_disc_bn& b = bn[l];
+        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || !b.num_batches_tracked)
+            return cx.fail(CID_ERR_INVALID, "null BatchNorm pointer");
+        if (!disc_finite_nonneg(b.eps)) return cx.fail(CID_ERR_INVALID, "eps must be finite and >= 0");
+        if (!(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
+            return cx.fail(CID_ERR_INVALID, "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
+    }
+    return sr_train_plan(N, H, W, h->scale, p) == CID_OK ? (int)CID_OK : sr_train_shape_fail(cx, N, H, W);
+}
+
+int sr_train_run(const Call& cx, cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, unsigned flags,
+                 const cid_disc_bn* bn, const SrTrainPlan& p, const SrTrainBufs& b);
+
 }  // namespace
 
 extern "C" {
@@ -70,43 +126,38 @@ int cid_sr_forward_train(cid_sr_t h, const void* in, int in_fmt, void* out, int 
                          const cid_disc_bn* bn, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h) return CID_ERR_INVALID;
     const Call cx(h, "cid_sr_forward_train", stream);
-    if (const int rc = check_image_io(cx, in, in_fmt, out, out_fmt, workspace)) return rc;
-    if (!bn) return cx.fail(CID_ERR_INVALID, "null pointer");
-    if (flags & ~(unsigned)CID_SR_RAW) return cx.fail(CID_ERR_INVALID, "unknown flags");
-    if ((flags & CID_SR_RAW) && out_fmt != CID_FMT_F32_NCHW) return cx.fail(CID_ERR_INVALID, "CID_SR_RAW needs an fp32 output");
-    for (int l = 0; l < S_TRAIN_BNS; ++l) {
-        const cid_disc_bn& b = bn[l];
-        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || !b.num_batches_tracked)
-            return cx.fail(CID_ERR_INVALID, "null BatchNorm pointer");
-        if (!disc_finite_nonneg(b.eps)) return cx.fail(CID_ERR_INVALID, "eps must be finite and >= 0");
-        if (!(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
-            return cx.fail(CID_ERR_INVALID, "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
-    }
-    if (N < 1 || H < 1 || W < 1) return cx.fail(CID_ERR_SHAPE, "input shape not accepted (N, H, W >= 1)");
     SrTrainPlan p;
-    if (sr_train_plan(N, H, W, h->scale, p) != CID_OK)
-        return (long long)N * H * W == 1 ? cx.h->fail(CID_ERR_SHAPE, "Expected more than 1 value per channel when training")
-                                         : cx.fail(CID_ERR_SHAPE, "input shape not accepted (scale^2 * H * W < 2^31)");
+    if (const int rc = sr_train_check(cx, h, in, in_fmt, out, out_fmt, N, H, W, flags, bn, workspace, p)) return rc;
     if (const int rc = cx.room(workspace, workspace_bytes, p.total, "cid_sr_train_workspace_bytes")) return rc;
     if (const int rc = cx.uploaded()) return rc;
+    return sr_train_run(cx, h, in, in_fmt, out, out_fmt, N, H, W, flags, bn, p, sr_train_bufs(workspace, p));
+}
+
+}  // extern "C"
+
+namespace {
+
+int sr_train_run(const Call& cx, cid_sr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, unsigned flags,
+                 const cid_disc_bn* bn, const SrTrainPlan& p, const SrTrainBufs& b) {
     const hipStream_t s = cx.s;
-    char* ws = static_cast<char*>(workspace);
-    float* x0 = reinterpret_cast<float*>(ws + p.x0);
-    float* z[2] = {reinterpret_cast<float*>(ws + p.z[0]), reinterpret_cast<float*>(ws + p.z[1])};
-    float* trunk = reinterpret_cast<float*>(ws + p.trunk);
-    double* slab = reinterpret_cast<double*>(ws + p.slab);
-    float* st = reinterpret_cast<float*>(ws + p.st);
+    float* x0 = b.x0;
+    float* trunk = b.trunk;
+    double* slab = b.slab;
+    float* st = b.st;
     const float* blob = h->dev_blob;
     const long long rows = (long long)N * p.ctiles;
 
     if (const int rc = cx.launches(N, "head", [&](int n0, int n) {
         const SrHeadArgs a{in, x0, blob, H, W, H, W, 0, 0, n0};
         const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)n);
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_sr_head<true>, grid, dim3(D_THREADS), 0, s, a);
+        const SrHeadSavedArgs as{a, b.pre0};
+        if (b.pre0 && in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL((k_sr_head<true, true>), grid, dim3(D_THREADS), 0, s, as);
+        else if (b.pre0) hipLaunchKernelGGL((k_sr_head<false, true>), grid, dim3(D_THREADS), 0, s, as);
+        else if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_sr_head<true>, grid, dim3(D_THREADS), 0, s, a);
         else hipLaunchKernelGGL(k_sr_head<false>, grid, dim3(D_THREADS), 0, s, a);
     })) return rc;
-    // launches 0 .. 9: the blocks' convolutions, x0 -> z[0] -> z[1] -> z[0] ..., each followed by its BatchNorm's statistics;
-    // launch 10: mid(BN_9(z[1])) + x0 -> trunk
+    // launches 0 .. 9: the blocks' convolutions, x0 -> z[0] -> z[1] -> ..., each followed by its BatchNorm's statistics;
+    // launch 10: mid(BN_9(z[9])) + x0 -> trunk
     for (int l = 0; l <= S_TRAIN_BNS; ++l) {
         if (l == S_TRAIN_BNS) {   // every statistics launch has read its counter
             SrBnCountArgs c{};
@@ -116,8 +167,8 @@ int cid_sr_forward_train(cid_sr_t h, const void* in, int in_fmt, void* out, int 
         }
         if (const int rc = cx.launches(N, "trunk", [&](int n0, int n) {
             SrTrainConvArgs a{};
-            a.in = l == 0 ? x0 : z[(l - 1) % 2];
-            a.out = l == S_TRAIN_BNS ? trunk : z[l % 2];
+            a.in = l == 0 ? x0 : b.z[l - 1];
+            a.out = l == S_TRAIN_BNS ? trunk : b.z[l];
             a.res = x0;
             a.w = blob + kEsrHeadSeg + (size_t)l * kEsrConvSeg;
             a.st_in = l == 0 ? nullptr : st + (size_t)(l - 1) * 128;
@@ -136,19 +187,23 @@ int cid_sr_forward_train(cid_sr_t h, const void* in, int in_fmt, void* out, int 
             else hipLaunchKernelGGL((k_sr_train_conv<ST_IN_BN, ST_EPI_STATS>), grid, block, 0, s, a);
         })) return rc;
         if (l < S_TRAIN_BNS &&
-            disc_stats_launch(bn[l], 64, slab, rows, (double)N * (double)H * (double)W, st + (size_t)l * 128, nullptr, s) != hipSuccess)
+            disc_stats_launch(bn[l], 64, slab, rows, (double)N * (double)H * (double)W, st + (size_t)l * 128,
+                              b.mi ? b.mi + (size_t)l * 128 : nullptr, s) != hipSuccess)
             return cx.hip("bn stats");
     }
     // the upscale stages and the tail: cid_sr_forward's launches, which this call leaves as they are
     const float* u = trunk;
     int Hu = H, Wu = W;
     for (int k = 0; k < p.stages; ++k) {
-        float* dst = reinterpret_cast<float*>(ws + p.up[k]);
+        float* dst = b.up[k];
         const int tiles_x = (Wu + D_TW - 1) / D_TW;
         const int tiles = ((Hu + DiscGeom<64, 128, 1>::TH - 1) / DiscGeom<64, 128, 1>::TH) * tiles_x;
         if (const int rc = cx.launches(N, "upscale", [&](int n0, int n) {
             const SrUpArgs a{u, dst, blob + h->up_off(k), Hu, Wu, tiles_x, n0};
-            hipLaunchKernelGGL(k_sr_up, dim3((unsigned)tiles, (unsigned)n, 2), dim3(D_THREADS), 0, s, a);
+            const dim3 grid((unsigned)tiles, (unsigned)n, 2);
+            const SrUpSavedArgs as{a, b.pre_up[k]};
+            if (b.pre0) hipLaunchKernelGGL(k_sr_up<true>, grid, dim3(D_THREADS), 0, s, as);
+            else hipLaunchKernelGGL(k_sr_up<>, grid, dim3(D_THREADS), 0, s, a);
         })) return rc;
         u = dst;
         Hu *= 2;
@@ -165,4 +220,4 @@ int cid_sr_forward_train(cid_sr_t h, const void* in, int in_fmt, void* out, int 
     });
 }
 
-}  // extern "C"
+}  // namespace

@@ -18,6 +18,7 @@
 #include "resize_kernels.h"
 #include "esrgan_kernels.h"
 #include "srgan_kernels.h"
+#include "srgan_bwd_kernels.h"
 #include "cgan_kernels.h"
 #include "lpips_kernels.h"
 #include "vgg_kernels.h"
@@ -1518,6 +1519,7 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
 #include "api/esrgan.h"           // cid_esr_*
 #include "api/srgan.h"            // cid_sr_*
 #include "api/srgan_train.h"      // cid_sr_*: the train-mode forward (batch-statistics BatchNorm)
+#include "api/srgan_backward.h"   // cid_sr_*: saved train forward, backward, masks
 #include "api/cgan.h"             // cid_cg_*
 #include "api/lpips.h"            // cid_lpips_*
 #include "api/vgg.h"              // cid_vgg_*

@@ -24,6 +24,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "esrgan_kernels.h"
 
 namespace cid {
@@ -40,8 +42,13 @@ struct SrHeadArgs {
     int n0;
 };
 
-template <bool U8>
-__global__ void __launch_bounds__(D_THREADS) k_sr_head(const SrHeadArgs a) {
+// SAVE (cid_sr_forward_saved): the sums before PReLU go to a.pre as well, x0's layout; the backward's masks and slope gradient need them.
+struct SrHeadSavedArgs : SrHeadArgs {
+    float* pre;
+};
+
+template <bool U8, bool SAVE = false>
+__global__ void __launch_bounds__(D_THREADS) k_sr_head(const std::conditional_t<SAVE, SrHeadSavedArgs, SrHeadArgs> a) {
     const int p = blockIdx.x * D_THREADS + threadIdx.x;
     const long long HWp = (long long)a.Hp * a.Wp;
     if (p >= HWp) return;
@@ -95,6 +102,11 @@ __global__ void __launch_bounds__(D_THREADS) k_sr_head(const SrHeadArgs a) {
         d_f32x4* o = reinterpret_cast<d_f32x4*>(a.x0 + ((n * 8 + cb) * (size_t)HWp + p) * 8);
         o[0] = d_f32x4{v[0], v[1], v[2], v[3]};
         o[1] = d_f32x4{v[4], v[5], v[6], v[7]};
+        if constexpr (SAVE) {
+            d_f32x4* q = reinterpret_cast<d_f32x4*>(a.pre + ((n * 8 + cb) * (size_t)HWp + p) * 8);
+            q[0] = d_f32x4{acc[cb * 8], acc[cb * 8 + 1], acc[cb * 8 + 2], acc[cb * 8 + 3]};
+            q[1] = d_f32x4{acc[cb * 8 + 4], acc[cb * 8 + 5], acc[cb * 8 + 6], acc[cb * 8 + 7]};
+        }
     }
 }
 
@@ -117,7 +129,13 @@ struct SrUpArgs {
     int n0;
 };
 
-__global__ void __launch_bounds__(D_THREADS, 2) k_sr_up(const SrUpArgs a) {
+// SAVE (cid_sr_forward_saved): the shuffled sums before PReLU go to a.pre as well, out's layout.
+struct SrUpSavedArgs : SrUpArgs {
+    float* pre;
+};
+
+template <bool SAVE = false>
+__global__ void __launch_bounds__(D_THREADS, 2) k_sr_up(const std::conditional_t<SAVE, SrUpSavedArgs, SrUpArgs> a) {
     using G = DiscGeom<64, 128, 1>;
     constexpr int WM = G::WM, TH = G::TH, HWD = G::HWD, NPIX = G::NPIX, XSTR = G::XSTR, WSTR = G::WSTR;
     __shared__ float lds_x[8 * XSTR];
@@ -203,6 +221,7 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_sr_up(const SrUpArgs a) {
             if (iy < a.H) {
                 const int oy = 2 * iy + (kq >> 1);
                 d_f32x4 y = acc[ct][pt] + b4;
+                if constexpr (SAVE) *reinterpret_cast<d_f32x4*>(a.pre + (((n * 8 + co / 8) * Ho + oy) * (size_t)Wo + ox) * 8 + (co & 7)) = y;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) y[r] = e_prelu(y[r], slope);
                 *reinterpret_cast<d_f32x4*>(a.out + (((n * 8 + co / 8) * Ho + oy) * (size_t)Wo + ox) * 8 + (co & 7)) = y;

@@ -13,8 +13,15 @@ count, the mean and the minimum time, and the fp32-MFMA bound of the trunk and u
 64x64 -> 256x256 at scale 4, and at B=8, next to a stock copy of the network in train mode on ATen/MIOpen (under no_grad, as this
 forward has no autograd history either) and to this build's own eval forward: 3 warm-up calls, median of 5 windows of 20 calls.
 
+--backward times the differentiable train forward and its backward (SRGANGenerator(batch_stats=True, autograd=True):
+cid_sr_pack_weights_device + cid_sr_forward_saved, then cid_sr_backward under loss.backward()) at the same two shapes and protocol:
+(a) forward_saved against this build's cid_sr_forward_train, (b) forward_saved + backward against ATen/MIOpen autograd on a copy of
+the stock layers in train mode in the same process; the loss is (out * G).sum() with a resident G.  It prints the saved-buffer and
+backward-workspace sizes.
+
     python celebrity_image_denoiser_amd/csrc/tools/srgan_bench.py [--reps 5] [--iters 10] [--case N,H,W ...] [--scale 4]
                                                                   [--no-aten] [--no-u8] [--json out.json] [--trace N,H,W] [--train]
+                                                                  [--backward]
 """
 import argparse
 import csv
@@ -149,6 +156,61 @@ def run_train_case(n, h, w, args):
     return row
 
 
+def run_backward_case(n, h, w, args):
+    """forward_saved and forward_saved + backward: HIP against its own plain train forward and against ATen/MIOpen autograd."""
+    import copy
+    import ctypes
+
+    import torch
+
+    import celebrity_image_denoiser_amd as cid
+    from celebrity_image_denoiser_amd import _lib, synth
+
+    _, _, x = setup(n, h, w, args.scale)
+    sd = synth.make_srgan_state_dict("default", args.scale)
+    plain = cid.load_srgan(sd, scale_factor=args.scale, device="cuda:0", strict=True, batch_stats=True).train()
+    model = cid.load_srgan(sd, scale_factor=args.scale, device="cuda:0", strict=True, batch_stats=True, autograd=True).train()
+    stock = copy.deepcopy(torch.nn.ModuleDict({k: getattr(model, k) for k in ("initial", "res_blocks", "mid", "upscale", "final")})).train()
+    G = torch.rand((n, 3, args.scale * h, args.scale * w), device="cuda:0") * 2 - 1
+    G /= G.numel()
+
+    def stock_step():
+        for p in stock.parameters():
+            p.grad = None
+        x0 = stock["initial"](x)
+        (torch.tanh(stock["final"](stock["upscale"](stock["mid"](stock["res_blocks"](x0)) + x0))) * G).sum().backward()
+
+    def hip_step():
+        for p in model.parameters():
+            p.grad = None
+        (model(x) * G).sum().backward()
+
+    def hip_forward_saved():
+        model(x)    # with grad enabled: pack on the device + cid_sr_forward_saved; the context is dropped with the result
+
+    sizes = {}
+    for key, fn in (("saved_bytes", "cid_sr_saved_bytes"), ("backward_workspace_bytes", "cid_sr_backward_workspace_bytes"),
+                    ("forward_workspace_bytes", "cid_sr_train_workspace_bytes")):
+        v = ctypes.c_size_t()
+        assert getattr(_lib.lib(), fn)(n, h, w, args.scale, ctypes.byref(v)) == 0
+        sizes[key] = v.value
+    flops = sr_flops(n, h, w, args.scale)
+    row = {"N": n, "H": h, "W": w, "scale": args.scale, "mode": "backward", **sizes}
+    with torch.no_grad():
+        row["hip_train"] = summary(timed(lambda: plain(x), args.reps, args.iters, 3), n, flops)
+    row["hip_forward_saved"] = summary(timed(hip_forward_saved, args.reps, args.iters, 3), n, flops)
+    row["hip_step"] = summary(timed(hip_step, args.reps, args.iters, 3), n, 3 * flops)
+    ms = lambda r: f"{r['ms_median']:.3f} ms [{r['ms_min']:.3f}-{r['ms_max']:.3f}]"   # noqa: E731
+    line = (f"backward B={n:3d} {h}x{w} x{args.scale} | forward_train {ms(row['hip_train'])} | forward_saved {ms(row['hip_forward_saved'])} "
+            f"({row['hip_forward_saved']['ms_median'] / row['hip_train']['ms_median']:.2f}x) | forward_saved + backward {ms(row['hip_step'])}")
+    if not args.no_aten:
+        row["aten_step"] = summary(timed(stock_step, args.reps, args.iters, 3), n, 3 * flops)
+        line += f" | aten forward + backward {ms(row['aten_step'])} | hip/aten {row['hip_step']['ms_median'] / row['aten_step']['ms_median']:.2f}"
+    line += f" | saved {sizes['saved_bytes'] / 2 ** 20:.1f} MiB, backward workspace {sizes['backward_workspace_bytes'] / 2 ** 20:.1f} MiB"
+    print(line, flush=True)
+    return row
+
+
 def run_traced(n, h, w, args):
     """The child of --trace: a few plain forwards, nothing else."""
     import torch
@@ -236,6 +298,7 @@ def main():
     ap.add_argument("--trace", default=None, help="N,H,W: per-launch times of this case from one rocprofv3 --kernel-trace run")
     ap.add_argument("--trace-calls", type=int, default=4)
     ap.add_argument("--train", action="store_true", help="the train-mode forward at the trainer's shapes (B=16 and B=8, 64x64)")
+    ap.add_argument("--backward", action="store_true", help="forward_saved and forward_saved + backward at the trainer's shapes")
     ap.add_argument("--traced-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -244,17 +307,17 @@ def main():
         run_traced(*shape(args.traced_child), args)
         return
     rows = []
-    if args.train and not args.child:
+    if (args.train or args.backward) and not args.child:
         args.iters = 20 if args.iters == ap.get_default("iters") else args.iters
     if args.child:
-        rows = [(run_train_case if args.train else run_case)(*shape(c), args) for c in args.case]
+        rows = [(run_backward_case if args.backward else run_train_case if args.train else run_case)(*shape(c), args) for c in args.case]
     elif args.case or not args.trace:
-        for c in ([shape(c) for c in args.case] if args.case else TRAIN_CASES if args.train else CASES):
+        for c in ([shape(c) for c in args.case] if args.case else TRAIN_CASES if args.train or args.backward else CASES):
             # each case in a process of its own: allocator state and clocks of one do not reach the next
             with tempfile.NamedTemporaryFile(suffix=".json") as tf:
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case", ",".join(map(str, c)), "--scale", str(args.scale),
                        "--reps", str(args.reps), "--iters", str(args.iters), "--json", tf.name]
-                cmd += ["--no-aten"] * args.no_aten + ["--no-u8"] * args.no_u8 + ["--train"] * args.train
+                cmd += ["--no-aten"] * args.no_aten + ["--no-u8"] * args.no_u8 + ["--train"] * args.train + ["--backward"] * args.backward
                 subprocess.run(cmd, check=True)
                 rows += json.load(open(tf.name))
     if args.trace:

@@ -849,6 +849,77 @@ int cid_sr_train_stage_view(const char* stage, int N, int H, int W, int scale_fa
                             int* channel_block);
 
 /*
+ * The backward pass of that train-mode generator: g_loss.backward() of the SRGAN trainer's step (sr_ganTrainGNew.py:408) from
+ * grad_out = d loss / d fake_hr down to every parameter.  The family mirrors cid_srd_forward_saved / cid_srd_backward: per-call saved
+ * buffer, what is null is not written, the same call twice gives the same bits, no host synchronisation.  There is no input
+ * gradient: lr_img is data.
+ *
+ * cid_sr_forward_saved is cid_sr_forward_train with an fp32 output and a caller-owned PER-CALL saved buffer next to the workspace
+ * (cid_sr_train_workspace_bytes; what the backward does not need stays there: the activated x0 and stage outputs, the slab).  out
+ * and the BatchNorm buffer updates are bit-identical to cid_sr_forward_train.  The saved buffer keeps, without overlap: the head's
+ * sums v0 before its PReLU, the ten raw z_l, mid's result t, every upscale stage's shuffled sums v_k before its PReLU, the ten
+ * (scale, shift) and (mean, invstd) tables, and out.  Every PReLU mask of the backward is decided on a saved PRE-activation (v0, v_k,
+ * or BN_l(z_l) recomputed with the forward's own fmaf), so it is the forward's decision for any slope, 0 and negative ones included.
+ * cid_sr_saved_bytes(N, H, W, scale), with a(v) = v rounded up to 256 and t = N * 64 * H * W * 4:
+ *     12 a(t) + sum_{k=1..stages} a(4^k t) + a(10*64*2*4) + a(10*64*2*8) + a(N*3*sH*sW*4)
+ *
+ * cid_sr_backward: `in` is the forward's input (the head's weight gradient reads it, fp32 or uint8 through the forward's own
+ * normalisation), grad_out fp32 [N,3,sH,sW], flags the forward's (CID_SR_RAW: grad_out belongs to the sums before tanh), bn the
+ * forward's array (only gamma is read).  `g` holds one pointer per parameter tensor in the module's layouts; a null pointer means the
+ * tensor is not wanted.  The whole chain runs whatever is asked for.  BatchNorm's backward carries the two batch sums,
+ * dz = k * (g - m1 - xh * m2); the GEMM-shaped gradients (3x3 data and weight gradients of the trunk and the upscale stages, final's
+ * data and weight gradient) run on the exact-fp32 MFMA, a weight gradient accumulating in fp32 inside one workgroup's range of
+ * tiles; the head's K = 243 weight gradient runs in fp64 on the VALU; every reduction across workgroups is fp64 in a fixed order
+ * through a slab (or per-workgroup partials) and a reduce launch, no atomics.  The workspace may hold anything on entry.  Checked on the host before any launch:
+ *   CID_ERR_INVALID    null h / in / grad_out / bn / bn[l].gamma / saved / g / workspace, unknown format or flags, misaligned fp32
+ *                      pointer (the gradient tensors included)
+ *   CID_ERR_SHAPE      as cid_sr_forward_train
+ *   CID_ERR_WORKSPACE  saved buffer or workspace too small or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_sr_pack_weights_device builds the forward's blob from the parameter tensors in DEVICE memory with one launch and attaches it:
+ * byte for byte what cid_sr_set_weight + cid_sr_set_bn_eps + cid_sr_upload_weights produce, mid's identity fold, the zero gaps and the
+ * ten eval-mode folds (taken in fp64 from bn[l]'s gamma, beta, running_mean, running_var and eps, rounded as the host rounds them)
+ * included.  dev_params holds the 3 + 45 + 2 + 3 * stages + 2 parameter tensors in the module's order: initial.0.weight,
+ * initial.0.bias, initial.1.weight, per block 0.weight 0.bias 1.weight 1.bias 2.weight 3.weight 3.bias 4.weight 4.bias, mid.weight,
+ * mid.bias, per stage (3k).weight (3k).bias (3k+2).weight, final.weight, final.bias.  A trainer calls it after every optimizer step.
+ *   CID_ERR_INVALID    null h / dev_params / bn / device_blob, a null or not 4-byte-aligned parameter pointer, a null gamma, beta,
+ *                      running_mean or running_var, an eps that is not finite or negative
+ *   CID_ERR_WORKSPACE  device_blob not 256-byte aligned
+ *
+ * cid_sr_saved_masks is a testing aid as cid_srd_saved_masks: the 1 + 5 + stages PReLU decisions as the backward takes them, uint8
+ * (1 where the slope is 1): masks[0] the head [N,64,H,W], masks[1..5] the blocks' PReLUs (after res_blocks.i.1) [N,64,H,W],
+ * masks[6 + k] stage k [N,64,2^(k+1) H,2^(k+1) W].
+ */
+typedef struct {
+    float* head_w;        /* initial.0.weight [64,3,9,9]                         */
+    float* head_b;        /* initial.0.bias [64]                                 */
+    float* head_slope;    /* initial.1.weight [1]                                */
+    float* conv_w[10];    /* res_blocks.i.0.weight (2i), res_blocks.i.3.weight (2i+1) */
+    float* conv_b[10];    /* their biases                                        */
+    float* gamma[10];     /* res_blocks.i.1.weight (2i), res_blocks.i.4.weight (2i+1) */
+    float* beta[10];      /* their biases                                        */
+    float* slope[5];      /* res_blocks.i.2.weight [1]                           */
+    float* mid_w;         /* mid.weight [64,64,3,3]                              */
+    float* mid_b;         /* mid.bias [64]                                       */
+    float* up_w[3];       /* upscale.3k.weight [256,64,3,3]                      */
+    float* up_b[3];       /* upscale.3k.bias [256]                               */
+    float* up_slope[3];   /* upscale.(3k+2).weight [1]                           */
+    float* final_w;       /* final.weight [3,64,9,9]                             */
+    float* final_b;       /* final.bias [3]                                      */
+} cid_sr_grads;
+int cid_sr_saved_bytes(int N, int H, int W, int scale_factor, size_t* bytes);
+int cid_sr_forward_saved(cid_sr_t h, const void* in, int in_fmt, float* out, int N, int H, int W, unsigned flags, const cid_disc_bn* bn,
+                         void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int cid_sr_backward_workspace_bytes(int N, int H, int W, int scale_factor, size_t* bytes);
+int cid_sr_backward(cid_sr_t h, const void* in, int in_fmt, const float* grad_out, int N, int H, int W, unsigned flags,
+                    const cid_disc_bn* bn, const void* saved, size_t saved_bytes, const cid_sr_grads* g, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int cid_sr_pack_weights_device(cid_sr_t h, const float* const* dev_params, const cid_disc_bn* bn, void* device_blob, void* stream);
+int cid_sr_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int W, int scale_factor, unsigned char* const* masks,
+                       void* stream);
+
+/*
  * The server's fourth model — CGANGenerator(n_classes = 10, latent_dim = 100) (backend/app.py:105-143), the "cgan" branch of /enhance,
  * label-conditioned branch (cond a 1-D integer tensor).  Eval mode, fp32; the output is always 64 x 64:
  *
