@@ -33,6 +33,8 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
     LPIPS(net) / load_lpips(lin_ckpt, backbone, net=net)   lpips.LPIPS(net='alex'), the trainers' third metric, or net='vgg', the ESRGAN
                                   trainer's: metrics.lpips(a, b, model) -> float64 [N]; evaluate(denoised, clean, lpips=model) fills
                                   the third value
+    ESRGANDiscriminator(input_shape) / load_esrgan_discriminator(ckpt)   the ESRGAN trainer's discriminator, forward only: fp32 logits
+                                  [N,1]; esrgan_trainer_losses(D, denoised, clean) -> that trainer's d_loss, gan_loss, pixel_loss, g_loss
     VGGPerceptualLoss() / load_vgg_loss(backbone)          the SRGAN and denoise trainers' content loss, MSE of vgg16.features[:16];
                                   with autograd=True differentiable with respect to its first operand (HIP backward), else the
                                   value only, no autograd history
@@ -64,6 +66,9 @@ _LAZY = {
     "SRGANDiscriminator": ("srgan_disc", "SRGANDiscriminator"),
     "load_srgan_discriminator": ("srgan_disc", "load_srgan_discriminator"),
     "srgan_trainer_losses": ("srgan_disc", "srgan_trainer_losses"),
+    "ESRGANDiscriminator": ("esrgan_disc", "ESRGANDiscriminator"),
+    "load_esrgan_discriminator": ("esrgan_disc", "load_esrgan_discriminator"),
+    "esrgan_trainer_losses": ("esrgan_disc", "esrgan_trainer_losses"),
     "Adam": ("optim", "Adam"),
     "ESRGANGenerator": ("esrgan", "ESRGANGenerator"),
     "load_esrgan": ("esrgan", "load_esrgan"),

@@ -28,6 +28,8 @@ CID_VGG_LPIPS, CID_VGG_CONTENT = 0, 1
 CID_VGG_NUM_WEIGHTS = 33
 CID_SRD_NUM_WEIGHTS = 14
 CID_VGG_MAX_SIDE = 512
+CID_ESD_NUM_WEIGHTS = 10
+CID_ESD_MAX_SIDE = 4096
 
 
 class AdamTensor(ctypes.Structure):
@@ -127,6 +129,19 @@ SYMBOLS = {
                                     _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "cid_srd_pack_weights_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "cid_srd_saved_masks": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "cid_esd_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int]),
+    "cid_esd_destroy": (None, [_c.c_void_p]),
+    "cid_esd_last_error": (_c.c_char_p, [_c.c_void_p]),
+    "cid_esd_set_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "cid_esd_packed_weights_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
+    "cid_esd_upload_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "cid_esd_export_packed": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t]),
+    "cid_esd_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_esd_forward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                   _c.c_void_p]),
+    "cid_esd_losses": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "cid_esd_trainer_losses": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                          _c.c_void_p, _c.c_void_p]),
     "cid_disc_saved_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
     "cid_disc_forward_saved": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                           _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
@@ -288,7 +303,7 @@ def check(handle, code: int):
 
 
 def check_abi(abi: str, handle, code: int):
-    """check() for the handle of the family cid_<abi>_*: "esr", "sr", "cg", "lpips", "vgg", "disc" or "srd"."""
+    """check() for the handle of the family cid_<abi>_*: "esr", "sr", "cg", "lpips", "vgg", "disc", "srd" or "esd"."""
     if code != CID_OK:
         msg = getattr(lib(), f"cid_{abi}_last_error")(handle) if handle else None
         raise CidError(code, (msg.decode() if msg else "") or f"cid error {code}")

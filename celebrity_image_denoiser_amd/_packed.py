@@ -1,5 +1,5 @@
 """What the modules over a cid_<abi>_* weight-store handle share (ESRGANGenerator, SRGANGenerator, CGANGenerator, LPIPS,
-VGGPerceptualLoss, SRGANDiscriminator): the handle, the packed blob, the grow-only workspace and the decode of a stored stage.
+VGGPerceptualLoss, SRGANDiscriminator, ESRGANDiscriminator): the handle, the packed blob, the grow-only workspace and the decode of a stored stage.
 
 A subclass sets `_abi`, builds its layers, calls `_create(...)`, and keeps its forward and its shape errors.  Where it differs it
 overrides `_batchnorms()` (BatchNorm layers whose eps the library needs), `_key()` (state_dict key -> library key) and `_tensors()`
@@ -59,7 +59,7 @@ def load_into(model, source, device, strict: bool):
 
 
 class PackedModule(nn.Module):
-    _abi = ""     # the C ABI family: "esr", "sr", "cg", "lpips", "vgg" or "srd"
+    _abi = ""     # the C ABI family: "esr", "sr", "cg", "lpips", "vgg", "srd" or "esd"
     _form = ()    # the leading `what` argument of cid_vgg_workspace_bytes / cid_vgg_stage_view; the other families have none
 
     def _create(self, *args) -> None:

@@ -11,6 +11,7 @@
 #include "noise_kernels.h"
 #include "disc_kernels.h"
 #include "srgan_disc_kernels.h"
+#include "esrgan_disc_kernels.h"
 #include "disc_bwd_kernels.h"
 #include "gen_bwd_kernels.h"
 #include "gen_pack_kernels.h"
@@ -1221,6 +1222,7 @@ int cid_launch_work_ex(cid_handle_t h, int i, int N, int H, int W, double* flops
 #include "api/disc_backward.h"    // cid_disc_*: saved forward, backward, device pack, masks, losses
 #include "api/srgan_disc.h"       // cid_srd_*: the SRGAN trainer's discriminator, forward and losses
 #include "api/srgan_disc_backward.h"   // cid_srd_*: saved forward, backward, device pack, masks
+#include "api/esrgan_disc.h"      // cid_esd_*: the ESRGAN trainer's discriminator, forward and losses
 #include "api/adam.h"             // cid_adam_step
 
 // ---- the generator's backward pass (gen_bwd_kernels.h) ----

@@ -638,6 +638,52 @@ def srgan_inputs_u8(n: int, h: int, w: int, first_index: int = 0) -> np.ndarray:
     return add_gaussian_noise(clean_images_u8(n, h, w, first_index), 25.0, first_index)
 
 
+# ---- the ESRGAN trainer's Discriminator (backend/trainingcode/esrgan_code/models.py:36-71) ----
+
+ESRGAN_DISC_CONVS = (("conv1", 3, 64), ("conv2", 64, 128), ("conv3", 128, 256), ("conv4", 256, 512))
+ESRGAN_DISC_TRAINED_CONV_GAIN = 1.5    # "trained": conv weights U(+-gain / sqrt(fan_in)), biases U(+-0.05)
+ESRGAN_DISC_TRAINED_FC_GAIN = 12.0     # "trained": fc.weight U(+-gain / sqrt(features)), fc.bias 0.25
+
+
+def esrgan_disc_param_shapes(input_shape=(3, 256, 256)) -> "OrderedDict[str, tuple]":
+    """state_dict key -> (shape, dtype name) of the ESRGAN Discriminator(input_shape), in the module's own order.  No buffers."""
+    h, w = int(input_shape[1]), int(input_shape[2])
+    out: "OrderedDict[str, tuple]" = OrderedDict()
+    for name, cin, cout in ESRGAN_DISC_CONVS:
+        out[name + ".weight"] = ((cout, cin, 3, 3), "float32")
+        out[name + ".bias"] = ((cout,), "float32")
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    out["fc.weight"] = ((1, 512 * h * w), "float32")
+    out["fc.bias"] = ((1,), "float32")
+    return out
+
+
+def make_esrgan_disc_state_dict(kind: str = "default", input_shape=(3, 256, 256), seed: int = WEIGHT_SEED) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights keyed like the reference's ESRGAN Discriminator state_dict, from the hash streams "esrgan_disc:<kind>:<key>".
+    kind="default": every tensor U(+-1/sqrt(fan_in)), the scale of PyTorch's default Conv2d / Linear initialisation; four such layers
+        shrink the signal, so the logits stay within a few hundredths of fc.bias.
+    kind="trained": convolution weights 1.5 times that with biases U(+-0.05), and fc.weight U(+-12/sqrt(features)) with fc.bias 0.25:
+        the logits of the noisy face-like test images differ from image to image and stay within about +-1.5 at every input size (well
+        inside +-4), so BCE-with-logits runs on its curved part, not on its asymptotes, and the fc gain does not amplify the float32
+        rounding of conv4's output beyond what the parity bound leaves."""
+    if kind not in ("default", "trained"):
+        raise ValueError(f"unknown weight set {kind!r}")
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for key, (shape, _) in esrgan_disc_param_shapes(input_shape).items():
+        n = int(np.prod(shape))
+        u = 2.0 * hash_uniform(seed, _fnv1a64("esrgan_disc:" + kind + ":" + key), n) - 1.0
+        layer, leaf = key.rsplit(".", 1)
+        fan_in = n if key == "fc.weight" else int(np.prod(esrgan_disc_param_shapes(input_shape)[layer + ".weight"][0][1:]))
+        v = u / math.sqrt(fan_in)
+        if kind == "trained":
+            if layer == "fc":
+                v = u * ESRGAN_DISC_TRAINED_FC_GAIN / math.sqrt(fan_in) if leaf == "weight" else np.full(n, 0.25)
+            else:
+                v = u * ESRGAN_DISC_TRAINED_CONV_GAIN / math.sqrt(fan_in) if leaf == "weight" else u * 0.05
+        sd[key] = np.asarray(v).astype(np.float32).reshape(shape)
+    return sd
+
+
 # ---- the server's CGANGenerator (backend/app.py:105-143): parameter shapes, synthetic weights and the latent's streams ----
 
 CGAN_LATENT_DIM = 100

@@ -576,6 +576,72 @@ int cid_srd_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int
                         void* stream);
 
 /*
+ * The ESRGAN trainer's discriminator — Discriminator (backend/trainingcode/esrgan_code/models.py:36-71), which that trainer calls
+ * three times per step (esrgan_train.py:104-119) for d_loss = 0.5 * (BCEWithLogits(D(clean), 1) + BCEWithLogits(D(denoised), 0)) and
+ * g_loss = MSE(denoised, clean) + 1e-3 * BCEWithLogits(D(denoised), 1).  Forward only; its own handle and blob.
+ *
+ *   conv1 Conv2d(3,64,3,s=2,p=1)  conv2 Conv2d(64,128,3,s=2,p=1)  conv3 Conv2d(128,256,3,s=2,p=1)  conv4 Conv2d(256,512,3,s=2,p=1),
+ *   LeakyReLU(0.2) after each; then view(N,-1) and fc = Linear(512*H4*W4, 1).  The output is the LOGIT, one per image: no sigmoid.
+ *   Layer sizes: H1 = (H-1)/2 + 1 (integer division), H2 = (H1-1)/2 + 1, H3, H4 likewise, and the same for W.
+ *
+ * The linear layer fixes the input size, so a handle is created for one (H, W): cid_esd_create(&d, H, W) with
+ * 1 <= H, W <= CID_ESD_MAX_SIDE (CID_ERR_SHAPE otherwise; the bound keeps fc.weight, 512*H4*W4 floats, at 128 MiB and every
+ * per-image pixel index within an int).  A uint8 input is decoded as ToTensor() does, u / 255 in [0,1] (the ESRGAN range, the
+ * arithmetic of cid_esr_forward), so a uint8 batch and its fp32 copy give identical bits.
+ *
+ * cid_esd_set_weight takes the ten tensors by their state_dict keys "conv{1,2,3,4}.{weight,bias}" ([Cout,Cin,3,3] / [Cout]),
+ * "fc.weight" ([1, 512*H4*W4] for the handle's input size, CID_ERR_SHAPE otherwise) and "fc.bias" ([1]), fp32 in the reference
+ * layout; any other key is CID_ERR_KEY.  The packed blob of cid_esd_packed_weights_bytes(H, W) bytes (0 for a size cid_esd_create
+ * refuses) holds, each segment 64-float aligned: conv1 as it came, weights then biases; conv2, conv3, conv4 as COUT/64 blocks, one
+ * per 64-channel part, [CIN/8][9 taps][8][64] (element ((ci/8 * 9 + tap) * 8 + ci%8) * 64 + co%64 of block co/64) followed by the
+ * part's 64 biases; fc.weight permuted from the reference's NCHW flatten (feature c*H4*W4 + y*W4 + x) into the activations' C8 order
+ * (position ((c/8 * H4*W4 + y*W4 + x) * 8 + c%8); fc.bias.  cid_esd_upload_weights needs all ten (CID_ERR_STATE otherwise) and waits
+ * for its copy.  cid_esd_export_packed copies the same bytes to host memory instead (CID_ERR_STATE while a tensor is missing,
+ * CID_ERR_WORKSPACE for a buffer smaller than the blob), for transports that move the blob themselves and for tests of the layout.
+ *
+ * cid_esd_forward: `in` is device fp32 [N,3,H,W] (CID_FMT_F32_NCHW) or uint8 [N,H,W,3] (CID_FMT_U8_NHWC), out_logit device fp32 [N].
+ * conv1 runs on the VALU, conv2 ... conv4 on the exact-fp32 MFMA with one accumulation chain per output element, the linear layer in
+ * fp64 in a fixed order, one workgroup per image: an image's logit depends only on (H, W), never on N or on its position in the batch.
+ * No atomics.  Asynchronous on `stream`; any N >= 1 (batches above 65,535 images run as several launches).  Checked before any launch,
+ * in this order:
+ *   CID_ERR_INVALID    null in / out_logit / workspace, unknown format, misaligned fp32 pointer
+ *   CID_ERR_SHAPE      N < 1; H or W different from the handle's
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_esd_workspace_bytes or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_esd_workspace_bytes(N, H, W), with a256(v) = v rounded up to a multiple of 256: the four ACTIVATED tensors a1 ... a4 (fp32, the
+ * C8 layout of cid_disc_forward, LeakyReLU applied) in four distinct regions, which is what a backward pass needs of the forward:
+ *     a1 at 0                          4 * N *  64 * H1 * W1 bytes
+ *     a2 at a256(|a1|)                 4 * N * 128 * H2 * W2
+ *     a3 at a256(|a1|) + a256(|a2|)    4 * N * 256 * H3 * W3
+ *     a4 at ... + a256(|a3|)           4 * N * 512 * H4 * W4;        total = a256(|a1|) + a256(|a2|) + a256(|a3|) + a256(|a4|)
+ *
+ * cid_esd_losses: logit_real = D(clean), logit_fake = D(denoised) (device fp32 [N]) -> device double out3[3] = the means over the
+ * batch of BCEWithLogits(real, 1), BCEWithLogits(fake, 0), BCEWithLogits(fake, 1), each term max(x,0) - x*y + log1p(exp(-|x|)) in
+ * fp64, one workgroup, fixed order: d_loss = 0.5 * (out3[0] + out3[1]), gan_loss = out3[2].  cid_esd_trainer_losses adds the pixel
+ * loss over denoised / clean (fp32 [N,3,H,W] or uint8 [N,H,W,3] read as u / 255; the reduction of cid_disc_losses) and forms the
+ * trainer's sums on the device: out4[4] = d_loss, gan_loss, pixel_loss = MSE(denoised, clean), g_loss = pixel_loss + 1e-3 * gan_loss
+ * (a rounded product, then a rounded sum).  Both: CID_ERR_INVALID for a null or misaligned pointer or an unknown format,
+ * CID_ERR_SHAPE for N < 1 (or H, W outside 1 ... CID_ESD_MAX_SIDE).
+ */
+typedef struct cid_esd_s* cid_esd_t;
+#define CID_ESD_NUM_WEIGHTS 10
+#define CID_ESD_MAX_SIDE 4096
+int cid_esd_create(cid_esd_t* out, int H, int W);
+void cid_esd_destroy(cid_esd_t d);
+const char* cid_esd_last_error(cid_esd_t d);
+int cid_esd_set_weight(cid_esd_t d, const char* key, const float* host_data, const int64_t* shape, int ndim);
+size_t cid_esd_packed_weights_bytes(int H, int W);
+int cid_esd_upload_weights(cid_esd_t d, void* device_blob, void* stream);
+int cid_esd_export_packed(cid_esd_t d, void* host_dst, size_t bytes);
+int cid_esd_workspace_bytes(int N, int H, int W, size_t* bytes);
+int cid_esd_forward(cid_esd_t d, const void* in, int in_fmt, float* out_logit, int N, int H, int W, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int cid_esd_losses(const float* logit_real, const float* logit_fake, int N, double* out3, void* stream);
+int cid_esd_trainer_losses(const float* logit_real, const float* logit_fake, const void* denoised, int d_fmt, const void* clean,
+                           int c_fmt, int N, int H, int W, double* out4, void* stream);
+
+/*
  * The generator's backward pass — g_loss.backward() through DenoiseGenerator in the trainer's generator step
  * (backend/trainingcode/denoise_gan_code/training.py:420-426; the module itself :59-74).  fp32 NCHW in and out, CID_DTYPE_F32 only.
  *
