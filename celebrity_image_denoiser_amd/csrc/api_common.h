@@ -28,6 +28,8 @@ struct HandleBase {
 };
 
 // Images per launch: a grid's y (and z) extent ends at 65,535, and the kernels that put one image in a block keep to it in x.
+// tests/test_large_batches.py runs every consumer of for_each_launch past it on the smallest images; the other large axis, a tensor
+// past 2^31 elements within one launch or across several, is tests/test_wide_offsets.py's.
 constexpr int kImagesPerLaunch = 65535;
 
 // launch(n0, images) for each launch of a batch of N images, up to the first one that fails.  Returns hipPeekAtLastError() of that

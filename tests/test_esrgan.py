@@ -23,9 +23,17 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 # 1x1: the window is all padding; 5x7: smaller than the 9x9 window and than a tile; 16x16: an exact trunk tile; 13x18, 37x53: partial
-# tiles on both axes, odd sizes; 3x24x40: batch stride, several tiles; 2x64x64: an exact tail tile row, several trunk tiles
-SHAPES = [(1, 1, 1), (1, 5, 7), (2, 16, 16), (1, 13, 18), (1, 37, 53), (3, 24, 40), (2, 64, 64)]
+# tiles on both axes, odd sizes; 3x24x40: batch stride, several tiles; 2x64x64: an exact tail tile row, several trunk tiles.
+# The tail tiles 16 rows x 64 columns (E_TAIL_TH, E_TAIL_TW), a thread owning 8 consecutive pixels of one row; the last three are the
+# shapes with more than one tail column (tx >= 1: the halo origin tx * 64 - 4, the store column tx * 64 + cx + j, tiles_x itself):
+# 1x20x70: two tail columns, the second 6 wide, so `ox < W` cuts inside one thread's segment; two tail rows, the second 4 deep;
+# 1x17x130: three tail columns, the last 2 wide; the second tail row is one image row; 9 trunk tile columns;
+# 2x33x65: batch stride with a 1-pixel second column and a 1-row third tail row (test_esrgan_host.py holds the list to this coverage)
+SHAPES = [(1, 1, 1), (1, 5, 7), (2, 16, 16), (1, 13, 18), (1, 37, 53), (3, 24, 40), (2, 64, 64), (1, 20, 70), (1, 17, 130), (2, 33, 65)]
 FIRST = {s: 1100 + 10 * i for i, s in enumerate(SHAPES)}
+# The uint8 cases: of the float64 oracle's own bytes ("default", R = 8) 51.8% are 0 or 255 at 1x37x53 (first index 1140) and 54.2% at
+# 1x20x70 (first index 1170), inside u8_check's window [0.05, 0.60] before any kernel runs (test_esrgan_host.py asserts it).
+U8_SHAPES = [(1, 37, 53), (1, 20, 70)]
 FIXTURES = {("default", 8, (2, 16, 16)), ("hot", 8, (2, 16, 16)), ("default", 8, (1, 13, 18)), ("hot", 8, (1, 13, 18)),
             ("default", 1, (1, 5, 7)), ("hot", 1, (1, 5, 7)), ("default", 0, (1, 1, 1))}
 
@@ -107,8 +115,8 @@ def test_uint8_path_against_the_server_fixture():
     u8_check(got.cpu().numpy(), fx["out_u8"])
 
 
-def test_uint8_path_against_the_oracle():
-    shape = (1, 37, 53)
+@pytest.mark.parametrize("shape", U8_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_uint8_path_against_the_oracle(shape):
     got = enhance_u8(model_of("default", 8), torch.from_numpy(input_u8(shape)).to(DEV))
     u8_check(got.cpu().numpy(), esrgan_oracle.to_u8(reference("default", 8, shape)["out"]))
 
@@ -146,13 +154,14 @@ def _guarded(nbytes, fill):
     return buf, start
 
 
+@pytest.mark.parametrize("shape", [(1, 37, 53), (1, 17, 130)], ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("out_u8", [False, True], ids=["f32", "u8"])
-def test_nan_prefill_changes_nothing_and_guard_regions_stay_untouched(out_u8):
+def test_nan_prefill_changes_nothing_and_guard_regions_stay_untouched(out_u8, shape):
     """Workspace and output start as NaN bits (0xFF bytes), with 4 KiB guard regions of 0xA5 before and after each: the result is
     finite and equal to the module's, and no guard byte changes (no read of an unwritten word reaches a result, no write leaves
-    its buffer)."""
+    its buffer).  At 1x17x130 the last of three tail columns is 2 pixels wide: a tail store past the last column of the last
+    row lands in the guard behind the output."""
     m = model_of("hot", 8)
-    shape = (1, 37, 53)
     n, h, w = shape
     x = torch.from_numpy(input_of("hot", 8, shape)).to(DEV)
     want = m(x, out_dtype=torch.uint8 if out_u8 else torch.float32)

@@ -209,3 +209,45 @@ def test_oracle_agrees_with_the_uint8_fixture():
     assert d.max() <= 1 and (d != 0).mean() <= 1e-3
     sat = ((want == 0) | (want == 255)).mean()
     assert 0.05 <= sat <= 0.60, sat
+
+
+def test_the_parity_shapes_cross_every_tile_edge():
+    """test_esrgan.SHAPES against the tiling of csrc/esrgan_kernels.h, restated here: k_esr_conv owns 16 x 16 output pixels (DiscGeom's
+    TH and D_TW), k_esr_tail 16 rows x 64 columns (E_TAIL_TH, E_TAIL_TW) with 8 consecutive pixels of a row per thread (E_TAIL_PX).
+    The list must keep a shape for every edge the tail's column index tx and the plan's tiles_x take part in, so that none of
+    them can leave the list unnoticed."""
+    import test_esrgan
+
+    trunk, tail_h, tail_w, px = 16, 16, 64, 8
+    cols = lambda w: -(-w // tail_w)   # noqa: E731
+    rows = lambda h: -(-h // tail_h)   # noqa: E731
+    shapes = test_esrgan.SHAPES
+    assert len(set(shapes)) == len(shapes)
+    # >= 2 tail columns, the last one partial and cut inside one thread's 8-pixel segment
+    assert any(cols(w) >= 2 and w % tail_w and (w % tail_w) % px for _, h, w in shapes)
+    assert any(cols(w) >= 3 for _, h, w in shapes)
+    assert any(cols(w) >= 2 and w % tail_w == 1 for _, h, w in shapes)            # a last column of one pixel
+    assert any(rows(h) >= 2 and h % tail_h for _, h, w in shapes)                 # a partial last tail row
+    assert any(rows(h) >= 2 and h % tail_h == 1 for _, h, w in shapes)            # ... of a single image row
+    assert any(h % tail_h == 0 and w % tail_w == 0 for _, h, w in shapes)         # an exact tail tile
+    assert any(h < 9 and w < 9 for _, h, w in shapes)                             # smaller than the 9 x 9 window
+    assert any(n > 1 and rows(h) * cols(w) > 1 for n, h, w in shapes)             # batch stride over several tail tiles
+    assert any(n > 1 and cols(w) >= 2 for n, h, w in shapes)                      # ... and over several tail columns
+    assert any(h % trunk == 0 and w % trunk == 0 for _, h, w in shapes)           # an exact trunk tile
+    assert any(-(-w // trunk) >= 9 for _, h, w in shapes)                         # many trunk tile columns
+    # the uint8 and guard cases reach tx >= 1 too
+    assert any(cols(w) >= 2 for _, h, w in test_esrgan.U8_SHAPES)
+    assert all(s in shapes for s in test_esrgan.U8_SHAPES)
+
+
+def test_the_oracle_alone_meets_the_saturation_window_of_the_uint8_shapes():
+    """u8_check wants 5-60% of the expected bytes at 0 or 255.  That is a property of the inputs and the weights: the float64 oracle
+    alone must meet it for every shape of test_esrgan.U8_SHAPES, before any kernel runs."""
+    import test_esrgan
+
+    sd = synth.make_esrgan_state_dict("default", 8)
+    for shape in test_esrgan.U8_SHAPES:
+        want = esrgan_oracle.to_u8(esrgan_oracle.forward(sd, test_esrgan.input_of("default", 8, shape), 8)["out"])
+        sat = float(((want == 0) | (want == 255)).mean())
+        print(shape, test_esrgan.FIRST[shape], f"{sat:.4f}")
+        assert 0.05 <= sat <= 0.60, (shape, sat)

@@ -13,6 +13,9 @@ or written at another image's index shows.  Gradients with respect to parameters
 zero except on SEAM, zero rows contribute exact zeros, and the true gradient is that of the 10-image batch x[SEAM].  Train-mode
 BatchNorm couples the whole batch; at 1 x 1 the whole batch runs through the float64 reference.
 
+This file covers the axis N alone: at these sizes every tensor is a few MiB.  The large-tensor axis (an activation tensor of
+cid_esr_*, cid_sr_*, cid_cg_*, cid_srd_* or cid_esd_* past 2^31 elements, where a narrow offset shows) is tests/test_wide_offsets.py's.
+
 MS-SSIM is defined for min(H, W) > 160 only (cid_quality refuses smaller images), so the 7 x 7 case covers PSNR and SSIM and a
 case of its own runs all three metrics at 161 x 161."""
 import numpy as np
