@@ -1,5 +1,5 @@
 """What the modules over a cid_<abi>_* weight-store handle share (ESRGANGenerator, SRGANGenerator, CGANGenerator, LPIPS,
-VGGPerceptualLoss, SRGANDiscriminator, ESRGANDiscriminator): the handle, the packed blob, the grow-only workspace and the decode of a stored stage.
+VGGPerceptualLoss, DenoiseDiscriminator, SRGANDiscriminator, ESRGANDiscriminator): the handle, the packed blob, the grow-only workspace and the decode of a stored stage.
 
 A subclass sets `_abi`, builds its layers, calls `_create(...)`, and keeps its forward and its shape errors.  Where it differs it
 overrides `_batchnorms()` (BatchNorm layers whose eps the library needs), `_key()` (state_dict key -> library key) and `_tensors()`
@@ -43,15 +43,17 @@ def image_output(out_dtype, n: int, h: int, w: int, device):
     raise RuntimeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
 
 
-def load_into(model, source, device, strict: bool):
-    """The body of load_esrgan / load_srgan / load_cgan: `source` (a checkpoint path, a checkpoint dict, a state_dict or None) into
-    `model`, the model to `device` in eval mode, weights packed."""
+def load_into(model, source, device, strict: bool, key_candidates=None):
+    """The body of load_esrgan / load_srgan / load_cgan and of the BatchNorm discriminators' loaders: `source` (a checkpoint path, a
+    checkpoint dict, a state_dict or None) into `model`, the model to `device` in eval mode, weights packed.  `key_candidates`: where
+    the state_dict sits in a checkpoint dict, where that is not the generators' default (api.extract_state_dict)."""
     from .api import _read_checkpoint_file, extract_state_dict
 
+    where = () if key_candidates is None else (key_candidates,)
     if isinstance(source, str):
-        model.load_state_dict(_read_checkpoint_file(source), strict=strict)
+        model.load_state_dict(_read_checkpoint_file(source, *where), strict=strict)
     elif source is not None:
-        sd = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(v)) for k, v in extract_state_dict(source).items()}
+        sd = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(v)) for k, v in extract_state_dict(source, *where).items()}
         model.load_state_dict(sd, strict=strict)
     model.to(device).eval()
     model.pack_weights()
@@ -59,7 +61,7 @@ def load_into(model, source, device, strict: bool):
 
 
 class PackedModule(nn.Module):
-    _abi = ""     # the C ABI family: "esr", "sr", "cg", "lpips", "vgg", "srd" or "esd"
+    _abi = ""     # the C ABI family: "esr", "sr", "cg", "lpips", "vgg", "disc", "srd" or "esd"
     _form = ()    # the leading `what` argument of cid_vgg_workspace_bytes / cid_vgg_stage_view; the other families have none
 
     def _create(self, *args) -> None:

@@ -169,18 +169,8 @@ int cid_esd_set_weight(cid_esd_t d, const char* key, const float* data, const in
     if (!ok) return d->fail(CID_ERR_SHAPE, "cid_esd_set_weight: size mismatch for " + k);
     float* seg = d->staging.data() + d->blob.off[li];
     const size_t nw = (size_t)L.cout * L.cin * 9;
-    const size_t block = (size_t)L.cin * 9 * ESD_PART + ESD_PART;   // one part of an MFMA layer
-    if (li == 0) {
-        std::memcpy(is_bias ? seg + nw : seg, data, (is_bias ? (size_t)L.cout : nw) * sizeof(float));
-    } else if (is_bias) {
-        for (int co = 0; co < L.cout; ++co) seg[(size_t)(co / ESD_PART) * block + (size_t)L.cin * 9 * ESD_PART + co % ESD_PART] = data[co];
-    } else {
-        for (int co = 0; co < L.cout; ++co)
-            for (int ci = 0; ci < L.cin; ++ci)
-                for (int tap = 0; tap < 9; ++tap)
-                    seg[(size_t)(co / ESD_PART) * block + ((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * ESD_PART + co % ESD_PART] =
-                        data[((size_t)co * L.cin + ci) * 9 + tap];
-    }
+    if (li == 0) std::memcpy(is_bias ? seg + nw : seg, data, (is_bias ? (size_t)L.cout : nw) * sizeof(float));
+    else pack_mfma_layer(seg, is_bias ? nullptr : data, is_bias ? data : nullptr, L.cin, L.cout, ESD_PART);
     d->have[li][is_bias] = true;
     return CID_OK;
 }
@@ -201,12 +191,7 @@ int cid_esd_upload_weights(cid_esd_t d, void* device_blob, void* stream) {
     if (!device_blob) return d->fail(CID_ERR_INVALID, "cid_esd_upload_weights: null device pointer");
     if ((uintptr_t)device_blob & 255) return d->fail(CID_ERR_WORKSPACE, "cid_esd_upload_weights: blob must be 256-byte aligned");
     if (const int rc = esd_all_set(d, "cid_esd_upload_weights")) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, d->staging.data(), d->blob.total * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return d->fail(CID_ERR_HIP, std::string("cid_esd_upload_weights: ") + hipGetErrorString(e));
-    d->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
+    return d->upload_blob("cid_esd_upload_weights: ", device_blob, d->staging.data(), d->blob.total, stream);
 }
 
 int cid_esd_workspace_bytes(int N, int H, int W, size_t* bytes) {

@@ -421,12 +421,7 @@ int cid_vgg_upload_backward_weights(cid_vgg_t h, void* device_blob, void* stream
     if ((uintptr_t)device_blob & 255) return h->fail(CID_ERR_WORKSPACE, fn + "blob must be 256-byte aligned");
     h->bwd_staging.assign(vg_bwd_floats(), 0.f);
     vg_pack_backward(h, h->bwd_staging.data());
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->bwd_staging.data(), h->bwd_staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // the staging copy is pageable
-    if (e != hipSuccess) return h->fail(CID_ERR_HIP, fn + hipGetErrorString(e));
-    h->dev_bwd = static_cast<const float*>(device_blob);
-    return CID_OK;
+    return h->upload_blob(fn, device_blob, h->bwd_staging.data(), h->bwd_staging.size(), stream, &h->dev_bwd);
 }
 
 int cid_vgg_content_backward(cid_vgg_t h, const double* grad_out, float* grad_a, int N, int H, int W, unsigned flags, void* saved,

@@ -14,7 +14,7 @@ namespace cid {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline size_t align64(size_t floats) { return (floats + 63) & ~(size_t)63; }
+constexpr size_t align64(size_t floats) { return (floats + 63) & ~(size_t)63; }
 // An image operand: uint8 NHWC, or fp32 NCHW on a 4-byte boundary.
 inline bool fmt_ok(const void* p, int f) { return f == CID_FMT_U8_NHWC || (f == CID_FMT_F32_NCHW && ((uintptr_t)p & 3) == 0); }
 // A workspace plan's next region: the offset `at` stands at, which then moves past `bytes`, rounded up to 256.
@@ -25,7 +25,30 @@ struct HandleBase {
     std::string err;
     const float* dev_blob = nullptr;
     int fail(int code, const std::string& msg) { err = msg; return code; }
+    // The copy of cid_*_upload_weights: `floats` staged floats to `device_blob`, waited for (the staging copy is pageable host memory
+    // owned by the handle), then attached as *slot (the handle's blob unless it keeps a second one).  `fn` = "<entry point>: ".
+    int upload_blob(const std::string& fn, void* device_blob, const float* staged, size_t floats, void* stream, const float** slot = nullptr) {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        hipError_t e = hipMemcpyAsync(device_blob, staged, floats * sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(CID_ERR_HIP, fn + hipGetErrorString(e));
+        *(slot ? slot : &dev_blob) = static_cast<const float*>(device_blob);
+        return CID_OK;
+    }
 };
+
+// One MFMA convolution layer (3x3, CIN % 8 == 0) in the layout k_disc_conv and k_esd_conv read: cout / part blocks, one per `part`
+// output channels, each [CIN/8][9 taps][8][part] weights with its part biases right behind.  Writes the weights (`w`, reference
+// [cout][cin][3][3]) or the biases (`b`), whichever is not null, into the layer's segment `seg`.
+inline void pack_mfma_layer(float* seg, const float* w, const float* b, int cin, int cout, int part) {
+    const size_t nwp = (size_t)cin * 9 * part, block = nwp + part;
+    for (int co = 0; co < cout; ++co) {
+        float* dst = seg + (size_t)(co / part) * block + co % part;
+        if (b) dst[nwp] = b[co];
+        for (int ci = 0; w && ci < cin; ++ci)
+            for (int tap = 0; tap < 9; ++tap) dst[((size_t)((ci / 8) * 9 + tap) * 8 + ci % 8) * part] = w[((size_t)co * cin + ci) * 9 + tap];
+    }
+}
 
 // Images per launch: a grid's y (and z) extent ends at 65,535, and the kernels that put one image in a block keep to it in x.
 // tests/test_large_batches.py runs every consumer of for_each_launch past it on the smallest images; the other large axis, a tensor

@@ -806,12 +806,7 @@ int cid_upload_weights(cid_handle_t h, void* device_blob, void* stream) {
     if (!h) return CID_ERR_INVALID;
     if (!device_blob) return h->fail(CID_ERR_INVALID, "cid_upload_weights: null device pointer");
     if ((uintptr_t)device_blob & 255) return h->fail(CID_ERR_WORKSPACE, "cid_upload_weights: blob must be 256-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(device_blob, h->staging.data(), kBlob.total * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable host memory owned by the handle
-    if (e != hipSuccess) return h->fail(CID_ERR_HIP, std::string("cid_upload_weights: ") + hipGetErrorString(e));
-    h->dev_blob = static_cast<const float*>(device_blob);
-    return CID_OK;
+    return h->upload_blob("cid_upload_weights: ", device_blob, h->staging.data(), kBlob.total, stream);
 }
 
 int cid_pack_weights_device(cid_handle_t h, const float* const* dev_params, void* device_blob, void* stream) {
@@ -1218,8 +1213,8 @@ int cid_launch_work_ex(cid_handle_t h, int i, int N, int H, int W, double* flops
 #include "api/quality.h"          // cid_quality
 #include "api/noise.h"            // cid_add_noise
 #include "api/resize.h"           // cid_resize_*
-#include "api/disc_forward.h"     // cid_disc_*: weights, forward
-#include "api/disc_backward.h"    // cid_disc_*: saved forward, backward, device pack, masks, losses
+#include "api/disc_forward.h"     // the BatchNorm discriminators' shared description; cid_disc_*: weights, forward
+#include "api/disc_backward.h"    // their shared backward side; cid_disc_*: saved forward, backward, device pack, masks, losses
 #include "api/srgan_disc.h"       // cid_srd_*: the SRGAN trainer's discriminator, forward and losses
 #include "api/srgan_disc_backward.h"   // cid_srd_*: saved forward, backward, device pack, masks
 #include "api/esrgan_disc.h"      // cid_esd_*: the ESRGAN trainer's discriminator, forward and losses

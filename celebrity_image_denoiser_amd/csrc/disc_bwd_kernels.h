@@ -26,7 +26,8 @@
 //     one element.  Contraction over 8-channel chunks of dz; weights are read from the forward's packed blob, transposed in staging.
 //   * k_disc_wgrad0 / k_disc_wgrad0_reduce / k_disc_dgrad0: layer 0 (K = 27) on the VALU; LeakyReLU's mask is a0 > 0.
 //   * k_disc_masks: testing aid, the four masks as the kernels above decide them.
-//   * k_disc_pack: the forward's packed blob from the ten parameter tensors, on the device.
+//   * k_disc_pack: a discriminator's packed blob from its convolutions' parameter tensors, on the device (this one's ten, or the
+//     SRGAN discriminator's fourteen).
 // The SRGAN trainer's discriminator (cid_srd_backward, srgan_disc_bwd_kernels.h) runs its layers 0-10 on these kernels as they are
 // and its 128 -> 256 layer on further instantiations, through trailing template arguments that default to the kernels above: POOL, the
 // upstream gradient in a third form (D_UP_POOL: one value per image and channel, what an average pool passes down); CD_PART, the
@@ -723,42 +724,53 @@ __global__ void __launch_bounds__(D_THREADS) k_disc_masks(const DiscMaskArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The forward's packed blob from the ten parameter tensors (reference layouts, device memory): what cid_disc_set_weight +
-// cid_disc_upload_weights build on the host, byte for byte (alignment gaps are 0).
+// A discriminator's packed blob from its convolutions' parameter tensors (reference layouts, device memory): what cid_disc_set_weight
+// + cid_disc_upload_weights, or the SRGAN discriminator's pair, build on the host, byte for byte (alignment gaps are 0).  part[l] > 0:
+// layer l is packed [CIN/8][9 taps][8][part] with its part biases behind, one such block per part output channels (pack_mfma_layer,
+// api_common.h); part[l] = 0: it keeps the reference layout, weights then biases.
+constexpr int D_PACK_LAYERS = 7;
+
 struct DiscPackArgs {
-    const float* w[5];
-    const float* b[5];
+    const float* w[D_PACK_LAYERS];
+    const float* b[D_PACK_LAYERS];
     float* blob;
-    int off[5], cin[5], cout[5], kk[5];
+    int off[D_PACK_LAYERS], cin[D_PACK_LAYERS], cout[D_PACK_LAYERS], kk[D_PACK_LAYERS], part[D_PACK_LAYERS];
+    int layers;   // slots in use
     int total;
 };
 
 __global__ void __launch_bounds__(D_THREADS) k_disc_pack(const DiscPackArgs a) {
     const int i = blockIdx.x * D_THREADS + threadIdx.x;
     if (i >= a.total) return;
-    int l = 0, off = a.off[0], cout = a.cout[0], cin = a.cin[0], kk = a.kk[0];
+    int off = a.off[0], cout = a.cout[0], cin = a.cin[0], kk = a.kk[0], part = a.part[0];
     const float* w = a.w[0];
     const float* b = a.b[0];
 #pragma unroll
-    for (int k = 1; k < 5; ++k)
-        if (i >= a.off[k]) {
-            l = k;
+    for (int k = 1; k < D_PACK_LAYERS; ++k)
+        if (k < a.layers && i >= a.off[k]) {
             off = a.off[k];
             cout = a.cout[k];
             cin = a.cin[k];
             kk = a.kk[k];
+            part = a.part[k];
             w = a.w[k];
             b = a.b[k];
         }
     const int r = i - off, nw = cout * cin * kk;
     float v = 0.0f;
-    if (r < nw) {
-        if (l >= 1 && l <= 3) {   // [CIN/8][9 taps][8][COUT]
-            const int co = r % cout, q = r / cout, ci8 = q & 7, tap = (q >> 3) % 9, chunk = (q >> 3) / 9;
-            v = w[((size_t)co * cin + chunk * 8 + ci8) * 9 + tap];
-        } else {
-            v = w[r];
+    if (part > 0) {
+        const int nwp = cin * 9 * part, block = nwp + part;
+        const int pi = r / block, rr = r - pi * block;
+        if (pi < cout / part) {
+            if (rr < nwp) {
+                const int co = pi * part + rr % part, q = rr / part, ci8 = q & 7, tap = (q >> 3) % 9, chunk = (q >> 3) / 9;
+                v = w[((size_t)co * cin + chunk * 8 + ci8) * 9 + tap];
+            } else {
+                v = b[pi * part + rr - nwp];
+            }
         }
+    } else if (r < nw) {
+        v = w[r];
     } else if (r < nw + cout) {
         v = b[r - nw];
     }

@@ -20,12 +20,13 @@
 //     and the kernel is the single-part one.
 //   * k_disc_bn_stats (train): one workgroup per channel reduces the slab in a fixed order in fp64, writes the channel's (scale,
 //     shift) for the next layer's staging and updates running_mean / running_var in the module's own buffers.
-//   * k_disc_bn_eval (eval): (scale, shift) of all three BatchNorms from the running buffers.
+//   * k_disc_bn_eval (eval): (scale, shift) of all of a discriminator's BatchNorms from the running buffers, one workgroup each (three
+//     here, four in the SRGAN discriminator).
 //     Both also write the (mean, invstd) pairs in fp64 when the call keeps its tensors for a backward pass (cid_disc_forward_saved;
 //     the backward kernels are in disc_bwd_kernels.h).
 //   * k_disc_head: one 1024-thread workgroup per image: BN9 + LeakyReLU of z8, the global average (fp64, fixed order), the 1x1 convolution and
 //     the sigmoid.
-//   * k_disc_bn_count (train): num_batches_tracked += 1 of the three BatchNorms, after every statistics launch has read them.
+//   * k_disc_bn_count (train): num_batches_tracked += 1 of those BatchNorms, after every statistics launch has read them.
 //   * k_disc_losses: the trainer's BCE / MSE reductions over one batch (fp64, fixed order).
 // An image's tiles depend only on (H, W), never on N or on its position in the batch.
 #pragma once
@@ -331,16 +332,20 @@ __global__ void __launch_bounds__(D_THREADS) k_disc_bn_stats(const DiscStatsArgs
     }
 }
 
-// Eval-mode (scale, shift) of the three BatchNorms from their running buffers: grid = 3 layers, block = 128 channels.
+// Eval-mode (scale, shift) of a discriminator's BatchNorms from their running buffers: grid = its BatchNorms (up to D_MAX_BNS),
+// block = D_BN_MAXC channels.
+constexpr int D_MAX_BNS = 4;
+constexpr int D_BN_MAXC = 256;
+
 struct DiscBnEvalArgs {
-    const float* gamma[3];
-    const float* beta[3];
-    const float* running_mean[3];
-    const float* running_var[3];
-    double eps[3];
-    float* st[3];
-    int C[3];
-    double* mi[3];                // may be null: (running_mean, invstd) pairs [C] for the backward pass
+    const float* gamma[D_MAX_BNS];
+    const float* beta[D_MAX_BNS];
+    const float* running_mean[D_MAX_BNS];
+    const float* running_var[D_MAX_BNS];
+    double eps[D_MAX_BNS];
+    float* st[D_MAX_BNS];
+    int C[D_MAX_BNS];
+    double* mi[D_MAX_BNS];        // may be null: (running_mean, invstd) pairs [C] for the backward pass
 };
 
 // Channel c of one eval-mode BatchNorm: its (scale, shift) and, where `mi` is not null, its (running_mean, invstd).
@@ -355,18 +360,19 @@ __device__ __forceinline__ void d_bn_eval_channel(const float* gamma, const floa
     }
 }
 
-__global__ void __launch_bounds__(128) k_disc_bn_eval(const DiscBnEvalArgs a) {
+__global__ void __launch_bounds__(D_BN_MAXC) k_disc_bn_eval(const DiscBnEvalArgs a) {
     const int l = blockIdx.x, c = threadIdx.x;
     if (c >= a.C[l]) return;
     d_bn_eval_channel(a.gamma[l], a.beta[l], a.running_mean[l], a.running_var[l], a.eps[l], a.st[l], a.mi[l], c);
 }
 
-__global__ void __launch_bounds__(64) k_disc_bn_count(long long* a, long long* b, long long* c) {
-    if (threadIdx.x == 0) {
-        a[0] += 1;
-        b[0] += 1;
-        c[0] += 1;
-    }
+struct DiscBnCountArgs {
+    long long* count[D_MAX_BNS];
+    int n;
+};
+
+__global__ void __launch_bounds__(64) k_disc_bn_count(const DiscBnCountArgs a) {
+    if ((int)threadIdx.x < a.n) a.count[threadIdx.x][0] += 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@
 //   * k_srd_head_reduce: the sums over images, in image order, in fp64: dW15[j][c] = sum_n dh[n][j] * m[n][c] (a workgroup owns
 //     eight j and all 256 c), and in one more workgroup db15[j] = sum_n dh[n][j], dw17[j] = sum_n dl[n] * a16[n][j], db17 = sum_n dl[n].
 //   * k_srd_hidden_mask: testing aid, h > 0 as the kernels above decide it.
-//   * k_srd_pack: the forward's packed blob from the fourteen parameter tensors, on the device.
+// The device pack of its fourteen parameter tensors is k_disc_pack (disc_bwd_kernels.h).
 #pragma once
 #include "disc_bwd_kernels.h"
 #include "srgan_disc_kernels.h"
@@ -125,58 +125,6 @@ __global__ void __launch_bounds__(SRD_HEAD_C) k_srd_head_reduce(const SrdHeadRed
 __global__ void __launch_bounds__(D_THREADS) k_srd_hidden_mask(const double* hidden, unsigned char* out, long long total) {
     const long long o = (long long)blockIdx.x * D_THREADS + threadIdx.x;
     if (o < total) out[o] = hidden[o] > 0.0 ? 1 : 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The forward's packed blob from the fourteen parameter tensors (reference layouts, device memory): what cid_srd_set_weight +
-// cid_srd_upload_weights build on the host, byte for byte (alignment gaps are 0).  part[l] > 0: the layer is packed
-// [CIN/8][9 taps][8][part] with its part biases behind, one such block per part output channels.
-constexpr int SRD_PACK_LAYERS = 7;
-
-struct SrdPackArgs {
-    const float* w[SRD_PACK_LAYERS];
-    const float* b[SRD_PACK_LAYERS];
-    float* blob;
-    int off[SRD_PACK_LAYERS], cin[SRD_PACK_LAYERS], cout[SRD_PACK_LAYERS], kk[SRD_PACK_LAYERS], part[SRD_PACK_LAYERS];
-    int total;
-};
-
-__global__ void __launch_bounds__(D_THREADS) k_srd_pack(const SrdPackArgs a) {
-    const int i = blockIdx.x * D_THREADS + threadIdx.x;
-    if (i >= a.total) return;
-    int off = a.off[0], cout = a.cout[0], cin = a.cin[0], kk = a.kk[0], part = a.part[0];
-    const float* w = a.w[0];
-    const float* b = a.b[0];
-#pragma unroll
-    for (int k = 1; k < SRD_PACK_LAYERS; ++k)
-        if (i >= a.off[k]) {
-            off = a.off[k];
-            cout = a.cout[k];
-            cin = a.cin[k];
-            kk = a.kk[k];
-            part = a.part[k];
-            w = a.w[k];
-            b = a.b[k];
-        }
-    const int r = i - off, nw = cout * cin * kk;
-    float v = 0.0f;
-    if (part > 0) {
-        const int nwp = cin * 9 * part, block = nwp + part;
-        const int pi = r / block, rr = r - pi * block;
-        if (pi < cout / part) {
-            if (rr < nwp) {
-                const int co = pi * part + rr % part, q = rr / part, ci8 = q & 7, tap = (q >> 3) % 9, chunk = (q >> 3) / 9;
-                v = w[((size_t)co * cin + chunk * 8 + ci8) * 9 + tap];
-            } else {
-                v = b[pi * part + rr - nwp];
-            }
-        }
-    } else if (r < nw) {
-        v = w[r];
-    } else if (r < nw + cout) {
-        v = b[r - nw];
-    }
-    a.blob[i] = v;
 }
 
 }  // namespace cid

@@ -5,56 +5,18 @@
 // statistics kernel and the C8 layout of disc_kernels.h serve them unchanged.  What this file adds:
 //   * model.11, Conv2d(128, 256, 3, p=1), is k_disc_conv<128, 128, 1, true, STATS, 256>: the kernel keeps its 128-channel workgroup
 //     and the layer runs as two channel halves, grid z = half (disc_kernels.h).  No kernel text here.
-//   * k_srd_bn_eval (eval): (scale, shift) of the four BatchNorms from their running buffers: grid = 4 layers, block = 256 channels.
-//   * k_srd_bn_count (train): num_batches_tracked += 1 of the four BatchNorms.
+//   * The eval-mode (scale, shift) of its four BatchNorms and their counters' increment are k_disc_bn_eval and k_disc_bn_count, which
+//     take up to four BatchNorms of up to 256 channels.  No kernel text here either.
 //   * k_srd_head: one 1024-thread workgroup per image: BN12 + LeakyReLU of z11, the global average, Conv2d(256, 512, 1) + LeakyReLU,
 //     Conv2d(512, 1, 1) and the sigmoid, every sum in fp64 in a fixed order.
 //   * k_srd_losses: the SRGAN trainer's two BCE reductions over one batch (fp64, fixed order).
-//   * k_srd_bn_eval_saved, k_srd_head_saved: what cid_srd_forward_saved runs in their place.  The first also writes each BatchNorm's
-//     (running_mean, invstd) in fp64, the second also keeps the 256 pooled means and the 512 hidden pre-activations of each image, in
-//     fp64, for the backward's head (srgan_disc_bwd_kernels.h).  They share the plain kernels' arithmetic statement for statement.
+//   * k_srd_head_saved: what cid_srd_forward_saved runs in k_srd_head's place.  It also keeps the 256 pooled means and the 512 hidden
+//     pre-activations of each image, in fp64, for the backward's head (srgan_disc_bwd_kernels.h), and shares the plain kernel's
+//     arithmetic statement for statement.
 #pragma once
 #include "disc_kernels.h"
 
 namespace cid {
-
-constexpr int SRD_BNS = 4;
-constexpr int SRD_BN_MAXC = 256;
-
-struct SrdBnEvalArgs {
-    const float* gamma[SRD_BNS];
-    const float* beta[SRD_BNS];
-    const float* running_mean[SRD_BNS];
-    const float* running_var[SRD_BNS];
-    double eps[SRD_BNS];
-    float* st[SRD_BNS];
-    int C[SRD_BNS];
-};
-
-__global__ void __launch_bounds__(SRD_BN_MAXC) k_srd_bn_eval(const SrdBnEvalArgs a) {
-    const int l = blockIdx.x, c = threadIdx.x;
-    if (c >= a.C[l]) return;
-    d_bn_eval_channel(a.gamma[l], a.beta[l], a.running_mean[l], a.running_var[l], a.eps[l], a.st[l], nullptr, c);
-}
-
-struct SrdBnEvalSavedArgs {
-    SrdBnEvalArgs e;
-    double* mi[SRD_BNS];   // out: (running_mean, invstd) pairs [C]
-};
-
-__global__ void __launch_bounds__(SRD_BN_MAXC) k_srd_bn_eval_saved(const SrdBnEvalSavedArgs a) {
-    const int l = blockIdx.x, c = threadIdx.x;
-    if (c >= a.e.C[l]) return;
-    d_bn_eval_channel(a.e.gamma[l], a.e.beta[l], a.e.running_mean[l], a.e.running_var[l], a.e.eps[l], a.e.st[l], a.mi[l], c);
-}
-
-struct SrdBnCountArgs {
-    long long* count[SRD_BNS];
-};
-
-__global__ void __launch_bounds__(64) k_srd_bn_count(const SrdBnCountArgs a) {
-    if (threadIdx.x < SRD_BNS) a.count[threadIdx.x][0] += 1;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Head: BatchNorm12 + LeakyReLU of z11, AdaptiveAvgPool2d(1), Conv2d(256, 512, 1) + LeakyReLU, Conv2d(512, 1, 1), Sigmoid.

@@ -91,10 +91,10 @@ LAUNCHES = (
     ("k_disc_dgrad<128, 64, 1", "dgrad5"), ("k_disc_wgrad<64, 64, 2", "wgrad2"), ("k_disc_dgrad<64, 64, 2", "dgrad2"),
     ("k_disc_wgrad0_reduce", "wgrad0 red"), ("k_disc_wgrad0", "wgrad0"), ("k_disc_dgrad0", "dgrad0"),
     ("k_disc_wgrad_reduce", "wgrad red"), ("k_disc_bn_bwd_part", "bn sums"), ("k_disc_bn_bwd_reduce", "bn reduce"),
-    ("k_srd_head_bwd", "head bwd"), ("k_srd_head_reduce", "head red"), ("k_srd_pack", "pack"),
+    ("k_srd_head_bwd", "head bwd"), ("k_srd_head_reduce", "head red"), ("k_disc_pack", "pack"),
     ("k_disc_conv0", "conv0"), ("k_disc_conv<64, 64, 2", "conv2"), ("k_disc_conv<64, 128, 1", "conv5"),
     ("k_disc_conv<128, 128, 2", "conv8"), ("k_disc_conv<128, 128, 1", "conv11"), ("k_srd_head", "head"),
-    ("k_disc_bn_stats", "bn stats"), ("k_srd_bn_eval", "bn eval"), ("k_srd_bn_count", "bn count"))
+    ("k_disc_bn_stats", "bn stats"), ("k_disc_bn_eval", "bn eval"), ("k_disc_bn_count", "bn count"))
 
 
 def shares(path, case):

@@ -112,12 +112,7 @@ struct WeightStore : HandleBase {
         if (complete && first_missing() >= 0) return fail(CID_ERR_STATE, fn + keys[first_missing()].name + " not set");
         staging.assign(blob_floats, 0.f);
         pack(staging.data());
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        hipError_t e = hipMemcpyAsync(device_blob, staging.data(), staging.size() * sizeof(float), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);   // staging is pageable
-        if (e != hipSuccess) return fail(CID_ERR_HIP, fn + hipGetErrorString(e));
-        dev_blob = static_cast<const float*>(device_blob);
-        return CID_OK;
+        return upload_blob(fn, device_blob, staging.data(), staging.size(), stream);
     }
 };
 

@@ -20,10 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
-
-_CONVS = ("model.0", "model.2", "model.5", "model.8", "model.12")
-_BNS = (3, 6, 9)
+from . import _lib, _packed
 
 
 class _BnArg(ctypes.Structure):
@@ -33,10 +30,12 @@ class _BnArg(ctypes.Structure):
                 ("momentum", ctypes.c_double)]
 
 
-class _GradsArg(ctypes.Structure):
-    """cid_disc_grads (include/cid.h)."""
-    _fields_ = [("w", ctypes.c_void_p * 5), ("b", ctypes.c_void_p * 5), ("gamma", ctypes.c_void_p * 3),
-                ("beta", ctypes.c_void_p * 3), ("input", ctypes.c_void_p)]
+def _grads_arg(convs: int, bns: int):
+    """cid_disc_grads / cid_srd_grads (include/cid.h): the struct of a discriminator with that many convolutions and BatchNorms."""
+    class _GradsArg(ctypes.Structure):
+        _fields_ = [("w", ctypes.c_void_p * convs), ("b", ctypes.c_void_p * convs), ("gamma", ctypes.c_void_p * bns),
+                    ("beta", ctypes.c_void_p * bns), ("input", ctypes.c_void_p)]
+    return _GradsArg()
 
 
 def _out_side(s: int) -> int:
@@ -71,19 +70,173 @@ def named_bn_args(named, dev: torch.device):
     return arr
 
 
-class DenoiseDiscriminator(nn.Module):
-    """The reference's discriminator.  `self.model` is a Sequential of stock layers used as parameter containers, so state_dict keys,
-    .to(), load_state_dict(), .train() and .eval() behave as in the reference.  forward dispatches on self.training:
+class BatchNormDiscriminator(_packed.PackedModule):
+    """What DenoiseDiscriminator and SRGANDiscriminator (srgan_disc.py) share: a Sequential `self.model` of stock layers whose
+    convolutions `_CONVS` are packed into the blob and whose BatchNorms `_BNS` are call arguments (indices into the Sequential).
+    A subclass sets `_abi` and the two tuples, builds `self.model`, calls `_create()`, and names the BatchNorm that first sees a
+    single value (`_single_value_channels`).
+    forward dispatches on self.training:
       eval   BatchNorm with the running buffers;
-      train  BatchNorm with batch statistics, and the running buffers and num_batches_tracked of model.3 / model.6 / model.9 are
-             updated in place on the device, as nn.BatchNorm2d does (momentum and eps are read from the containers at every call).
+      train  BatchNorm with batch statistics, and the running buffers and num_batches_tracked are updated in place on the device,
+             as nn.BatchNorm2d does (momentum and eps are read from the containers at every call).
     The forward is asynchronous on the current stream.  With autograd=False (the default) it carries no autograd history.  With
     autograd=True, grad mode on and a parameter or the input requiring grad, it is differentiable once: each call keeps its own
-    activations (cid_disc_saved_bytes per call) until its backward has run, and weight changes are repacked on the device."""
+    activations (cid_<abi>_saved_bytes per call) until its backward has run, and weight changes are repacked on the device."""
+
+    _CONVS = ()
+    _BNS = ()
 
     def __init__(self, autograd: bool = False):
         super().__init__()
         self._autograd = bool(autograd)
+        self._bws = None           # backward workspace (uint8 tensor, grow-only)
+
+    # ------------------------------------------------------------------ weights
+    def _tensors(self):
+        # the convolution tensors; the BatchNorm tensors are call arguments.  p._version counts in-place updates made through the
+        # tensor API; after writes through `p.data` call pack_weights(force=True)
+        return [(f"model.{i}.{kind}", getattr(self.model[i], kind)) for i in self._CONVS for kind in ("weight", "bias")]
+
+    def _blob_bytes(self) -> int:
+        return self._fn("packed_weights_bytes")()
+
+    def pack_weights(self, force: bool = False) -> torch.Tensor:
+        """Repack the convolution tensors into the kernels' layout on the module's GPU (if they changed since the last call).
+        With autograd=True the pack runs on the device, into one blob that stays in place: a training loop changes the weights at
+        every step."""
+        if not self._autograd:
+            return super().pack_weights(force)
+        sig = self._signature()
+        if not force and self._blob is not None and sig == self._packed_sig:
+            return self._blob
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs only on an AMD GPU (HIP kernels behind libcid.so); move it with "
+                               ".to('cuda') first. There is no CPU fallback.")
+        ts = [t.detach() for _, t in self._tensors()]
+        if any(t.dtype != torch.float32 or t.device != dev for t in ts):
+            raise RuntimeError(f"{type(self).__name__}: convolution parameters must be float32 on {dev}")
+        ts = [t.contiguous() for t in ts]
+        if self._blob is None or self._blob.device != dev:
+            self._blob = torch.empty(self._blob_bytes(), dtype=torch.uint8, device=dev)
+        ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self._check(self._fn("pack_weights_device")(self._cid, ptrs, self._blob.data_ptr(), stream))
+        self._packed_sig = sig
+        return self._blob
+
+    # ------------------------------------------------------------------ forward
+    def _bn_args(self, dev: torch.device):
+        return bn_args(self.model, self._BNS, dev)
+
+    def _single_value_channels(self, h: int, w: int) -> int:
+        """Channels of the first BatchNorm that sees one value per channel, for an N = 1 input whose last map is 1 x 1."""
+        raise NotImplementedError
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """fp32 [N,3,H,W] in [-1,1] or uint8 [N,H,W,3] on the GPU -> fp32 [N] probabilities on the same GPU (the reference's
+        forward).  In train mode the BatchNorm running buffers are updated in place."""
+        fmt, (n, h, w) = self._image_input(x)
+        dev = self._input_device(x)
+        if n < 1 or h < 1 or w < 1:
+            raise RuntimeError(f"empty input {list(x.shape)}")
+        training = self.training
+        if training and n * _out_side(_out_side(h)) * _out_side(_out_side(w)) == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                             f"{torch.Size([n, self._single_value_channels(h, w), 1, 1])}")
+        bn = self._bn_args(dev)
+        self.pack_weights()
+        if self._autograd and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return _DiscFunction.apply(self, fmt, (n, h, w), training, x, *self.parameters())
+        self._ensure_workspace(dev, n, h, w, int(training))
+        x = x.detach().contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self._check(self._fn("forward")(self._cid, x.data_ptr(), fmt, out.data_ptr(), n, h, w, bn, int(training),
+                                            self._ws.data_ptr(), self._ws.numel(), stream))
+        return out
+
+
+class _DiscFunction(torch.autograd.Function):
+    """forward = cid_<abi>_forward_saved into a buffer owned by this call's context, backward = cid_<abi>_backward, for a
+    BatchNormDiscriminator `module`."""
+
+    @staticmethod
+    def forward(ctx, module, fmt, shape, training, x, *params):
+        n, h, w = shape
+        dev = x.device
+        need = ctypes.c_size_t()
+        module._check(module._fn("saved_bytes")(n, h, w, int(training), ctypes.byref(need)))
+        saved = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        xc = x.detach().contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        bn = module._bn_args(dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            module._check(module._fn("forward_saved")(module._cid, xc.data_ptr(), fmt, out.data_ptr(), n, h, w, bn, int(training),
+                                                      saved.data_ptr(), saved.numel(), stream))
+        ctx.module, ctx.fmt, ctx.shape, ctx.training = module, fmt, shape, training
+        ctx.saved, ctx.x = saved, xc
+        ctx.names = [k for k, _ in module.named_parameters()]
+        ctx.versions = [p._version for p in params]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_prob):
+        module = ctx.module
+        convs, bns = module._CONVS, module._BNS
+        params = list(module.parameters())
+        for name, p, v in zip(ctx.names, params, ctx.versions):
+            if p._version != v:
+                raise RuntimeError(f"{type(module).__name__}: parameter {name} was modified in place between a forward and its "
+                                   f"backward (version {p._version}, expected {v}); the gradient would be taken at the wrong weights")
+        n, h, w = ctx.shape
+        dev = ctx.x.device
+        needs = ctx.needs_input_grad
+        g = _grads_arg(len(convs), len(bns))
+        grads = [None] * len(params)
+        for i, (name, p) in enumerate(zip(ctx.names, params)):
+            if not needs[5 + i]:
+                continue
+            grads[i] = torch.empty(p.shape, dtype=torch.float32, device=dev)
+            idx, kind = int(name.split(".")[1]), name.rsplit(".", 1)[1]
+            if idx in convs:
+                (g.w if kind == "weight" else g.b)[convs.index(idx)] = grads[i].data_ptr()
+            else:
+                (g.gamma if kind == "weight" else g.beta)[bns.index(idx)] = grads[i].data_ptr()
+        grad_x = None
+        if needs[4] and ctx.fmt == _lib.CID_FMT_F32_NCHW:
+            grad_x = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+            g.input = grad_x.data_ptr()
+        need = ctypes.c_size_t()
+        module._check(module._fn("backward_workspace_bytes")(n, h, w, int(ctx.training), ctypes.byref(need)))
+        if module._bws is None or module._bws.numel() < need.value or module._bws.device != dev:
+            module._bws = None
+            module._bws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        gp = grad_prob.to(torch.float32).contiguous()
+        bn = module._bn_args(dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            module._check(module._fn("backward")(module._cid, ctx.x.data_ptr(), ctx.fmt, gp.data_ptr(), n, h, w, bn, int(ctx.training),
+                                                 ctx.saved.data_ptr(), ctx.saved.numel(), ctypes.byref(g), module._bws.data_ptr(),
+                                                 module._bws.numel(), stream))
+        ctx.saved = None
+        return (None, None, None, None, grad_x, *grads)
+
+
+class DenoiseDiscriminator(BatchNormDiscriminator):
+    """The reference's discriminator (BatchNormDiscriminator: state_dict keys, .to(), load_state_dict(), .train() and .eval() behave
+    as in the reference; train mode updates model.3 / model.6 / model.9 in place)."""
+
+    _abi = "disc"
+    _CONVS = (0, 2, 5, 8, 12)
+    _BNS = (3, 6, 9)
+
+    def __init__(self, autograd: bool = False):
+        super().__init__(autograd)
         self.model = nn.Sequential(
             nn.Conv2d(3, 64, kernel_size=3, padding=1),
             nn.LeakyReLU(0.2),
@@ -100,187 +253,10 @@ class DenoiseDiscriminator(nn.Module):
             nn.Conv2d(128, 1, kernel_size=1),
             nn.Sigmoid(),
         )
-        self._cid = ctypes.c_void_p()
-        _lib.check_disc(None, _lib.lib().cid_disc_create(ctypes.byref(self._cid)))
-        self._blob = None          # packed convolution weights on the device (uint8 tensor, owns the memory)
-        self._packed_sig = None
-        self._ws = None            # workspace (uint8 tensor, grow-only)
-        self._bws = None           # backward workspace (uint8 tensor, grow-only)
+        self._create()
 
-    def __del__(self):
-        try:
-            if getattr(self, "_cid", None):
-                _lib.lib().cid_disc_destroy(self._cid)
-                self._cid = None
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------------ weights
-    def _conv_params(self):
-        return [(f"{name}.{kind}", getattr(self.model[int(name.split('.')[1])], kind)) for name in _CONVS for kind in ("weight", "bias")]
-
-    def _signature(self):
-        # p._version counts in-place updates made through the tensor API; after writes through `p.data` call pack_weights(force=True)
-        return tuple((k, p.data_ptr(), p._version, str(p.device)) for k, p in self._conv_params())
-
-    def _device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    def pack_weights(self, force: bool = False) -> torch.Tensor:
-        """Repack the ten convolution tensors into the kernels' layout on the module's GPU (if they changed since the last call)."""
-        sig = self._signature()
-        if not force and self._blob is not None and sig == self._packed_sig:
-            return self._blob
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("DenoiseDiscriminator runs only on an AMD GPU (HIP kernels behind libcid.so); move it with "
-                               ".to('cuda') first. There is no CPU fallback.")
-        L = _lib.lib()
-        if self._autograd:
-            # a training loop changes the weights at every step: pack on the device, into one blob that stays in place
-            ts = [p.detach() for _, p in self._conv_params()]
-            if any(t.dtype != torch.float32 or t.device != dev for t in ts):
-                raise RuntimeError(f"DenoiseDiscriminator: convolution parameters must be float32 on {dev}")
-            ts = [t.contiguous() for t in ts]
-            if self._blob is None or self._blob.device != dev:
-                self._blob = torch.empty(L.cid_disc_packed_weights_bytes(), dtype=torch.uint8, device=dev)
-            ptrs = (ctypes.c_void_p * 10)(*[t.data_ptr() for t in ts])
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _lib.check_disc(self._cid, L.cid_disc_pack_weights_device(self._cid, ptrs, self._blob.data_ptr(), stream))
-            self._packed_sig = sig
-            return self._blob
-        for key, p in self._conv_params():
-            a = np.ascontiguousarray(p.detach().to("cpu", torch.float32).numpy())
-            shape = (ctypes.c_int64 * a.ndim)(*a.shape)
-            _lib.check_disc(self._cid, L.cid_disc_set_weight(self._cid, key.encode(), a.ctypes.data, shape, a.ndim))
-        blob = torch.empty(L.cid_disc_packed_weights_bytes(), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_disc(self._cid, L.cid_disc_upload_weights(self._cid, blob.data_ptr(), stream))
-        self._blob, self._packed_sig = blob, sig
-        return blob
-
-    # ------------------------------------------------------------------ forward
-    def _bn_args(self, dev: torch.device):
-        return bn_args(self.model, _BNS, dev)
-
-    def _ensure_workspace(self, n: int, h: int, w: int, training: bool, device: torch.device) -> None:
-        need = ctypes.c_size_t()
-        _lib.check_disc(self._cid, _lib.lib().cid_disc_workspace_bytes(n, h, w, int(training), ctypes.byref(need)))
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
-            if self._ws is not None:
-                torch.cuda.synchronize(self._ws.device)   # kernels of an earlier call may still use the old workspace
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=device)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """fp32 [N,3,H,W] in [-1,1] or uint8 [N,H,W,3] on the GPU -> fp32 [N] probabilities on the same GPU (reference forward,
-        training.py:97-98).  In train mode the BatchNorm running buffers are updated in place."""
-        if not isinstance(x, torch.Tensor):
-            raise TypeError("DenoiseDiscriminator expects a torch.Tensor")
-        if x.dtype == torch.uint8:
-            if x.dim() != 4 or x.shape[3] != 3:
-                raise RuntimeError(f"expected a uint8 input of shape [N,H,W,3], got {list(x.shape)}")
-            fmt, (n, h, w) = _lib.CID_FMT_U8_NHWC, (x.shape[0], x.shape[1], x.shape[2])
-        elif x.dtype == torch.float32:
-            if x.dim() != 4 or x.shape[1] != 3:
-                raise RuntimeError(f"expected a float32 input of shape [N,3,H,W], got {list(x.shape)}")
-            fmt, (n, h, w) = _lib.CID_FMT_F32_NCHW, (x.shape[0], x.shape[2], x.shape[3])
-        else:
-            raise RuntimeError(f"expected float32 [N,3,H,W] or uint8 [N,H,W,3] input, got {x.dtype}")
-        if x.device.type != "cuda":
-            raise RuntimeError("DenoiseDiscriminator.forward got a CPU tensor: this implementation is GPU-only (hand-written HIP "
-                               "kernels); there is no CPU fallback. Move the input with .to('cuda').")
-        dev = self._device()
-        if x.device != dev:
-            raise RuntimeError(f"input on {x.device} but module parameters on {dev}")
-        if n < 1 or h < 1 or w < 1:
-            raise RuntimeError(f"empty input {list(x.shape)}")
-        training = self.training
-        if training and n * _out_side(_out_side(h)) * _out_side(_out_side(w)) == 1:
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
-                             f"{torch.Size([n, 128, 1, 1])}")
-        bn = self._bn_args(dev)
-        self.pack_weights()
-        if self._autograd and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            return _DiscFunction.apply(self, fmt, (n, h, w), training, x, *self.parameters())
-        self._ensure_workspace(n, h, w, training, dev)
-        x = x.contiguous()
-        out = torch.empty(n, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_disc(self._cid, _lib.lib().cid_disc_forward(self._cid, x.data_ptr(), fmt, out.data_ptr(), n, h, w, bn,
-                                                                   int(training), self._ws.data_ptr(), self._ws.numel(), stream))
-        return out
-
-
-class _DiscFunction(torch.autograd.Function):
-    """forward = cid_disc_forward_saved into a buffer owned by this call's context, backward = cid_disc_backward."""
-
-    @staticmethod
-    def forward(ctx, module, fmt, shape, training, x, *params):
-        n, h, w = shape
-        dev = x.device
-        L = _lib.lib()
-        need = ctypes.c_size_t()
-        _lib.check_disc(module._cid, L.cid_disc_saved_bytes(n, h, w, int(training), ctypes.byref(need)))
-        saved = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        xc = x.detach().contiguous()
-        out = torch.empty(n, dtype=torch.float32, device=dev)
-        bn = module._bn_args(dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_disc(module._cid, L.cid_disc_forward_saved(module._cid, xc.data_ptr(), fmt, out.data_ptr(), n, h, w, bn,
-                                                                  int(training), saved.data_ptr(), saved.numel(), stream))
-        ctx.module, ctx.fmt, ctx.shape, ctx.training = module, fmt, shape, training
-        ctx.saved, ctx.x = saved, xc
-        ctx.names = [k for k, _ in module.named_parameters()]
-        ctx.versions = [p._version for p in params]
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_prob):
-        module = ctx.module
-        params = list(module.parameters())
-        for name, p, v in zip(ctx.names, params, ctx.versions):
-            if p._version != v:
-                raise RuntimeError(f"DenoiseDiscriminator: parameter {name} was modified in place between a forward and its backward "
-                                   f"(version {p._version}, expected {v}); the gradient would be taken at the wrong weights")
-        n, h, w = ctx.shape
-        dev = ctx.x.device
-        L = _lib.lib()
-        needs = ctx.needs_input_grad
-        g = _GradsArg()
-        grads = [None] * len(params)
-        for i, (name, p) in enumerate(zip(ctx.names, params)):
-            if not needs[5 + i]:
-                continue
-            grads[i] = torch.empty(p.shape, dtype=torch.float32, device=dev)
-            layer, kind = name.rsplit(".", 1)
-            if layer in _CONVS:
-                (g.w if kind == "weight" else g.b)[_CONVS.index(layer)] = grads[i].data_ptr()
-            else:
-                (g.gamma if kind == "weight" else g.beta)[_BNS.index(int(layer.split(".")[1]))] = grads[i].data_ptr()
-        grad_x = None
-        if needs[4] and ctx.fmt == _lib.CID_FMT_F32_NCHW:
-            grad_x = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
-            g.input = grad_x.data_ptr()
-        need = ctypes.c_size_t()
-        _lib.check_disc(module._cid, L.cid_disc_backward_workspace_bytes(n, h, w, int(ctx.training), ctypes.byref(need)))
-        if module._bws is None or module._bws.numel() < need.value or module._bws.device != dev:
-            module._bws = None
-            module._bws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        gp = grad_prob.to(torch.float32).contiguous()
-        bn = module._bn_args(dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check_disc(module._cid, L.cid_disc_backward(module._cid, ctx.x.data_ptr(), ctx.fmt, gp.data_ptr(), n, h, w, bn,
-                                                             int(ctx.training), ctx.saved.data_ptr(), ctx.saved.numel(),
-                                                             ctypes.byref(g), module._bws.data_ptr(), module._bws.numel(), stream))
-        ctx.saved = None
-        return (None, None, None, None, grad_x, *grads)
+    def _single_value_channels(self, h: int, w: int) -> int:
+        return 128
 
 
 def load_discriminator(source: Union[str, Mapping, None] = None, device: Optional[Union[str, torch.device]] = None,
@@ -289,22 +265,8 @@ def load_discriminator(source: Union[str, Mapping, None] = None, device: Optiona
     training.py:362, read with the torch-free reader), a checkpoint dict or a state_dict; "module." prefixes are stripped as for
     the generator.  `source=None` keeps the default initialisation.  `autograd=True` makes the forward differentiable
     (DenoiseDiscriminator).  Returns the module in eval mode."""
-    from .api import _read_checkpoint_file, extract_state_dict
-
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    if device is None or torch.device(device).type != "cuda":
-        raise RuntimeError("celebrity_image_denoiser_amd.load_discriminator: an AMD GPU is required (no CPU fallback)")
-    model = DenoiseDiscriminator(autograd=autograd)
-    if isinstance(source, str):
-        model.load_state_dict(_read_checkpoint_file(source, key_candidates=("discriminator",)), strict=strict)
-    elif source is not None:
-        sd = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(v))
-              for k, v in extract_state_dict(source, ("discriminator",)).items()}
-        model.load_state_dict(sd, strict=strict)
-    model.to(device).eval()
-    model.pack_weights()
-    return model
+    device = _packed.cuda_device(device, "load_discriminator")
+    return _packed.load_into(DenoiseDiscriminator(autograd=autograd), source, device, strict, key_candidates=("discriminator",))
 
 
 def _image_operand(x: torch.Tensor, what: str):
