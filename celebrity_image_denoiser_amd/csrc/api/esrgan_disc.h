@@ -1,5 +1,6 @@
 // The ESRGAN trainer's discriminator (cid_esd_*): weight packing, workspace plan, the forward's launches and the trainer's losses;
-// kernels in esrgan_disc_kernels.h.  Host code.
+// kernels in esrgan_disc_kernels.h.  The entry points that run the forward (cid_esd_forward, cid_esd_forward_saved) are in
+// esrgan_disc_backward.h, next to the backward pass.  Host code.
 #pragma once
 #include "../api_common.h"
 #include "../esrgan_disc_kernels.h"
@@ -116,6 +117,12 @@ int esd_all_set(cid_esd_t d, const char* fn) {
     return CID_OK;
 }
 
+// The text of CID_ERR_SHAPE for an input that is not the handle's size.
+std::string esd_size_message(const cid_esd_s* d, int H, int W) {
+    return "input is " + std::to_string(H) + "x" + std::to_string(W) + " but the handle was created for " + std::to_string(d->H) + "x" +
+           std::to_string(d->W) + " (the linear layer fixes it)";
+}
+
 }  // namespace
 
 extern "C" {
@@ -199,25 +206,6 @@ int cid_esd_workspace_bytes(int N, int H, int W, size_t* bytes) {
     if (!esd_side_ok(H, W)) return CID_ERR_SHAPE;
     EsdPlan p(H, W);
     return plan_bytes(esd_plan(N, H, W, p), p, bytes);
-}
-
-int cid_esd_forward(cid_esd_t d, const void* in, int in_fmt, float* out_logit, int N, int H, int W, void* workspace, size_t workspace_bytes,
-                    void* stream) {
-    if (!d) return CID_ERR_INVALID;
-    const Call cx(d, "cid_esd_forward", stream);
-    if (!in || !out_logit || !workspace) return cx.fail(CID_ERR_INVALID, "null pointer");
-    if (in_fmt != CID_FMT_F32_NCHW && in_fmt != CID_FMT_U8_NHWC) return cx.fail(CID_ERR_INVALID, "unknown input format");
-    if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)out_logit & 3))
-        return cx.fail(CID_ERR_INVALID, "misaligned fp32 operand");
-    if (N < 1) return cx.fail(CID_ERR_SHAPE, "N >= 1 required");
-    if (H != d->H || W != d->W)
-        return cx.fail(CID_ERR_SHAPE, "input is " + std::to_string(H) + "x" + std::to_string(W) + " but the handle was created for " +
-                                          std::to_string(d->H) + "x" + std::to_string(d->W) + " (the linear layer fixes it)");
-    EsdPlan p(H, W);
-    if (esd_plan(N, H, W, p) != CID_OK) return cx.fail(CID_ERR_SHAPE, "input shape not accepted");
-    if (const int rc = cx.room(workspace, workspace_bytes, p.total, "cid_esd_workspace_bytes")) return rc;
-    if (const int rc = cx.uploaded()) return rc;
-    return esd_forward_run(cx, *d, in, in_fmt, out_logit, N, p, static_cast<char*>(workspace));
 }
 
 int cid_esd_losses(const float* logit_real, const float* logit_fake, int N, double* out3, void* stream) {

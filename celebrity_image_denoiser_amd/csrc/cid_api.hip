@@ -1217,7 +1217,8 @@ int cid_launch_work_ex(cid_handle_t h, int i, int N, int H, int W, double* flops
 #include "api/disc_backward.h"    // their shared backward side; cid_disc_*: saved forward, backward, device pack, masks, losses
 #include "api/srgan_disc.h"       // cid_srd_*: the SRGAN trainer's discriminator, forward and losses
 #include "api/srgan_disc_backward.h"   // cid_srd_*: saved forward, backward, device pack, masks
-#include "api/esrgan_disc.h"      // cid_esd_*: the ESRGAN trainer's discriminator, forward and losses
+#include "api/esrgan_disc.h"      // cid_esd_*: the ESRGAN trainer's discriminator, weights, forward plan and losses
+#include "api/esrgan_disc_backward.h"  // cid_esd_*: forward, saved forward, backward, device pack
 #include "api/adam.h"             // cid_adam_step
 
 // ---- the generator's backward pass (gen_bwd_kernels.h) ----

@@ -70,6 +70,31 @@ def named_bn_args(named, dev: torch.device):
     return arr
 
 
+def device_pack(module, what: str, force: bool = False) -> torch.Tensor:
+    """pack_weights() of a differentiable module (the BatchNorm discriminators, ESRGANDiscriminator): the tensors of
+    `module._tensors()`, in that order, repacked by cid_<abi>_pack_weights_device on the module's GPU into one blob that stays in
+    place (if they changed since the last call).  `what` names the tensors in the error text."""
+    sig = module._signature()
+    if not force and module._blob is not None and sig == module._packed_sig:
+        return module._blob
+    dev = module._device()
+    if dev.type != "cuda":
+        raise RuntimeError(f"{type(module).__name__} runs only on an AMD GPU (HIP kernels behind libcid.so); move it with "
+                           ".to('cuda') first. There is no CPU fallback.")
+    ts = [t.detach() for _, t in module._tensors()]
+    if any(t.dtype != torch.float32 or t.device != dev for t in ts):
+        raise RuntimeError(f"{type(module).__name__}: {what} must be float32 on {dev}")
+    ts = [t.contiguous() for t in ts]
+    if module._blob is None or module._blob.device != dev:
+        module._blob = torch.empty(module._blob_bytes(), dtype=torch.uint8, device=dev)
+    ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        module._check(module._fn("pack_weights_device")(module._cid, ptrs, module._blob.data_ptr(), stream))
+    module._packed_sig = sig
+    return module._blob
+
+
 class BatchNormDiscriminator(_packed.PackedModule):
     """What DenoiseDiscriminator and SRGANDiscriminator (srgan_disc.py) share: a Sequential `self.model` of stock layers whose
     convolutions `_CONVS` are packed into the blob and whose BatchNorms `_BNS` are call arguments (indices into the Sequential).
@@ -106,25 +131,7 @@ class BatchNormDiscriminator(_packed.PackedModule):
         every step."""
         if not self._autograd:
             return super().pack_weights(force)
-        sig = self._signature()
-        if not force and self._blob is not None and sig == self._packed_sig:
-            return self._blob
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} runs only on an AMD GPU (HIP kernels behind libcid.so); move it with "
-                               ".to('cuda') first. There is no CPU fallback.")
-        ts = [t.detach() for _, t in self._tensors()]
-        if any(t.dtype != torch.float32 or t.device != dev for t in ts):
-            raise RuntimeError(f"{type(self).__name__}: convolution parameters must be float32 on {dev}")
-        ts = [t.contiguous() for t in ts]
-        if self._blob is None or self._blob.device != dev:
-            self._blob = torch.empty(self._blob_bytes(), dtype=torch.uint8, device=dev)
-        ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self._check(self._fn("pack_weights_device")(self._cid, ptrs, self._blob.data_ptr(), stream))
-        self._packed_sig = sig
-        return self._blob
+        return device_pack(self, "convolution parameters", force)
 
     # ------------------------------------------------------------------ forward
     def _bn_args(self, dev: torch.device):

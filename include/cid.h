@@ -578,7 +578,7 @@ int cid_srd_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int
 /*
  * The ESRGAN trainer's discriminator — Discriminator (backend/trainingcode/esrgan_code/models.py:36-71), which that trainer calls
  * three times per step (esrgan_train.py:104-119) for d_loss = 0.5 * (BCEWithLogits(D(clean), 1) + BCEWithLogits(D(denoised), 0)) and
- * g_loss = MSE(denoised, clean) + 1e-3 * BCEWithLogits(D(denoised), 1).  Forward only; its own handle and blob.
+ * g_loss = MSE(denoised, clean) + 1e-3 * BCEWithLogits(D(denoised), 1).  Its own handle and blob; the backward pass follows below.
  *
  *   conv1 Conv2d(3,64,3,s=2,p=1)  conv2 Conv2d(64,128,3,s=2,p=1)  conv3 Conv2d(128,256,3,s=2,p=1)  conv4 Conv2d(256,512,3,s=2,p=1),
  *   LeakyReLU(0.2) after each; then view(N,-1) and fc = Linear(512*H4*W4, 1).  The output is the LOGIT, one per image: no sigmoid.
@@ -640,6 +640,61 @@ int cid_esd_forward(cid_esd_t d, const void* in, int in_fmt, float* out_logit, i
 int cid_esd_losses(const float* logit_real, const float* logit_fake, int N, double* out3, void* stream);
 int cid_esd_trainer_losses(const float* logit_real, const float* logit_fake, const void* denoised, int d_fmt, const void* clean,
                            int c_fmt, int N, int H, int W, double* out4, void* stream);
+
+/*
+ * The ESRGAN discriminator's backward pass (that trainer's d_loss.backward(), esrgan_train.py:107, and the adversarial half of
+ * g_loss.backward(), :119).  The family mirrors cid_srd_forward_saved / cid_srd_backward above where the model allows it: there is no
+ * BatchNorm, so no `bn`, no `training` and no masks entry; the LeakyReLU decisions are a_l > 0 on the saved activated tensors.
+ * Gradients of conv1 ... conv4 and fc in fp32; every reduction across workgroups accumulates in fp64 in a fixed order, no atomics; the
+ * GEMMs of conv2, conv3, conv4 (data and weight gradient) run on the exact-fp32 MFMA, conv1 on the VALU.  The same call twice gives
+ * the same bits; an image's input gradient depends only on its grad_logit value and (H, W), never on N or its place in the batch.
+ *
+ * cid_esd_saved_bytes(N, H, W) is the formula of cid_esd_workspace_bytes, and returns its codes: a1 ... a4 at the offsets listed
+ * there, each rounded up to 256 bytes.  cid_esd_forward_saved is cid_esd_forward with a caller-owned PER-CALL buffer in place of the
+ * workspace: the same launches, the same argument checks in the same order with the same codes (a saved buffer that is too small or
+ * not 256-byte aligned is CID_ERR_WORKSPACE), and logits and the four saved tensors byte-identical to cid_esd_forward.
+ *
+ * cid_esd_backward: `in`, in_fmt, N, H, W and `saved` are those of the cid_esd_forward_saved call to differentiate, grad_logit the
+ * device fp32 [N] gradient of the loss with respect to the logits; the packed weights must still be the ones that call used.  `g`
+ * holds device fp32 pointers in the order conv1, conv2, conv3, conv4, fc and the reference layouts: w [Cout,Cin,3,3] and b [Cout] for
+ * the convolutions, w[4] = fc.weight [1, 512*H4*W4] in the reference's NCHW-flatten order (not C8), b[4] = fc.bias [1], and input
+ * [N,3,H,W].  Results OVERWRITE their outputs.  A null pointer skips that output and the work only it needs: the chain runs fc >
+ * conv4 > conv3 > conv2 > conv1 > input and stops at the deepest stage asked for; without g->input there is no conv1 data gradient.
+ * A uint8 input has no gradient.  Asynchronous on `stream`, no host synchronisation; any N >= 1.  Checked before any launch, in this
+ * order:
+ *   CID_ERR_INVALID    null in / grad_logit / saved / g / workspace, unknown format, misaligned fp32 operand or gradient pointer,
+ *                      g->input with a uint8 input
+ *   CID_ERR_SHAPE      N < 1; H or W different from the handle's (the forward's message)
+ *   CID_ERR_WORKSPACE  saved buffer smaller than cid_esd_saved_bytes, workspace smaller than cid_esd_backward_workspace_bytes, or
+ *                      either not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_esd_backward_workspace_bytes(N, H, W), with a256 as above, T(l) = ceil(H_l / 4) * ceil(W_l / 16) the weight-gradient items per
+ * image of conv l and S(l) = min(N * T(l), max(s_l, ceil(N * T(l) / 2048))) its splits, s_2 = 64, s_3 = 16, s_4 = 2 (a workgroup adds at
+ * most 2,048 items into its fp32 accumulators):
+ *     a256(4*N*64*H1*W1) + a256(4*N*128*H2*W2) + a256(4*N*256*H3*W3)                      gradients of a1, a2, a3
+ *   + a256(4 * 9 * max(S(2)*128*64, S(3)*256*128, S(4)*512*256))                          fp32 weight-gradient partials
+ *   + a256(8 * max(S(2)*128, S(3)*256, S(4)*512))                                         fp64 bias-gradient partials
+ *   + a256(8 * 64*28 * min(N * ceil(H1*W1 / 64), 256))                                    fp64 partials of conv1
+ *
+ * cid_esd_pack_weights_device builds the forward's blob from the ten parameter tensors in DEVICE memory (state_dict order:
+ * conv1.weight, conv1.bias, ... conv4.bias, fc.weight, fc.bias) with one kernel and attaches it: byte for byte what
+ * cid_esd_export_packed hands out after cid_esd_set_weight x 10, the C8 permutation of fc.weight, the zero padding that aligns every
+ * segment to 64 floats and fc.bias's own segment included.  CID_ERR_INVALID for a null or misaligned pointer, CID_ERR_WORKSPACE for
+ * a blob that is not 256-byte aligned.
+ */
+typedef struct {
+    float* w[5];         /* conv1, conv2, conv3, conv4, fc .weight */
+    float* b[5];         /* conv1, conv2, conv3, conv4, fc .bias   */
+    float* input;        /* fp32 [N,3,H,W]                         */
+} cid_esd_grads;
+int cid_esd_saved_bytes(int N, int H, int W, size_t* bytes);
+int cid_esd_forward_saved(cid_esd_t d, const void* in, int in_fmt, float* out_logit, int N, int H, int W, void* saved,
+                          size_t saved_bytes, void* stream);
+int cid_esd_backward_workspace_bytes(int N, int H, int W, size_t* bytes);
+int cid_esd_backward(cid_esd_t d, const void* in, int in_fmt, const float* grad_logit, int N, int H, int W, const void* saved,
+                     size_t saved_bytes, const cid_esd_grads* g, void* workspace, size_t workspace_bytes, void* stream);
+int cid_esd_pack_weights_device(cid_esd_t d, const float* const* dev_params, void* device_blob, void* stream);
 
 /*
  * The generator's backward pass — g_loss.backward() through DenoiseGenerator in the trainer's generator step
