@@ -610,7 +610,10 @@ def test_hip_graph_capture_and_replay(weight_sets):
     assert torch.equal(static_y, m(x2)) and not torch.equal(m(x1), m(x2))
 
 
-@pytest.mark.parametrize("wset,tol", [("default", 5e-4), ("hot", 5e-3)])
+FP16_TOL = {"default": 5e-4, "hot": 5e-3}     # max|delta| of the half-storage path per weight set (tests/test_operand_edges.py reads it)
+
+
+@pytest.mark.parametrize("wset,tol", list(FP16_TOL.items()))
 def test_fp16_storage_path(weight_sets, golden_dir, wset, tol):
     """BASELINE configs[4]: half storage + fp16 MFMA (fp32 accumulators) against the fp32 golden output.
     A separate numerical contract: every stored activation and weight is rounded to half (2^-11 relative), so the
