@@ -185,6 +185,11 @@ SYMBOLS = {
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "cid_esr_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
                                       _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "cid_esr_train_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "cid_esr_forward_train": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                         _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "cid_esr_train_stage_view": (_c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t),
+                                            _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "cid_sr_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int]),
     "cid_sr_destroy": (None, [_c.c_void_p]),
     "cid_sr_last_error": (_c.c_char_p, [_c.c_void_p]),

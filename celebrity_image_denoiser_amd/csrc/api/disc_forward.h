@@ -222,6 +222,19 @@ hipError_t disc_conv_launch(const DiscConvArgs& base, int layer, const DiscPlan&
 
 bool disc_finite_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
 
+// The checks of bn[0 .. count - 1] every entry point that takes cid_disc_bn shares; momentum and the counter count in train mode.
+int disc_check_bn(const Call& cx, const cid_disc_bn* bn, int count, int training) {
+    for (int l = 0; l < count; ++l) {
+        const cid_disc_bn& b = bn[l];
+        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || (training && !b.num_batches_tracked))
+            return cx.fail(CID_ERR_INVALID, "null BatchNorm pointer");
+        if (!disc_finite_nonneg(b.eps)) return cx.fail(CID_ERR_INVALID, "eps must be finite and >= 0");
+        if (training && !(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
+            return cx.fail(CID_ERR_INVALID, "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
+    }
+    return CID_OK;
+}
+
 // The argument checks every forward entry point of the discriminators shares, in the order cid.h documents, then the plan; `buf` is
 // its workspace or saved buffer.
 int disc_check_forward(const Call& cx, const DiscNet& net, const void* in, int in_fmt, const float* out, int N, int H, int W,
@@ -231,14 +244,7 @@ int disc_check_forward(const Call& cx, const DiscNet& net, const void* in, int i
     if ((in_fmt == CID_FMT_F32_NCHW && ((uintptr_t)in & 3)) || ((uintptr_t)out & 3))
         return cx.fail(CID_ERR_INVALID, "misaligned fp32 operand");
     if (training != 0 && training != 1) return cx.fail(CID_ERR_INVALID, "training must be 0 or 1");
-    for (int l = 0; l < net.nbn; ++l) {
-        const cid_disc_bn& b = bn[l];
-        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || (training && !b.num_batches_tracked))
-            return cx.fail(CID_ERR_INVALID, "null BatchNorm pointer");
-        if (!disc_finite_nonneg(b.eps)) return cx.fail(CID_ERR_INVALID, "eps must be finite and >= 0");
-        if (training && !(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
-            return cx.fail(CID_ERR_INVALID, "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
-    }
+    if (const int rc = disc_check_bn(cx, bn, net.nbn, training)) return rc;
     if (disc_plan(net, N, H, W, training, p) != CID_OK)
         return training && N >= 1 && H >= 1 && W >= 1 && (long long)H * W <= 0x7fffffffLL
                    ? cx.h->fail(CID_ERR_SHAPE, "Expected more than 1 value per channel when training")

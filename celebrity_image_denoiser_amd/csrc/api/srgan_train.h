@@ -78,14 +78,7 @@ int sr_train_check(const Call& cx, cid_sr_t h, const void* in, int in_fmt, void*
     if (!bn) return cx.fail(CID_ERR_INVALID, "null pointer");
     if (flags & ~(unsigned)CID_SR_RAW) return cx.fail(CID_ERR_INVALID, "unknown flags");
     if ((flags & CID_SR_RAW) && out_fmt != CID_FMT_F32_NCHW) return cx.fail(CID_ERR_INVALID, "CID_SR_RAW needs an fp32 output");
-    for (int l = 0; l < S_TRAIN_BNS; ++l) {
-        const cid_disc_bn& b = bn[l];
-        if (!b.gamma || !b.beta || !b.running_mean || !b.running_var || !b.num_batches_tracked)
-            return cx.fail(CID_ERR_INVALID, "null BatchNorm pointer");
-        if (!disc_finite_nonneg(b.eps)) return cx.fail(CID_ERR_INVALID, "eps must be finite and >= 0");
-        if (!(disc_finite_nonneg(b.momentum) || b.momentum == CID_DISC_MOMENTUM_NONE))
-            return cx.fail(CID_ERR_INVALID, "momentum must be finite and >= 0, or CID_DISC_MOMENTUM_NONE");
-    }
+    if (const int rc = disc_check_bn(cx, bn, S_TRAIN_BNS, 1)) return rc;
     return sr_train_plan(N, H, W, h->scale, p) == CID_OK ? (int)CID_OK : sr_train_shape_fail(cx, N, H, W);
 }
 

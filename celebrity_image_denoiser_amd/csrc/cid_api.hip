@@ -1517,6 +1517,7 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
 #include "api/esrgan.h"           // cid_esr_*
 #include "api/srgan.h"            // cid_sr_*
 #include "api/srgan_train.h"      // cid_sr_*: the train-mode forward (batch-statistics BatchNorm)
+#include "api/esrgan_train.h"     // cid_esr_*: the train-mode forward (batch-statistics BatchNorm under the blocks' skips)
 #include "api/srgan_backward.h"   // cid_sr_*: saved train forward, backward, masks
 #include "api/cgan.h"             // cid_cg_*
 #include "api/lpips.h"            // cid_lpips_*

@@ -25,7 +25,8 @@
 
 namespace cid {
 
-enum { ST_IN_RAW = 0, ST_IN_BN = 1, ST_IN_BN_PRELU = 2 };   // what the staging applies to the input
+// what the staging applies to the input; ST_IN_RES_BN is the ESRGAN generator's (esrgan_train_kernels.h): res + BN(z), stored as well
+enum { ST_IN_RAW = 0, ST_IN_BN = 1, ST_IN_BN_PRELU = 2, ST_IN_RES_BN = 3 };
 enum { ST_EPI_STATS = 0, ST_EPI_RES = 1 };                  // z + slab row, or res + z
 
 constexpr int S_TRAIN_BNS = 10;   // res_blocks.i.1, res_blocks.i.4, i = 0 .. 4
@@ -45,8 +46,11 @@ struct SrTrainConvArgs {
     int n0;
 };
 
+// The tile itself, shared with k_esr_train_conv (esrgan_train_kernels.h).  ST_IN_RES_BN only: `res_in` is the tensor the staged
+// BatchNorm is added to and `r_out` the tensor that sum is stored to, both C8 like `a.in`; the other modes pass null and read neither.
+// `a` comes by value, as a kernel's own argument does: by reference the STATS instantiations take one more SGPR.
 template <int IN, int EPI>
-__global__ void __launch_bounds__(D_THREADS, 2) k_sr_train_conv(const SrTrainConvArgs a) {
+__device__ __forceinline__ void sr_train_conv_tile(const SrTrainConvArgs a, const float* res_in, float* r_out) {
     using G = DiscGeom<64, 64, 1>;
     constexpr int WM = G::WM, TH = G::TH, HWD = G::HWD, NPIX = G::NPIX, XSTR = G::XSTR, WSTR = G::WSTR;
     constexpr bool STATS = EPI == ST_EPI_STATS;
@@ -99,6 +103,13 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_sr_train_conv(const SrTrainCon
                             v[j] = d_bn(lds_st[2 * (c + j)], v[j], lds_st[2 * (c + j) + 1]);
                             if (IN == ST_IN_BN_PRELU) v[j] = e_prelu(v[j], slope);
                         }
+                    }
+                    if (IN == ST_IN_RES_BN) {
+                        // the block's output res + BN(z), eval's association; the tile that owns the pixel (its interior, not the
+                        // halo ring) stores it, and every neighbour that stages the pixel computes the same bits
+                        const size_t at = ((n * 8 + chunk) * plane + (size_t)iy * a.W + ix) * 8 + h * 4;
+                        v = *reinterpret_cast<const d_f32x4*>(res_in + at) + v;
+                        if (hy >= 1 && hy <= TH && hx >= 1 && hx <= D_TW) *reinterpret_cast<d_f32x4*>(r_out + at) = v;
                     }
                 }
 #pragma unroll
@@ -195,6 +206,11 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_sr_train_conv(const SrTrainCon
             a.slab[(size_t)(tid * 2 + 1) * a.rows + row] = t2;
         }
     }
+}
+
+template <int IN, int EPI>
+__global__ void __launch_bounds__(D_THREADS, 2) k_sr_train_conv(const SrTrainConvArgs a) {
+    sr_train_conv_tile<IN, EPI>(a, nullptr, nullptr);
 }
 
 // num_batches_tracked += 1 of the ten BatchNorms, after every statistics launch has read them.

@@ -5,10 +5,16 @@ Cases: B=16 256^2 and B=256 128^2.  For each: median ms per call over --reps win
 TFLOP/s (2 * MACs of the 9x9 head, the 2 R trunk convolutions and the 9x9 tail: 1.242 MFLOP per pixel at R = 8) and its share of the
 157.3 TFLOP/s fp32 MFMA peak.  --residuals 0 times head + tail alone; the trunk's time per launch is the difference to R = 8 over 16.
 
+--train times the TRAIN-mode forward (ESRGANGenerator(batch_stats=True), cid_esr_forward_train) at the ESRGAN trainer's shape, B=8
+256x256, and at B=16, next to this build's own eval forward and to a stock copy of the network in train mode on ATen/MIOpen (under
+no_grad, as this forward has no autograd history either).  The three run in one process and take turns window by window: 3 warm-up
+calls each, then the median of 5 windows of 20 calls [min-max], "default" weights, inputs resident.
+
     python celebrity_image_denoiser_amd/csrc/tools/esrgan_bench.py [--reps 5] [--iters 10] [--case N,H,W ...] [--residuals 8]
-                                                                   [--no-aten] [--u8] [--json out.json]
+                                                                   [--no-aten] [--u8] [--json out.json] [--train]
 """
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -24,6 +30,7 @@ from celebrity_image_denoiser_amd import synth  # noqa: E402
 
 MFMA_F32_PEAK = 157.3e12
 CASES = ((16, 256, 256), (256, 128, 128))
+TRAIN_CASES = ((8, 256, 256), (16, 256, 256))
 
 
 def esr_flops(n, h, w, r):
@@ -55,6 +62,54 @@ def timed(fn, reps, iters):
     return out
 
 
+def timed_in_turn(fns, reps, iters, warmup=3):
+    """timed() of several callables whose windows alternate: clocks and cache state of one window reach every contender alike."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[k].append(e0.elapsed_time(e1) / iters)
+    return out
+
+
+def run_train_case(n, h, w, r, args):
+    """One train forward: HIP, this build's eval forward, and the stock layers in train mode on ATen/MIOpen."""
+    dev = "cuda:0"
+    sd = synth.make_esrgan_state_dict("default", r)
+    train = cid.load_esrgan(sd, num_residuals=r, device=dev, strict=True, batch_stats=True).train()
+    evalm = cid.load_esrgan(sd, num_residuals=r, device=dev, strict=True)   # its own module: its fold never goes stale
+    # the stock layers of the module, copied (their BatchNorm buffers move) and run as the reference's forward does
+    stock = copy.deepcopy(torch.nn.ModuleDict({k: getattr(train, k) for k in ("initial", "residuals", "final")})).train()
+    u8 = torch.from_numpy(synth.esrgan_inputs_u8(min(n, 16), h, w)).to(dev).repeat((n + 15) // 16, 1, 1, 1)[:n].contiguous()
+    x = u8.to(torch.float32).div(255.0).permute(0, 3, 1, 2).contiguous()
+
+    def stock_forward():
+        with torch.no_grad():
+            return aten_forward(stock, x)
+
+    fns = [lambda: train(x), lambda: evalm(x)] + ([] if args.no_aten else [stock_forward])
+    times = timed_in_turn(fns, args.reps, args.iters)
+    flops = esr_flops(n, h, w, r)
+    row = {"N": n, "H": h, "W": w, "R": r, "gflop": flops / 1e9, "mode": "train"}
+    row["hip_train"], row["hip_eval"] = summary(times[0], n, flops), summary(times[1], n, flops)
+    line = f"train B={n:3d} {h}x{w} R={r} | " + fmt("hip train", row["hip_train"]) + " | " + fmt("hip eval", row["hip_eval"])
+    line += f" | train/eval {row['hip_train']['ms_median'] / row['hip_eval']['ms_median']:.2f}"
+    if not args.no_aten:
+        row["aten_train"] = summary(times[2], n, flops)
+        line += " | " + fmt("aten train", row["aten_train"]) + f" | hip/aten {row['hip_train']['ms_median'] / row['aten_train']['ms_median']:.2f}"
+    print(line, flush=True)
+    return row
+
+
 def summary(t, n, flops):
     med = statistics.median(t)
     return {"ms_median": med, "ms_min": min(t), "ms_max": max(t), "images_per_s": n / med * 1e3,
@@ -75,12 +130,20 @@ def main():
     ap.add_argument("--no-aten", action="store_true", help="skip the ATen/MIOpen baseline")
     ap.add_argument("--u8", action="store_true", help="also time the uint8 -> uint8 path")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--train", action="store_true", help="the train-mode forward at the trainer's shapes (B=8 and B=16, 256x256)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("esrgan_bench needs a GPU")
     dev = "cuda:0"
     cases = [tuple(int(v) for v in c.split(",")) for c in args.case] if args.case else CASES
     r = args.residuals
+    if args.train:
+        args.iters = 20 if args.iters == ap.get_default("iters") else args.iters
+        rows = [run_train_case(n, h, w, r, args) for n, h, w in (cases if args.case else TRAIN_CASES)]
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     model = cid.load_esrgan(synth.make_esrgan_state_dict("default", r), num_residuals=r, device=dev, strict=True)
     rows = []
     for n, h, w in cases:

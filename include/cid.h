@@ -839,7 +839,7 @@ int cid_resize(cid_resize_plan_t p, const void* src_u8_nhwc, void* dst, int dst_
  * blob (cid_esr_packed_weights_bytes(h), 256-byte aligned, caller-owned device memory), copies it and attaches it; it needs every
  * tensor (CID_ERR_STATE otherwise) and waits for its copy, as cid_disc_upload_weights does.  Each BatchNorm is folded there into
  * y = fmaf(s, z, t) with s = gamma / sqrt(running_var + eps) and t = beta - running_mean * s, derived in fp64 and rounded once to
- * fp32: train-mode BatchNorm is out of scope.  PReLU is v > 0 ? v : a * v for any slope a.
+ * fp32 (train-mode BatchNorm: cid_esr_forward_train, below).  PReLU is v > 0 ? v : a * v for any slope a.
  *
  * cid_esr_forward: in is fp32 [N,3,H,W] in [0,1] (CID_FMT_F32_NCHW; the server feeds ToTensor() alone) or uint8 [N,H,W,3]
  * (CID_FMT_U8_NHWC), read as (float)u / 255.0f with a true division: a uint8 image and its /255 fp32 copy give identical bits.
@@ -871,6 +871,47 @@ int cid_esr_workspace_bytes(int N, int H, int W, size_t* bytes);
 int cid_esr_forward(cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, void* workspace,
                     size_t workspace_bytes, void* stream);
 int cid_esr_stage_view(const char* stage, int N, int H, int W, size_t* offset_bytes, int* C, int* Hs, int* Ws, int* channel_block);
+
+/*
+ * The same generator in TRAIN mode: the first line of the ESRGAN trainer's step, denoised = G(noisy) after G.train()
+ * (backend/trainingcode/esrgan_code/esrgan_train.py:89-121).  Forward only; the output carries no gradient.
+ *
+ * cid_esr_forward_train is cid_esr_forward with the 2 R BatchNorms on the statistics of THIS batch.  bn[0 .. 2R-1] describe
+ * residuals.0.block.1, residuals.0.block.4, residuals.1.block.1, ..., a cid_disc_bn each, with the semantics of cid_sr_forward_train:
+ * device pointers, eps and momentum as the containers hold them (CID_DISC_MOMENTUM_NONE for momentum=None), normalisation with the
+ * batch mean and the BIASED batch variance over N*H*W values per channel, running = (1 - m) * running + m * batch_stat with the
+ * UNBIASED variance for running_var, num_batches_tracked += 1, all on the device without host synchronisation.  Convolution weights,
+ * biases and PReLU slopes come from the blob cid_esr_upload_weights made; its folded (s, t) are not read and the blob is not changed,
+ * so upload again before the next cid_esr_forward.  in, out, in_fmt and out_fmt are cid_esr_forward's; the output is the raw sum.
+ *
+ * A block's output is r_i = r_{i-1} + BN_{2i+1}(z_{2i+1}) (r_{-1} = x1), and BN_{2i+1}'s statistics exist only after the convolution
+ * that makes z_{2i+1} has run over the whole batch.  So the next block's first convolution forms r_i = res + fmaf(scale, z, shift)
+ * (eval's expression and association) while it stages its input, and the tile that owns a pixel stores it: each element of r_i is
+ * written once, and the block outputs alternate between two tensors, apart from x1.  The tail's input
+ * x1 + (r_{R-2} + BN_{2R-1}(z_{2R-1})) is an elementwise launch.  Launches for R >= 1 (4 R + 4): head, 2 R x (convolution,
+ * statistics), one counter launch, the sum, tail.  Each convolution stores its raw z and per-tile fp64 sums of z and z^2 (one slab row
+ * per tile); the statistics launch reduces them in a fixed order.  No atomics: the same call on the same buffers gives the same bits.
+ * With R = 0 there is no BatchNorm: the call is cid_esr_forward's two launches on this workspace, bn may be NULL and N*H*W == 1 is
+ * accepted.  Checked on the host before any launch (a refused call updates nothing):
+ *   CID_ERR_INVALID    null pointer (any of bn[l]'s five included), unknown format, misaligned fp32 operand, an eps or momentum that
+ *                      is not finite or negative (other than CID_DISC_MOMENTUM_NONE)
+ *   CID_ERR_SHAPE      N < 1, H < 1, W < 1, H*W >= 2^31; with R > 0, N*H*W == 1 ("Expected more than 1 value per channel when training")
+ *   CID_ERR_WORKSPACE  workspace smaller than cid_esr_train_workspace_bytes(N, H, W, R) or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_esr_train_workspace_bytes: with a(v) = v rounded up to 256, t = N * 64 * H * W * 4 and tiles = ceil(H/16) * ceil(W/16),
+ *   5 a(t)                                 x1, the two raw z tensors the convolutions alternate between, the two tensors the block
+ *                                          outputs and the tail's input alternate between
+ *   + a(64 * 2 * N * tiles * 8)            the slab (reused by all 2 R convolutions)
+ *   + 2 R * a(64 * 2 * 4)                  one (scale, shift) table per BatchNorm, each kept
+ * (num_residuals outside [0, CID_ESR_MAX_RESIDUALS] -> CID_ERR_INVALID).  cid_esr_train_stage_view is cid_esr_stage_view for that
+ * workspace: "x1" and "tail_in".
+ */
+int cid_esr_train_workspace_bytes(int N, int H, int W, int num_residuals, size_t* bytes);
+int cid_esr_forward_train(cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W, const cid_disc_bn* bn,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int cid_esr_train_stage_view(const char* stage, int N, int H, int W, int num_residuals, size_t* offset_bytes, int* C, int* Hs, int* Ws,
+                             int* channel_block);
 
 /*
  * The server's third model — SRGANGenerator(scale_factor = 4) (backend/app.py:145-186; the same class in
