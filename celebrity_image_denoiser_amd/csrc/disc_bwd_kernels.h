@@ -18,7 +18,8 @@
 //     per channel reduces it in a fixed order, writes dgamma, dbeta and the channel's coef.
 //   * k_disc_wgrad<CD, CX, S, BN_IN, HEAD>: weight gradient of layers 2, 5, 8 as a GEMM [CD] x [9 * CX] contracted over pixels.  A
 //     workgroup owns 16 input channels (144 columns) and a contiguous range of (image, 4 x 16 pixel tile) items; the dz tile is the
-//     A operand, the activated input halo the B operand, k = four pixel rows of one column.  It writes its own partial tile;
+//     A operand, the activated input halo the B operand, k = four pixel rows of one column.  It writes its own partial tile, and
+//     folds its fp32 accumulators into that tile every D_WG_CHUNK items once a range is longer than that (large N);
 //     k_disc_wgrad_reduce sums the partials (fp64, fixed order) into [Cout, Cin, 3, 3].  The workgroups of channel block 0 also sum
 //     dz per channel: the bias gradient.
 //   * k_disc_dgrad<CD, CX, S, HEAD>: data gradient of layers 8, 5, 2 in gather form: a workgroup owns a tile of INPUT pixels (for
@@ -423,6 +424,12 @@ struct DiscWgradArgs {
 };
 
 constexpr int D_WG_TH = 4;   // output rows per item: the four k of one MFMA
+// A workgroup's range of items grows with N (items / splits), and one fp32 chain over all of it drifts: 2.4e-5 of max|dW| over the
+// 1640 items a workgroup gets at N = 35000 of 24 x 40, against 2e-6 up to about a hundred.  Past D_WG_CHUNK items the accumulators
+// are folded into the workgroup's own partial tile in memory every D_WG_CHUNK items (each lane adds to the words it wrote itself),
+// so that both chains stay short and no register is spent on it; a range of at most D_WG_CHUNK items never folds and keeps the
+// bits it always had.
+constexpr int D_WG_CHUNK = 64;
 
 template <int S>
 struct DiscWgradGeom {
@@ -466,7 +473,26 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_wgrad(const DiscWgradArgs
     for (int r = 0; r < RT; ++r)
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) acc[r][tap] = d_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    const bool fold = it1 - it0 > D_WG_CHUNK;
     double bsum = 0.0;
+
+    // a lane holds dz channels 4*kq .. 4*kq+3 of its row tile for input channel l16
+    float* part = a.part + (((size_t)split * (CX / 16) + blk) * CD_TOTAL + co0) * 144;
+    auto store_acc = [&](bool add) {
+        float* dst = part;
+        asm volatile("" : "+v"(dst));   // the addresses are formed here, not kept in registers across the item loop
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float* o = dst + ((size_t)((wave * RT + r) * 16 + kq * 4 + e) * 9 + tap) * 16 + l16;
+                    *o = add ? *o + acc[r][tap][e] : acc[r][tap][e];
+                }
+                if (add) asm volatile("" ::: "memory");   // four loads in flight, not all 36 RT: a fold costs no registers
+            }
+    };
 
     const int zb = ((wave * RT) * 16 + l16) * ZSTR + kq * D_TW;
     const int ab = l16 * XSTR + kq * S * RS;
@@ -524,19 +550,15 @@ __global__ void __launch_bounds__(D_THREADS, 2) k_disc_wgrad(const DiscWgradArgs
                 for (int r = 0; r < RT; ++r) acc[r][tap] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[r], bv, acc[r][tap], 0, 0, 0);
             }
         }
+        if (fold && (item - it0 + 1) % D_WG_CHUNK == 0) {
+            store_acc(item - it0 + 1 > D_WG_CHUNK);   // the first fold writes: the workspace may hold anything
+#pragma unroll
+            for (int r = 0; r < RT; ++r)
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) acc[r][tap] = d_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
     }
-
-    // a lane holds dz channels 4*kq .. 4*kq+3 of its row tile for input channel l16
-    float* part = a.part + (((size_t)split * (CX / 16) + blk) * CD_TOTAL + co0) * 144;
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int co = (wave * RT + r) * 16 + kq * 4 + e;
-                part[((size_t)co * 9 + tap) * 16 + l16] = acc[r][tap][e];
-            }
+    store_acc(fold);
     if (blk == 0 && tid < CD) a.part_b[(size_t)split * CD_TOTAL + co0 + tid] = bsum;
 }
 

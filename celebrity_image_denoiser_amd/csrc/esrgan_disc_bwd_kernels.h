@@ -98,6 +98,8 @@ struct EsdWgradArgs {
     int tiles_x, tiles;
 };
 
+// Known limit, open ("fp32 weight-gradient chains that grow with N"): a workgroup's whole range of items is one
+// fp32 accumulation chain, as k_disc_wgrad's was before D_WG_CHUNK (disc_bwd_kernels.h); no test runs it at an N where that shows.
 template <int CD, int CX, bool FC>
 __global__ void __launch_bounds__(D_THREADS, 2) k_esd_wgrad(const EsdWgradArgs a) {
     using G = DiscWgradGeom<2>;

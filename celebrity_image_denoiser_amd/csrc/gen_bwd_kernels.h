@@ -206,6 +206,8 @@ struct GenWgradGeom {
     static_assert(RS >= HWD, "row stride");
 };
 
+// Known limit, open ("fp32 weight-gradient chains that grow with N"): a workgroup's whole range of items is one
+// fp32 accumulation chain, as k_disc_wgrad's was before D_WG_CHUNK (disc_bwd_kernels.h); no test runs it at an N where that shows.
 template <int CRB, bool CONVT>
 __global__ void __launch_bounds__(G_THREADS, 2) k_gen_wgrad(const GenWgradArgs a) {
     using G = GenWgradGeom<CONVT>;

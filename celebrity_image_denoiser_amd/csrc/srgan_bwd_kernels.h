@@ -350,6 +350,8 @@ struct SrgWgradArgs {
     int tiles_x, tiles;
 };
 
+// Known limit, open ("fp32 weight-gradient chains that grow with N"): a workgroup's whole range of items is one
+// fp32 accumulation chain, as k_disc_wgrad's was before D_WG_CHUNK (disc_bwd_kernels.h); no test runs it at an N where that shows.
 template <int DZ, int IN, int CD_TOTAL = 64>
 __global__ void __launch_bounds__(D_THREADS, 2) k_srg_wgrad(const SrgWgradArgs a) {
     static_assert((CD_TOTAL == 256) == (DZ == SG_DZ_SHUFFLE) && DZ != SG_DZ_PRELU, "a trunk convolution or an upscale stage");
@@ -688,6 +690,8 @@ struct SrgTailWgradArgs {
     int raw;
 };
 
+// Known limit, open ("fp32 weight-gradient chains that grow with N"): a workgroup's whole range of items is one
+// fp32 accumulation chain, as k_disc_wgrad's was before D_WG_CHUNK (disc_bwd_kernels.h); no test runs it at an N where that shows.
 template <bool PRELU_IN>
 __global__ void __launch_bounds__(D_THREADS, 2) k_srg_tail_wgrad(const SrgTailWgradArgs a) {
     constexpr int ZSTR = DiscWgradGeom<1>::ZSTR;

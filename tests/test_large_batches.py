@@ -13,6 +13,10 @@ or written at another image's index shows.  Gradients with respect to parameters
 zero except on SEAM, zero rows contribute exact zeros, and the true gradient is that of the 10-image batch x[SEAM].  Train-mode
 BatchNorm couples the whole batch; at 1 x 1 the whole batch runs through the float64 reference.
 
+The train-mode entry points of the server's generators and of the SRGAN trainer (cid_esr_forward_train, cid_sr_forward_train,
+cid_sr_forward_saved + cid_sr_backward), whose launches carry the first image into slab rows and reductions as well, take the same
+split in tests/test_train_batches.py, over two seams (N = 2 * 65,535 + 9) and with the whole batch held to float64.
+
 This file covers the axis N alone: at these sizes every tensor is a few MiB.  The large-tensor axis (an activation tensor of
 cid_esr_*, cid_sr_*, cid_cg_*, cid_srd_* or cid_esd_* past 2^31 elements, where a narrow offset shows) is tests/test_wide_offsets.py's.
 

@@ -17,12 +17,13 @@ offset or a narrow size on the host reads or writes another image's memory there
       entry point in a fresh 0xFF-filled workspace, and the seam image that holds the 2^31-element boundary is held to the family's
       float64 oracle under the family's own bound, which anchors the bit comparison to something other than the code under test.
 
-Train-mode BatchNorm (cid_sr_forward_train, cid_sr_forward_saved + cid_sr_backward, cid_srd_* with training = 1) couples the whole
-batch: an image alone is another computation, and the float64 oracle of a batch whose tensors pass 2^31 elements is out of reach on
-a CPU (tens of TFLOP in float64; no smaller problem has the same statistics).  So, as the statistics are per-channel sums that
-test_large_batches.py already checks over 65,544 images, these cases cover eval mode: cid_sr_forward, cid_srd_forward(training = 0)
-and cid_srd_forward_saved + cid_srd_backward(training = 0).  Parameter gradients sum over the batch: there grad_prob is zero off the
-seam images and the gradients are those of the seam images as a small batch, under the rule of tests/test_srgan_disc_backward.py.
+Train-mode BatchNorm (cid_esr_forward_train, cid_sr_forward_train, cid_sr_forward_saved + cid_sr_backward, cid_srd_* with
+training = 1) couples the whole batch: an image alone is another computation, so (d) does not apply.  Those calls are held past 2^31
+elements by tests/test_train_batches.py, on batches that repeat a block of seven images (such a batch has the block's statistics,
+so the block's float64 oracle is the oracle of every image).  The cases here cover eval mode: cid_sr_forward,
+cid_srd_forward(training = 0) and cid_srd_forward_saved + cid_srd_backward(training = 0).  Parameter gradients sum over the batch:
+there grad_prob is zero off the seam images and the gradients are those of the seam images as a small batch, under the rule of
+tests/test_srgan_disc_backward.py.
 
 Every case needs less than the 70 GiB of test_gpu_parity.py::test_batch_past_2_31_elements_per_buffer and skips below its need plus
 that test's 20 GiB of headroom; each frees its buffers afterwards.
@@ -202,11 +203,16 @@ def test_the_cases_cross_what_they_claim():
 
 
 # ------------------------------------------------------------------------------------------------------------------ (b), (c) helpers
+def _skip_below(need):
+    """The skip rule of every case here and in test_train_batches.py: the case's own bytes plus HEADROOM must be free."""
+    free, _ = torch.cuda.mem_get_info()
+    if free < need + HEADROOM:
+        pytest.skip(f"needs {need / GIB:.0f} GiB of free device memory and {HEADROOM // GIB} GiB of headroom")
+
+
 def _case(family):
     c = crossing(family)
-    free, _ = torch.cuda.mem_get_info()
-    if free < c["need"] + HEADROOM:
-        pytest.skip(f"needs {c['need'] / GIB:.0f} GiB of free device memory and {HEADROOM // GIB} GiB of headroom")
+    _skip_below(c["need"])
     print(f"\n{family}: N = {c['n']}, past 2^31 elements: " + ", ".join(f"{k} = {c['n'] * c['per'][k]}" for k in c["past"])
           + f"; seam {c['seam']}; anchor {c['anchor']}; {c['need'] / GIB:.1f} GiB")
     return c
