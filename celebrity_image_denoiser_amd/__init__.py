@@ -23,7 +23,8 @@ Public surface (mirrors what the reference's callers use, reference backend/app.
                                   interchanges with torch.optim.Adam's
     ESRGANGenerator(num_residuals=8) / load_esrgan(ckpt)   the server's ESRGAN model (eval mode); enhance(model, x) -> the raw
                                   fp32 output, enhance_u8(model, u8) -> the server's uint8 view; with batch_stats=True a
-                                  train-mode forward (batch-statistics BatchNorm under the blocks' skips): the ESRGAN trainer's G(noisy)
+                                  train-mode forward (batch-statistics BatchNorm under the blocks' skips): the ESRGAN trainer's G(noisy),
+                                  with autograd=True as well a differentiable one (HIP backward pass): its g_loss.backward()
     SRGANGenerator(scale_factor=4) / load_srgan(ckpt)      the server's SRGAN model (eval mode): super_resolve(model, x) -> fp32 at
                                   scale times the size, super_resolve_u8(model, u8) -> the server's padded uint8 view; with
                                   batch_stats=True a train-mode forward (batch-statistics BatchNorm), with autograd=True as well a

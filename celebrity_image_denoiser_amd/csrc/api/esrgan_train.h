@@ -1,7 +1,7 @@
 // The ESRGAN generator in train mode (cid_esr_forward_train): workspace plan, argument checks and launch sequence.  Head and tail are
 // cid_esr_forward's launches (esrgan.h); the trunk runs on esrgan_train_kernels.h with the statistics kernel and the cid_disc_bn
 // contract of the discriminators (disc_forward.h).  The run takes a struct of buffer pointers, as sr_train_run does (srgan_train.h), so
-// that a saved forward can point the same launches into a buffer of its own.  Host code.
+// that cid_esr_forward_saved (esrgan_backward.h) can point the same launches into its saved buffer.  Host code.
 #pragma once
 #include "../esrgan_train_kernels.h"
 #include "disc_forward.h"
@@ -54,6 +54,7 @@ struct EsrTrainBufs {
     double* slab;
     float* st[2 * kEsrMaxBlocks];    // one (scale, shift) table per BatchNorm
     double* mi[2 * kEsrMaxBlocks];   // one (mean, invstd) table per BatchNorm, or null
+    float* v0;                       // the head's sums before PReLU (cid_esr_forward_saved), or null
 };
 
 EsrTrainBufs esr_train_bufs(void* workspace, int R, const EsrTrainPlan& p) {
@@ -70,6 +71,12 @@ EsrTrainBufs esr_train_bufs(void* workspace, int R, const EsrTrainPlan& p) {
     return b;
 }
 
+// The message of a shape esr_train_plan refused.
+int esr_train_shape_fail(const Call& cx, int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1 || (long long)N * H * W != 1) return cx.fail(CID_ERR_SHAPE, "input shape not accepted (N, H, W >= 1, H*W < 2^31)");
+    return cx.h->fail(CID_ERR_SHAPE, "Expected more than 1 value per channel when training");
+}
+
 int esr_train_check(const Call& cx, cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W,
                     const cid_disc_bn* bn, const void* workspace, EsrTrainPlan& p) {
     if (const int rc = check_image_io(cx, in, in_fmt, out, out_fmt, workspace)) return rc;
@@ -77,9 +84,7 @@ int esr_train_check(const Call& cx, cid_esr_t h, const void* in, int in_fmt, voi
         if (!bn) return cx.fail(CID_ERR_INVALID, "null pointer");
         if (const int rc = disc_check_bn(cx, bn, 2 * h->R, 1)) return rc;
     }
-    if (esr_train_plan(N, H, W, h->R, p) == CID_OK) return CID_OK;
-    if (N < 1 || H < 1 || W < 1 || (long long)N * H * W != 1) return cx.fail(CID_ERR_SHAPE, "input shape not accepted (N, H, W >= 1, H*W < 2^31)");
-    return cx.h->fail(CID_ERR_SHAPE, "Expected more than 1 value per channel when training");
+    return esr_train_plan(N, H, W, h->R, p) == CID_OK ? CID_OK : esr_train_shape_fail(cx, N, H, W);
 }
 
 int esr_train_run(const Call& cx, cid_esr_t h, const void* in, int in_fmt, void* out, int out_fmt, int N, int H, int W,
@@ -137,7 +142,11 @@ int esr_train_run(const Call& cx, cid_esr_t h, const void* in, int in_fmt, void*
     if (const int rc = cx.launches(N, "head", [&](int n0, int n) {
         const EsrHeadArgs a{in, b.x1, R == 0 ? b.tail_in : nullptr, blob, H, W, n0};
         const dim3 grid((unsigned)(((long long)H * W + D_THREADS - 1) / D_THREADS), (unsigned)n);
-        if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_esr_head<true>, grid, dim3(D_THREADS), 0, s, a);
+        if (b.v0) {
+            const EsrHeadSavedArgs sa{a, b.v0};
+            if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL((k_esr_head<true, true>), grid, dim3(D_THREADS), 0, s, sa);
+            else hipLaunchKernelGGL((k_esr_head<false, true>), grid, dim3(D_THREADS), 0, s, sa);
+        } else if (in_fmt == CID_FMT_U8_NHWC) hipLaunchKernelGGL(k_esr_head<true>, grid, dim3(D_THREADS), 0, s, a);
         else hipLaunchKernelGGL(k_esr_head<false>, grid, dim3(D_THREADS), 0, s, a);
     })) return rc;
     // launches 0 .. 2R-1: the blocks' convolutions, x1 -> z[0] -> z[1] -> ..., each followed by its BatchNorm's statistics.  An even

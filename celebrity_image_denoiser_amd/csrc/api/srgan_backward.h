@@ -84,6 +84,74 @@ int sr_bwd_plan(int N, int H, int W, int scale, SrBwdPlan& q) {
     return CID_OK;
 }
 
+// The kernel + reduce pairs cid_sr_backward and cid_esr_backward (esrgan_backward.h) launch, over one call's stream and scratch regions.
+struct SrgLaunch {
+    const Call& cx;
+    int N;
+    float* coef;
+    double* bnslab;
+    double* chan;
+    float* part;
+    double* part_b;
+    double* part9;
+
+    // sums of one tensor with a PReLU: strips -> per channel -> the slope's gradient
+    template <class K>
+    int slope_sums(K kernel, const SrgDz& dz, const float* st, const double* mi, const float* slope, const float* gamma, float* dgamma,
+                   float* dbeta, float* dslope, int Hl, int Wl, const char* what) const {
+        const hipStream_t s = cx.s;
+        const dim3 block(D_THREADS);
+        const long long P = (long long)Hl * Wl;
+        const int strips = (int)((P + D_BN_STRIP - 1) / D_BN_STRIP);
+        const long long rows = (long long)N * strips;
+        if (const int rc = cx.launches(N, what, [&](int n0, int n) {
+            const SrgBnPartArgs a{dz, st, mi, slope, bnslab, rows, P, strips, n0};
+            hipLaunchKernelGGL(kernel, dim3((unsigned)strips, (unsigned)n), block, 0, s, a);
+        })) return rc;
+        const SrgBnRedArgs r{bnslab, rows, (double)N * (double)P, gamma, st, mi, slope, coef, dgamma, dbeta, chan};
+        hipLaunchKernelGGL(k_srg_bn_reduce, dim3(64), block, 0, s, r);
+        if (slope && dslope) hipLaunchKernelGGL(k_srg_sum, dim3(1), block, 0, s, chan, 64LL, dslope);
+        return hipPeekAtLastError() == hipSuccess ? CID_OK : cx.hip(what);
+    }
+    // weight and bias gradient of a 3x3 convolution at Hl x Wl (parts = 4: an upscale stage's 256 packed columns)
+    template <class K>
+    int wgrad(K kernel, int parts, const SrgDz& dz, const float* ain, const float* st_in, const float* slope_in, float* dw, float* db, int Hl,
+              int Wl, const char* what) const {
+        if (!dw && !db) return CID_OK;
+        const hipStream_t s = cx.s;
+        const dim3 block(D_THREADS);
+        const int tiles_x = (Wl + D_TW - 1) / D_TW, tiles = ((Hl + D_WG_TH - 1) / D_WG_TH) * tiles_x;
+        const long long items = (long long)N * tiles;
+        const int splits = (int)std::min<long long>(items, parts == 1 ? kSrWgSplits : kSrWgUpSplits);
+        const SrgWgradArgs a{dz, ain, st_in, slope_in, part, part_b, items, splits, Hl, Wl, tiles_x, tiles};
+        hipLaunchKernelGGL(kernel, dim3((unsigned)splits, 4, (unsigned)parts), block, 0, s, a);
+        if (parts == 1) {
+            const DiscWgradReduceArgs r{part, part_b, dw, db, splits, 64, 64};
+            hipLaunchKernelGGL(k_disc_wgrad_reduce, dim3((64 * 64 * 9 + 64 + D_THREADS - 1) / D_THREADS), block, 0, s, r);
+        } else {
+            const SrgWgradReduceArgs r{part, part_b, dw, db, splits};
+            hipLaunchKernelGGL(k_srg_wgrad_reduce, dim3((256 * 64 * 9 + 256 + D_THREADS - 1) / D_THREADS), block, 0, s, r);
+        }
+        return hipPeekAtLastError() == hipSuccess ? CID_OK : cx.hip(what);
+    }
+    // data gradient of a 3x3 convolution: out = add + dgrad (add null: dgrad)
+    template <class K>
+    int dgrad(K kernel, const SrgDz& dz, const float* w, float* out, const float* add, int Hl, int Wl, const char* what) const {
+        const hipStream_t s = cx.s;
+        const int tiles_x = (Wl + D_TW - 1) / D_TW, tiles = ((Hl + 15) / 16) * tiles_x;
+        return cx.launches(N, what, [&](int n0, int n) {
+            const SrgDgradArgs a{dz, w, out, add, Hl, Wl, tiles_x, n0};
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)n), dim3(D_THREADS), 0, s, a);
+        });
+    }
+    // the reduce of k_srg_wgrad243's and k_srg_tail_wgrad's partials
+    int reduce9(float* dw, float* db, int splits, int head, const char* what) const {
+        const SrgWgrad9ReduceArgs r{part9, dw, db, splits, head};
+        hipLaunchKernelGGL(k_srg_wgrad243_reduce, dim3((64 * SG_W9_K + D_THREADS - 1) / D_THREADS), dim3(D_THREADS), 0, cx.s, r);
+        return hipPeekAtLastError() == hipSuccess ? CID_OK : cx.hip(what);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -169,52 +237,7 @@ int cid_sr_backward(cid_sr_t h, const void* in, int in_fmt, const float* grad_ou
     const auto up_slope = [&](int k) { return blob + h->up_off(k) + S_UP_SLOPE; };
     const dim3 block(D_THREADS);
 
-    // sums of one tensor with a PReLU: strips -> per channel -> the slope's gradient
-    const auto slope_sums = [&](auto kernel, const SrgDz& dz, const float* st, const double* mi, const float* slope, const float* gamma,
-                                float* dgamma, float* dbeta, float* dslope, int Hl, int Wl, const char* what) {
-        const long long P = (long long)Hl * Wl;
-        const int strips = (int)((P + D_BN_STRIP - 1) / D_BN_STRIP);
-        const long long rows = (long long)N * strips;
-        if (const int rc = cx.launches(N, what, [&](int n0, int n) {
-            const SrgBnPartArgs a{dz, st, mi, slope, bnslab, rows, P, strips, n0};
-            hipLaunchKernelGGL(kernel, dim3((unsigned)strips, (unsigned)n), block, 0, s, a);
-        })) return rc;
-        const SrgBnRedArgs r{bnslab, rows, (double)N * (double)P, gamma, st, mi, slope, coef, dgamma, dbeta, chan};
-        hipLaunchKernelGGL(k_srg_bn_reduce, dim3(64), block, 0, s, r);
-        if (slope && dslope) hipLaunchKernelGGL(k_srg_sum, dim3(1), block, 0, s, chan, 64LL, dslope);
-        return hipPeekAtLastError() == hipSuccess ? CID_OK : cx.hip(what);
-    };
-    // weight and bias gradient of a 3x3 convolution at Hl x Wl
-    const auto wgrad = [&](auto kernel, int parts, const SrgDz& dz, const float* ain, const float* st_in, const float* slope_in, float* dw,
-                           float* db, int Hl, int Wl, const char* what) {
-        if (!dw && !db) return (int)CID_OK;
-        const int tiles_x = (Wl + D_TW - 1) / D_TW, tiles = ((Hl + D_WG_TH - 1) / D_WG_TH) * tiles_x;
-        const long long items = (long long)N * tiles;
-        const int splits = (int)std::min<long long>(items, parts == 1 ? kSrWgSplits : kSrWgUpSplits);
-        const SrgWgradArgs a{dz, ain, st_in, slope_in, part, part_b, items, splits, Hl, Wl, tiles_x, tiles};
-        hipLaunchKernelGGL(kernel, dim3((unsigned)splits, 4, (unsigned)parts), block, 0, s, a);
-        if (parts == 1) {
-            const DiscWgradReduceArgs r{part, part_b, dw, db, splits, 64, 64};
-            hipLaunchKernelGGL(k_disc_wgrad_reduce, dim3((64 * 64 * 9 + 64 + D_THREADS - 1) / D_THREADS), block, 0, s, r);
-        } else {
-            const SrgWgradReduceArgs r{part, part_b, dw, db, splits};
-            hipLaunchKernelGGL(k_srg_wgrad_reduce, dim3((256 * 64 * 9 + 256 + D_THREADS - 1) / D_THREADS), block, 0, s, r);
-        }
-        return hipPeekAtLastError() == hipSuccess ? CID_OK : cx.hip(what);
-    };
-    const auto dgrad = [&](auto kernel, const SrgDz& dz, const float* w, float* out, const float* add, int Hl, int Wl, const char* what) {
-        const int tiles_x = (Wl + D_TW - 1) / D_TW, tiles = ((Hl + 15) / 16) * tiles_x;
-        return cx.launches(N, what, [&](int n0, int n) {
-            const SrgDgradArgs a{dz, w, out, add, Hl, Wl, tiles_x, n0};
-            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)n), block, 0, s, a);
-        });
-    };
-    const auto reduce9 = [&](float* dw, float* db, int splits, int head, const char* what) {
-        const SrgWgrad9ReduceArgs r{part9, dw, db, splits, head};
-        hipLaunchKernelGGL(k_srg_wgrad243_reduce, dim3((64 * SG_W9_K + D_THREADS - 1) / D_THREADS), block, 0, s, r);
-        return hipPeekAtLastError() == hipSuccess ? CID_OK : cx.hip(what);
-    };
-
+    const SrgLaunch lx{cx, N, coef, bnslab, chan, part, part_b, part9};
     // ---- final: bias, weights, and the gradient of its input -> A
     if (g->final_b) {
         const long long P = (long long)Hs * Ws;
@@ -235,7 +258,7 @@ int cid_sr_backward(cid_sr_t h, const void* in, int in_fmt, const float* grad_ou
                                  tiles_x, tiles, raw};
         if (S) hipLaunchKernelGGL(k_srg_tail_wgrad<true>, dim3((unsigned)splits), block, 0, s, a);
         else hipLaunchKernelGGL(k_srg_tail_wgrad<false>, dim3((unsigned)splits), block, 0, s, a);
-        if (const int rc = reduce9(g->final_w, nullptr, splits, 0, "final wgrad")) return rc;
+        if (const int rc = lx.reduce9(g->final_w, nullptr, splits, 0, "final wgrad")) return rc;
     }
     {
         const int tiles_x = (Ws + D_TW - 1) / D_TW, tiles = ((Hs + 15) / 16) * tiles_x;
@@ -250,15 +273,15 @@ int cid_sr_backward(cid_sr_t h, const void* in, int in_fmt, const float* grad_ou
         const int Hk = H << k, Wk = W << k;
         const SrgDz dz{sv.v[k], AB[cur], up_slope(k)};
         if (g->up_slope[k])
-            if (const int rc = slope_sums(k_srg_bn_part<SG_DZ_PRELU>, dz, nullptr, nullptr, up_slope(k), nullptr, nullptr, nullptr,
+            if (const int rc = lx.slope_sums(k_srg_bn_part<SG_DZ_PRELU>, dz, nullptr, nullptr, up_slope(k), nullptr, nullptr, nullptr,
                                           g->up_slope[k], 2 * Hk, 2 * Wk, "upscale slope"))
                 return rc;
-        const int rc = k == 0 ? wgrad(k_srg_wgrad<SG_DZ_SHUFFLE, SG_IN_RAW, 256>, 4, dz, sv.t, nullptr, nullptr, g->up_w[k], g->up_b[k], Hk, Wk,
+        const int rc = k == 0 ? lx.wgrad(k_srg_wgrad<SG_DZ_SHUFFLE, SG_IN_RAW, 256>, 4, dz, sv.t, nullptr, nullptr, g->up_w[k], g->up_b[k], Hk, Wk,
                                       "upscale wgrad")
-                              : wgrad(k_srg_wgrad<SG_DZ_SHUFFLE, SG_IN_PRELU, 256>, 4, dz, sv.v[k - 1], nullptr, up_slope(k - 1), g->up_w[k],
+                              : lx.wgrad(k_srg_wgrad<SG_DZ_SHUFFLE, SG_IN_PRELU, 256>, 4, dz, sv.v[k - 1], nullptr, up_slope(k - 1), g->up_w[k],
                                       g->up_b[k], Hk, Wk, "upscale wgrad");
         if (rc) return rc;
-        if (const int rc2 = dgrad(k_srg_dgrad<256, SG_DZ_SHUFFLE>, dz, blob + h->up_off(k), AB[1 - cur], nullptr, Hk, Wk, "upscale dgrad"))
+        if (const int rc2 = lx.dgrad(k_srg_dgrad<256, SG_DZ_SHUFFLE>, dz, blob + h->up_off(k), AB[1 - cur], nullptr, Hk, Wk, "upscale dgrad"))
             return rc2;
         cur = 1 - cur;
     }
@@ -266,35 +289,35 @@ int cid_sr_backward(cid_sr_t h, const void* in, int in_fmt, const float* grad_ou
     // ---- mid
     {
         const SrgDz dz{nullptr, dt, nullptr};
-        if (const int rc = wgrad(k_srg_wgrad<SG_DZ_PLAIN, SG_IN_BN>, 1, dz, sv.z[9], sv.st + 9 * 128, nullptr, g->mid_w, g->mid_b, H, W, "mid wgrad"))
+        if (const int rc = lx.wgrad(k_srg_wgrad<SG_DZ_PLAIN, SG_IN_BN>, 1, dz, sv.z[9], sv.st + 9 * 128, nullptr, g->mid_w, g->mid_b, H, W, "mid wgrad"))
             return rc;
-        if (const int rc = dgrad(k_srg_dgrad<64, SG_DZ_PLAIN>, dz, conv_seg(S_TRAIN_BNS), T[0], nullptr, H, W, "mid dgrad")) return rc;
+        if (const int rc = lx.dgrad(k_srg_dgrad<64, SG_DZ_PLAIN>, dz, conv_seg(S_TRAIN_BNS), T[0], nullptr, H, W, "mid dgrad")) return rc;
     }
     // ---- BatchNorm l and convolution l, l = 9 .. 0: T[tc] holds the gradient of A_l(BN_l(z_l))
     int tc = 0;
     for (int l = S_TRAIN_BNS - 1; l >= 0; --l) {
         const float* act = l % 2 == 0 ? block_slope(l / 2) : nullptr;   // the PReLU behind BN_l
         const SrgDz dz{sv.z[l], T[tc], coef};
-        if (const int rc = slope_sums(k_srg_bn_part<SG_DZ_BN>, dz, sv.st + l * 128, sv.mi + l * 128, act, bn[l].gamma, g->gamma[l], g->beta[l],
+        if (const int rc = lx.slope_sums(k_srg_bn_part<SG_DZ_BN>, dz, sv.st + l * 128, sv.mi + l * 128, act, bn[l].gamma, g->gamma[l], g->beta[l],
                                       act ? g->slope[l / 2] : nullptr, H, W, "bn sums"))
             return rc;
         int rc;
         if (l == 0)
-            rc = wgrad(k_srg_wgrad<SG_DZ_BN, SG_IN_PRELU>, 1, dz, sv.v0, nullptr, head_slope, g->conv_w[l], g->conv_b[l], H, W, "wgrad");
+            rc = lx.wgrad(k_srg_wgrad<SG_DZ_BN, SG_IN_PRELU>, 1, dz, sv.v0, nullptr, head_slope, g->conv_w[l], g->conv_b[l], H, W, "wgrad");
         else if (l % 2)
-            rc = wgrad(k_srg_wgrad<SG_DZ_BN, SG_IN_BN_PRELU>, 1, dz, sv.z[l - 1], sv.st + (l - 1) * 128, block_slope((l - 1) / 2), g->conv_w[l],
+            rc = lx.wgrad(k_srg_wgrad<SG_DZ_BN, SG_IN_BN_PRELU>, 1, dz, sv.z[l - 1], sv.st + (l - 1) * 128, block_slope((l - 1) / 2), g->conv_w[l],
                        g->conv_b[l], H, W, "wgrad");
         else
-            rc = wgrad(k_srg_wgrad<SG_DZ_BN, SG_IN_BN>, 1, dz, sv.z[l - 1], sv.st + (l - 1) * 128, nullptr, g->conv_w[l], g->conv_b[l], H, W, "wgrad");
+            rc = lx.wgrad(k_srg_wgrad<SG_DZ_BN, SG_IN_BN>, 1, dz, sv.z[l - 1], sv.st + (l - 1) * 128, nullptr, g->conv_w[l], g->conv_b[l], H, W, "wgrad");
         if (rc) return rc;
         // x0 has two gradients: through res_blocks.0.0 and through the skip into t
-        if (const int rc2 = dgrad(k_srg_dgrad<64, SG_DZ_BN>, dz, conv_seg(l), T[1 - tc], l == 0 ? dt : nullptr, H, W, "dgrad")) return rc2;
+        if (const int rc2 = lx.dgrad(k_srg_dgrad<64, SG_DZ_BN>, dz, conv_seg(l), T[1 - tc], l == 0 ? dt : nullptr, H, W, "dgrad")) return rc2;
         tc = 1 - tc;
     }
     // ---- head: T[tc] holds the gradient of x0
     const SrgDz dz0{sv.v0, T[tc], head_slope};
     if (g->head_slope)
-        if (const int rc = slope_sums(k_srg_bn_part<SG_DZ_PRELU>, dz0, nullptr, nullptr, head_slope, nullptr, nullptr, nullptr, g->head_slope, H,
+        if (const int rc = lx.slope_sums(k_srg_bn_part<SG_DZ_PRELU>, dz0, nullptr, nullptr, head_slope, nullptr, nullptr, nullptr, g->head_slope, H,
                                       W, "head slope"))
             return rc;
     if (!g->head_w && !g->head_b) return CID_OK;
@@ -302,8 +325,8 @@ int cid_sr_backward(cid_sr_t h, const void* in, int in_fmt, const float* grad_ou
     const long long items = (long long)N * H * segs;
     const int splits = (int)std::min<long long>(items, kSrW9Splits);
     const SrgWgrad9Args a9{dz0, in, part9, items, splits, segs, H, W, in_fmt == CID_FMT_U8_NHWC};
-    hipLaunchKernelGGL(k_srg_wgrad243, dim3((unsigned)splits), block, 0, s, a9);
-    return reduce9(g->head_w, g->head_b, splits, 1, "head wgrad");
+    hipLaunchKernelGGL(k_srg_wgrad243<>, dim3((unsigned)splits), block, 0, s, a9);
+    return lx.reduce9(g->head_w, g->head_b, splits, 1, "head wgrad");
 }
 
 int cid_sr_pack_weights_device(cid_sr_t h, const float* const* dev_params, const cid_disc_bn* bn, void* device_blob, void* stream) {

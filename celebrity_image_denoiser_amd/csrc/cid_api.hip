@@ -1519,6 +1519,7 @@ int cid_backward(cid_handle_t h, const float* in, const float* out, const float*
 #include "api/srgan_train.h"      // cid_sr_*: the train-mode forward (batch-statistics BatchNorm)
 #include "api/esrgan_train.h"     // cid_esr_*: the train-mode forward (batch-statistics BatchNorm under the blocks' skips)
 #include "api/srgan_backward.h"   // cid_sr_*: saved train forward, backward, masks
+#include "api/esrgan_backward.h"  // cid_esr_*: saved train forward, backward, device pack, masks
 #include "api/cgan.h"             // cid_cg_*
 #include "api/lpips.h"            // cid_lpips_*
 #include "api/vgg.h"              // cid_vgg_*

@@ -10,6 +10,7 @@
 //   * k_esr_head<U8>: the 9x9 3 -> 64 convolution + bias + PReLU on the VALU, one thread per pixel with the 64 channel sums in
 //     registers; the K = 243 weights are wave-uniform and come through scalar loads.  It reads fp32 [N,3,H,W] or uint8 [N,H,W,3]
 //     as (float)u / 255.0f (a true division) and writes x1; with R = 0 it also writes x1 + x1, the tensor the tail reads then.
+//     k_esr_head<U8, true> also stores the sums before PReLU (cid_esr_forward_saved).
 //   * k_esr_conv<EPI>: the 3x3 64 -> 64 convolution as an implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32), in the tiling of
 //     k_disc_conv<64, 64, 1> (a 256-thread workgroup owns 16 x 16 output pixels and all 64 channels; weights are the A operand,
 //     so a lane's four accumulators are four consecutive channels of one pixel and leave as one 16-byte store).  BatchNorm uses
@@ -27,6 +28,8 @@
 // in the batch.  No atomics.  Offsets are 64-bit; only a pixel index inside one image is an int (H * W < 2^31 is checked on the host).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "disc_kernels.h"
 
@@ -48,8 +51,13 @@ struct EsrHeadArgs {
     int n0;             // first image of this launch (grid y = image - n0)
 };
 
-template <bool U8>
-__global__ void __launch_bounds__(D_THREADS) k_esr_head(const EsrHeadArgs a) {
+// SAVE (cid_esr_forward_saved): the sums before PReLU go to a.pre as well, x1's layout; the backward's mask and slope gradient need them.
+struct EsrHeadSavedArgs : EsrHeadArgs {
+    float* pre;
+};
+
+template <bool U8, bool SAVE = false>
+__global__ void __launch_bounds__(D_THREADS) k_esr_head(const std::conditional_t<SAVE, EsrHeadSavedArgs, EsrHeadArgs> a) {
     const int p = blockIdx.x * D_THREADS + threadIdx.x;
     const long long HW = (long long)a.H * a.W;
     if (p >= HW) return;
@@ -94,6 +102,11 @@ __global__ void __launch_bounds__(D_THREADS) k_esr_head(const EsrHeadArgs a) {
             d_f32x4* o2 = reinterpret_cast<d_f32x4*>(a.twice + at);
             o2[0] = d_f32x4{v[0] + v[0], v[1] + v[1], v[2] + v[2], v[3] + v[3]};
             o2[1] = d_f32x4{v[4] + v[4], v[5] + v[5], v[6] + v[6], v[7] + v[7]};
+        }
+        if constexpr (SAVE) {
+            d_f32x4* q = reinterpret_cast<d_f32x4*>(a.pre + at);
+            q[0] = d_f32x4{acc[cb * 8], acc[cb * 8 + 1], acc[cb * 8 + 2], acc[cb * 8 + 3]};
+            q[1] = d_f32x4{acc[cb * 8 + 4], acc[cb * 8 + 5], acc[cb * 8 + 6], acc[cb * 8 + 7]};
         }
     }
 }

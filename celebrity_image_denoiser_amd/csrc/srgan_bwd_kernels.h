@@ -25,7 +25,7 @@
 //     reduce maps packed columns back to convolution channels.
 //   * k_srg_tail_dgrad: final's 3 -> 64 data gradient, K = (3, 9, 12): kw padded to three MFMA k-steps with zero weights.
 //   * k_srg_wgrad243 + k_srg_wgrad243_reduce: the head's weight and bias gradient on the VALU in fp64, thread = (one of 64 channels,
-//     a quarter of K = 244): dz x input patches (fp32 or uint8), K's last slot is the bias.
+//     a quarter of K = 244): dz x input patches (fp32 or uint8), K's last slot is the bias.  <true> reads uint8 as u / 255 (ESRGAN).
 //   * k_srg_tail_wgrad<PRELU_IN>: final's weight gradient on the MFMA, 64 input channels x (co, kh) x kw per 4 x 16 pixel item; the
 //     same reduce.
 //   * k_srg_tail_bias_part: final's bias gradient.
@@ -617,6 +617,8 @@ struct SrgWgrad9Args {
     int u8;
 };
 
+// UNIT_U8: a uint8 image is read as (float)u / 255.0f, the ESRGAN generator's head (k_esr_head), not as d_u8's Normalize(0.5, 0.5).
+template <bool UNIT_U8 = false>
 __global__ void __launch_bounds__(D_THREADS) k_srg_wgrad243(const SrgWgrad9Args a) {
     __shared__ float lds_d[SG_W9_PX * 64];        // [pixel][c]
     __shared__ float lds_p[SG_W9_PX * SG_W9_K];   // [pixel][k]
@@ -651,8 +653,12 @@ __global__ void __launch_bounds__(D_THREADS) k_srg_wgrad243(const SrgWgrad9Args 
                     const int iy = y + kh - 4, ix = x0 + px + kw - 4;
                     if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
                         const size_t pix = (size_t)iy * a.W + ix;
-                        if (a.u8) v = d_u8(static_cast<const unsigned char*>(a.img)[(n * plane + pix) * 3 + c3]);
-                        else v = static_cast<const float*>(a.img)[(n * 3 + c3) * plane + pix];
+                        if (a.u8) {
+                            const unsigned char u = static_cast<const unsigned char*>(a.img)[(n * plane + pix) * 3 + c3];
+                            v = UNIT_U8 ? (float)u / 255.0f : d_u8(u);
+                        } else {
+                            v = static_cast<const float*>(a.img)[(n * 3 + c3) * plane + pix];
+                        }
                     }
                 }
             }

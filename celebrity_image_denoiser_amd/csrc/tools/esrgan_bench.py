@@ -10,8 +10,15 @@ TFLOP/s (2 * MACs of the 9x9 head, the 2 R trunk convolutions and the 9x9 tail: 
 no_grad, as this forward has no autograd history either).  The three run in one process and take turns window by window: 3 warm-up
 calls each, then the median of 5 windows of 20 calls [min-max], "default" weights, inputs resident.
 
+--backward times the differentiable step (ESRGANGenerator(batch_stats=True, autograd=True): cid_esr_pack_weights_device +
+cid_esr_forward_saved, then cid_esr_backward under loss.backward()) at the trainer's shape, B=8 256x256, R=8, next to the forward of
+that step alone and to loss.backward() through a stock copy of the network on ATen/MIOpen autograd, in the same protocol: one process,
+windows in turn, 3 warm-up steps each, the median of 5 windows of 5 steps [min-max].  A step is out = G(x); (out * g).sum().backward()
+with .grad set to None before it.  It also prints what one call holds: the saved buffer is (3R+1) tensors of N*64*H*W*4 bytes plus
+the BatchNorm tables, 3.36 GB at that shape, next to the train workspace and the backward workspace.
+
     python celebrity_image_denoiser_amd/csrc/tools/esrgan_bench.py [--reps 5] [--iters 10] [--case N,H,W ...] [--residuals 8]
-                                                                   [--no-aten] [--u8] [--json out.json] [--train]
+                                                                   [--no-aten] [--u8] [--json out.json] [--train | --backward]
 """
 import argparse
 import copy
@@ -110,6 +117,51 @@ def run_train_case(n, h, w, r, args):
     return row
 
 
+def run_backward_case(n, h, w, r, args):
+    """One generator step: HIP forward with history, HIP forward + backward, and the stock layers under ATen autograd."""
+    import ctypes
+
+    from celebrity_image_denoiser_amd import _lib
+
+    dev = "cuda:0"
+    sd = synth.make_esrgan_state_dict("default", r)
+    model = cid.load_esrgan(sd, num_residuals=r, device=dev, strict=True, batch_stats=True, autograd=True).train()
+    stock = copy.deepcopy(torch.nn.ModuleDict({k: getattr(model, k) for k in ("initial", "residuals", "final")})).train()
+    u8 = torch.from_numpy(synth.esrgan_inputs_u8(min(n, 16), h, w)).to(dev).repeat((n + 15) // 16, 1, 1, 1)[:n].contiguous()
+    x = u8.to(torch.float32).div(255.0).permute(0, 3, 1, 2).contiguous()
+    g = torch.rand((n, 3, h, w), device=dev, generator=torch.Generator(dev).manual_seed(7)).mul_(2).sub_(1).div_(n * 3 * h * w)
+
+    def hip_forward():
+        model(x)    # with grad enabled: pack on the device + cid_esr_forward_saved; the context is dropped with the result
+
+    def hip_step():
+        model.zero_grad(set_to_none=True)
+        (model(x) * g).sum().backward()
+
+    def aten_step():
+        stock.zero_grad(set_to_none=True)
+        (aten_forward(stock, x) * g).sum().backward()
+
+    fns = [hip_forward, hip_step] + ([] if args.no_aten else [aten_step])
+    times = timed_in_turn(fns, args.reps, args.iters)
+    flops = 3.0 * esr_flops(n, h, w, r)   # forward + data gradient + weight gradient, the input gradient of the head aside
+    row = {"N": n, "H": h, "W": w, "R": r, "mode": "backward", "gflop_step": flops / 1e9}
+    need = ctypes.c_size_t()
+    for key, fn in (("saved_bytes", "cid_esr_saved_bytes"), ("backward_workspace_bytes", "cid_esr_backward_workspace_bytes"),
+                    ("train_workspace_bytes", "cid_esr_train_workspace_bytes")):
+        assert getattr(_lib.lib(), fn)(n, h, w, r, ctypes.byref(need)) == 0
+        row[key] = need.value
+    row["hip_forward_saved"], row["hip_step"] = summary(times[0], n, flops / 3), summary(times[1], n, flops)
+    line = (f"backward B={n:3d} {h}x{w} R={r} | saved {row['saved_bytes'] / 1e9:.2f} GB, backward workspace "
+            f"{row['backward_workspace_bytes'] / 1e9:.2f} GB, train workspace {row['train_workspace_bytes'] / 1e9:.2f} GB\n  "
+            + fmt("hip forward_saved", row["hip_forward_saved"]) + "\n  " + fmt("hip forward+backward", row["hip_step"]))
+    if not args.no_aten:
+        row["aten_step"] = summary(times[2], n, flops)
+        line += "\n  " + fmt("aten forward+backward", row["aten_step"]) + f"\n  hip/aten {row['hip_step']['ms_median'] / row['aten_step']['ms_median']:.2f}"
+    print(line, flush=True)
+    return row
+
+
 def summary(t, n, flops):
     med = statistics.median(t)
     return {"ms_median": med, "ms_min": min(t), "ms_max": max(t), "images_per_s": n / med * 1e3,
@@ -131,12 +183,20 @@ def main():
     ap.add_argument("--u8", action="store_true", help="also time the uint8 -> uint8 path")
     ap.add_argument("--json", default=None)
     ap.add_argument("--train", action="store_true", help="the train-mode forward at the trainer's shapes (B=8 and B=16, 256x256)")
+    ap.add_argument("--backward", action="store_true", help="forward + backward of the generator step at the trainer's shape (B=8, 256x256)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("esrgan_bench needs a GPU")
     dev = "cuda:0"
     cases = [tuple(int(v) for v in c.split(",")) for c in args.case] if args.case else CASES
     r = args.residuals
+    if args.backward:
+        args.iters = 5 if args.iters == ap.get_default("iters") else args.iters
+        rows = [run_backward_case(n, h, w, r, args) for n, h, w in (cases if args.case else TRAIN_CASES[:1])]
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     if args.train:
         args.iters = 20 if args.iters == ap.get_default("iters") else args.iters
         rows = [run_train_case(n, h, w, r, args) for n, h, w in (cases if args.case else TRAIN_CASES)]

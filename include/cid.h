@@ -914,6 +914,74 @@ int cid_esr_train_stage_view(const char* stage, int N, int H, int W, int num_res
                              int* channel_block);
 
 /*
+ * The backward pass of that train-mode generator: g_loss.backward() of the ESRGAN trainer's step (esrgan_train.py:115-121) from
+ * grad_out = d loss / d denoised down to every parameter.  The family mirrors cid_sr_forward_saved / cid_sr_backward (below): per-call
+ * saved buffer, what is null is not written and costs no launch of its own, the same call twice gives the same bits, no host
+ * synchronisation.  There is no input gradient: noisy is data.  With R = 0 there is no BatchNorm and bn may be NULL.
+ *
+ * cid_esr_forward_saved is cid_esr_forward_train with an fp32 output and a caller-owned PER-CALL saved buffer next to the workspace
+ * (cid_esr_train_workspace_bytes; x1 and the slab stay there: the backward forms x1 from v0).  out and the BatchNorm buffer updates are
+ * bit-identical to cid_esr_forward_train.  The saved buffer keeps, without overlap: the head's sums v0 before its PReLU, the 2 R raw
+ * z_l, the block outputs r_0 .. r_{R-2}, tail_in, and the 2 R (scale, shift) and (mean, invstd) tables.  Every PReLU mask of the
+ * backward is decided on a saved PRE-activation (v0, or BN_2i(z_2i) recomputed with the forward's own fmaf), so it is the forward's
+ * decision for any slope, 0 and negative ones included.
+ * cid_esr_saved_bytes(N, H, W, R), with a(v) = v rounded up to 256 and t = N * 64 * H * W * 4:
+ *     (R >= 1 ? 3 R + 1 : 2) a(t) + a(2R*64*2*4) + a(2R*64*2*8)
+ *
+ * cid_esr_backward: `in` is the forward's input (the head's weight gradient reads it, fp32 or uint8 as the forward reads it), grad_out
+ * fp32 [N,3,H,W] (the output is the raw sum, so it is taken as it is), bn the forward's array (only gamma is read).  `g` holds one
+ * pointer per parameter tensor in the module's layouts; a null pointer means the tensor is not wanted.  With r_{-1} = x1 and G_i the
+ * gradient of r_i: final gives dT = d tail_in; the outer skip gives G_{R-1} = dT; block i gives BN_{2i+1}'s and convolution 2i+1's
+ * gradients from G_i, then BN_2i's, the block's slope's and convolution 2i's, and G_{i-1} = G_i + (convolution 2i's data gradient),
+ * added in that order; d x1 = G_{-1} + dT in that order (R = 0: dT + dT); then the head.  BatchNorm's backward carries the two batch
+ * sums, dz = k * (g - m1 - xh * m2); the 3x3 data and weight gradients and final's run on the exact-fp32 MFMA, a weight gradient
+ * accumulating in fp32 inside one workgroup's range of tiles; the head's K = 243 weight gradient runs in fp64 on the VALU; every
+ * reduction across workgroups is fp64 in a fixed order through a slab (or per-workgroup partials) and a reduce launch, no atomics.
+ * The workspace may hold anything on entry.  cid_esr_backward_workspace_bytes(N, H, W, R), with strips = ceil(H*W / 512):
+ *     (R >= 1 ? 4 : 2) a(t) + a(64*8*4) + a(64*3*N*strips*8) + a(64*8) + a(128*4*64*144*4) + a(128*64*8) + a(512*64*244*8)
+ * Checked on the host before any launch:
+ *   CID_ERR_INVALID    null h / in / grad_out / saved / g / workspace, with R > 0 null bn / bn[l].gamma, unknown format, misaligned
+ *                      fp32 pointer (the gradient tensors included)
+ *   CID_ERR_SHAPE      as cid_esr_forward_train
+ *   CID_ERR_WORKSPACE  saved buffer or workspace too small or not 256-byte aligned
+ *   CID_ERR_STATE      weights not uploaded
+ *
+ * cid_esr_pack_weights_device builds the forward's blob from the parameter tensors in DEVICE memory with one launch and attaches it:
+ * byte for byte what cid_esr_set_weight + cid_esr_set_bn_eps + cid_esr_upload_weights produce, the zero gaps and the 2 R eval-mode
+ * folds (taken in fp64 from bn[l]'s gamma, beta, running_mean, running_var and eps, rounded as the host rounds them) included.
+ * dev_params holds the 3 + 9 R + 2 parameter tensors in the module's order: initial.0.weight, initial.0.bias, initial.1.weight, per
+ * block block.0.weight block.0.bias block.1.weight block.1.bias block.2.weight block.3.weight block.3.bias block.4.weight block.4.bias,
+ * final.weight, final.bias.  A trainer calls it after every optimizer step.
+ *   CID_ERR_INVALID    null h / dev_params / device_blob, a null or not 4-byte-aligned parameter pointer, with R > 0 a null bn, gamma,
+ *                      beta, running_mean or running_var, an eps that is not finite or negative
+ *   CID_ERR_WORKSPACE  device_blob not 256-byte aligned
+ *
+ * cid_esr_saved_masks is a testing aid as cid_sr_saved_masks: the 1 + R PReLU decisions as the backward takes them, uint8 [N,64,H,W]
+ * (1 where the slope is 1): masks[0] the head, masks[1 + i] block i's PReLU (after residuals.i.block.1).
+ */
+typedef struct {
+    float* head_w;        /* initial.0.weight [64,3,9,9]                                          */
+    float* head_b;        /* initial.0.bias [64]                                                  */
+    float* head_slope;    /* initial.1.weight [1]                                                 */
+    float* conv_w[32];    /* residuals.i.block.0.weight (2i), residuals.i.block.3.weight (2i+1)   */
+    float* conv_b[32];    /* their biases                                                         */
+    float* gamma[32];     /* residuals.i.block.1.weight (2i), residuals.i.block.4.weight (2i+1)   */
+    float* beta[32];      /* their biases                                                         */
+    float* slope[16];     /* residuals.i.block.2.weight [1]                                       */
+    float* final_w;       /* final.weight [3,64,9,9]                                              */
+    float* final_b;       /* final.bias [3]                                                       */
+} cid_esr_grads;
+int cid_esr_saved_bytes(int N, int H, int W, int num_residuals, size_t* bytes);
+int cid_esr_forward_saved(cid_esr_t h, const void* in, int in_fmt, float* out, int N, int H, int W, const cid_disc_bn* bn, void* saved,
+                          size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int cid_esr_backward_workspace_bytes(int N, int H, int W, int num_residuals, size_t* bytes);
+int cid_esr_backward(cid_esr_t h, const void* in, int in_fmt, const float* grad_out, int N, int H, int W, const cid_disc_bn* bn,
+                     const void* saved, size_t saved_bytes, const cid_esr_grads* g, void* workspace, size_t workspace_bytes, void* stream);
+int cid_esr_pack_weights_device(cid_esr_t h, const float* const* dev_params, const cid_disc_bn* bn, void* device_blob, void* stream);
+int cid_esr_saved_masks(const void* saved, size_t saved_bytes, int N, int H, int W, int num_residuals, unsigned char* const* masks,
+                        void* stream);
+
+/*
  * The server's third model — SRGANGenerator(scale_factor = 4) (backend/app.py:145-186; the same class in
  * backend/trainingcode/srgan_code/sr_ganTrainGNew.py:19-51), the "srgan" branch of /enhance.  Eval mode, fp32:
  *
